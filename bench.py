@@ -11,7 +11,12 @@ resident in HBM before the timed region.  Weights are random-init (name-keyed
 generator, ppst_amd/weights.py) with non-zero noise weights so the noise path is
 exercised; data is synthetic.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--precision bf16x3|bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--precision bf16x3|bf16] [--full] [--dump-outputs DIR]
+    --full:          behind the headline, the conv rooflines (a profiled region of its own), the upfirdn2d HBM rate, the
+                     train / hires / grid extras and the CPU-oracle baseline; a plain run sets up, warms up, times the K steps
+                     and prints the line
+    --dump-outputs:  after the timed steps, the arrays the last timed step returned as DIR/<name>.npy (float32 / float64,
+                     64 MB at most); the inputs are seeded, so two builds can be compared output for output
     N>1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
           (or just `python bench.py --gpus N`: with WORLD_SIZE unset the program starts its N ranks itself -- child processes
           through torch.distributed.run, like the reference's launcher, experiments/tmux_launcher.py:84-90 -- before it touches
@@ -35,6 +40,29 @@ sys.path.insert(0, ROOT)
 FLOP_PER_SWAP = 2189e9           # SURVEY.md section 8d / BASELINE.md section 3 (dense conv/GEMM only)
 PEAK_BF16_DENSE_TF = 2500.0      # MI355X_MICROARCH.md: BF16 MFMA dense peak
 HBM_PEAK_GBS = 8000.0
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: all files together
+PROF_STEPS_MAX = 50              # --full: steps of the profiled swap region (~82 bracketed conv launches per step; the pool holds 16384)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor} as path/<name>.npy, float64 kept, every other dtype written as float32.  Arrays are written
+    smallest first, each within an even share of what is left of DUMP_MAX_BYTES; one over its share is replaced by a fixed sample
+    of its flattened elements (seeded: the same indices for the same shape on every run and every build)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for k, v in arrays.items():
+        t = torch.as_tensor(v).detach().cpu()
+        arrs[k] = (t.double() if t.dtype == torch.float64 else t.float()).numpy()
+    left = DUMP_MAX_BYTES
+    for n, k in enumerate(sorted(arrs, key=lambda k_: arrs[k_].nbytes)):
+        a = arrs[k]
+        share = left // (len(arrs) - n) - 4096          # (room for the .npy header)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
+        left -= os.path.getsize(os.path.join(path, k + ".npy"))
 
 
 def _variant(info):
@@ -297,7 +325,7 @@ FLOP_PER_IMAGE_PASS = (23.7 + 22.7 + 753.9) * 1e9     # E1 + E2 + G with feature
 FLOP_PER_PAIR_PASS = (17.2 + 38.8 + 486.2) * 1e9      # corrm + E2 with warp + G decode
 
 
-def bench_grid(args, rank, world, dev, barrier, max_over_ranks):
+def bench_grid(args, rank, world, dev, barrier, max_over_ranks, outputs=None):
     """BASELINE configs[2]: swapping_grid over an 8 x 8 folder at 512x512 with the guided-filter post-process
     (content_style_grid_generation_evaluator.py:36-99).  One step = the whole grid: 16 per-image passes + one exchange
     + 64 pair passes, images and pairs sharded over the ranks (strong scaling: the grid is fixed as N grows)."""
@@ -334,6 +362,8 @@ def bench_grid(args, rank, world, dev, barrier, max_over_ranks):
         torch.cuda.synchronize()
         gf_ms = e0.elapsed_time(e1) / 5
     assert all(torch.isfinite(v).all() for v in out.values())
+    if outputs is not None:          # --dump-outputs: this rank's pairs of the last step, in (content, style) order
+        outputs["grid"] = torch.stack([out[k] for k in sorted(out)])
     pairs = 64 * args.steps
     flop = args.steps * (16 * FLOP_PER_IMAGE_PASS + 64 * FLOP_PER_PAIR_PASS)
     passes = {"bf16x3": 3, "fp16x2": 2}.get(args.precision, 1)
@@ -355,7 +385,7 @@ def bench_grid(args, rank, world, dev, barrier, max_over_ranks):
             "algorithmic_tflops_whole_job": flop / dt / 1e12}
 
 
-def bench_train(args, rank, world, dev, barrier, max_over_ranks):
+def bench_train(args, rank, world, dev, barrier, max_over_ranks, outputs=None):
     """BASELINE configs[3]: CelebAMaskHQ_default train step at 512x512, batch 2 per GPU (the reference's default), random
     init, synthetic images + label maps.  One step = one discriminator iteration (with the lazy R1 pass every 16th) and
     one generator iteration (PPSTOptimizer.train_one_step twice), data parallel: flat gradient all-reduce per network."""
@@ -402,6 +432,8 @@ def bench_train(args, rank, world, dev, barrier, max_over_ranks):
     ops.prof_collect()
     ops.prof_enable(False)
     assert all(v == v for v in list(dl.values()) + list(gl.values())), "NaN loss"
+    if outputs is not None:          # --dump-outputs: the losses of the last D and G iterations
+        outputs.update({"loss_" + k: v for k, v in {**dl, **gl}.items()})
     assert ops.ksplit_check(), "a K-split conv launch gave up waiting for its partner blocks (ppst_conv_ksplit_check)"
     # one R1 pass alone (zero_grad -> compute_R1_loss -> x16 -> backward -> Adam on D), warmed up once
     r1_ms = None
@@ -460,7 +492,7 @@ def bench_train(args, rank, world, dev, barrier, max_over_ranks):
             "losses": {**dl, **gl}}
 
 
-def bench_hires(args, rank, world, dev, barrier, max_over_ranks):
+def bench_hires(args, rank, world, dev, barrier, max_over_ranks, outputs=None):
     """BASELINE configs[4]: 1024x1024 swap + guided-filter post-process, fp16 generator with fp32 style modulation (precision
     mode 3: fp16 MFMA operands, fp32 accumulate / instance-norm statistics / StyleMod), one GPU per batch.  The correspondence
     recipe does not exist at 1024^2 in the reference (its matching assumes 64 x 64 feature maps), so a
@@ -495,6 +527,8 @@ def bench_hires(args, rank, world, dev, barrier, max_over_ranks):
         conv_ms, conv_launches, conv_flop = ops.prof_collect()
         ops.prof_enable(False)
         assert torch.isfinite(out).all()
+        if outputs is not None:
+            outputs["swapped"] = out
         # the guided filter alone, HIP events on the launch stream (= torch's current stream): uint8 guide + uint8 source in,
         # float image out of the command; algorithmic minimum 9 bytes per pixel with uint8 I/O
         sp, _ = model(content, command="encode")
@@ -647,6 +681,88 @@ def bench_stub(args, rank, world):
         dist.destroy_process_group()
 
 
+def swap_full(args, model, content, style, rank, world, dev, barrier, max_over_ranks):
+    """--full, swap workload: the conv rooflines over a profiled region of its own behind the timed steps (HIP events bracket
+    every conv launch, at most PROF_STEPS_MAX steps so that the event pool holds them), the upfirdn2d HBM rate, the extras and
+    the CPU-oracle baseline.  Every rank runs the profiled region (its barriers and max-reduction); rank 0 gets the keys."""
+    from ppst_amd import glue, ops
+    B = args.batch
+    n_prof = min(args.steps, PROF_STEPS_MAX)
+    with torch.no_grad():
+        # which of the bracketed conv launches belong to StyledConv (the "modulated_conv2d" of BASELINE's metric (ii)): every
+        # ConvPlan call is one ppst_conv2d_mfma launch, counted in order; those issued inside Generator.styled_conv are tagged
+        tag = {"n": 0, "depth": 0, "styled": set()}
+        plan_call, g_cls = ops.ConvPlan.__call__, type(model.G)
+        styled_conv = g_cls.styled_conv
+
+        def counted_call(self, *a, **k):
+            if tag["depth"]:
+                tag["styled"].add(tag["n"])
+            tag["n"] += 1
+            return plan_call(self, *a, **k)
+
+        def tagged_styled_conv(self, *a, **k):
+            tag["depth"] += 1
+            try:
+                return styled_conv(self, *a, **k)
+            finally:
+                tag["depth"] -= 1
+        barrier()
+        ops.ConvPlan.__call__, g_cls.styled_conv = counted_call, tagged_styled_conv
+        ops.prof_enable(True)
+        t0 = time.perf_counter()
+        for _ in range(n_prof):
+            out = swap_step(model, content, style, 1.0, glue)
+        barrier()
+        dt = time.perf_counter() - t0
+        ops.ConvPlan.__call__, g_cls.styled_conv = plan_call, styled_conv
+        detail = ops.prof_detail()
+        conv_ms, conv_launches, conv_flop = ops.prof_collect()
+        ops.prof_enable(False)
+    assert torch.isfinite(out).all()
+    assert len(detail) == tag["n"] == conv_launches, (len(detail), tag["n"], conv_launches)
+    st_ms = sum(detail[i][0] for i in tag["styled"])
+    st_flop = sum(detail[i][1] for i in tag["styled"])
+
+    dt = max_over_ranks(dt)
+    res = {}
+    if rank == 0:
+        passes = {"bf16x3": 3, "fp16x2": 2}.get(args.precision, 1)
+        achieved = conv_flop / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+        peak = PEAK_BF16_DENSE_TF / passes
+        res["roofline"] = {
+            "kernel": "ppst_conv2d_mfma: conv_wino_kernel (3x3 stride-1 layers, Winograd F(2,3) along x) + conv_mfma_kernel + "
+                      "conv_mfma2_kernel + conv1x1_stream_kernel + conv3x3_direct_kernel (StyledConv / EqualConv2d / nn.Conv2d "
+                      "implicit GEMM, all launches)",
+            "bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+            "peak_note": "bf16 dense MFMA 2500 TF / %d MFMA passes per algorithmic MAC (a builder-defined ceiling of the DIRECT form: "
+                         "secondary since round 5, see frac_issued)" % passes,
+            "frac_note": "achieved = ALGORITHMIC conv flop (2 * MACs of the direct form) / kernel time.  conv_wino_kernel issues 2/3 "
+                         "of the direct form's MFMAs for the same algorithmic MACs (and the nine-product fused upscale, "
+                         "ppst_conv_args.variant 11, 0.64 of its four-phase form's), so since round 4 this fraction and the matrix-pipe "
+                         "busy counter (mfma_busy_frac_pmc) no longer move together: the counter is what the pipe did, frac is what "
+                         "the path got done against the direct form's ceiling",
+            "frac_vs_dense_bf16": achieved / PEAK_BF16_DENSE_TF, **issued_fields(detail),
+            "launches": conv_launches, "kernel_ms_total": conv_ms, "profiled_steps": n_prof,
+            "share_of_step_time": conv_ms * 1e-3 / dt, "traffic": conv_traffic(), "traffic_source": conv_traffic_source(),
+            "effective_clock_ghz_pmc": conv_pmc(), "mfma_busy_frac_pmc": conv_mfma_busy(),
+        }
+        st_ach = st_flop / (st_ms * 1e-3) / 1e12 if st_ms > 0 else 0.0
+        res["roofline_modulated_conv2d"] = {
+            "kernel": "the same kernels, only the launches issued by StyledConv (stylegan2_layers.py:439-475: the generator's 3x3 and "
+                      "fused-upscale convs with noise / bias / leaky-ReLU epilogue and instance-norm statistics) -- BASELINE metric (ii)",
+            "bound": "mfma", "achieved": st_ach, "peak": peak, "unit": "TFLOP/s", "frac": st_ach / peak,
+            "frac_vs_dense_bf16": st_ach / PEAK_BF16_DENSE_TF, **issued_fields([detail[i] for i in sorted(tag["styled"])]),
+            "launches": len(tag["styled"]), "kernel_ms_total": st_ms,
+            "share_of_step_time": st_ms * 1e-3 / dt}
+        res["roofline_upfirdn2d"] = upfirdn2d_rate(B, dev)
+        if world == 1 and not args.no_extras and args.precision == "bf16x3":
+            res["extra"] = extras(args, dev)
+        if world == 1 and not args.no_cpu_baseline:
+            res["cpu_baseline"] = cpu_baseline(0)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -656,13 +772,21 @@ def main():
     ap.add_argument("--precision", default="bf16x3", choices=["bf16x3", "bf16", "fp16", "fp16x2"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--train-batch", type=int, default=2, help="--workload train: images per GPU (the reference's default is 2; SURVEY 8d also asks for 8)")
-    ap.add_argument("--no-extras", action="store_true", help="swap workload on one GPU: skip the train / hires sub-measurements of the default line")
+    ap.add_argument("--no-extras", action="store_true", help="swap workload on one GPU: skip the train / hires sub-measurements of the --full line")
+    ap.add_argument("--full", action="store_true",
+                    help="swap workload: behind the headline, also the conv rooflines (a profiled region of its own), the upfirdn2d HBM rate, "
+                         "the extras (--no-extras skips them) and the CPU-oracle baseline (--no-cpu-baseline skips it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         "64 MB at most: a fixed, seeded sample of a larger output)")
     ap.add_argument("--workload", default="swap", choices=["swap", "grid", "train", "hires", "stub"],
                     help="swap: BASELINE configs[1] (the headline line); grid: configs[2], 8x8 folder at 512 with the guided filter, "
                          "images and pairs sharded over the ranks; train: configs[3], one D (+ lazy R1) and one G iteration per step; "
                          "hires: configs[4], 1024x1024 encode / decode + guided filter (use --precision fp16)")
     ap.add_argument("--conv-variant", type=int, default=None, help="2 (default): N-256 / 128x64-wave-tile kernel where eligible; 0: the 64x64-wave-tile kernel everywhere; 1: one-wave-per-SIMD experiment")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -673,6 +797,7 @@ def main():
         raise SystemExit("launch with torch.distributed.run --nproc-per-node %d (WORLD_SIZE=%d)" % (args.gpus, world))
     if args.workload == "stub":
         return bench_stub(args, rank, world)
+    torch.manual_seed(0)         # the train workload draws its noise from the global generators: same inputs on every run
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     dist = None
@@ -701,9 +826,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
+    outputs = {} if args.dump_outputs else None
     if args.workload != "swap":
-        res = {"grid": bench_grid, "train": bench_train, "hires": bench_hires}[args.workload](args, rank, world, dev, barrier, max_over_ranks)
+        res = {"grid": bench_grid, "train": bench_train, "hires": bench_hires}[args.workload](args, rank, world, dev, barrier, max_over_ranks,
+                                                                                              outputs=outputs)
         if rank == 0:
+            if outputs is not None:
+                dump_outputs(args.dump_outputs, outputs)
             print(json.dumps(res))
         if dist is not None:
             dist.destroy_process_group()
@@ -720,90 +849,35 @@ def main():
         for _ in range(args.warmup):
             out = swap_step(model, content, style, 1.0, glue)
         barrier()
-        # which of the bracketed conv launches belong to StyledConv (the "modulated_conv2d" of BASELINE's metric (ii)): every
-        # ConvPlan call is one ppst_conv2d_mfma launch, counted in order; those issued inside Generator.styled_conv are tagged
-        tag = {"n": 0, "depth": 0, "styled": set()}
-        plan_call, g_cls = ops.ConvPlan.__call__, type(model.G)
-        styled_conv = g_cls.styled_conv
-
-        def counted_call(self, *a, **k):
-            if tag["depth"]:
-                tag["styled"].add(tag["n"])
-            tag["n"] += 1
-            return plan_call(self, *a, **k)
-
-        def tagged_styled_conv(self, *a, **k):
-            tag["depth"] += 1
-            try:
-                return styled_conv(self, *a, **k)
-            finally:
-                tag["depth"] -= 1
-        ops.ConvPlan.__call__, g_cls.styled_conv = counted_call, tagged_styled_conv
-        ops.prof_enable(True)
         t0 = time.perf_counter()
         for _ in range(args.steps):
             out = swap_step(model, content, style, 1.0, glue)
         barrier()
         dt = time.perf_counter() - t0
-        ops.ConvPlan.__call__, g_cls.styled_conv = plan_call, styled_conv
-        detail = ops.prof_detail()
-        conv_ms, conv_launches, conv_flop = ops.prof_collect()
-        ops.prof_enable(False)
     assert torch.isfinite(out).all()
-    assert len(detail) == tag["n"] == conv_launches, (len(detail), tag["n"], conv_launches)
-    st_ms = sum(detail[i][0] for i in tag["styled"])
-    st_flop = sum(detail[i][1] for i in tag["styled"])
-
     dt = max_over_ranks(dt)
+    if rank == 0 and outputs is not None:
+        dump_outputs(args.dump_outputs, {"swapped": out})
 
+    swaps = world * B * args.steps
+    res = {
+        "metric": "512x512 portrait swaps/sec/GPU", "value": swaps / dt, "unit": "swaps/s (all GPUs)",
+        "per_gpu": swaps / dt / world, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": DTYPE_NOTE[args.precision],
+        "data": "synthetic",
+        "config": {"workload": "simple_swapping 512x512 batch=%d per GPU, generator+encoders forward only (BASELINE configs[1])" % B,
+                   "recipe": "encode(content) + the E1/E2 of extract_feat_from_image(content | style) as one batch of 3B images; the two "
+                             "generator feature passes (extract_feat) and Rselfcorr as one batch of 2B; corrm + encode2 + decode.  Same "
+                             "work as the reference's command sequence, batched: nothing is skipped or cached",
+                   "image_parallel": "1 batch per rank, no data-path collective"},
+        "algorithmic_tflops_whole_job": swaps * FLOP_PER_SWAP / dt / 1e12,
+    }
+    if args.full:
+        full = swap_full(args, model, content, style, rank, world, dev, barrier, max_over_ranks)
+        if rank == 0:
+            res.update(full)
     if rank == 0:
-        swaps = world * B * args.steps
-        passes = {"bf16x3": 3, "fp16x2": 2}.get(args.precision, 1)
-        achieved = conv_flop / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-        peak = PEAK_BF16_DENSE_TF / passes
-        res = {
-            "metric": "512x512 portrait swaps/sec/GPU", "value": swaps / dt, "unit": "swaps/s (all GPUs)",
-            "per_gpu": swaps / dt / world, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": DTYPE_NOTE[args.precision],
-            "data": "synthetic",
-            "config": {"workload": "simple_swapping 512x512 batch=%d per GPU, generator+encoders forward only (BASELINE configs[1])" % B,
-                       "recipe": "encode(content) + the E1/E2 of extract_feat_from_image(content | style) as one batch of 3B images; the two "
-                                 "generator feature passes (extract_feat) and Rselfcorr as one batch of 2B; corrm + encode2 + decode.  Same "
-                                 "work as the reference's command sequence, batched: nothing is skipped or cached",
-                       "image_parallel": "1 batch per rank, no data-path collective"},
-            "algorithmic_tflops_whole_job": swaps * FLOP_PER_SWAP / dt / 1e12,
-            "roofline": {
-                "kernel": "ppst_conv2d_mfma: conv_wino_kernel (3x3 stride-1 layers, Winograd F(2,3) along x) + conv_mfma_kernel + "
-                          "conv_mfma2_kernel + conv1x1_stream_kernel + conv3x3_direct_kernel (StyledConv / EqualConv2d / nn.Conv2d "
-                          "implicit GEMM, all launches)",
-                "bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                "peak_note": "bf16 dense MFMA 2500 TF / %d MFMA passes per algorithmic MAC (a builder-defined ceiling of the DIRECT form: "
-                             "secondary since round 5, see frac_issued)" % passes,
-                "frac_note": "achieved = ALGORITHMIC conv flop (2 * MACs of the direct form) / kernel time.  conv_wino_kernel issues 2/3 "
-                             "of the direct form's MFMAs for the same algorithmic MACs (and the nine-product fused upscale, "
-                             "ppst_conv_args.variant 11, 0.64 of its four-phase form's), so since round 4 this fraction and the matrix-pipe "
-                             "busy counter (mfma_busy_frac_pmc) no longer move together: the counter is what the pipe did, frac is what "
-                             "the path got done against the direct form's ceiling",
-                "frac_vs_dense_bf16": achieved / PEAK_BF16_DENSE_TF, **issued_fields(detail),
-                "launches": conv_launches, "kernel_ms_total": conv_ms,
-                "share_of_step_time": conv_ms * 1e-3 / dt, "traffic": conv_traffic(), "traffic_source": conv_traffic_source(),
-                "effective_clock_ghz_pmc": conv_pmc(), "mfma_busy_frac_pmc": conv_mfma_busy(),
-            },
-        }
-        st_ach = st_flop / (st_ms * 1e-3) / 1e12 if st_ms > 0 else 0.0
-        res["roofline_modulated_conv2d"] = {
-            "kernel": "the same kernels, only the launches issued by StyledConv (stylegan2_layers.py:439-475: the generator's 3x3 and "
-                      "fused-upscale convs with noise / bias / leaky-ReLU epilogue and instance-norm statistics) -- BASELINE metric (ii)",
-            "bound": "mfma", "achieved": st_ach, "peak": peak, "unit": "TFLOP/s", "frac": st_ach / peak,
-            "frac_vs_dense_bf16": st_ach / PEAK_BF16_DENSE_TF, **issued_fields([detail[i] for i in sorted(tag["styled"])]),
-            "launches": len(tag["styled"]), "kernel_ms_total": st_ms,
-            "share_of_step_time": st_ms * 1e-3 / dt}
-        res["roofline_upfirdn2d"] = upfirdn2d_rate(B, dev)
-        if world == 1 and not args.no_extras and args.precision == "bf16x3":
-            res["extra"] = extras(args, dev)
-        if world == 1 and not args.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(0)
         print(json.dumps(res))
     if dist is not None:
         dist.destroy_process_group()

@@ -1,7 +1,7 @@
 set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out
-python bench.py --steps 20 --warmup 3 > $O/r03_bench.json 2> $O/r03_bench.err
+python bench.py --full --steps 20 --warmup 3 > $O/r03_bench.json 2> $O/r03_bench.err
 echo "bench done" ; cut -c1-300 $O/r03_bench.json
 rocprofv3 --kernel-trace --stats -d $O/prof_r03 -o sw -- python3 bench.py --steps 8 --warmup 1 --no-cpu-baseline > $O/r03_bench_under_rocprof.json 2> $O/r03_rocprof.err
 python tests/prof_summary.py $O/prof_r03/sw_results.db 9 $O/r03_bench_kernel_stats.csv > $O/r03_bench_prof_summary.txt
@@ -22,5 +22,5 @@ python bench.py --workload train --precision bf16 --steps 5 --warmup 2 > $O/r03_
 python bench.py --workload hires --precision fp16 --batch 4 --steps 5 --warmup 2 > $O/r03_bench_hires_fp16.json 2> $O/r03_bench_hires.err
 python bench.py --workload hires --batch 4 --steps 5 --warmup 2 > $O/r03_bench_hires_bf16x3.json 2>> $O/r03_bench_hires.err
 python bench.py --workload grid --steps 3 --warmup 1 > $O/r03_bench_grid.json 2> $O/r03_bench_grid.err
-python bench.py --precision fp16 --steps 10 --warmup 2 --no-cpu-baseline > $O/r03_bench_fp16.json 2> /dev/null
+python bench.py --full --precision fp16 --steps 10 --warmup 2 --no-cpu-baseline > $O/r03_bench_fp16.json 2> /dev/null
 echo ALL DONE

@@ -8,7 +8,7 @@ name = sys.argv[1] if len(sys.argv) > 1 else "UP9"
 steps = sys.argv[2] if len(sys.argv) > 2 else "10"
 for on in (False, True, False, True):
     getattr(ops, name)["value"] = on
-    sys.argv = ["bench.py", "--no-cpu-baseline", "--no-extras", "--steps", steps, "--warmup", "2"]
+    sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--no-extras", "--steps", steps, "--warmup", "2"]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main()
