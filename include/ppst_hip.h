@@ -542,6 +542,19 @@ int ppst_resample_u8(const void* x, void* y, int B, int in_h, int in_w, int C, i
  * [B][H][W][C] -> fp32 NCHW, (v/255 - mean)/std in that operation order. */
 int ppst_u8_to_tensor(const void* x, void* y, int B, int H, int W, int C, float mean, float stdv, void* stream);
 
+/* PNG encode on the device (ppst_amd/csrc/png.hip): uint8 HWC [B][H][W][C], C = 1 (grey) or 3 (RGB), 8 bits per sample, ->
+ * B complete PNG files.  Per row the filter with the smallest sum of absolute signed bytes (libpng's heuristic, ties to the
+ * lowest filter number); the filtered stream is cut into 32 KB pieces, each one dynamic-Huffman deflate block of literals
+ * (or a stored block when that is not smaller) in an IDAT chunk of its own; deterministic, independent of the batch.
+ *   ppst_png_bound   bytes one file can take (stored-block worst case included; a multiple of 16); PPST_EINVAL for bad sizes
+ *   ppst_png_ws      bytes of the caller-owned workspace (> 0, also for B = 0)
+ *   ppst_png_encode  files: [B][ppst_png_bound(H, W, C)] bytes, file i starts at i * bound; sizes: int64 [B], the file lengths.
+ *                    Bytes of a slot behind its file's length are not written.  img_u8, files, work: 16-byte aligned.
+ * H, W >= 1; C other than 1 / 3, or H * (1 + W * C) >= 2^31 - 64: PPST_EINVAL. */
+int64_t ppst_png_bound(int H, int W, int C);
+int64_t ppst_png_ws(int B, int H, int W, int C);
+int ppst_png_encode(const void* img_u8, void* files, void* sizes, int B, int H, int W, int C, void* work, void* stream);
+
 /* ------------------------------------------------------- post-process ---- */
 /* util.tensor2im quantisation (util/util.py:98-131): NCHW fp32 [-1,1] ->
  * HWC uint8, ((x+1)/2*255) clipped and truncated. */

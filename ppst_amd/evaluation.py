@@ -13,7 +13,8 @@
 The recipes take and return tensors.  The folder-level front ends at the end of this file (``evaluate_swap_files``,
 ``evaluate_grid_folder``) add what the reference's evaluators do around them: decode (PIL, a thread pool), resize + normalise
 on the device (ppst_amd/imageio.py, Pillow-exact), the uint8 quantisation on the device (glue.tensor2im), PNG encode in the
-thread pool (zlib releases the GIL: the encode of one batch overlaps the next batch's kernels), the reference's file names.
+thread pool (zlib releases the GIL: the encode of one batch overlaps the next batch's kernels) or -- ``png="device"`` -- on
+the GPU (imageio.encode_png: the threads only write bytes), the reference's file names.
 """
 import torch
 
@@ -190,22 +191,51 @@ def _save_png(args):
     return path
 
 
-def save_images(images, paths, pool=None):
-    """images: (B,3,H,W) in [-1,1] on the device -> PNG files.  util.tensor2im quantisation (util/util.py:98-131) on the
-    device, one device-to-host copy of the uint8 batch, encode on the pool's threads (returns the futures when a pool is
-    given: the caller overlaps them with the next batch and joins at the end)."""
-    u8 = glue.tensor2im(images).cpu().numpy()
-    jobs = [(u8[i], p) for i, p in enumerate(paths)]
+def _write_file(args):
+    blob, path = args
+    with open(path, "wb") as f:
+        f.write(blob)
+    return path
+
+
+PNG_ENCODERS = ("host", "device")
+
+
+def _check_encoder(encoder):
+    if encoder not in PNG_ENCODERS:
+        raise ValueError("PNG encoder must be one of %s, not %r" % (PNG_ENCODERS, encoder))
+
+
+def write_png_batch(u8, paths, pool=None, encoder="host"):
+    """u8: (B,H,W,C) uint8 on the device -> one PNG file per image, the half of the file output both front ends share.
+    ``host``: one device-to-host copy of the batch, ``Image.fromarray(arr).save(path)`` per image; ``device``: the files are
+    encoded on the GPU (imageio.encode_png) and only their bytes are copied and written.  The per-image jobs run on ``pool``'s
+    threads when one is given (the futures are returned: the caller overlaps them with the next batch and joins at the end)."""
+    _check_encoder(encoder)
+    if encoder == "device":
+        from . import imageio
+        job, jobs = _write_file, list(zip(imageio.encode_png(u8), paths))
+    else:
+        arr = u8.cpu().numpy()
+        job, jobs = _save_png, [(arr[i], p) for i, p in enumerate(paths)]
     if pool is None:
-        return [_save_png(j) for j in jobs]
-    return [pool.submit(_save_png, j) for j in jobs]
+        return [job(j) for j in jobs]
+    return [pool.submit(job, j) for j in jobs]
 
 
-def evaluate_swap_files(model, structure_path, texture_path, out_dir, alphas=(1.0,), load_size=512, device="cuda"):
+def save_images(images, paths, pool=None, encoder="host"):
+    """images: (B,3,H,W) in [-1,1] on the device -> PNG files.  util.tensor2im quantisation (util/util.py:98-131) on the
+    device, then write_png_batch (``encoder``: "host" = Pillow on the pool's threads, "device" = the HIP encoder)."""
+    _check_encoder(encoder)
+    return write_png_batch(glue.tensor2im(images), paths, pool, encoder)
+
+
+def evaluate_swap_files(model, structure_path, texture_path, out_dir, alphas=(1.0,), load_size=512, device="cuda", png="host"):
     """evaluation/simple_swapping_evaluator.py:38-76: one structure image, one texture image, one output per mix alpha named
-    <structure>_<texture>_<alpha %.2f>.png (ToPILImage quantisation of the clamped image, :61-62).  Returns the paths."""
+    <structure>_<texture>_<alpha %.2f>.png (ToPILImage quantisation of the clamped image, :61-62).  ``png``: where the files are
+    encoded (write_png_batch).  Returns the paths."""
     import os
-    from PIL import Image
+    _check_encoder(png)
     os.makedirs(out_dir, exist_ok=True)
     c, s_ = load_images([os.path.expanduser(structure_path), os.path.expanduser(texture_path)], load_size, device)
     outs = simple_swap(model, c, s_, alphas)
@@ -213,19 +243,20 @@ def evaluate_swap_files(model, structure_path, texture_path, out_dir, alphas=(1.
     paths = []
     for alpha in alphas:
         path = os.path.join(out_dir, "%s_%s_%.2f.png" % (stem(structure_path), stem(texture_path), alpha))
-        Image.fromarray(to_uint8_image(outs[alpha])[0].cpu().numpy()).save(path)
-        paths.append(path)
+        paths += write_png_batch(to_uint8_image(outs[alpha])[:1], [path], None, png)
     return paths
 
 
 def evaluate_grid_folder(model, dataroot, out_dir, rank=0, world=1, smooth=True, load_size=512, device="cuda", workers=8,
-                         pair_batch=8, image_batch=8):
+                         pair_batch=8, image_batch=8, png="host"):
     """evaluation/content_style_grid_generation_evaluator.py:36-99 over <dataroot>/content/* and <dataroot>/style/*: every
     (content, style) pair, guided-filter post-process with the content as guide; files land in <out_dir>/images/ under the
     reference's names (<content>_<style>.png, the inputs as <name>.png; util/html.py:51-75 -- the HTML index itself is not
     written).  All images must come out of the preprocessing at one size (the reference batches them the same way).
-    Multi-GPU: every rank reads all inputs (they are small), computes its share (swapping_grid) and writes its own files."""
+    Multi-GPU: every rank reads all inputs (they are small), computes its share (swapping_grid) and writes its own files.
+    ``png``: "host" = Pillow on the worker threads, "device" = the HIP encoder (the threads only write the bytes)."""
     import os
+    _check_encoder(png)
     from concurrent.futures import ThreadPoolExecutor
     cdir, sdir = os.path.join(dataroot, "content"), os.path.join(dataroot, "style")
     ls = lambda d: sorted(os.path.join(d, f) for f in os.listdir(d) if f.lower().endswith(_IMG_EXT))
@@ -242,12 +273,12 @@ def evaluate_grid_folder(model, dataroot, out_dir, rank=0, world=1, smooth=True,
         contents, styles = torch.cat(imgs[:len(cpaths)], 0), torch.cat(imgs[len(cpaths):], 0)
         futures = []
         if rank == 0:   # the top row / first column of the reference's page: the inputs themselves
-            futures += save_images(torch.cat((contents, styles), 0), [os.path.join(img_dir, stem(p) + ".png") for p in cpaths + spaths], pool)
+            futures += save_images(torch.cat((contents, styles), 0), [os.path.join(img_dir, stem(p) + ".png") for p in cpaths + spaths], pool, png)
         out = swapping_grid(model, contents, styles, rank, world, smooth, pair_batch, image_batch)
         keys = sorted(out)
         for k in range(0, len(keys), pair_batch):
             chunk = keys[k:k + pair_batch]
             names = [os.path.join(img_dir, "%s_%s.png" % (stem(cpaths[i]), stem(spaths[j]))) for i, j in chunk]
-            futures += save_images(torch.stack([out[ij] for ij in chunk], 0), names, pool)
+            futures += save_images(torch.stack([out[ij] for ij in chunk], 0), names, pool, png)
         written = [f.result() for f in futures]
     return written

@@ -9,6 +9,9 @@ Host logic here = sizes (Python ``round``: half to even, like the reference) and
 coefficient tables (Resample.c ``precompute_coeffs`` + ``normalize_coeffs_8bpc``: double-precision
 bicubic weights, normalised, 22-bit fixed point); the pixel arithmetic is integer HIP kernels
 (csrc/imageio.hip), bit-identical to Pillow.
+
+The other end of the pipeline is here too: ``encode_png`` turns a uint8 batch on the device into PNG files (csrc/png.hip:
+row filters, deflate and checksums as HIP kernels) and brings only the file bytes to the host.
 """
 import math
 
@@ -123,3 +126,14 @@ def preprocess_resize(img, load_size=512):
     if (w2, h2) != (load_size, load_size):
         x = resize_bicubic_u8(x, h2, w2)
     return to_tensor_normalized(x)
+
+
+def encode_png(u8):
+    """(B,H,W,C) uint8 on the device (C = 1: grey, 3: RGB) -> list of B ``bytes``, each a complete PNG file.
+    Two device-to-host copies per batch: the B sizes, then the batch's file slots cut at the longest file."""
+    files, sizes = ops.png_encode(u8)
+    if files.shape[0] == 0:
+        return []
+    n = sizes.cpu().tolist()
+    host = files[:, :max(n)].cpu().numpy()
+    return [host[i, :n[i]].tobytes() for i in range(len(n))]

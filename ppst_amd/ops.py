@@ -1987,6 +1987,23 @@ def guided_filter(guide_u8, src_u8, r=30, eps=(0.02 * 255) ** 2, want_u8=False):
     return (out, out_u8) if want_u8 else out
 
 
+def png_encode(u8):
+    """(B,H,W,C) uint8 on the device, C = 1 or 3 -> (files (B, bound) uint8, sizes (B,) int64), both on the device: file i is
+    files[i, :sizes[i]] (csrc/png.hip).  The workspace comes from torch's allocator; nothing synchronises the host."""
+    if not isinstance(u8, torch.Tensor) or not u8.is_cuda or u8.dtype != torch.uint8 or u8.dim() != 4:
+        raise RuntimeError("png_encode needs a CUDA uint8 (B,H,W,C) tensor (no CPU fallback)")
+    u8 = u8.contiguous()
+    B, H, W, C = u8.shape
+    bound = lib.ppst_png_bound(H, W, C)
+    if bound < 0:
+        raise RuntimeError("png_encode: unsupported image shape %s (C must be 1 or 3)" % (tuple(u8.shape),))
+    files = torch.empty((B, bound), device=u8.device, dtype=torch.uint8)
+    sizes = torch.empty((B,), device=u8.device, dtype=torch.int64)
+    work = torch.empty(lib.ppst_png_ws(B, H, W, C), device=u8.device, dtype=torch.uint8)
+    check(lib.ppst_png_encode(_p(u8), _p(files), _p(sizes), B, H, W, C, _p(work), _stream()), "ppst_png_encode")
+    return files, sizes
+
+
 # --------------------------------------------------------------- profiling ----
 PROF_ON = {"value": False}
 
