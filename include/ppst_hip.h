@@ -555,6 +555,46 @@ int64_t ppst_png_bound(int H, int W, int C);
 int64_t ppst_png_ws(int B, int H, int W, int C);
 int ppst_png_encode(const void* img_u8, void* files, void* sizes, int B, int H, int W, int C, void* work, void* stream);
 
+/* ------------------------------------------------ LPIPS-AlexNet metric ---- */
+/* LPIPS v0.1, net = 'alex', lpips = True, spatial = False, normalize = False, eval mode (csrc/lpips.hip): for two fp32 image
+ * batches a, b (B, 3, H, W)
+ *   x' = (x - shift) / scale per channel;  relu1..relu5 of torchvision's AlexNet `features` (conv 11x11 s4 p2 -> 64, pool 3 s2,
+ *   conv 5x5 p2 -> 192, pool 3 s2, conv 3x3 p1 -> 384 -> 256 -> 256; floor sizes, zero padding, bias);
+ *   per layer n(f) = f / (sqrt(sum_c f^2) + 1e-10), s_l = mean_hw sum_c lin_l[c] (n(fa) - n(fb))^2;  result sum_l s_l per image.
+ * The weights are frozen: there is a forward and an INPUT gradient, no weight gradient.  fp32 storage and arithmetic.  Where
+ * sqrt(sum_c f^2) is exactly 0 the gradient to that pixel's features is defined as 0 (autograd of the formula gives NaN).
+ * Pool ties go to the first maximum in row-major window order.  Every reduction has a fixed order: repeated calls are
+ * bit-identical.  The caller owns every buffer; all of them 16-byte aligned.
+ *   ppst_lpips_pack_floats  floats of the packed weights
+ *   ppst_lpips_pack     once per weight set: weight / bias / lin are host arrays of five device pointers -- the conv weights in
+ *                       torch layout [Cout][Cin][K][K] (64x3x11x11, 192x64x5x5, 384x192x3x3, 256x384x3x3, 256x256x3x3), their
+ *                       biases, and the lin weights [C_l]; shift, scale: 3 floats each.  Forward and (flipped, transposed)
+ *                       gradient forms are both written to `pack`.
+ *   ppst_lpips_dims     hw[10] = (h, w) of the five feature maps of an H x W image
+ *   ppst_lpips_ws       bytes of the forward workspace for n images through the trunk (n = 2B for the metric)
+ *   ppst_lpips_trunk    the na images of a, then the nb images of b (either count may be 0), as ONE batch through the trunk;
+ *                       *_strides: 4 element strides (n, c, y, x) of the source tensors (any layout).  Leaves the five maps,
+ *                       the pooled maps and the pools' arg-max bytes in ws.
+ *   ppst_lpips_feature  copies map `layer` (0..4) of a workspace filled by ppst_lpips_trunk(n images) to contiguous NCHW
+ *   ppst_lpips_tail     after ppst_lpips_trunk(na = nb = B): out[B] = the metric.  ws is written (block partial sums).
+ *   ppst_lpips_bwd_ws   bytes of the backward scratch; which: 1 = gradient to a, 2 = to b, 3 = both
+ *   ppst_lpips_backward ga / gb (B, 3, H, W) contiguous = d(sum_b gout[b] * out[b]) / d a, b, from the workspace the forward
+ *                       left (read only).  Only the requested half of the trunk is walked back.
+ * H, W < 31 (the second pool would have no full window) or > 16384, a negative count, which outside 1..3: PPST_EINVAL; a
+ * count of 0 is a no-op; null pointers PPST_ENULL. */
+int64_t ppst_lpips_pack_floats(void);
+int ppst_lpips_pack(const void* const* weight, const void* const* bias, const void* const* lin, const void* shift, const void* scale,
+                    void* pack, void* stream);
+int ppst_lpips_dims(int H, int W, int* hw);
+int64_t ppst_lpips_ws(int n, int H, int W);
+int ppst_lpips_trunk(const void* pack, const void* a, const int64_t* a_strides, int na, const void* b, const int64_t* b_strides, int nb,
+                     int H, int W, void* ws, void* stream);
+int ppst_lpips_feature(const void* ws, int n, int H, int W, int layer, void* out_nchw, void* stream);
+int ppst_lpips_tail(const void* pack, void* ws, int B, int H, int W, void* out, void* stream);
+int64_t ppst_lpips_bwd_ws(int B, int H, int W, int which);
+int ppst_lpips_backward(const void* pack, const void* ws, const void* gout, int B, int H, int W, int which, void* ga, void* gb,
+                        void* bws, void* stream);
+
 /* ------------------------------------------------------- post-process ---- */
 /* util.tensor2im quantisation (util/util.py:98-131): NCHW fp32 [-1,1] ->
  * HWC uint8, ((x+1)/2*255) clipped and truncated. */

@@ -126,6 +126,15 @@ _SIGS = {
     "ppst_png_bound": (i64, [i32, i32, i32]),
     "ppst_png_ws": (i64, [i32, i32, i32, i32]),
     "ppst_png_encode": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "ppst_lpips_pack_floats": (i64, []),
+    "ppst_lpips_pack": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+    "ppst_lpips_dims": (i32, [i32, i32, ctypes.POINTER(i32)]),
+    "ppst_lpips_ws": (i64, [i32, i32, i32]),
+    "ppst_lpips_trunk": (i32, [vp, vp, ctypes.POINTER(i64), i32, vp, ctypes.POINTER(i64), i32, i32, i32, vp, vp]),
+    "ppst_lpips_feature": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    "ppst_lpips_tail": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "ppst_lpips_bwd_ws": (i64, [i32, i32, i32, i32]),
+    "ppst_lpips_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "ppst_guided_filter_ws": (i64, [i32, i32, i32]),
     "ppst_guided_filter": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),
     "ppst_smooth_local_affine_ws": (i64, [i32, i32, i32]),

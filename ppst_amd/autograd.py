@@ -677,6 +677,24 @@ class L1LossFn(Function):
         return ops.scale_by(da, g), None, None
 
 
+class LpipsFn(Function):
+    """LPIPS-AlexNet of two (B,3,H,W) fp32 batches -> (B,1,1,1) (csrc/lpips.hip); ``pack`` = ops.lpips_pack(...) (frozen weights:
+    no gradient).  Only the inputs that ask get a gradient, and only their half of the trunk is walked back.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, a, b, pack):
+        out, ws = ops.lpips_forward(pack, a, b)
+        ctx.pack, ctx.ws, ctx.shape = pack, ws, tuple(a.shape)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        B, _, H, W = ctx.shape
+        ga, gb = ops.lpips_backward(ctx.pack, ctx.ws, _c(g), B, H, W, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return ga, gb, None
+
+
 class LsganFn(Function):
     """weight * mean((pred - target)^2) (models/networks/loss.py:11-18)."""
 

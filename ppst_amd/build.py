@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libppst_hip.so")
 # two-pass fp16 mode, the 8-row two-block tile): tuning builds only -- the production library carries what runs.
 EXPERIMENTS = os.environ.get("PPST_EXPERIMENTS") == "1"
 SOURCES = ["upfirdn2d.hip", "fused_bias_act.hip", "elementwise.hip", "linear.hip", "conv_mfma.hip", "conv_mfma2.hip", "conv1x1.hip", "conv_wino.hip", "conv_f32.hip",
-           "corr.hip", "guided_filter.hip", "train.hip", "train_g.hip", "imageio.hip", "smooth_filter.hip", "png.hip"] + (["conv_ksplit.hip"] if EXPERIMENTS else [])
+           "corr.hip", "guided_filter.hip", "train.hip", "train_g.hip", "imageio.hip", "smooth_filter.hip", "png.hip", "lpips.hip"] + (["conv_ksplit.hip"] if EXPERIMENTS else [])
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result"] + (["-DPPST_EXPERIMENTS"] if EXPERIMENTS else [])
 # per-file flags.  conv_wino.hip: its staging arithmetic runs inside the MFMA stream and the kernel sits at 256 registers -- with SLP
 # vectorisation hipcc packs it into v_pk_* (operand pairs assembled with moves, 1 100 packed instructions, spills in the

@@ -2004,6 +2004,89 @@ def png_encode(u8):
     return files, sizes
 
 
+# ------------------------------------------------------- LPIPS-AlexNet metric ----
+LPIPS_CHANNELS = (64, 192, 384, 256, 256)
+
+
+def lpips_pack(weights, biases, lins, shift, scale):
+    """Five conv weights (torch layout), biases and lin vectors + the scaling layer's shift / scale, all fp32 on the device ->
+    the packed forward + input-gradient weights of csrc/lpips.hip (once per weight set: they are frozen)."""
+    ts = list(weights) + list(biases) + list(lins) + [shift, scale]
+    for t in ts:
+        _chk(t, "lpips weight")
+        if not t.is_contiguous():
+            raise RuntimeError("lpips_pack needs contiguous tensors")
+    arr = lambda seq: (ctypes.c_void_p * 5)(*[t.data_ptr() for t in seq])
+    pack = torch.empty(lib.ppst_lpips_pack_floats(), device=shift.device, dtype=torch.float32)
+    check(lib.ppst_lpips_pack(arr(weights), arr(biases), arr(lins), _p(shift), _p(scale), _p(pack), _stream()), "ppst_lpips_pack")
+    return pack
+
+
+def lpips_dims(H, W):
+    """[(h, w)] of relu1..relu5 for an H x W image; raises below 31 pixels a side."""
+    hw = (ctypes.c_int * 10)()
+    check(lib.ppst_lpips_dims(H, W, hw), "ppst_lpips_dims (images of at least 31 x 31)")
+    return [(hw[2 * l], hw[2 * l + 1]) for l in range(5)]
+
+
+def _lpips_img(t, name):
+    _chk(t, name)
+    if t.dim() != 4 or t.shape[1] != 3:
+        raise RuntimeError("%s must be (B, 3, H, W), got %s" % (name, tuple(t.shape)))
+    return (ctypes.c_int64 * 4)(*t.stride())
+
+
+def lpips_trunk(pack, a, b=None):
+    """a (and b) (B,3,H,W) fp32, any strides, as one batch through scaling layer + AlexNet trunk -> the workspace holding the five
+    post-ReLU maps (channels-last), the pooled maps and the pools' arg-max."""
+    sa = _lpips_img(a, "lpips input")
+    na, _, H, W = a.shape
+    nb, sb = 0, None
+    if b is not None:
+        sb = _lpips_img(b, "lpips input")
+        if b.shape != a.shape:
+            raise RuntimeError("lpips inputs differ in shape: %s and %s" % (tuple(a.shape), tuple(b.shape)))
+        nb = na
+    nbytes = lib.ppst_lpips_ws(na + nb, H, W)
+    if nbytes < 0:
+        raise RuntimeError("lpips: unsupported image size %d x %d (at least 31 x 31)" % (H, W))
+    ws = torch.empty(nbytes, device=a.device, dtype=torch.uint8)
+    check(lib.ppst_lpips_trunk(_p(pack), _p(a), sa, na, _p(b), sb, nb, H, W, _p(ws), _stream()), "ppst_lpips_trunk")
+    return ws
+
+
+def lpips_feature(ws, n, H, W, layer):
+    h, w = lpips_dims(H, W)[layer]
+    out = torch.empty((n, LPIPS_CHANNELS[layer], h, w), device=ws.device, dtype=torch.float32)
+    check(lib.ppst_lpips_feature(_p(ws), n, H, W, layer, _p(out), _stream()), "ppst_lpips_feature")
+    return out
+
+
+def lpips_forward(pack, a, b):
+    """-> (out (B,1,1,1), workspace for lpips_backward)"""
+    ws = lpips_trunk(pack, a, b)
+    B, _, H, W = a.shape
+    out = torch.empty((B, 1, 1, 1), device=a.device, dtype=torch.float32)
+    check(lib.ppst_lpips_tail(_p(pack), _p(ws), B, H, W, _p(out), _stream()), "ppst_lpips_tail")
+    return out, ws
+
+
+def lpips_backward(pack, ws, gout, B, H, W, need_a, need_b):
+    """input gradients (ga, gb) (None where not asked for) of sum_b gout[b] * out[b]"""
+    _chk(gout, "lpips grad_output")
+    which = (1 if need_a else 0) | (2 if need_b else 0)
+    if which == 0:
+        return None, None
+    gout = gout.reshape(-1).contiguous()
+    if gout.numel() != B:
+        raise RuntimeError("lpips grad_output must have %d elements" % B)
+    ga = torch.empty((B, 3, H, W), device=ws.device, dtype=torch.float32) if need_a else None
+    gb = torch.empty((B, 3, H, W), device=ws.device, dtype=torch.float32) if need_b else None
+    bws = torch.empty(lib.ppst_lpips_bwd_ws(B, H, W, which), device=ws.device, dtype=torch.uint8)
+    check(lib.ppst_lpips_backward(_p(pack), _p(ws), _p(gout), B, H, W, which, _p(ga), _p(gb), _p(bws), _stream()), "ppst_lpips_backward")
+    return ga, gb
+
+
 # --------------------------------------------------------------- profiling ----
 PROF_ON = {"value": False}
 

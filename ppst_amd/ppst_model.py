@@ -157,7 +157,9 @@ class PPSTModel(nn.Module):
         os.symlink(checkpoint_name, sympath)
         return os.path.join(savedir, checkpoint_name)
 
-    def load(self, checkpoint_path=None, force=None, verbose=True):
+    def load(self, checkpoint_path=None, force=None, verbose=True, perceptual=False):
+        """``perceptual=True``: also build the Cycwarp term's LPIPS metric from the ``loss_fn_alex.`` keys of the same file
+        (the reference stores them in every checkpoint it writes); an error if the file has none."""
         import os
         opt = self.opt
         if checkpoint_path is None:
@@ -194,6 +196,8 @@ class PPSTModel(nn.Module):
                     continue
                 own.copy_(param)
         self._weights_changed()  # packed weights / style tables / host scalars are stale
+        if perceptual:
+            self.set_perceptual_metric("lpips", state_dict=sd, prefix="loss_fn_alex.")
         if verbose:
             print("checkpoint loaded from %s" % checkpoint_path)
         return True
@@ -201,7 +205,18 @@ class PPSTModel(nn.Module):
     def per_gpu_initialize(self):
         pass
 
-    def set_perceptual_metric(self, fn):
+    def set_perceptual_metric(self, fn, state_dict=None, prefix=""):
+        """``fn``: any differentiable callable (image_rec, real) -> tensor, or the string "lpips": the reference's metric
+        (ppst_amd/lpips.py) built from ``state_dict`` -- the keys of the lpips package under ``prefix`` ("loss_fn_alex." in a
+        checkpoint the reference wrote).  Opt-in, and outside the module registry either way: ``state_dict()`` and ``save()``
+        never see it."""
+        if isinstance(fn, str):
+            if fn != "lpips":
+                raise ValueError("unknown perceptual metric %r (\"lpips\" or a callable)" % fn)
+            if state_dict is None:
+                raise ValueError("set_perceptual_metric(\"lpips\") needs the state_dict that holds the metric's weights")
+            from .lpips import LPIPSAlex
+            fn = LPIPSAlex.from_state_dict(state_dict, prefix=prefix)
         self.__dict__["perceptual_metric"] = fn
         return self
 

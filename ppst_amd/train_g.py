@@ -459,8 +459,10 @@ class GeneratorTrainer:
             if lam("lambda_Cycwarp", 0.0) > 0.0:
                 # ppst_model.py:175-179: warp the image to the partner and back, compare with a perceptual metric.  The
                 # reference's metric is lpips.LPIPS(net='alex') (:61); its weights ship with neither the reference nor this
-                # image, so the metric is INJECTED: model.perceptual_metric(image_rec, real) -> tensor, any differentiable
-                # callable (parity of the LPIPS term itself is unpinned; the double warp and its backward are tested)
+                # project, so the metric is INJECTED: model.perceptual_metric(image_rec, real) -> tensor, any differentiable
+                # callable -- or model.set_perceptual_metric("lpips", state_dict=...): ppst_amd/lpips.py on the HIP path, weights from
+                # a checkpoint's loss_fn_alex.* keys (parity with the PUBLISHED weights is unpinned; the arithmetic, the double
+                # warp and its backward are tested)
                 metric = getattr(m, "perceptual_metric", None)
                 if metric is None:
                     raise RuntimeError("lambda_Cycwarp > 0 needs model.perceptual_metric (the reference uses lpips.LPIPS(net='alex'), "
@@ -528,6 +530,8 @@ class GeneratorTrainer:
             losses, metrics = self.compute_generator_losses(real, mask)
             total = None
             for v in losses.values():
+                if v.numel() > 1:          # a per-image term (the LPIPS metric returns (B,1,1,1)): ppst_optimizer.py:86 takes v.mean()
+                    v = v.mean().reshape(1)
                 total = v if total is None else total + v
             total.backward()
         out = {k: v.detach() for k, v in losses.items()}
