@@ -1977,6 +1977,9 @@ def guided_filter(guide_u8, src_u8, r=30, eps=(0.02 * 255) ** 2, want_u8=False):
     for t in (guide_u8, src_u8):
         if not t.is_cuda or t.dtype != torch.uint8:
             raise RuntimeError("guided_filter needs CUDA uint8 tensors")
+    if guide_u8.dim() != 4 or guide_u8.shape[3] != 3 or src_u8.shape != guide_u8.shape:      # (the kernels index both by the guide's extents)
+        raise RuntimeError("guided_filter needs guide and source of one shape (B,H,W,3), got %s and %s"
+                           % (tuple(guide_u8.shape), tuple(src_u8.shape)))
     guide_u8, src_u8 = guide_u8.contiguous(), src_u8.contiguous()
     B, H, W, _ = guide_u8.shape
     ws = torch.empty(lib.ppst_guided_filter_ws(B, H, W), device=guide_u8.device, dtype=torch.uint8)

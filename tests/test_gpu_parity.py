@@ -9,7 +9,9 @@ Tolerances (rel = max|a-b| / max|b|):
   fused conv, bf16x3 (fp32-class) ....... <= 3e-5 per layer
   assembled networks / full swap recipe . <= 1e-3 (BASELINE.json north_star tolerance)
   correspondence ........................ row arg-max agreement > 99.5 %
-  guided filter ......................... <= 1 uint8 LSB (parity unpinned vs OpenCV)
+  guided filter ......................... <= 1 uint8 LSB (parity unpinned vs OpenCV); the boundary-aware
+                                          bar against float64, every radius, the edge extents and the tuned instances:
+                                          tests/test_gpu_guided_filter.py
 """
 import os
 import sys
