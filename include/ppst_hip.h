@@ -178,7 +178,7 @@ typedef struct ppst_pack_job {
   int64_t total;              /* n_groups * ceil(cout / bn) * nsteps * 4 * bn */
   int64_t block0;
   float scale;
-  int32_t cout, bn, nsteps, n_groups, x3, f16, nblocks;   /* x3: precision 0 (hi + lo planes); f16: precision 3 / 4 */
+  int32_t cout, bn, nsteps, n_groups, x3, f16, nblocks;   /* x3: precision 0 (hi + lo planes); f16: precision 3 */
   int32_t dual;               /* 1: ppst_conv_pack_dual semantics (the N tile holds two output column phases) */
                               /* (x3 = 2 with f16 = 0 / 1: ppst_conv_pack_k64 semantics -- the lo planes hold channels 32-63 of a 64-channel step) */
 } ppst_pack_job;
@@ -232,8 +232,8 @@ typedef struct ppst_conv_args {
   int32_t in_off_y, in_off_x;    /* input pixel = tile pixel + tap + in_off (e.g. -pad) */
   int32_t out_sy, out_sx;        /* output pixel stride (2 for the transposed conv) ... */
   int32_t act;                   /* PPST_ACT_* | 0x100: residual joins AFTER the activation */
-  int32_t precision;             /* 0 bf16x3 (fp32-class), 1 bf16 single pass, 3 fp16 single pass, 4 fp16 two-pass
-                                    (activation hi + lo, weight fp16); ppst_conv_pack with the same value */
+  int32_t precision;             /* 0 bf16x3 (fp32-class), 1 bf16 single pass, 3 fp16 single pass; ppst_conv_pack with the
+                                    same value */
   int32_t res_ld;
   int32_t tile_h, tile_w;        /* logical (pre-scatter) output extent tiled by 16x16 */
   int32_t halo;                  /* 0: every tap is (0,0) (1x1 conv); 1: taps in [-1,1]^2 */
@@ -258,28 +258,20 @@ typedef struct ppst_conv_args {
                                     channel offset: the kernel then requests a chunk's activations one step earlier
                                     (HBM latency no longer stalls the staging store).  0: bits 1.. are ignored. */
   int32_t variant;               /* 0: the 8-wave kernel (512 threads, wave tile 64 px x 64 ch; bn 64 / 128).
-                                    1: the fat-wave kernel (conv_mfma2.hip: 256 threads = one wave per SIMD, wave tile
-                                    128 px x 64 / 128 ch; bn 128 / 256; precision 0 only).  Its activation ring has two
-                                    slots: every chunk of the step table must span >= 2 steps (the early_a promise).
-                                    2: 8 waves x (128 px x 64 ch), bn = 256 (the production kernel for Cout % 256 == 0);
-                                    3: two 4-wave blocks per CU, bn = 128, one activation slot (experiment) -- both with
-                                    the early_a promise, precision 0.
+                                    1, 3, 8: retired numbers (forms that were measured, lost and removed: DESIGN.md section 4);
+                                    not reused, PPST_EINVAL.
+                                    2: conv_mfma2.hip -- 8 waves x (128 px x 64 ch), bn = 256 (the production kernel for
+                                    Cout % 256 == 0); its activation ring has two slots: every chunk of the step table must
+                                    span >= 2 steps (the early_a promise).
                                     4 / 5 / 6 (conv1x1.hip, precision 0, one group, unit output stride, no in_off):
                                     4: all taps (0,0) (halo 0), bn = 64, in and out extents equal;
                                     5: any taps in [-1,1]^2, bn = 64;
                                     6: plain 3x3 stride-1 tables only -- nsteps = 9 * chunks and step 9c + 3(dy+1) + (dx+1)
                                        is tap (dy, dx) of chunk c; bn = 64, or 128 for Cout in 65..128.  The table lives on
                                        the device and is not re-read: the CALLER owns this promise (as with a_slots).
-                                    7: conv_mfma2.hip with 8 waves as 4 (M) x 2 (N): block tile 32 x 16 px x 128 ch, one
-                                       activation slot; bn = 128, tile_rows = 32, the early_a promise (precision 0: experiment, measured
-                                       slower; precision 1 / 3: a production form with TWO activation slots -- the Cout = 128-class
-                                       layers of the single-pass modes).
-                                    8: conv_ksplit.hip -- bn = 128, the block's 8 waves as 2 (K) x 2 (M) x 2 (N): wave group k
-                                       takes the steps of parity k (wave tile 128 px x 64 ch), the two partial sums meet in
-                                       LDS before the epilogue.  Needs the early_a promise, precision 0, unit output stride
-                                       and steps[i].w bit 2 = parity of the chunk step i belongs to (the activation slot).
-                                       NOT bit-identical to the others (the K sum is split in two: <= 1.1e-6 relative);
-                                       experiment, measured 3-7 % slower than variant 0.
+                                    7: conv_mfma2.hip with 8 waves as 4 (M) x 2 (N): block tile 32 x 16 px x 128 ch, two
+                                       activation slots; bn = 128, tile_rows = 32, halo 1, the early_a promise, precision 1 / 3 only
+                                       (the Cout = 128-class layers of the single-pass modes; precision 0: PPST_EINVAL).
                                     10: conv_wino.hip -- plain 3x3 stride-1 tables only (the variant-6 promise: nsteps = 9 * chunks,
                                        steps[9c].x = first channel of chunk c), wpack from ppst_conv_pack_wino, bn = 128,
                                        tile_rows = 16, one group, unit strides, precision 0.  Winograd F(2,3) along x: fp32-class
@@ -293,18 +285,14 @@ typedef struct ppst_conv_args {
                                        32-channel chunk the shifts (0,0), (-1,0), (0,-1), (-1,-1).  fp32-class (<= 3e-5 against
                                        float64), NOT bit-identical to the 4x4 forms (other summation order).
                                     9: conv_mfma2.hip with 6 m-tiles per wave: block tile 24 x 16 px x 128 ch (wave tile 96 px x 64 ch),
-                                       TWO activation slots; bn = 128, tile_rows = 24, the early_a promise, precision 0
-                                       (experiment: bit-identical, +-1.5 % of variant 0 -- the 36-step tiles of the Cout = 128
-                                       layers are prologue / epilogue bound, not wave-tile bound).
-                                       With k64 (precision 1 / 3, io_st != 0) a production form: the Cout = 128-class layers of the
-                                       single-pass modes on half-stored activations.
-                                    Variants 0-7 and 9 give bit-identical outputs; the per-tile statistics differ in the last
+                                       TWO activation slots; bn = 128, tile_rows = 24, the early_a promise, with k64 only
+                                       (precision 1 / 3, io_st != 0: the Cout = 128-class layers of the single-pass modes on
+                                       half-stored activations; without k64: PPST_EINVAL).
+                                    Variants 0, 2, 4-7 and 9 give bit-identical outputs; the per-tile statistics differ in the last
                                     bit between variants (other summation tree).  The library returns PPST_EINVAL for a
                                     variant whose shape conditions do not hold. */
-  int32_t in_presplit;           /* experiment (PPST_EXPERIMENTS builds): x is pre-split -- per pixel and 8-channel group 32 bytes
-                                    [hi x 8 | lo x 8] bf16 (ppst_presplit), same pixel stride in_ld -- and the activation tile is
-                                    staged by LDS-DMA.  variant 0, bn 128, halo 1, precision 0, no in_scale_shift, every chunk of
-                                    the step table >= 4 steps (the caller's promise, like early_a). */
+  int32_t reserved0;             /* must be 0 (PPST_EINVAL otherwise): the slot of a removed experiment, kept so that the fields
+                                    behind it stay where they are */
   int32_t dual_b;                /* 1 (variant 2, bn 256, n_groups 2, halo 1, precision 0 / 1 / 3, out_sy = out_sx = 2): the fused 4x4 stride-2
                                     upscale (stylegan2_layers.py:312-321) with Cout % 128 == 0 as TWO row phases whose N tile of 256
                                     is [column phase 0: 128 channels | column phase 1: 128 channels] -- wpack from
@@ -371,11 +359,6 @@ int ppst_conv2d_mfma(const ppst_conv_args* a, void* stream);
 int64_t ppst_conv_pack_wino_bytes(int cout, int cin);
 int ppst_conv_pack_wino(const void* w, int64_t sn, int64_t sc, int64_t sy, int64_t sx, float scale, int cout, int cin,
                         void* out, void* stream);
-/* fp32 NHWC [npix][x_ld] -> the pre-split layout of ppst_conv_args.in_presplit in y [npix][y_ld] (C % 8 == 0) */
-int ppst_presplit(const void* x, void* y, int64_t npix, int C, int x_ld, int y_ld, void* stream);
-/* 1 when the library was built with PPST_EXPERIMENTS=1: the measured-and-off forms (variants 1 / 3 / 7 / 8 / 9, precision 4,
- * in_presplit) are then compiled in; the production build returns PPST_EINVAL for them. */
-int ppst_has_experiments(void);
 /* Exact-fp32 twin of ppst_conv2d_mfma (v_mfma_f32_32x32x2_f32; a->wpack, bn, precision, a_slots, early_a are ignored):
  * same step table / padding / epilogue semantics, weights read from the fp32 tensor itself -- element (n, c, ky, kx) at
  * w[n*sn + c*sc + ky*sy + kx*sx], step s of group g uses w[n][src_c .. src_c+31][src_ky][src_kx] * wscale (src_c < 0:

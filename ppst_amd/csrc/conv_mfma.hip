@@ -25,8 +25,6 @@
 //    ordering so that co-resident blocks of one XCD stream the same weight blobs from its L2.
 #include "common.h"
 
-__device__ __attribute__((aligned(16))) float g_conv_zero[4] = {0.f, 0.f, 0.f, 0.f};
-
 struct ConvKArgs {
   const float* x;
   const unsigned short* wpack;
@@ -78,25 +76,11 @@ extern "C" int ppst_conv_clock_buffer(void* buf, int n) {   // diagnostic build 
 // statistics and StyleMod stay fp32 as in every mode.
 typedef _Float16 __attribute__((ext_vector_type(8))) half8;
 __device__ __forceinline__ unsigned short f2h(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
-// x = hi + lo with hi, lo IEEE half: 22 significant bits while |x| stays inside the half range (activations do)
-__device__ __forceinline__ void split_f16(float x, unsigned short& hi, unsigned short& lo) {
-  const _Float16 h = (_Float16)x;
-  hi = __builtin_bit_cast(unsigned short, h);
-  lo = __builtin_bit_cast(unsigned short, (_Float16)(x - (float)h));
-}
-// X2 (with F16, !X3): two passes -- the activation as fp16 hi + lo (22 significant bits), the weight rounded once to
-// fp16 (11 bits): al*b + ah*b.  A measured experiment: 2/3 of the MFMAs of the fp32-class mode.
-// PRES (experiment, PPST_EXPERIMENTS builds; VERDICT r2 "lever (i)"): the input is PRE-SPLIT -- per pixel and 8-channel group 32
-// bytes [hi x 8 | lo x 8] bf16, same bytes and pixel stride as the fp32 tensor (ppst_presplit) -- and the activation tile is
-// staged by LDS-DMA like the weights: no registers, no conversion, no staging store.  Two activation slots (needs chunks of
-// >= 4 steps), no normalise-on-load.
-template <int WM, int WN, int HALO, bool X3, bool INSS, int NAS = 0, bool F16 = false, bool X2 = false, bool PRES = false,
-          int IOS = PPST_ST_F32>
+template <int WM, int WN, int HALO, bool X3, bool INSS, int NAS = 0, bool F16 = false, int IOS = PPST_ST_F32>
 __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(ConvKArgs a) {
-  constexpr bool ALO = X3 || X2;                         // the activation tile has lo planes
   // IOS: storage type of x, residual and y (common.h).  Half storage exists for the single-pass modes only, in the operand type of
   // the mode: a staged element then reaches LDS as loaded (no conversion) unless normalise-on-load rewrites it.
-  static_assert(IOS == PPST_ST_F32 || (!X3 && !X2 && !PRES && IOS == (F16 ? PPST_ST_F16 : PPST_ST_BF16)), "half storage: single-pass modes");
+  static_assert(IOS == PPST_ST_F32 || (!X3 && IOS == (F16 ? PPST_ST_F16 : PPST_ST_BF16)), "half storage: single-pass modes");
   constexpr int ES = IOS == PPST_ST_F32 ? 4 : 2;         // bytes per stored element
   constexpr int NT = 64 * WM * WN;
   constexpr int TH = 4 * WM, TW = 16;
@@ -104,7 +88,7 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
   // bytes.  (The 256-B rounding is layout hygiene, not a bank requirement: a 16-lane ds_read_b128 / ds_write_b64 group stays inside
   // one plane.  The 8-row two-block form drops it so that two 77-KB blocks fit the CU's 160 KB.)
   constexpr int PLANE = (WM == 2) ? HP * 16 : ((HP * 16 + 255) / 256) * 256;
-  constexpr int NPL = ALO ? 8 : 4;                       // planes per A buffer (hi g0..3, lo g0..3)
+  constexpr int NPL = X3 ? 8 : 4;                       // planes per A buffer (hi g0..3, lo g0..3)
   constexpr int NPLB = X3 ? 8 : 4;                       // planes per weight blob
   constexpr int ABUF = NPL * PLANE;
   constexpr int BN = 64 * WN;
@@ -118,8 +102,7 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
 
   // A ring slots (hazard note at the main loop): 3 in general; NAS = 1 / 2 when the step table has no more chunks
   // than that (smaller LDS footprint, two blocks per CU).
-  constexpr int NA = PRES ? 2 : (NAS ? NAS : 3);
-  static_assert(!PRES || (NT == 512 && HP <= 384 && !INSS && X3), "pre-split staging: the 8-wave tile kernel, 6 pieces per plane");
+  constexpr int NA = NAS ? NAS : 3;
   constexpr int EPI_TILE = 64 * 36;                              // floats per wave: 64 px x (32 ch + 4 pad)
   constexpr int EPI_BYTES = (NT / 64) * EPI_TILE * 4 + WM * BN * 2 * 4;  // transposition tiles + stats scratch
   constexpr int MAIN_BYTES = NA * ABUF + 2 * BBUF;
@@ -175,7 +158,7 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
   constexpr int A_WCH = (HP + 7) / 8;                      // wave-chunks of 8 pixels x 8 float4
   constexpr int A_IT2 = (A_WCH * 64 + NT - 1) / NT;
   float4 ra[A_IT2];
-  constexpr int A_NLOADS = PRES ? 6 : A_IT2 + (INSS ? 2 : 0);   // vector-memory operations of one a_load / a_dma
+  constexpr int A_NLOADS = A_IT2 + (INSS ? 2 : 0);         // vector-memory operations of one a_load
 
   // A staging.  One wave-instruction covers 8 pixels x 128 B (fully coalesced global read);
   // inside it lane l -> plane g = l>>4, pixel (l>>1)&7, half h = l&1, so the 16 lanes of a
@@ -214,38 +197,6 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
   // right behind the weight DMA of the step (one L2 round trip per chunk).  Padding items carry the offset -1 (0xffffffff): out of
   // the descriptor's range, the hardware returns zeros and the staging store needs no select.
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, a.in_h * a.in_w * a.in_ld * ES, 0x00020000);
-  // PRES: piece k (0..5) of this wave is plane (wave + 8k) / 6, pixels 64 j .. 64 j + 63 with j = (wave + 8k) % 6; a piece is one
-  // global_load_lds_dwordx4 (1 KB of one plane); out-of-image pixels of a zero-padded conv read a 16-byte zero word
-  int poff[6];
-  if (PRES) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const int pix = 64 * ((wave + 8 * k) % 6) + lane;
-      int o = -1;
-      if (pix < HP) {
-        int hy = pix / HW, hx = pix - hy * HW;
-        int iy = ty0 + hy - HALO + a.in_off_y, ix = tx0 + hx - HALO + a.in_off_x;
-        bool inb = iy >= 0 && iy < a.in_h && ix >= 0 && ix < a.in_w;
-        if (inb || a.pad_mode != PPST_PAD_ZERO) {
-          iy = pad_index(iy, a.in_h, a.pad_mode);
-          ix = pad_index(ix, a.in_w, a.pad_mode);
-          o = (iy * a.in_w + ix) * a.in_ld * 4;
-        }
-      }
-      poff[k] = o;
-    }
-  }
-  auto a_dma = [&](int chan_off, int slot) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const int i = wave + 8 * k, pl = i / 6, j = i - pl * 6;       // wave-uniform
-      const unsigned char* src = (const unsigned char*)g_conv_zero;
-      if (poff[k] >= 0) src = xb + poff[k] + chan_off * 4 + (pl & 3) * 32 + (pl >> 2) * 16;
-      if (64 * j + lane < HP)
-        __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
-                                         (void __attribute__((address_space(3)))*)(smA + slot * ABUF + pl * PLANE + j * 1024), 16, 0, 0);
-    }
-  };
   auto a_load = [&](int chan_off) {
 #pragma unroll
     for (int it = 0; it < A_IT2; ++it) {
@@ -289,8 +240,7 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
           hv = raw; lv = make_uint2(0u, 0u);       // stored in the operand type already
         } else if (F16) {
           unsigned short h0, h1, h2, h3, l0, l1, l2, l3;
-          if (X2) { split_f16(v.x, h0, l0); split_f16(v.y, h1, l1); split_f16(v.z, h2, l2); split_f16(v.w, h3, l3); }
-          else { h0 = f2h(v.x); h1 = f2h(v.y); h2 = f2h(v.z); h3 = f2h(v.w); l0 = l1 = l2 = l3 = 0; }
+          h0 = f2h(v.x); h1 = f2h(v.y); h2 = f2h(v.z); h3 = f2h(v.w); l0 = l1 = l2 = l3 = 0;
           hv = make_uint2((unsigned)h0 | ((unsigned)h1 << 16), (unsigned)h2 | ((unsigned)h3 << 16));
           lv = make_uint2((unsigned)l0 | ((unsigned)l1 << 16), (unsigned)l2 | ((unsigned)l3 << 16));
         } else {
@@ -298,7 +248,7 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
         }
         int off = (l >> 4) * PLANE + pix * 16 + (l & 1) * 8;
         *(uint2*)(base + off) = hv;
-        if (ALO) *(uint2*)(base + 4 * PLANE + off) = lv;
+        if (X3) *(uint2*)(base + 4 * PLANE + off) = lv;
       }
     }
   };
@@ -367,20 +317,18 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
   int4 d = steps[0];
   int dy0 = d.y, dx0 = d.z, sl0 = 0;
   int dy1 = d.y, dx1 = d.z, sl1 = 0;
-  if (PRES) a_dma(d.x, 0); else a_load(d.x);
+  a_load(d.x);
   b_dma(0, 0);
-  if (!PRES) a_store(0);
+  a_store(0);
   if (nst > 1) {
     d = steps[1];
     dy1 = d.y; dx1 = d.z;
     sl1 = (d.w & 1) ? 1 : 0;
     b_dma(1, 1);
-    if (!PRES) {                    // (pre-split: chunks span >= 4 steps, steps 1 and 2 open none)
-      if (d.w & 1) a_load(d.x);
-      if (d.w & 1) a_store(sl1);
-      // early mode: the chunk opened by step 2 is staged during step 0 and must already be in registers
-      if (a.early_a && (d.w & 2)) a_load(d.w >> 8);
-    }
+    if (d.w & 1) a_load(d.x);
+    if (d.w & 1) a_store(sl1);
+    // early mode: the chunk opened by step 2 is staged during step 0 and must already be in registers
+    if (a.early_a && (d.w & 2)) a_load(d.w >> 8);
   }
   int4 dE = d, dO = d;                       // descriptor of step s+2, alternating register sets
   if (nst > 2) dE = steps[2];
@@ -395,7 +343,7 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
   bf16x8 ah, al;
   ld_b(b0h, b0l, 0);
   ah = *(const bf16x8*)(smA + A_OFF(sl0, dy0, dx0, 0));
-  if (ALO) al = *(const bf16x8*)(smA + A_OFF(sl0, dy0, dx0, 0) + 4 * PLANE);
+  if (X3) al = *(const bf16x8*)(smA + A_OFF(sl0, dy0, dx0, 0) + 4 * PLANE);
   // drain the prologue's LDS reads so both edges into the loop header carry an empty LDS
   // scoreboard (otherwise hipcc makes the first MFMAs of every step wait for the prefetch
   // reads issued just before them)
@@ -424,116 +372,71 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
 #define TR_DECL
 #define TR_FLUSH(s, flag)
 #endif
-// timing ablations (tests/conv_ablate.sh): results are WRONG with any of these defined
-#ifdef PPST_ABL_NOA
-#define ABL_A(c) false
-#else
-#define ABL_A(c) (c)
-#endif
-#ifdef PPST_ABL_NOB
-#define ABL_B(c) false
-#else
-#define ABL_B(c) (c)
-#endif
-#if defined(PPST_ABL_NOLDS) || defined(PPST_ABL_NOLDS_A)
-#define ABL_LA(c) false
-#else
-#define ABL_LA(c) (c)
-#endif
-#if defined(PPST_ABL_NOLDS) || defined(PPST_ABL_NOLDS_B)
-#define ABL_LB(c) false
-#else
-#define ABL_LB(c) (c)
-#endif
-#ifdef PPST_ABL_NOBAR
-#define ABL_BAR(x)
-#else
-#define ABL_BAR(x) x
-#endif
-#define ABL_MFMA_GROUP(bch, bcl, mt)                                                                  \
+#define MFMA_GROUP(bch, bcl, mt)                                                                      \
   _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) {                                                  \
     if (X3) {                                                                                         \
       acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bch[nt], acc[mt][nt], 0, 0, 0);       \
       acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bcl[nt], acc[mt][nt], 0, 0, 0);       \
     }                                                                                                 \
-    if (X2) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, al), __builtin_bit_cast(half8, bch[nt]), acc[mt][nt], 0, 0, 0); \
     if (F16) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, ah), __builtin_bit_cast(half8, bch[nt]), acc[mt][nt], 0, 0, 0); \
     else acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bch[nt], acc[mt][nt], 0, 0, 0);    \
   }
 #define TOP_WORK(bnh, bnl, s, D2)                                                                     \
-  if (ABL_B(has2)) b_dma((s) + 2, (s) & 1);                                                           \
+  if (has2) b_dma((s) + 2, (s) & 1);                                                                  \
   /* the counted vmcnt(A_NLOADS) at the step barrier assumes the weight DMA was ISSUED before the */  \
   /* activation loads (vmcnt retires in issue order): pin that order                              */  \
   __builtin_amdgcn_sched_barrier(0);                                                                  \
   {   /* early mode: the chunk that step s+3 opens (stored during step s+1); else the chunk of step s+2 (stored   */ \
       /* in this step).  ONE a_load call site: two would make hipcc merge their results with copies + vmcnt(0).    */ \
-    const bool ld_ = a.early_a ? ABL_A(has2 && (D2.w & 2)) : newA2;                                    \
+    const bool ld_ = a.early_a ? (has2 && (D2.w & 2)) : newA2;                                        \
     const int ch_ = a.early_a ? (D2.w >> 8) : D2.x;                                                   \
-    if (ld_) { if (PRES) a_dma(ch_, (sl2 == NA - 1) ? 0 : sl2 + 1); else a_load(ch_); a_early = a.early_a != 0; } \
+    if (ld_) { a_load(ch_); a_early = a.early_a != 0; }                                               \
   }                                                                                                   \
-  if (ABL_LB(has1)) ld_b(bnh, bnl, ((s) + 1) & 1);
-#define STEP_HEAD_IF(cond, bnh, bnl, s, D2, D3)                                                       \
-  if (cond) {                                                                                         \
+  if (has1) ld_b(bnh, bnl, ((s) + 1) & 1);
+#define STEP_HEAD(bnh, bnl, s, D2, D3)                                                                \
+  {                                                                                                   \
     D3 = steps[(s) + 3];   /* the host pads the table: always in bounds, ignored past the end */       \
-    newA2 = ABL_A(has2 && (D2.w & 1));                                                                \
+    newA2 = has2 && (D2.w & 1);                                                                       \
     a_early = false;                                                                                  \
     sl2 = sl1;                                                                                        \
     if (newA2) sl2 = (sl1 == NA - 1) ? 0 : sl1 + 1;                                                   \
     TOP_WORK(bnh, bnl, s, D2)                                                                         \
   }
-// MFMA_FIRST (default): a step opens with the 12 MFMAs of its first M-tile group -- their operands were fetched
-// during the previous step -- and its non-MFMA head (descriptor, weight DMA issue, global loads, next-step B fragment
-// reads) follows while the matrix pipe runs them.  The in-kernel trace (-DPPST_CONV_TRACE) showed the pipe idle for
-// the ~365 cycles of the head of every step otherwise.  -DPPST_HEAD_FIRST restores the old order for A/B runs.
-#ifdef PPST_HEAD_FIRST
-#define MFMA_FIRST 0
-#else
-#define MFMA_FIRST 1
-#endif
-// -DPPST_PRIO_SWAP (experiment, measured: no effect -- two same-box A/B pairs, -0.5 % / +1.8 % on the step's conv time): the two waves of a SIMD take the issue priority in turns within a step (waves 4-7 for M-tile
-// groups 0-1, waves 0-3 for groups 2-3) instead of waves 0-3 leading every step and waiting ~800 cycles at its barrier.
-#ifdef PPST_PRIO_SWAP
-#define PRIO_SWAP(mt)                                                                                 \
-  if ((mt) == 0) { if (wave >= 4) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0); } \
-  if ((mt) == 2) { if (wave >= 4) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(2); }
-#else
-#define PRIO_SWAP(mt)
-#endif
+// A step opens with the 12 MFMAs of its first M-tile group -- their operands were fetched during the previous step -- and
+// its non-MFMA head (descriptor, weight DMA issue, global loads, next-step B fragment reads) follows while the matrix pipe
+// runs them.  The in-kernel trace (-DPPST_CONV_TRACE) showed the pipe idle for the ~365 cycles of the head of every step
+// otherwise.
 #define CONV_STEP(bch, bcl, bnh, bnl, s, D2, D3, H1, H2)                                              \
   {                                                                                                   \
     TR_DECL TR(0)                                                                                     \
     const bool has1 = (H1), has2 = (H2);   /* steps s+1 / s+2 exist (compile-time true in the steady-state loop) */ \
     bool newA2, a_early;                                                                              \
     int sl2;                                                                                          \
-    STEP_HEAD_IF(MFMA_FIRST == 0, bnh, bnl, s, D2, D3)                                                \
     TR(1)                                                                                             \
     _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) {                                                \
       bf16x8 nh, nl;                                                                                  \
-      if (!ABL_LA(true)) {                                                                            \
-        nh = ah; nl = al;                                                                             \
-      } else if (mt < 3) {                                                                            \
+      if (mt < 3) {                                                                                   \
         nh = *(const bf16x8*)(smA + A_OFF(sl0, dy0, dx0, mt + 1));                                    \
-        if (ALO) nl = *(const bf16x8*)(smA + A_OFF(sl0, dy0, dx0, mt + 1) + 4 * PLANE);               \
+        if (X3) nl = *(const bf16x8*)(smA + A_OFF(sl0, dy0, dx0, mt + 1) + 4 * PLANE);                \
       } else if (has1) {                                                                              \
         nh = *(const bf16x8*)(smA + A_OFF(sl1, dy1, dx1, 0));                                         \
-        if (ALO) nl = *(const bf16x8*)(smA + A_OFF(sl1, dy1, dx1, 0) + 4 * PLANE);                    \
+        if (X3) nl = *(const bf16x8*)(smA + A_OFF(sl1, dy1, dx1, 0) + 4 * PLANE);                     \
       }                                                                                               \
-      PRIO_SWAP(mt)                                                                                   \
-      ABL_MFMA_GROUP(bch, bcl, mt)                                                                    \
-      if (MFMA_FIRST && mt == 0) {                                                                    \
+      MFMA_GROUP(bch, bcl, mt)                                                                        \
+      if (mt == 0) {                                                                                  \
         /* the matrix pipe is running the 12 MFMAs of group 0 (operands fetched during the previous */ \
         /* step): the step's non-MFMA head goes here instead of in front of them                    */ \
         __builtin_amdgcn_sched_barrier(0);                                                            \
-        STEP_HEAD_IF(true, bnh, bnl, s, D2, D3)                                                       \
+        STEP_HEAD(bnh, bnl, s, D2, D3)                                                                \
         __builtin_amdgcn_sched_barrier(0);                                                            \
       }                                                                                               \
       if (mt == 1) { TR(2) }                                                                          \
       if (mt == 3) { TR(3) }                                                                          \
       ah = nh;                                                                                        \
-      if (ALO) al = nl;                                                                               \
+      if (X3) al = nl;                                                                                \
       /* convert + write the next chunk's tile while the last MFMA group executes: the VALU   */     \
       /* work of the staging store overlaps the matrix pipe instead of following it            */     \
-      if (!PRES && mt == 2 && newA2) a_store(sl2);                                                    \
+      if (mt == 2 && newA2) a_store(sl2);                                                             \
     }                                                                                                 \
     TR(4)                                                                                             \
     /* hipcc (ROCm 7.2) does NOT add vmcnt(0) for an in-flight LDS-DMA at this barrier (it only  */  \
@@ -546,7 +449,7 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
     TR(5)                                                                                             \
     /* raw barrier: __syncthreads() carries a fence for which hipcc drains vmcnt to 0 -- including the early    */  \
     /* activation load.  LDS writes of this step (staging store) are drained here by hand.                      */  \
-    ABL_BAR(asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");)                          \
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                                   \
     TR(6)                                                                                             \
     TR_FLUSH(s, newA2)                                                                                \
     dy0 = dy1; dx0 = dx1; sl0 = sl1;                                                                  \
@@ -565,7 +468,7 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
     if (s + 1 < nst) CONV_STEP(b1h, b1l, b0h, b0l, s + 1, dO, dE, s + 2 < nst, s + 3 < nst)
   }
 #undef CONV_STEP
-#undef STEP_HEAD_IF
+#undef STEP_HEAD
 #undef TOP_WORK
 #undef A_OFF
 
@@ -747,38 +650,6 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
 #endif
 }
 
-// fp32 NHWC -> pre-split layout (experiment): per pixel and 8-channel group [hi x 8 | lo x 8] bf16 in the group's own 32 bytes
-__global__ __launch_bounds__(256) void presplit_kernel(const float* __restrict__ x, unsigned* __restrict__ y, int64_t npix, int C, int x_ld,
-                                                       int y_ld) {
-  const int groups = C >> 3;
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < npix * groups; t += (int64_t)gridDim.x * 256) {
-    const int64_t p = t / groups;
-    const int g8 = (int)(t - p * groups);
-    const float* src = x + p * x_ld + g8 * 8;
-    unsigned hi[4], lo[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      unsigned short h0, l0, h1, l1;
-      split_bf16(src[2 * q], h0, l0);
-      split_bf16(src[2 * q + 1], h1, l1);
-      hi[q] = (unsigned)h0 | ((unsigned)h1 << 16);
-      lo[q] = (unsigned)l0 | ((unsigned)l1 << 16);
-    }
-    unsigned* o = y + p * y_ld + g8 * 8;
-    *(uint4*)o = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-    *(uint4*)(o + 4) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-  }
-}
-extern "C" int ppst_presplit(const void* x, void* y, int64_t npix, int C, int x_ld, int y_ld, void* stream) {
-  if (npix < 0 || C <= 0 || C % 8 || x_ld < C || y_ld < C || x_ld % 4 || y_ld % 4) return PPST_EINVAL;
-  if (npix == 0) return PPST_OK;
-  if (!x || !y) return PPST_ENULL;
-  int64_t blocks = cdiv64(npix * (C >> 3), 256);
-  if (blocks > 65536) blocks = 65536;
-  PPST_LAUNCH(presplit_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const float*)x, (unsigned*)y, npix, C, x_ld, y_ld);
-  return PPST_LAUNCH_CHECK();
-}
-
 // ------------------------------------------------------------ weight packing --
 // out[group][ntile][step][hilo][g][n_local][j] = split_bf16(scale * w[n][src_c+8g+j][ky][kx])
 struct PackJob {            // == ppst_pack_job of include/ppst_hip.h
@@ -858,7 +729,7 @@ extern "C" int ppst_conv_pack(const void* w, int64_t sn, int64_t sc, int64_t sy,
                               const int32_t* src_c, const int32_t* src_ky, const int32_t* src_kx, int nsteps, int n_groups,
                               int precision, void* out, void* stream) {
   if (cout <= 0 || (bn != 64 && bn != 128 && bn != 256) || nsteps <= 0 || (n_groups != 1 && n_groups != 4) ||
-      (precision != 0 && precision != 1 && precision != 3 && precision != 4))
+      (precision != 0 && precision != 1 && precision != 3))
     return PPST_EINVAL;
   if (!w || !src_c || !src_ky || !src_kx || !out) return PPST_ENULL;
   int n_tiles = (cout + bn - 1) / bn;
@@ -866,7 +737,7 @@ extern "C" int ppst_conv_pack(const void* w, int64_t sn, int64_t sc, int64_t sy,
   j.w = (const float*)w; j.sn = sn; j.sc = sc; j.sy = sy; j.sx = sx; j.src_c = src_c; j.src_ky = src_ky; j.src_kx = src_kx;
   j.out = (unsigned short*)out; j.total = (int64_t)n_groups * n_tiles * nsteps * 4 * bn; j.block0 = 0; j.scale = scale;
   j.cout = cout; j.bn = bn; j.nsteps = nsteps; j.n_groups = n_groups; j.x3 = precision == 0 ? 1 : 0;
-  j.f16 = (precision == 3 || precision == 4) ? 1 : 0;
+  j.f16 = precision == 3 ? 1 : 0;
   j.dual = 0;
   j.nblocks = pack_blocks(j.total);
   PPST_LAUNCH(conv_pack_kernel, dim3((unsigned)j.nblocks), dim3(256), 0, as_stream(stream), j);
@@ -1094,18 +965,6 @@ int ppst_conv1x1_stream_launch(const ppst_conv_args* a, int n_tiles, int tiles, 
 int ppst_conv_direct_launch(const ppst_conv_args* a, int n_tiles, int tiles_y, int tiles_x, hipStream_t st);         // conv1x1.hip
 int ppst_conv3x3_direct_launch(const ppst_conv_args* a, int n_tiles, int tiles_y, int tiles_x, hipStream_t st);      // conv1x1.hip
 int ppst_conv_wino_launch(const ppst_conv_args* a, int n_tiles, int tiles_y, int tiles_x, hipStream_t st);            // conv_wino.hip
-#ifdef PPST_EXPERIMENTS
-int ppst_conv_ksplit_launch(const ppst_conv_args* a, int n_tiles, int tiles_y, int tiles_x, hipStream_t st);         // conv_ksplit.hip
-#endif
-// The measured-and-off kernel forms (variants 1 / 3 / 7 / 8 / 9, the two-pass fp16 mode, the 8-row two-block tile) are compiled
-// only into a PPST_EXPERIMENTS=1 build (python -m ppst_amd.build with that variable set); the production library rejects them.
-extern "C" int ppst_has_experiments(void) {
-#ifdef PPST_EXPERIMENTS
-  return 1;
-#else
-  return 0;
-#endif
-}
 
 // ---- the across-block K split (common.h): shape checks of ppst_conv_args.ksplit / ksplit_starts against the launch, then the caller's
 // workspace (include/ppst_hip.h)
@@ -1131,11 +990,11 @@ int ppst_ksplit_prepare_(const ppst_conv_args* a, int64_t tiles, int acc_regs, i
 // (tile_rows 15 = variant 11: blocks of 15 x 15 input positions)
 extern "C" int ppst_conv_tiles(int tile_h, int tile_w, int tile_rows) { return cdiv(tile_h, tile_rows) * cdiv(tile_w, tile_rows == 15 ? 15 : 16); }
 
-template <int WM, int WN, int HALO, bool X3, int NAS = 0, bool F16 = false, bool X2 = false, int IOS = PPST_ST_F32>
+template <int WM, int WN, int HALO, bool X3, int NAS = 0, bool F16 = false, int IOS = PPST_ST_F32>
 static void launch_conv(const ConvKArgs& k, int blocks, hipStream_t st) {
   const dim3 grid(blocks, k.ks.S > 1 ? k.ks.S : 1);
-  if (k.in_ss) PPST_LAUNCH((conv_mfma_kernel<WM, WN, HALO, X3, true, NAS, F16, X2, false, IOS>), grid, dim3(64 * WM * WN), 0, st, k);
-  else PPST_LAUNCH((conv_mfma_kernel<WM, WN, HALO, X3, false, NAS, F16, X2, false, IOS>), grid, dim3(64 * WM * WN), 0, st, k);
+  if (k.in_ss) PPST_LAUNCH((conv_mfma_kernel<WM, WN, HALO, X3, true, NAS, F16, IOS>), grid, dim3(64 * WM * WN), 0, st, k);
+  else PPST_LAUNCH((conv_mfma_kernel<WM, WN, HALO, X3, false, NAS, F16, IOS>), grid, dim3(64 * WM * WN), 0, st, k);
 }
 
 extern "C" int ppst_conv2d_mfma(const ppst_conv_args* a, void* stream) {
@@ -1145,7 +1004,7 @@ extern "C" int ppst_conv2d_mfma(const ppst_conv_args* a, void* stream) {
       (a->n_groups != 1 && a->n_groups != 4 && !(a->n_groups == 2 && a->dual_b)) || a->pad_mode < 0 ||
       (a->dual_b && (a->variant != 2 || a->bn != 256 || a->n_groups != 2 || a->halo != 1 || (a->precision != 0 && a->precision != 1 && a->precision != 3) || a->out_sy != 2 || a->out_sx != 2 || !a->early_a)) ||
       a->pad_mode > 2 || a->tile_h <= 0 || a->tile_w <= 0 || a->out_sy <= 0 || a->out_sx <= 0 ||
-      (a->precision != 0 && a->precision != 1 && a->precision != 3 && a->precision != 4) || a->halo < 0 || a->halo > 1 || (a->bn != 64 && a->bn != 128 && a->bn != 256) || (a->residual && a->res_ld < a->cout) ||
+      (a->precision != 0 && a->precision != 1 && a->precision != 3) || a->halo < 0 || a->halo > 1 || (a->bn != 64 && a->bn != 128 && a->bn != 256) || (a->residual && a->res_ld < a->cout) ||
       a->variant < 0 || a->variant > 11 || (a->variant == 0 && a->bn == 256) ||
       // variant 11 = conv_mfma2.hip UP9: the fused 4x4 stride-2 upscale as the un-blurred 3x3 transposed conv (nine products per input
       // pixel instead of sixteen) + its 2x2 box sum in the epilogue; wpack from ppst_conv_pack_up9, steps = per 32-channel chunk the
@@ -1161,15 +1020,12 @@ extern "C" int ppst_conv2d_mfma(const ppst_conv_args* a, void* stream) {
                             a->in_h != a->out_h || a->in_w != a->out_w || a->nsteps % 9 != 0 || a->tile_rows != 16 ||
                             // (its LDS copy of the normalise-on-load table holds 32 chunks = 1024 input channels)
                             (a->in_scale_shift && a->nsteps / 9 > 32))) ||
-      ((a->variant >= 1 && a->variant <= 3 || a->variant == 7 || a->variant == 9) &&
+      ((a->variant == 2 || a->variant == 7 || a->variant == 9) &&
        ((a->precision != 0 && !((a->variant == 2 || a->variant == 7 || (a->variant == 9 && a->k64)) && (a->precision == 1 || a->precision == 3))) || a->bn == 64 || !a->early_a)) ||
       (a->variant == 7 && (a->bn != 128 || a->tile_rows != 32)) ||
       // variant 9 = conv_mfma2.hip with 6 m-tiles per wave: block tile 24 x 16 px x 128 ch, two activation slots
       (a->variant == 9 && (a->bn != 128 || a->tile_rows != 24)) ||
-      // variant 8 = conv_ksplit.hip: two K-groups of four 128 px x 64 ch waves; bn = 128, bf16x3, chunks of >= 2 steps (and the
-      // caller's promise: 2-step chunks start at even steps, steps[i].w bit 2 = parity of step i's chunk index)
-      (a->variant == 8 && (a->precision != 0 || a->bn != 128 || !a->early_a)) ||
-      (a->variant == 2 && a->bn != 256) || (a->variant == 3 && a->bn != 128) ||
+      (a->variant == 2 && a->bn != 256) ||
       // variant 4 = the 1x1 streaming kernel (conv1x1.hip): all taps (0,0), one group, unit strides, bf16x3, 64-wide blobs
       (a->variant == 4 && ((a->precision != 0 && a->precision != 1 && a->precision != 3) || a->bn != 64 || a->halo != 0 || a->n_groups != 1 || a->out_sy != 1 || a->out_sx != 1 ||
                            a->in_off_y != 0 || a->in_off_x != 0 || a->tile_h != a->out_h || a->tile_w != a->out_w ||
@@ -1186,25 +1042,20 @@ extern "C" int ppst_conv2d_mfma(const ppst_conv_args* a, void* stream) {
       (a->tile_rows != 16 && !(a->variant == 7 && a->tile_rows == 32) && !(a->variant == 9 && a->tile_rows == 24) && !(a->variant == 11 && a->tile_rows == 15) &&
        !(a->variant == 0 && a->tile_rows == 8 && a->bn == 128 && a->halo == 1 && a->early_a && a->precision == 0)) || (a->in_scale_shift && a->in_c <= 0) || a->a_slots < 0 || a->a_slots > 3)
     return PPST_EINVAL;
-#ifndef PPST_EXPERIMENTS
-  if (a->variant == 1 || a->variant == 3 || (a->variant == 7 && a->precision == 0) || a->variant == 8 || (a->variant == 9 && !a->k64) || a->precision == 4 ||
-      a->in_presplit)
-    return PPST_EINVAL;          // experiment forms: not in this build (variant 7 is a production form in the single-pass modes)
-#endif
-  // pre-split input (experiment): the 8-wave tile kernel only, chunks of >= 4 steps (the caller's promise with early_a), no
-  // normalise-on-load
+  // retired forms (measured and removed): variants 1 / 3 / 8, variant 7 in the fp32-class mode (a production
+  // form in the single-pass modes), variant 9 without k64; the reserved field must be 0
+  if (a->variant == 1 || a->variant == 3 || (a->variant == 7 && a->precision == 0) || a->variant == 8 || (a->variant == 9 && !a->k64) ||
+      a->reserved0)
+    return PPST_EINVAL;
   // half-precision activation storage (x, residual, y): the single-pass modes, in the operand type of the mode (1 -> bfloat16,
   // 3 -> IEEE half); kernel families 0 (16-row tiles), 2 (N-256), 4 / 5 / 6 (streaming 1x1 / direct)
   if (a->io_st && (a->io_st != (a->precision == 3 ? PPST_ST_F16 : a->precision == 1 ? PPST_ST_BF16 : -1) ||
-                   (a->tile_rows != 16 && a->variant != 7 && !(a->variant == 9 && a->k64)) || a->in_presplit ||
+                   (a->tile_rows != 16 && a->variant != 7 && !(a->variant == 9 && a->k64)) ||
                    !(a->variant == 0 || a->variant == 2 || a->variant == 4 || a->variant == 5 || a->variant == 6 || a->variant == 7 || (a->variant == 9 && a->k64))))
     return PPST_EINVAL;
   // 64 input channels per step (conv_mfma2.hip K64): single-pass modes on half-stored activations, the N-256 geometry (plain or phase
   // pairs) or the 24 x 16 px x 128 ch tile
   if (a->k64 && (!a->io_st || !a->halo || !((a->variant == 2 && a->bn == 256) || (a->variant == 9 && a->bn == 128 && a->tile_rows == 24)) || !a->early_a))
-    return PPST_EINVAL;
-  if (a->in_presplit && (a->variant != 0 || a->bn != 128 || a->halo != 1 || a->precision != 0 || !a->early_a || a->tile_rows != 16 ||
-                         a->in_scale_shift))
     return PPST_EINVAL;
   // the epilogues address one image with 32-bit element offsets
   // (+ one tile row of slack: lanes beyond the image edge form their offset too, and only then mask the access)
@@ -1248,7 +1099,7 @@ extern "C" int ppst_conv2d_mfma(const ppst_conv_args* a, void* stream) {
   if (a->ksplit > 1) {
     // the tile kernel (variant 0, 16-row tiles); the N-256 and Winograd kernels take theirs in their own launchers
     if (a->variant == 0) {
-      if ((a->tile_rows != 16 && a->tile_rows != 8) || a->in_presplit) return PPST_EINVAL;
+      if (a->tile_rows != 16 && a->tile_rows != 8) return PPST_EINVAL;
       const int e0 = ppst_ksplit_prepare_(a, blocks, 64, (a->bn == 128 && a->tile_rows == 16) ? 512 : 256, &k.ks);
       if (e0 != PPST_OK) return e0;
     } else if (a->variant != 2 && a->variant != 10) return PPST_EINVAL;
@@ -1268,44 +1119,30 @@ extern "C" int ppst_conv2d_mfma(const ppst_conv_args* a, void* stream) {
              : a->variant == 5 ? ppst_conv_direct_launch(a, k.n_tiles, k.tiles_y, k.tiles_x, st)
              : a->variant == 6 ? ppst_conv3x3_direct_launch(a, k.n_tiles, k.tiles_y, k.tiles_x, st)
              : a->variant == 10 ? ppst_conv_wino_launch(a, k.n_tiles, k.tiles_y, k.tiles_x, st)
-#ifdef PPST_EXPERIMENTS
-             : a->variant == 8 ? ppst_conv_ksplit_launch(a, k.n_tiles, k.tiles_y, k.tiles_x, st)
-#endif
                                : ppst_conv2d_mfma2_launch(a, k.n_tiles, k.tiles_y, k.tiles_x, st);
     if (slot >= 0) (void)hipEventRecord(g_ev[slot][1], st);
     return e2;
   }
   const bool x3 = a->precision == 0;
-  const bool f16 = a->precision == 3, x2 = a->precision == 4, hs = a->io_st != 0;
-#ifdef PPST_EXPERIMENTS
-#define X2_LAUNCH(WM_, WN_, H_) launch_conv<WM_, WN_, H_, false, 0, true, true>(k, blocks, st)
-#else
-#define X2_LAUNCH(WM_, WN_, H_) (void)0      /* precision 4 was rejected above */
-#endif
+  const bool f16 = a->precision == 3, hs = a->io_st != 0;
 #define DISPATCH(WM_, WN_)                                                                                         \
   do {                                                                                                             \
-    if (a->halo) { if (x3) launch_conv<WM_, WN_, 1, true>(k, blocks, st); else if (x2) X2_LAUNCH(WM_, WN_, 1); else if (f16 && hs) launch_conv<WM_, WN_, 1, false, 0, true, false, PPST_ST_F16>(k, blocks, st); else if (f16) launch_conv<WM_, WN_, 1, false, 0, true>(k, blocks, st); else if (hs) launch_conv<WM_, WN_, 1, false, 0, false, false, PPST_ST_BF16>(k, blocks, st); else launch_conv<WM_, WN_, 1, false>(k, blocks, st); } \
-    else         { if (x3) launch_conv<WM_, WN_, 0, true>(k, blocks, st); else if (x2) X2_LAUNCH(WM_, WN_, 0); else if (f16 && hs) launch_conv<WM_, WN_, 0, false, 0, true, false, PPST_ST_F16>(k, blocks, st); else if (f16) launch_conv<WM_, WN_, 0, false, 0, true>(k, blocks, st); else if (hs) launch_conv<WM_, WN_, 0, false, 0, false, false, PPST_ST_BF16>(k, blocks, st); else launch_conv<WM_, WN_, 0, false>(k, blocks, st); } \
+    if (a->halo) { if (x3) launch_conv<WM_, WN_, 1, true>(k, blocks, st); else if (f16 && hs) launch_conv<WM_, WN_, 1, false, 0, true, PPST_ST_F16>(k, blocks, st); else if (f16) launch_conv<WM_, WN_, 1, false, 0, true>(k, blocks, st); else if (hs) launch_conv<WM_, WN_, 1, false, 0, false, PPST_ST_BF16>(k, blocks, st); else launch_conv<WM_, WN_, 1, false>(k, blocks, st); } \
+    else         { if (x3) launch_conv<WM_, WN_, 0, true>(k, blocks, st); else if (f16 && hs) launch_conv<WM_, WN_, 0, false, 0, true, PPST_ST_F16>(k, blocks, st); else if (f16) launch_conv<WM_, WN_, 0, false, 0, true>(k, blocks, st); else if (hs) launch_conv<WM_, WN_, 0, false, 0, false, PPST_ST_BF16>(k, blocks, st); else launch_conv<WM_, WN_, 0, false>(k, blocks, st); } \
   } while (0)
   // (round 1 measured 8-row tiles -- two 80-KB blocks per CU -- 35 % slower: only one block was ever resident.  Round 3
   //  re-instantiates them at 77 KB with the two-slot ring of the early_a tables: see ops.TWO_BLOCK_8ROW.)
-  // small-K layers on the 64-channel tile: a shallower activation ring (59 / 48 / 80 KB of LDS instead of
-  // 145 / 112) puts two blocks on a CU, so one block's loads and stores overlap the other's MFMAs
-#ifdef PPST_EXPERIMENTS
-  if (a->in_presplit) PPST_LAUNCH((conv_mfma_kernel<4, 2, 1, true, false, 0, false, false, true>), dim3(blocks), dim3(512), 0, st, k);
-  else
-#endif
   // 8 x 16-px tiles, two 4-wave blocks per CU: the same per-pixel MFMA sequence as the 16-row tile (bit-identical outputs); a
   // wash on full grids, but twice the blocks where ONE small image per launch leaves the chip under-filled
   // (64 x 64 layers of the train step at batch 2: 64 blocks for 256 CUs)
   if (a->tile_rows == 8) launch_conv<2, 2, 1, true, 2>(k, blocks, st);
-  else
-  if (a->bn == 64 && x3 && a->halo == 1 && a->a_slots == 1) launch_conv<4, 1, 1, true, 1>(k, blocks, st);
+  // small-K layers on the 64-channel tile: a shallower activation ring (59 / 48 / 80 KB of LDS instead of
+  // 145 / 112) puts two blocks on a CU, so one block's loads and stores overlap the other's MFMAs
+  else if (a->bn == 64 && x3 && a->halo == 1 && a->a_slots == 1) launch_conv<4, 1, 1, true, 1>(k, blocks, st);
   else if (a->bn == 64 && x3 && a->halo == 0 && a->a_slots == 1) launch_conv<4, 1, 0, true, 1>(k, blocks, st);
   else if (a->bn == 64 && x3 && a->halo == 0 && a->a_slots == 2) launch_conv<4, 1, 0, true, 2>(k, blocks, st);
   else if (a->bn == 128) DISPATCH(4, 2); else DISPATCH(4, 1);
 #undef DISPATCH
-#undef X2_LAUNCH
   int e = PPST_LAUNCH_CHECK();
   if (slot >= 0) (void)hipEventRecord(g_ev[slot][1], st);
   return e;

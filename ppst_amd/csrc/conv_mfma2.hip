@@ -1,11 +1,12 @@
-// Fused implicit-GEMM convolution, "one fat wave per SIMD" variant (round 2).
+// Fused implicit-GEMM convolution, the fat-wave-tile forms (round 2).
 //
 // Same operation, step tables, weight blobs' meaning, padding modes, normalise-on-load and epilogue as conv_mfma.hip
 // (the StyledConv / EqualConv2d conv of stylegan2_layers.py:184-193, 305-347, 467-475) -- a different decomposition:
 //
 //   conv_mfma.hip : 512 threads = 8 waves (2 per SIMD), wave tile 64 px x 64 ch  (4 x 4 MFMA tiles, 48 MFMAs / K-step)
-//   this file     : 256 threads = 4 waves (1 per SIMD), wave tile 128 px x 16*NT ch (8 x NT tiles, NT = 4 or 8:
-//                   96 / 192 MFMAs per wave and K-step), block tile 16x16 px x (128 | 256) channels, up to 512 VGPRs.
+//   this file     : 512 threads = 8 waves (2 per SIMD), wave tile 128 (96) px x 64 ch (8 (6) x 4 MFMA tiles, 96 (72) MFMAs per
+//                   wave and K-step), block tile 16x16 px x 256 ch or 32 (24) x 16 px x 128 ch.  (It began as ONE wave per SIMD
+//                   with up to 512 VGPRs and 128-channel wave tiles: measured slower and removed)
 //
 // Why (profiles/r01_conv_trace.txt): the 8-wave kernel's K-step took ~2450 cycles for the 1536 its
 // MFMAs need.  v_mfma_f32_16x16x32_bf16 holds its SIMD's issue port for 8 of its 16 cycles, so a step leaves 768 issue
@@ -17,7 +18,7 @@
 // activation tile is fetched on the 256/512-channel layers (PMC showed reads at 2.0x the algorithmic bytes).
 //
 // LDS: activation ring of 2 slots (43 KB each; legal because every chunk of the step table spans >= 2 steps -- the
-// host only selects this kernel for such tables) + weight ring of 2 slots (16 / 32 KB) = 118 / 151 KB, one block per CU.
+// host only selects this kernel for such tables) + weight ring of 2 slots (16 / 32 KB each), one block per CU.
 #include "common.h"
 
 struct Conv2KArgs {
@@ -70,39 +71,35 @@ __device__ __forceinline__ int pad_index2(int i, int n, int mode) {
   return i < 0 ? 0 : (i >= n ? n - 1 : i);
 }
 
-// WNW: waves along N (2: one wave per SIMD, 256 threads; 4: two waves per SIMD, 512 threads, wave tile 128 px x 64 ch,
-// block tile 16x16 px x 256 ch -- the "8-phase template" geometry of the CDNA GEMM guide).  BDB: weight fragments of the
-// next step double-buffered in registers (WNW = 2) or reloaded at the end of the step (WNW = 4: 256 registers per wave).
-// NA_: activation ring slots.  1 (with WNW = 2, NT = 4, BDB = false): 75 KB of LDS and <= 256 registers, so TWO 4-wave blocks
-// share a CU -- the 128 px x 64 ch wave tile for layers whose Cout is only 128.  With one slot a new chunk is stored at the
-// END of the step before it is used, between two barriers; the CU's other block fills that bubble.
-// WMW: waves along M (8 tile rows each).  4 (with WNW = 2, NT = 4, BDB = false, NA_ = 1): block tile 32 x 16 px x 128 ch --
-// the 128 px x 64 ch wave tile, two waves per SIMD, for layers whose Cout is only 128 (variant 7).  Its activation slot is
-// 78 KB, so there is one, and a new chunk is stored at the end of the step before it is used (the NA_ = 1 path).
+// WNW x WMW: waves along N x M, eight per block (two per SIMD), each with MT_ m-tiles (16-pixel rows) x 4 n-tiles (16 channels):
+//   4 x 2, MT_ = 8: block tile 16 x 16 px x 256 ch, wave tile 128 px x 64 ch -- the "8-phase template" geometry of the CDNA GEMM guide
+//                   (variant 2: Cout % 256 == 0);
+//   2 x 4, MT_ = 8: block tile 32 x 16 px x 128 ch (variant 7: the Cout = 128-class layers of the single-pass modes, whose hi planes
+//                   alone are 39 KB per activation slot);
+//   2 x 4, MT_ = 6: block tile 24 x 16 px x 128 ch, wave tile 96 px x 64 ch (variant 9, with K64: two 60-KB slots + 32 KB of weights).
+// One register set of weight fragments, reloaded at the end of the step (256 registers per wave); two activation slots.
 // PREC: 0 the fp32-class bf16 hi+lo form (three MFMAs per product); 1 / 3 single-pass bf16 / fp16 (the reduced-precision modes
-// of ops.set_precision: one plane set in LDS, one MFMA) -- instantiated for the production geometry (variant 2) only.
+// of ops.set_precision: one plane set in LDS, one MFMA).
 typedef _Float16 __attribute__((ext_vector_type(8))) half8_2;
 __device__ __forceinline__ unsigned short f2h_2(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
-// MT_: m-tiles (16-pixel rows) per wave.  6 (with WMW = 4, WNW = 2, NT = 4, BDB = false, NA_ = 2): block tile 24 x 16 px x 128 ch,
-// wave tile 96 px x 64 ch (variant 9) -- the largest wave tile for Cout = 128 layers whose activation ring still has TWO slots
-// (2 x 60 KB + 32 KB of weights = 152 KB): 20 ds_read_b128 per 72 MFMAs, and the chunk store overlaps the MFMAs as in variant 2.
 // DUAL (round 4, with WNW = 4, bn = 256): the fused upscale with Cout = 128 as TWO output-phase pairs instead of four phases -- the
 // N tile of 256 is [phase b = 0: 128 channels | phase b = 1: 128 channels] of one row phase a (= the group), N-waves 0-1 / 2-3.  A
 // step is a tap ROW dy with one tap COLUMN per b (steps[i].z = (dx_b0 + 1) | (dx_b1 + 1) << 8): every wave multiplies in every
 // step, the activation tile is staged once for two phases, and the layer runs on this kernel's 128 x 64 wave tiles instead of
 // the tile kernel's 64 x 64.  Per output element the MFMA sequence is the tile kernel's (dy-major taps): bit-identical outputs.
-template <int NT, int HALO, bool INSS, int WNW = 2, bool BDB = true, int NA_ = 2, int WMW = 2, int PREC = 0, int MT_ = 8, bool DUAL = false,
-          int IOS = PPST_ST_F32, bool UP9 = false, bool K64 = false, bool KS = false>
-__global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : ((WNW * WMW == 8 || NA_ == 1) ? 2 : 1)) void conv_mfma2_kernel(Conv2KArgs a) {
+template <int HALO, bool INSS, int WNW, int WMW = 2, int PREC = 0, int MT_ = 8, bool DUAL = false, int IOS = PPST_ST_F32, bool UP9 = false,
+          bool K64 = false, bool KS = false>
+__global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : (WNW * WMW == 8 ? 2 : 1)) void conv_mfma2_kernel(Conv2KArgs a) {
+  constexpr int NT = 4;                                   // n-tiles (16 channels) per wave
   constexpr bool X3 = PREC == 0;
   // K64 (single-pass modes on half-stored activations): a step covers 64 input channels instead of 32 -- channels 0-31 of the chunk sit
   // where the x3 form keeps its hi planes, channels 32-63 where it keeps its lo planes (activation tile and weight blob alike), and a
   // product is two MFMAs (first half x first half + second half x second half) instead of three.  Same LDS image sizes, registers
   // and step pipeline as the fp32-class kernel; half the steps (barriers, fragment waits, DMA issues) per MFMA of the 32-channel
   // single-pass form, which spent two thirds of a step beside its matrix work (0.27-0.41 of the single-pass ceiling at 1024^2).
-  static_assert(!K64 || (PREC != 0 && IOS != PPST_ST_F32 && !UP9 && !BDB), "K64: single-pass precision on half-stored activations");
+  static_assert(!K64 || (PREC != 0 && IOS != PPST_ST_F32 && !UP9), "K64: single-pass precision on half-stored activations");
   constexpr bool X3L = X3 || K64;                          // the LDS images have eight planes
-  static_assert(!UP9 || (NT == 4 && HALO == 1 && !INSS && WNW == 4 && !BDB && NA_ == 2 && WMW == 2 && PREC == 0 && MT_ == 8 && !DUAL &&
+  static_assert(!UP9 || (HALO == 1 && !INSS && WNW == 4 && WMW == 2 && PREC == 0 && MT_ == 8 && !DUAL &&
                          IOS == PPST_ST_F32), "UP9: the production geometry, fp32-class, fp32 storage");
   // IOS: storage type of x, residual and y (ppst_conv_args.io_st; conv_mfma.hip): the single-pass modes, in their operand type
   static_assert(IOS == PPST_ST_F32 || IOS == (PREC == 3 ? PPST_ST_F16 : PREC == 1 ? PPST_ST_BF16 : -1), "half storage: single-pass modes");
@@ -117,7 +114,7 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : ((WNW * WMW =
   constexpr int BN = WNW * 16 * NT;                       // WNW N-waves
   constexpr int BPLANE = BN * 16;
   constexpr int BBUF = (X3L ? 8 : 4) * BPLANE;
-  constexpr int NA = NA_;
+  constexpr int NA = 2;                                   // activation ring slots
   constexpr int EPI_TILE = 64 * 36;
   constexpr int EPI_BYTES = NWV * EPI_TILE * 4 + WMW * BN * 2 * 4;
   constexpr int MAIN_BYTES = NA * ABUF + 2 * BBUF;
@@ -319,7 +316,7 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : ((WNW * WMW =
     b_dma(1, 1, UP9 ? 0x3 : 0xF);
     if (d.w & 1) a_load(d.x);
     if (d.w & 1) a_store(sl1);
-    if (NA > 1 && a.early_a && (d.w & 2)) a_load(d.w >> 8);
+    if (a.early_a && (d.w & 2)) a_load(d.w >> 8);
   }
   int4 dE = d, dO = d;
   if (nst > 2) dE = steps[2];
@@ -330,7 +327,7 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : ((WNW * WMW =
   }
   __syncthreads();
 
-  bf16x8 b0h[NT], b0l[NT], b1h[BDB ? NT : 1], b1l[BDB ? NT : 1];
+  bf16x8 b0h[NT], b0l[NT];
   bf16x8 ah, al;
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
@@ -341,77 +338,54 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : ((WNW * WMW =
   if (X3L) al = *(const bf16x8*)(smA + A_OFF(sl0, dy0, dx0, 0) + 4 * PLANE);
   __builtin_amdgcn_s_waitcnt(0xC07F);
 
-  // One K-step.  bc* = this step's weight fragments (read during the previous step); bn* receive the next step's:
-  // one n-tile pair per m-tile group, so the 2*NT reads are spread over the step.  The next A fragment (m-tile mt+1, or
-  // m-tile 0 of step s+1) is read one group ahead.  The non-MFMA head (descriptor, weight DMA, activation loads) follows
-  // the first group's MFMAs; the staging store of a new chunk sits under the second-to-last group.
-// -DPPST_ABL_HALFBAR (timing ablation, results WRONG: races): only every second step ends in a barrier -- what a 4-slot weight ring
-// with one barrier per step pair could gain at most.  Measured: +-1 % on the N-256 layers; <= 3 % with 64 px x 64 ch waves (the tile
-// kernel's geometry instantiated on this loop, itself 3-5 % slower than conv_mfma.hip: commit bf39429).
-#ifdef PPST_ABL_HALFBAR
-#define HALFBAR_IF(s) if (((s) & 1) != 0)
-#else
-#define HALFBAR_IF(s)
-#endif
-#define STEP2(bch, bcl, bnh, bnl, s, D2, D3, H1, H2) STEP2M(bch, bcl, bnh, bnl, s, D2, D3, H1, H2, 0xF, 0xF)
-#define STEP2M(bch, bcl, bnh, bnl, s, D2, D3, H1, H2, MASK, MASKN) STEP2N(bch, bcl, bnh, bnl, s, D2, D3, H1, H2, MASK, MASKN, 0xF)
-#define STEP2N(bch, bcl, bnh, bnl, s, D2, D3, H1, H2, MASK, MASKN, MASK2)   /* MASK2: the types of step s + 2 (its weight DMA) */   /* MASK / MASKN: n-tiles this / the next step multiplies (UP9) */ \
+  // One K-step.  b0h / b0l = this step's weight fragments; the next step's replace them at the end of the step.  The next A
+  // fragment (m-tile mt+1, or m-tile 0 of step s+1) is read one group ahead.  The non-MFMA head (descriptor, weight DMA,
+  // activation loads) follows the first group's MFMAs; the staging store of a new chunk sits under the second-to-last group.
+#define STEP2(s, D2, D3, H1, H2) STEP2N(s, D2, D3, H1, H2, 0xF, 0xF, 0xF)
+#define STEP2N(s, D2, D3, H1, H2, MASK, MASKN, MASK2)   /* MASK2: the types of step s + 2 (its weight DMA) */   /* MASK / MASKN: n-tiles this / the next step multiplies (UP9) */ \
   {                                                                                                           \
     const bool has1 = (H1), has2 = (H2);                                                                      \
     TR2_DECL TR2(0)                                                                                           \
     bool newA2 = false, a_early = false;                                                                      \
     int sl2 = sl1;                                                                                            \
-    if (NA == 1 && freshA) {   /* this step's chunk was stored at the end of the previous step */             \
-      ah = *(const bf16x8*)(smA + A_OFF(0, dy0, dx0, 0));                                                     \
-      if (X3L) al = *(const bf16x8*)(smA + A_OFF(0, dy0, dx0, 0) + 4 * PLANE);                                         \
-    }                                                                                                         \
-    const bool storeA = NA == 1 && pendA;   /* the next step opens a chunk: store it at the end of this one */ \
     _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) {                                                       \
       bf16x8 nh, nl;                                                                                          \
       if (mt < MT - 1) {                                                                                      \
         nh = *(const bf16x8*)(smA + A_OFF(sl0, dy0, dx0, mt + 1));                                            \
         if (X3L) nl = *(const bf16x8*)(smA + A_OFF(sl0, dy0, dx0, mt + 1) + 4 * PLANE);                                \
-      } else if (has1 && !storeA) {                                                                           \
+      } else if (has1) {                                                                                      \
         nh = *(const bf16x8*)(smA + A_OFF(sl1, dy1, dx1, 0));                                                 \
         if (X3L) nl = *(const bf16x8*)(smA + A_OFF(sl1, dy1, dx1, 0) + 4 * PLANE);                                     \
-      }                                                                                                       \
-      if (BDB && has1 && mt >= 1 && mt - 1 < NT) {   /* next step's B fragment pair nt = mt - 1 */            \
-        bnh[mt - 1] = *(const bf16x8*)B_ADDR(((s) + 1) & 1, mt - 1);                                          \
-        if (X3L) bnl[mt - 1] = *(const bf16x8*)(B_ADDR(((s) + 1) & 1, mt - 1) + 4 * BPLANE);                           \
-      }                                                                                                       \
-      if (BDB && NT == 8 && has1 && mt == MT - 1) {                                                           \
-        bnh[NT - 1] = *(const bf16x8*)B_ADDR(((s) + 1) & 1, NT - 1);                                          \
-        if (X3L) bnl[NT - 1] = *(const bf16x8*)(B_ADDR(((s) + 1) & 1, NT - 1) + 4 * BPLANE);                           \
       }                                                                                                       \
       _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) {                                                     \
         if (!(((MASK) >> nt) & 1)) continue;                                                                  \
         if (X3) {                                                                                             \
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bch[nt], acc[mt][nt], 0, 0, 0);           \
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bcl[nt], acc[mt][nt], 0, 0, 0);           \
+          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, b0h[nt], acc[mt][nt], 0, 0, 0);           \
+          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b0l[nt], acc[mt][nt], 0, 0, 0);           \
         }                                                                                                     \
         if (K64) {   /* channels 32-63 of the chunk: the "lo" images */                                       \
           if (PREC == 3)                                                                                      \
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_2, al), __builtin_bit_cast(half8_2, bcl[nt]), acc[mt][nt], 0, 0, 0); \
+            acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_2, al), __builtin_bit_cast(half8_2, b0l[nt]), acc[mt][nt], 0, 0, 0); \
           else                                                                                                \
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bcl[nt], acc[mt][nt], 0, 0, 0);         \
+            acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, b0l[nt], acc[mt][nt], 0, 0, 0);         \
         }                                                                                                     \
         if (PREC == 3)                                                                                        \
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_2, ah), __builtin_bit_cast(half8_2, bch[nt]), acc[mt][nt], 0, 0, 0); \
+          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_2, ah), __builtin_bit_cast(half8_2, b0h[nt]), acc[mt][nt], 0, 0, 0); \
         else                                                                                                  \
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bch[nt], acc[mt][nt], 0, 0, 0);           \
+          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b0h[nt], acc[mt][nt], 0, 0, 0);           \
       }                                                                                                       \
       if (mt == 0) {                                                                                          \
         __builtin_amdgcn_sched_barrier(0);                                                                    \
         D3 = steps[(s) + 3];                                                                                  \
         newA2 = has2 && (D2.w & 1);                                                                           \
-        if (NA > 1 && newA2) sl2 = sl1 ^ 1;                                                                   \
+        if (newA2) sl2 = sl1 ^ 1;                                                                             \
         if (has2) b_dma((s) + 2, (s) & 1, (MASK2));                                                           \
         __builtin_amdgcn_sched_barrier(0);   /* DMA issued before the activation loads: counted vmcnt below */ \
         {                                                                                                     \
-          const bool early_ = NA > 1 && a.early_a;                                                            \
+          const bool early_ = a.early_a != 0;                                                                 \
           const bool ld_ = early_ ? (has2 && (D2.w & 2)) : newA2;                                             \
           const int ch_ = early_ ? (D2.w >> 8) : D2.x;                                                        \
-          if (ld_) { a_load(ch_); a_early = NA == 1 || early_; }                                              \
+          if (ld_) { a_load(ch_); a_early = early_; }                                                         \
         }                                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                    \
         TR2(1)                                                                                                \
@@ -419,73 +393,56 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : ((WNW * WMW =
       if (mt == 3) { TR2(2) }                                                                                 \
       ah = nh;                                                                                                \
       al = nl;                                                                                                \
-      if (NA > 1 && mt == MT - 2 && newA2) a_store(sl2);                                                      \
+      if (mt == MT - 2 && newA2) a_store(sl2);                                                                \
     }                                                                                                         \
     TR2(3)                                                                                                    \
-    if (storeA) {   /* every wave has read the old chunk -> overwrite the only slot */                        \
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                                         \
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                        \
-      a_store(0);                                                                                             \
-    }                                                                                                         \
-    if (!BDB && has1) {   /* single register set: the next step's weight fragments replace this step's, now dead */ \
+    if (has1) {   /* single register set: the next step's weight fragments replace this step's, now dead */     \
       _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) {                                                     \
         if (!(((MASKN) >> nt) & 1)) continue;                                                                 \
-        bnh[nt] = *(const bf16x8*)B_ADDR(((s) + 1) & 1, nt);                                                  \
-        if (X3L) bnl[nt] = *(const bf16x8*)(B_ADDR(((s) + 1) & 1, nt) + 4 * BPLANE);                                   \
+        b0h[nt] = *(const bf16x8*)B_ADDR(((s) + 1) & 1, nt);                                                  \
+        if (X3L) b0l[nt] = *(const bf16x8*)(B_ADDR(((s) + 1) & 1, nt) + 4 * BPLANE);                                   \
       }                                                                                                       \
     }                                                                                                         \
     TR2(4)                                                                                                    \
     if (a_early) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(A_NLOADS) : "memory");                              \
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                     \
     TR2(5)                                                                                                    \
-    HALFBAR_IF(s) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                             \
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                                           \
     TR2(6)                                                                                                    \
     TR2_FLUSH(s, newA2)                                                                                       \
-    freshA = storeA; pendA = newA2;                                                                           \
     dy0 = dy1; dx0 = dx1; sl0 = sl1;                                                                          \
     if (has2) { dy1 = D2.y; dx1 = DXW(D2.z); }                                                                \
     sl1 = sl2;                                                                                                \
   }
   int s = 0;
-  bool freshA = false, pendA = false;
   if (UP9) {
     // chunks of four steps = the four input shifts (0,0), (-1,0), (0,-1), (-1,-1); the n-tiles of a wave are the four u types
     // [ee, eo, oe, oo] of its 16 channels, and a shift feeds 4 / 2 / 2 / 1 of them: nine products per input pixel instead of the
     // sixteen of the four-phase form (masks are compile-time: the skipped MFMAs and fragment reads are not in the code)
     for (; s + 5 < nst; s += 4) {
-      STEP2N(b0h, b0l, b0h, b0l, s, dE, dO, true, true, 0xF, 0x3, 0x5)
-      STEP2N(b0h, b0l, b0h, b0l, s + 1, dO, dE, true, true, 0x3, 0x5, 0x1)
-      STEP2N(b0h, b0l, b0h, b0l, s + 2, dE, dO, true, true, 0x5, 0x1, 0xF)
-      STEP2N(b0h, b0l, b0h, b0l, s + 3, dO, dE, true, true, 0x1, 0xF, 0x3)
+      STEP2N(s, dE, dO, true, true, 0xF, 0x3, 0x5)
+      STEP2N(s + 1, dO, dE, true, true, 0x3, 0x5, 0x1)
+      STEP2N(s + 2, dE, dO, true, true, 0x5, 0x1, 0xF)
+      STEP2N(s + 3, dO, dE, true, true, 0x1, 0xF, 0x3)
     }
     for (; s < nst; s += 4) {
-      STEP2N(b0h, b0l, b0h, b0l, s, dE, dO, s + 1 < nst, s + 2 < nst, 0xF, 0x3, 0x5)
-      STEP2N(b0h, b0l, b0h, b0l, s + 1, dO, dE, s + 2 < nst, s + 3 < nst, 0x3, 0x5, 0x1)
-      STEP2N(b0h, b0l, b0h, b0l, s + 2, dE, dO, s + 3 < nst, s + 4 < nst, 0x5, 0x1, 0xF)
-      STEP2N(b0h, b0l, b0h, b0l, s + 3, dO, dE, s + 4 < nst, s + 5 < nst, 0x1, 0xF, 0x3)
+      STEP2N(s, dE, dO, s + 1 < nst, s + 2 < nst, 0xF, 0x3, 0x5)
+      STEP2N(s + 1, dO, dE, s + 2 < nst, s + 3 < nst, 0x3, 0x5, 0x1)
+      STEP2N(s + 2, dE, dO, s + 3 < nst, s + 4 < nst, 0x5, 0x1, 0xF)
+      STEP2N(s + 3, dO, dE, s + 4 < nst, s + 5 < nst, 0x1, 0xF, 0x3)
     }
   } else
-  if (BDB) {
+  {
     for (; s + 3 < nst; s += 2) {
-      STEP2(b0h, b0l, b1h, b1l, s, dE, dO, true, true)
-      STEP2(b1h, b1l, b0h, b0l, s + 1, dO, dE, true, true)
+      STEP2(s, dE, dO, true, true)
+      STEP2(s + 1, dO, dE, true, true)
     }
     for (; s < nst; s += 2) {
-      STEP2(b0h, b0l, b1h, b1l, s, dE, dO, s + 1 < nst, s + 2 < nst)
-      if (s + 1 < nst) STEP2(b1h, b1l, b0h, b0l, s + 1, dO, dE, s + 2 < nst, s + 3 < nst)
-    }
-  } else {
-    for (; s + 3 < nst; s += 2) {
-      STEP2(b0h, b0l, b0h, b0l, s, dE, dO, true, true)
-      STEP2(b0h, b0l, b0h, b0l, s + 1, dO, dE, true, true)
-    }
-    for (; s < nst; s += 2) {
-      STEP2(b0h, b0l, b0h, b0l, s, dE, dO, s + 1 < nst, s + 2 < nst)
-      if (s + 1 < nst) STEP2(b0h, b0l, b0h, b0l, s + 1, dO, dE, s + 2 < nst, s + 3 < nst)
+      STEP2(s, dE, dO, s + 1 < nst, s + 2 < nst)
+      if (s + 1 < nst) STEP2(s + 1, dO, dE, s + 2 < nst, s + 3 < nst)
     }
   }
 #undef STEP2
-#undef STEP2M
 #undef STEP2N
 #undef A_OFF
 #undef DXW
@@ -547,9 +504,6 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : ((WNW * WMW =
         const bool ok = okx && yl < 15 && ty0 + yl < a.tile_h && oy < a.out_h;
         nzv[mt][q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(nrs, ok ? (oy * a.out_w + oxg) * 4 : (int)0x80000000, 0, 0));
       }
-#ifdef UP9_ABL_NOEPI
-    if (a.out_scale != 123.f) return;
-#endif
     // x + 1 neighbours of the first row
     float ee_n = __shfl_down(acc[0][0][0], 16, 64);       // ee[y][column 4 (g + 1)] for j = 3
 #pragma unroll
@@ -752,7 +706,7 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : ((WNW * WMW =
     else if (resm == 1) epi_passes(EpiC<A_>{}, EpiC<1>{});                                            \
     else epi_passes(EpiC<A_>{}, EpiC<2>{});                                                           \
   } while (0)
-    if (!(WNW == 4 && NA_ == 2 && X3)) epi_passes(EpiR{act}, EpiR{resm});   // experiments / reduced precision: one generic instance
+    if (!X3) epi_passes(EpiR{act}, EpiR{resm});        // reduced-precision kernels: one generic instance
     else if (act == PPST_ACT_LRELU) EPI_GO(PPST_ACT_LRELU);
     else if (act == PPST_ACT_PRELU) EPI_GO(PPST_ACT_PRELU);
     else EPI_GO(PPST_ACT_NONE);
@@ -799,7 +753,7 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : ((WNW * WMW =
 #endif
 }
 
-// Entry used by ppst_conv2d_mfma (conv_mfma.hip) when a->bn is 256, or 128 with the fat-wave variant requested.
+// Entry used by ppst_conv2d_mfma (conv_mfma.hip) for the variants 2, 7, 9 and 11.
 int ppst_conv2d_mfma2_launch(const ppst_conv_args* a, int n_tiles, int tiles_y, int tiles_x, hipStream_t st) {
   Conv2KArgs k;
   k.x = (const float*)a->x; k.wpack = (const unsigned short*)a->wpack; k.steps = (const int4*)a->steps; k.y = (float*)a->y;
@@ -830,8 +784,8 @@ int ppst_conv2d_mfma2_launch(const ppst_conv_args* a, int n_tiles, int tiles_y, 
     const dim3 gridk(blocks, k.ks.S);
 #define LKS(HALO_, PREC_, IOS_, K64_)                                                                            \
   do {                                                                                                          \
-    if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<4, HALO_, true, 4, false, 2, 2, PREC_, 8, false, IOS_, false, K64_, true>), gridk, dim3(512), 0, st, k);   \
-    else PPST_LAUNCH((conv_mfma2_kernel<4, HALO_, false, 4, false, 2, 2, PREC_, 8, false, IOS_, false, K64_, true>), gridk, dim3(512), 0, st, k);          \
+    if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<HALO_, true, 4, 2, PREC_, 8, false, IOS_, false, K64_, true>), gridk, dim3(512), 0, st, k);   \
+    else PPST_LAUNCH((conv_mfma2_kernel<HALO_, false, 4, 2, PREC_, 8, false, IOS_, false, K64_, true>), gridk, dim3(512), 0, st, k);          \
   } while (0)
     if (a->precision == 0) { if (a->halo) LKS(1, 0, PPST_ST_F32, false); else LKS(0, 0, PPST_ST_F32, false); }
     else if (a->precision == 1) { if (a->k64) LKS(1, 1, PPST_ST_BF16, true); else if (a->halo) LKS(1, 1, PPST_ST_BF16, false); else LKS(0, 1, PPST_ST_BF16, false); }
@@ -844,14 +798,14 @@ int ppst_conv2d_mfma2_launch(const ppst_conv_args* a, int n_tiles, int tiles_y, 
 #define LK(PREC_, IOS_)                                                                                          \
   do {                                                                                                          \
     if (a->variant == 2 && a->dual_b) {                                                                         \
-      if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<4, 1, true, 4, false, 2, 2, PREC_, 8, true, IOS_, false, true>), grid, dim3(512), 0, st, k);   \
-      else PPST_LAUNCH((conv_mfma2_kernel<4, 1, false, 4, false, 2, 2, PREC_, 8, true, IOS_, false, true>), grid, dim3(512), 0, st, k);          \
+      if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<1, true, 4, 2, PREC_, 8, true, IOS_, false, true>), grid, dim3(512), 0, st, k);   \
+      else PPST_LAUNCH((conv_mfma2_kernel<1, false, 4, 2, PREC_, 8, true, IOS_, false, true>), grid, dim3(512), 0, st, k);          \
     } else if (a->variant == 2 && a->halo) {                                                                    \
-      if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<4, 1, true, 4, false, 2, 2, PREC_, 8, false, IOS_, false, true>), grid, dim3(512), 0, st, k);  \
-      else PPST_LAUNCH((conv_mfma2_kernel<4, 1, false, 4, false, 2, 2, PREC_, 8, false, IOS_, false, true>), grid, dim3(512), 0, st, k);         \
+      if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<1, true, 4, 2, PREC_, 8, false, IOS_, false, true>), grid, dim3(512), 0, st, k);  \
+      else PPST_LAUNCH((conv_mfma2_kernel<1, false, 4, 2, PREC_, 8, false, IOS_, false, true>), grid, dim3(512), 0, st, k);         \
     } else if (a->variant == 9 && a->halo) {   /* Cout = 128-class layers: 24 x 16 px x 128 ch tiles (two 61-KB activation slots) */ \
-      if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<4, 1, true, 2, false, 2, 4, PREC_, 6, false, IOS_, false, true>), grid, dim3(512), 0, st, k);  \
-      else PPST_LAUNCH((conv_mfma2_kernel<4, 1, false, 2, false, 2, 4, PREC_, 6, false, IOS_, false, true>), grid, dim3(512), 0, st, k);         \
+      if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<1, true, 2, 4, PREC_, 6, false, IOS_, false, true>), grid, dim3(512), 0, st, k);  \
+      else PPST_LAUNCH((conv_mfma2_kernel<1, false, 2, 4, PREC_, 6, false, IOS_, false, true>), grid, dim3(512), 0, st, k);         \
     } else return PPST_EINVAL;                                                                                  \
   } while (0)
     if (a->precision == 3) LK(3, PPST_ST_F16); else LK(1, PPST_ST_BF16);
@@ -859,28 +813,18 @@ int ppst_conv2d_mfma2_launch(const ppst_conv_args* a, int n_tiles, int tiles_y, 
     return PPST_LAUNCH_CHECK();
   }
   if (a->variant == 11) {     // the fused upscale as nine products per input pixel + box sum (UP9); shape conditions checked by the entry point
-    PPST_LAUNCH((conv_mfma2_kernel<4, 1, false, 4, false, 2, 2, 0, 8, false, PPST_ST_F32, true>), grid, dim3(512), 0, st, k);
+    PPST_LAUNCH((conv_mfma2_kernel<1, false, 4, 2, 0, 8, false, PPST_ST_F32, true>), grid, dim3(512), 0, st, k);
     return PPST_LAUNCH_CHECK();
   }
-#define L2(NT_, HALO_, WNW_, BDB_, NA_)                                                                         \
+#define L2(HALO_)                                                                                               \
   do {                                                                                                          \
-    if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<NT_, HALO_, true, WNW_, BDB_, NA_>), grid, dim3(128 * WNW_), 0, st, k);  \
-    else PPST_LAUNCH((conv_mfma2_kernel<NT_, HALO_, false, WNW_, BDB_, NA_>), grid, dim3(128 * WNW_), 0, st, k);         \
-  } while (0)
-#define L7(HALO_)                                                                                               \
-  do {                                                                                                          \
-    if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<4, HALO_, true, 2, false, 1, 4>), grid, dim3(512), 0, st, k);   \
-    else PPST_LAUNCH((conv_mfma2_kernel<4, HALO_, false, 2, false, 1, 4>), grid, dim3(512), 0, st, k);          \
-  } while (0)
-#define L9(HALO_)                                                                                               \
-  do {                                                                                                          \
-    if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<4, HALO_, true, 2, false, 2, 4, 0, 6>), grid, dim3(512), 0, st, k);   \
-    else PPST_LAUNCH((conv_mfma2_kernel<4, HALO_, false, 2, false, 2, 4, 0, 6>), grid, dim3(512), 0, st, k);          \
+    if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<HALO_, true, 4>), grid, dim3(512), 0, st, k);                   \
+    else PPST_LAUNCH((conv_mfma2_kernel<HALO_, false, 4>), grid, dim3(512), 0, st, k);                          \
   } while (0)
 #define L2Q(HALO_, PREC_, IOS_)                                                                                 \
   do {                                                                                                          \
-    if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<4, HALO_, true, 4, false, 2, 2, PREC_, 8, false, IOS_>), grid, dim3(512), 0, st, k);   \
-    else PPST_LAUNCH((conv_mfma2_kernel<4, HALO_, false, 4, false, 2, 2, PREC_, 8, false, IOS_>), grid, dim3(512), 0, st, k);          \
+    if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<HALO_, true, 4, 2, PREC_, 8, false, IOS_>), grid, dim3(512), 0, st, k);   \
+    else PPST_LAUNCH((conv_mfma2_kernel<HALO_, false, 4, 2, PREC_, 8, false, IOS_>), grid, dim3(512), 0, st, k);          \
   } while (0)
 #define L2P(HALO_, PREC_)                                                                                       \
   do {                                                                                                          \
@@ -888,8 +832,8 @@ int ppst_conv2d_mfma2_launch(const ppst_conv_args* a, int n_tiles, int tiles_y, 
   } while (0)
 #define L2D(PREC_, IOS_)                                                                                        \
   do {                                                                                                          \
-    if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<4, 1, true, 4, false, 2, 2, PREC_, 8, true, IOS_>), grid, dim3(512), 0, st, k);   \
-    else PPST_LAUNCH((conv_mfma2_kernel<4, 1, false, 4, false, 2, 2, PREC_, 8, true, IOS_>), grid, dim3(512), 0, st, k);          \
+    if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<1, true, 4, 2, PREC_, 8, true, IOS_>), grid, dim3(512), 0, st, k);   \
+    else PPST_LAUNCH((conv_mfma2_kernel<1, false, 4, 2, PREC_, 8, true, IOS_>), grid, dim3(512), 0, st, k);          \
   } while (0)
   if (a->variant == 2 && a->dual_b) {     // Cout % 128 == 0 fused upscale as two phase pairs (halo 1)
     if (a->precision == 3) { if (a->io_st) L2D(3, PPST_ST_F16); else L2D(3, PPST_ST_F32); }
@@ -901,8 +845,8 @@ int ppst_conv2d_mfma2_launch(const ppst_conv_args* a, int n_tiles, int tiles_y, 
   // ceiling on 128 -> 128 @1024^2, bound by fragment reads and barriers per MFMA
 #define L7Q(HALO_, PREC_, IOS_)                                                                                 \
   do {                                                                                                          \
-    if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<4, HALO_, true, 2, false, 2, 4, PREC_, 8, false, IOS_>), grid, dim3(512), 0, st, k);   \
-    else PPST_LAUNCH((conv_mfma2_kernel<4, HALO_, false, 2, false, 2, 4, PREC_, 8, false, IOS_>), grid, dim3(512), 0, st, k);          \
+    if (k.in_ss) PPST_LAUNCH((conv_mfma2_kernel<HALO_, true, 2, 4, PREC_, 8, false, IOS_>), grid, dim3(512), 0, st, k);   \
+    else PPST_LAUNCH((conv_mfma2_kernel<HALO_, false, 2, 4, PREC_, 8, false, IOS_>), grid, dim3(512), 0, st, k);          \
   } while (0)
 #define L7P(PREC_)                                                                                              \
   do {                                                                                                          \
@@ -915,20 +859,9 @@ int ppst_conv2d_mfma2_launch(const ppst_conv_args* a, int n_tiles, int tiles_y, 
   if (a->variant == 2 && a->precision == 1) { if (a->halo) L2P(1, 1); else L2P(0, 1); }
   else if (a->variant == 2 && a->precision == 3) { if (a->halo) L2P(1, 3); else L2P(0, 3); }
   else if (a->variant == 2) {            // 8 waves, wave tile 128 px x 64 ch, N tile 256: the production form
-    if (a->halo) L2(4, 1, 4, false, 2); else L2(4, 0, 4, false, 2);
+    if (a->halo) L2(1); else L2(0);
   }
-#ifdef PPST_EXPERIMENTS                  // measured and off: only in a PPST_EXPERIMENTS=1 build
-  else if (a->variant == 9) {                 // 8 waves = 4 (M) x 2 (N), wave tile 96 px x 64 ch, block 24 x 16 px x 128 ch, two slots
-    if (a->halo) L9(1); else L9(0);
-  } else if (a->variant == 7) {                 // 8 waves = 4 (M) x 2 (N), wave tile 128 px x 64 ch, block 32 x 16 px x 128 ch, one slot
-    if (a->halo) L7(1); else L7(0);
-  } else if (a->variant == 3) {          // two 4-wave blocks per CU, wave tile 128 px x 64 ch, N tile 128, one activation slot
-    if (a->halo) L2(4, 1, 2, false, 1); else L2(4, 0, 2, false, 1);
-  } else if (a->bn == 256) { if (a->halo) L2(8, 1, 2, true, 2); else L2(8, 0, 2, true, 2); }
-  else { if (a->halo) L2(4, 1, 2, true, 2); else L2(4, 0, 2, true, 2); }
-#else
   else return PPST_EINVAL;
-#endif
 #undef L2
   return PPST_LAUNCH_CHECK();
 }

@@ -58,20 +58,8 @@ __device__ __forceinline__ int wino_pad_index(int i, int n, int mode) {
   return i < 0 ? 0 : (i >= n ? n - 1 : i);
 }
 
-// Timing ablations (tests/build_wino_variant.sh; results WRONG on purpose): -DWINO_ABL_NOB no weight-fragment loads in the loop,
-// -DWINO_ABL_NOSTAGE no activation staging in the loop, -DWINO_ABL_NOSTSTORE its loads only, -DWINO_ABL_NOLDSW its arithmetic
-// without the LDS stores, -DWINO_ABL_NOA no LDS fragment reads, -DWINO_ABL_NOMFMA no MFMAs, -DWINO_ABL_NOEPI no output transform /
-// epilogue, -DWINO_ABL_NOBAR no chunk barrier (races).  Their numbers: DESIGN.md section 4 (j).
-#ifdef WINO_ABL_NOA
-#define WINO_LDA(dst, off, keep) dst = keep
-#else
-#define WINO_LDA(dst, off, keep) dst = *(const bf16x8*)(smem + (off))
-#endif
-#ifdef WINO_ABL_NOMFMA
-#define WINO_MFMA(a_, b_, c_) asm volatile("" ::"v"(a_), "v"(b_))
-#else
+#define WINO_LDA(dst, off) dst = *(const bf16x8*)(smem + (off))
 #define WINO_MFMA(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_, b_, c_, 0, 0, 0)
-#endif
 #define WINO_STEP_BYTES 8192   // one wave's weight fragments of one K-step: 4 n-tiles x (hi | lo) x 64 lanes x 16 B
 #define WINO_OOB ((int)0x80000000)   // buffer-load offset of a padding item: out of range of every image (< 2^31 bytes) -> zeros
 
@@ -79,15 +67,11 @@ __device__ __forceinline__ int wino_pad_index(int i, int n, int mode) {
 // plain instructions (microarch guide), and this kernel's staging runs in the MFMA stream.  Same conversions, same subtraction:
 // bit-identical to split_bf16x4.
 __device__ __forceinline__ void wino_split4(float4 v, uint2& hi, uint2& lo) {
-#ifdef WINO_PK_SPLIT
-  split_bf16x4(v, hi, lo);
-#else
   const unsigned h0 = f2bf_pk((ppst_f2){v.x, v.y}), h1 = f2bf_pk((ppst_f2){v.z, v.w});
   const float rx = v.x - __uint_as_float(h0 << 16), ry = v.y - __uint_as_float(h0 & 0xffff0000u);
   const float rz = v.z - __uint_as_float(h1 << 16), rw = v.w - __uint_as_float(h1 & 0xffff0000u);
   hi = make_uint2(h0, h1);
   lo = make_uint2(f2bf_pk((ppst_f2){rx, ry}), f2bf_pk((ppst_f2){rz, rw}));
-#endif
 }
 
 // the value of lane ^ 8 (row_ror:8 -- a rotation by 8 inside each row of 16 lanes); hipcc folds the move into the consuming VALU
@@ -107,15 +91,11 @@ __device__ __forceinline__ int wino_lane() {
 }
 
 // INMODE: normalise on load -- 0 off, 1 affine only (in_act none: the StyledConv conv2 case), 2 affine + activation
-// FAT: four waves (ONE per SIMD, up to 512 registers) instead of eight: a wave takes a transform position with all 128 channels
-// (wave tile 128 pairs x 128 ch, 256 accumulator registers), reads every A fragment ONCE per K-step (16 ds_read_b128 per 192 MFMAs
-// instead of 32 per 96 ... reloaded half a step ahead) and has no SIMD
-// partner running the same program phase.
-template <int INMODE, bool FAT, bool KS = false>
-__global__ __launch_bounds__(FAT ? 256 : 512, FAT ? 1 : 2) void conv_wino_kernel(WinoKArgs a) {
+template <int INMODE, bool KS = false>
+__global__ __launch_bounds__(512, 2) void conv_wino_kernel(WinoKArgs a) {
   constexpr bool INSS = INMODE != 0;
-  constexpr int NWV = FAT ? 4 : 8, NTH = 64 * NWV, NTW = FAT ? 8 : 4;      // waves, threads, n-tiles per wave
-  constexpr int NRND = FAT ? 5 : 3;                                        // halo rows a wave stages per chunk: wave + NWV * round
+  constexpr int NWV = 8, NTH = 64 * NWV, NTW = 4;                          // waves, threads, n-tiles per wave
+  constexpr int NRND = 3;                                                  // halo rows a wave stages per chunk: wave + NWV * round
   constexpr int NP = 8, HH = 18;
   constexpr int PLANE = HH * NP * 16;      // one k-group plane of one transform position: 2304 B (a multiple of 256)
   constexpr int XIB = 8 * PLANE;           // hi g0..3 | lo g0..3
@@ -143,7 +123,7 @@ __global__ __launch_bounds__(FAT ? 256 : 512, FAT ? 1 : 2) void conv_wino_kernel
   const int ty0 = tyi * 16, tx0 = txi * 16;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int xi = FAT ? wave : wave >> 1, nh = FAT ? 0 : wave & 1;
+  const int xi = wave >> 1, nh = wave & 1;
   const int r16 = lane & 15, g = lane >> 4;
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -154,7 +134,7 @@ __global__ __launch_bounds__(FAT ? 256 : 512, FAT ? 1 : 2) void conv_wino_kernel
   StepPtr steps = (StepPtr)a.steps;
   // across-block K split (ppst_conv_args.ksplit, conv_mfma.hip): this block's chunks; its weight stream starts 3 c0 steps in
   int nchunk = a.nchunk, c0 = 0;
-  if (KS && !FAT && a.ks.S > 1) {      // (instances of their own: the plain ones -- the swap path's -- keep their register allocation)
+  if (KS && a.ks.S > 1) {      // (instances of their own: the plain ones -- the swap path's -- keep their register allocation)
     int s0, s1;
     ks_range(a.ks, (int)blockIdx.y, s0, s1);
     c0 = s0 / 9;
@@ -274,20 +254,12 @@ __global__ __launch_bounds__(FAT ? 256 : 512, FAT ? 1 : 2) void conv_wino_kernel
       V0 = make_float4(wino_swap1(B0_.x) + sgn * B0_.x, wino_swap1(B0_.y) + sgn * B0_.y, wino_swap1(B0_.z) + sgn * B0_.z, wino_swap1(B0_.w) + sgn * B0_.w);
       V1 = make_float4(wino_swap1(B1_.x) + sgn * B1_.x, wino_swap1(B1_.y) + sgn * B1_.y, wino_swap1(B1_.z) + sgn * B1_.z, wino_swap1(B1_.w) + sgn * B1_.w);
     }
-#ifdef WINO_ABL_NOSTSTORE
-    asm volatile("" ::"v"(V0.x), "v"(V0.y), "v"(V0.z), "v"(V0.w), "v"(V1.x), "v"(V1.y), "v"(V1.z), "v"(V1.w));
-    return;
-#endif
     uint2 h0, l0, h1, l1;
     wino_split4(V0, h0, l0);
     wino_split4(V1, h1, l1);
     unsigned char* dst = smem + (slot * ABUF + hrow * NP * 16) + i * XIB + stb;
-#ifdef WINO_ABL_NOLDSW       /* the arithmetic without the LDS stores */
-    asm volatile("" ::"v"(h0.x), "v"(h0.y), "v"(l0.x), "v"(l0.y), "v"(h1.x), "v"(h1.y), "v"(l1.x), "v"(l1.y));
-#else
     *(uint4*)dst = make_uint4(h0.x, h0.y, h1.x, h1.y);
     *(uint4*)(dst + 4 * PLANE) = make_uint4(l0.x, l0.y, l1.x, l1.y);
-#endif
   };
 
   // ---- weight fragments: this wave's stream [step][n-tile 0..3][hi | lo][lane][16 B], straight into registers
@@ -295,12 +267,9 @@ __global__ __launch_bounds__(FAT ? 256 : 512, FAT ? 1 : 2) void conv_wino_kernel
   const int64_t woff_ = ((((int64_t)ntile * 4 + xi) * 2 + nh) * (a.nchunk * 3) + c0 * 3) * WINO_STEP_BYTES;
   const unsigned char* wbase = a.wpack + (((int64_t)__builtin_amdgcn_readfirstlane((int)(woff_ >> 32)) << 32) |
                                           (unsigned)__builtin_amdgcn_readfirstlane((int)woff_));
-  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)wbase, 0, (FAT ? 2 : 1) * nsteps * WINO_STEP_BYTES, 0x00020000);
+  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)wbase, 0, nsteps * WINO_STEP_BYTES, 0x00020000);
   bf16x8 B0[2][2], B1[2][2];      // [n-tile of the half][hi, lo]
   auto load_b = [&](bf16x8 (&dst)[2][2], int s, int half) __attribute__((always_inline)) {
-#ifdef WINO_ABL_NOB
-    if (s > 0) return;
-#endif
     const int so = s * WINO_STEP_BYTES + half * 4096;
     const int lo16 = wino_lane() * 16;
 #pragma unroll
@@ -310,28 +279,10 @@ __global__ __launch_bounds__(FAT ? 256 : 512, FAT ? 1 : 2) void conv_wino_kernel
         dst[n][h] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, lo16 + (n * 2 + h) * 1024, so, 0));
   };
 
-  // (FAT) both halves of a step as one set of eight n-tiles; two sets: the next step's is requested at the top of this one
-  bf16x8 BxA[FAT ? 4 : 1][2], BxB[FAT ? 4 : 1][2];       // (FAT) n-tiles 0-3 / 4-7: each reloaded for the next step behind its half
-  auto load_b4 = [&](bf16x8 (&dst)[FAT ? 4 : 1][2], int st_, int half) __attribute__((always_inline)) {
-    if (!FAT) return;
-#ifdef WINO_ABL_NOB
-    if (st_ > 0) return;
-#endif
-    // (the pack keeps the two channel halves of a position as two streams of steps: n-tiles 4..7 come from the second)
-    const int so = st_ * WINO_STEP_BYTES + half * nsteps * WINO_STEP_BYTES;
-    const int lo16 = wino_lane() * 16;
-#pragma unroll
-    for (int n = 0; n < (FAT ? 4 : 1); ++n)
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-        dst[n][h] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, lo16 + (n * 2 + h) * 1024, so, 0));
-  };
-
   // ---- prologue: every request of the block's first chunk goes out at once (weight fragments of step 0, the halo rows, the
   // (a, s) table) -- the accumulators are not live yet, so every row has its register set -- then chunk 0 is staged into slot 0.
   // (Row by row with the weight request last: +-1.5 %, and the plain build then spills in its loop.)
-  if (FAT) { load_b4(BxA, 0, 0); load_b4(BxB, 0, 1); }
-  else { load_b(B0, 0, 0); load_b(B1, 0, 1); }
+  load_b(B0, 0, 0); load_b(B1, 0, 1);
   {
     float4 q[NRND][4];
 #pragma unroll
@@ -359,86 +310,6 @@ __global__ __launch_bounds__(FAT ? 256 : 512, FAT ? 1 : 2) void conv_wino_kernel
 
 #define WA_OFF(slot, dy, mt) ((slot) * ABUF + xi * XIB + g * PLANE + ((2 * (mt) + (dy)) * NP + r16) * 16)
   int s = 0;
-  if constexpr (FAT) {
-    // One wave per SIMD: the step is ONE stream of 192 MFMAs (8 m-tiles x 8 n-tiles x 3) with everything else in its gaps -- per
-    // m-tile one A fragment request (pinned one m-tile ahead), and the two halo rows of the step transformed piecewise between
-    // the m-tiles.  The next step's weight fragments (16 KB) go out at the top of the step into the other register set.
-    float4 rd2[4];
-    bf16x8 ah, al;
-    int slot = 0, chan_next = 0, aoff0 = 0;
-    // one K-step = two halves (n-tiles 0-3 with set A, 4-7 with set B): 96 MFMAs each; a set is reloaded for the next step right
-    // behind its half, i.e. half a step (~1.5 k cycles) ahead of its use.  The step's two halo rows are transformed piecewise
-    // between the m-tiles: round r0 in the first half, r1 in the second.
-    auto step_fat = [&](auto dy_c) __attribute__((always_inline)) {
-      constexpr int dy = decltype(dy_c)::value;
-      const int sn = s + 1 < nsteps ? s + 1 : s;
-      constexpr int r0 = 2 * dy, r1 = dy < 2 ? 2 * dy + 1 : 0;
-      stage_load(rd, r0, chan_next);
-      if (dy < 2) stage_load(rd2, r1, chan_next);
-      __builtin_amdgcn_sched_barrier(0);
-      const bool skip0 = stage_skip(r0);
-      int aoff1 = aoff0;
-      asm volatile("" : "+v"(aoff1));
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-#pragma unroll
-        for (int mt = 0; mt < 8; ++mt) {
-          bf16x8 nh_ = ah, nl_ = al;
-          if (mt < 7) {
-            WINO_LDA(nh_, (half ? aoff1 : aoff0) + (2 * (mt + 1) + dy) * NP * 16, ah);
-            WINO_LDA(nl_, (half ? aoff1 : aoff0) + (2 * (mt + 1) + dy) * NP * 16 + 4 * PLANE, al);
-          } else if (half == 0) {
-            WINO_LDA(nh_, aoff1 + dy * NP * 16, ah);
-            WINO_LDA(nl_, aoff1 + dy * NP * 16 + 4 * PLANE, al);
-          } else if (dy < 2) {
-            WINO_LDA(nh_, aoff0 + (dy + 1) * NP * 16, ah);
-            WINO_LDA(nl_, aoff0 + (dy + 1) * NP * 16 + 4 * PLANE, al);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          if (half == 0 && !skip0) {
-            if (mt == 3) stage_prep(rd, r0, chan_next, 0);
-            if (mt == 4) stage_prep(rd, r0, chan_next, 1);
-            if (mt == 5) stage_put(rd, r0, slot ^ 1, 0);
-            if (mt == 6) stage_put(rd, r0, slot ^ 1, 1);
-          }
-          if (half == 1 && dy < 2) {                        // (rounds 1 and 3 exist for every wave)
-            if (mt == 1) stage_prep(rd2, r1, chan_next, 0);
-            if (mt == 2) stage_prep(rd2, r1, chan_next, 1);
-            if (mt == 3) stage_put(rd2, r1, slot ^ 1, 0);
-            if (mt == 4) stage_put(rd2, r1, slot ^ 1, 1);
-          }
-#pragma unroll
-          for (int n = 0; n < 4; ++n) {
-            if (half == 0) {
-              WINO_MFMA(al, BxA[n][0], acc[mt][n]);
-              WINO_MFMA(ah, BxA[n][1], acc[mt][n]);
-              WINO_MFMA(ah, BxA[n][0], acc[mt][n]);
-            } else {
-              WINO_MFMA(al, BxB[n][0], acc[mt][4 + n]);
-              WINO_MFMA(ah, BxB[n][1], acc[mt][4 + n]);
-              WINO_MFMA(ah, BxB[n][0], acc[mt][4 + n]);
-            }
-          }
-          ah = nh_;
-          al = nl_;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (half == 0) load_b4(BxA, sn, 0); else load_b4(BxB, sn, 1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      ++s;
-    };
-    auto chunk_fat = [&](int c) __attribute__((always_inline)) {
-      slot = c & 1;
-      chan_next = steps[(c + 1 < nchunk ? c + 1 : c) * 9].x;
-      aoff0 = WA_OFF(slot, 0, 0);
-      ah = *(const bf16x8*)(smem + aoff0);
-      al = *(const bf16x8*)(smem + aoff0 + 4 * PLANE);
-      step_fat(EpiC<0>{}); step_fat(EpiC<1>{}); step_fat(EpiC<2>{});
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    };
-    for (int c = 0; c < nchunk; ++c) chunk_fat(c);
-  } else {
   // A fragment of m-tile mt (tile rows 2 mt, 2 mt + 1; 8 pairs each) for tap row dy: halo rows 2 mt + dy, 2 mt + dy + 1.
   //
   // Every vector-memory instruction of the loop is UNCONDITIONAL (the last step re-requests its own weight fragments, the last
@@ -460,20 +331,18 @@ __global__ __launch_bounds__(FAT ? 256 : 512, FAT ? 1 : 2) void conv_wino_kernel
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
       const int sn = s + 1 < nsteps ? s + 1 : s;
-#ifndef WINO_ABL_NOSTAGE
       stage_load(rd, dy, chan_next);
-#endif
       __builtin_amdgcn_sched_barrier(0);
       // half 0: n-tiles 0, 1
 #pragma unroll
       for (int mt = 0; mt < 8; ++mt) {
         bf16x8 nh_, nl_;
         if (mt < 7) {
-          WINO_LDA(nh_, aoff0 + (2 * (mt + 1) + dy) * NP * 16, ah);
-          WINO_LDA(nl_, aoff0 + (2 * (mt + 1) + dy) * NP * 16 + 4 * PLANE, al);
+          WINO_LDA(nh_, aoff0 + (2 * (mt + 1) + dy) * NP * 16);
+          WINO_LDA(nl_, aoff0 + (2 * (mt + 1) + dy) * NP * 16 + 4 * PLANE);
         } else {                                            // (the second half starts over at m-tile 0)
-          WINO_LDA(nh_, aoff1 + dy * NP * 16, ah);
-          WINO_LDA(nl_, aoff1 + dy * NP * 16 + 4 * PLANE, al);
+          WINO_LDA(nh_, aoff1 + dy * NP * 16);
+          WINO_LDA(nl_, aoff1 + dy * NP * 16 + 4 * PLANE);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -489,28 +358,24 @@ __global__ __launch_bounds__(FAT ? 256 : 512, FAT ? 1 : 2) void conv_wino_kernel
       load_b(B0, sn, 0);
       __builtin_amdgcn_sched_barrier(0);
       // half 1: n-tiles 2, 3
-#ifndef WINO_ABL_NOSTAGE
       const bool skip = stage_skip(dy);
-#endif
 #pragma unroll
       for (int mt = 0; mt < 8; ++mt) {
         bf16x8 nh_ = ah, nl_ = al;
         if (mt < 7) {
-          WINO_LDA(nh_, aoff1 + (2 * (mt + 1) + dy) * NP * 16, ah);
-          WINO_LDA(nl_, aoff1 + (2 * (mt + 1) + dy) * NP * 16 + 4 * PLANE, al);
+          WINO_LDA(nh_, aoff1 + (2 * (mt + 1) + dy) * NP * 16);
+          WINO_LDA(nl_, aoff1 + (2 * (mt + 1) + dy) * NP * 16 + 4 * PLANE);
         } else if (dy < 2) {
-          WINO_LDA(nh_, aoff0 + (dy + 1) * NP * 16, ah);
-          WINO_LDA(nl_, aoff0 + (dy + 1) * NP * 16 + 4 * PLANE, al);
+          WINO_LDA(nh_, aoff0 + (dy + 1) * NP * 16);
+          WINO_LDA(nl_, aoff0 + (dy + 1) * NP * 16 + 4 * PLANE);
         }
         __builtin_amdgcn_sched_barrier(0);
-#ifndef WINO_ABL_NOSTAGE
         if (!skip) {           // (the last chunk writes the dead slot once more: harmless, and no branch around the loads)
           if (mt == 2) stage_prep(rd, dy, chan_next, 0);
           if (mt == 3) stage_prep(rd, dy, chan_next, 1);
           if (mt == 4) stage_put(rd, dy, slot ^ 1, 0);
           if (mt == 6) stage_put(rd, dy, slot ^ 1, 1);
         }
-#endif
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
           WINO_MFMA(al, B1[n][0], acc[mt][2 + n]);
@@ -527,18 +392,13 @@ __global__ __launch_bounds__(FAT ? 256 : 512, FAT ? 1 : 2) void conv_wino_kernel
     }
     // chunk c + 1 is complete in its slot; every wave has left chunk c's.  (Raw barrier: the fence inside __syncthreads() would
     // drain vmcnt, i.e. wait for the weight fragments just requested for the next step.)
-#ifdef WINO_ABL_NOBAR
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-  }
   }
 #undef WA_OFF
 
   // ---- across-block K split: the partial sums are exchanged in the TRANSFORM domain (the output transform is linear): rows
   // 0 .. S-2 hand their 128 accumulator registers over and leave, row S-1 adds them (row order) and goes on
-  if (KS && !FAT && a.ks.S > 1) {
+  if (KS && a.ks.S > 1) {
     const int S = a.ks.S, y = (int)blockIdx.y;
     float* const slot0 = a.ks.scratch + (int64_t)wid * (S - 1) * (8 * NTW * 4 * NTH) + tid;
     if (y < S - 1) {
@@ -639,13 +499,6 @@ __global__ __launch_bounds__(FAT ? 256 : 512, FAT ? 1 : 2) void conv_wino_kernel
       }
     }
   };
-#ifdef WINO_ABL_NOEPI
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < NTW; ++j) asm volatile("" ::"v"(acc[i][j]));
-  if (a.B < 0)
-#endif
   if (act == PPST_ACT_LRELU) epi_passes(EpiC<PPST_ACT_LRELU>{});
   else if (act == PPST_ACT_PRELU) epi_passes(EpiC<PPST_ACT_PRELU>{});
   else epi_passes(EpiC<PPST_ACT_NONE>{});
@@ -690,7 +543,6 @@ int ppst_conv_wino_launch(const ppst_conv_args* a, int n_tiles, int tiles_y, int
   k.in_c = a->in_c; k.in_act = a->in_act;
   const int blocks = n_tiles * a->B * tiles_y * tiles_x;
   k.ks.scratch = nullptr; k.ks.flags = nullptr; k.ks.epoch = 0; k.ks.S = 1;
-#ifndef WINO_FAT
   if (a->ksplit > 1) {        // across-block K split: whole chunks per block (k.nchunk % S == 0 follows from nsteps % S with 9-step chunks
                               // only if the caller kept its promise; checked here)
     if (!a->ksplit_starts && k.nchunk % a->ksplit) return PPST_EINVAL;
@@ -699,24 +551,17 @@ int ppst_conv_wino_launch(const ppst_conv_args* a, int n_tiles, int tiles_y, int
     for (int i = 1; i < a->ksplit; ++i)
       if (k.ks.start[i] % 9) return PPST_EINVAL;           // whole chunks per block
   }
-#endif
   if (k.ks.S > 1) {
     const dim3 gridk(blocks, k.ks.S);
-    if (k.in_ss && k.in_act != PPST_ACT_NONE) PPST_LAUNCH((conv_wino_kernel<2, false, true>), gridk, dim3(512), 0, st, k);
-    else if (k.in_ss) PPST_LAUNCH((conv_wino_kernel<1, false, true>), gridk, dim3(512), 0, st, k);
-    else PPST_LAUNCH((conv_wino_kernel<0, false, true>), gridk, dim3(512), 0, st, k);
+    if (k.in_ss && k.in_act != PPST_ACT_NONE) PPST_LAUNCH((conv_wino_kernel<2, true>), gridk, dim3(512), 0, st, k);
+    else if (k.in_ss) PPST_LAUNCH((conv_wino_kernel<1, true>), gridk, dim3(512), 0, st, k);
+    else PPST_LAUNCH((conv_wino_kernel<0, true>), gridk, dim3(512), 0, st, k);
     return PPST_LAUNCH_CHECK();
   }
   const dim3 grid(blocks);
-#ifdef WINO_FAT
-  if (k.in_ss && k.in_act != PPST_ACT_NONE) PPST_LAUNCH((conv_wino_kernel<2, true>), dim3(blocks), dim3(256), 0, st, k);
-  else if (k.in_ss) PPST_LAUNCH((conv_wino_kernel<1, true>), dim3(blocks), dim3(256), 0, st, k);
-  else PPST_LAUNCH((conv_wino_kernel<0, true>), dim3(blocks), dim3(256), 0, st, k);
-#else
-  if (k.in_ss && k.in_act != PPST_ACT_NONE) PPST_LAUNCH((conv_wino_kernel<2, false>), grid, dim3(512), 0, st, k);
-  else if (k.in_ss) PPST_LAUNCH((conv_wino_kernel<1, false>), grid, dim3(512), 0, st, k);
-  else PPST_LAUNCH((conv_wino_kernel<0, false>), grid, dim3(512), 0, st, k);
-#endif
+  if (k.in_ss && k.in_act != PPST_ACT_NONE) PPST_LAUNCH((conv_wino_kernel<2>), grid, dim3(512), 0, st, k);
+  else if (k.in_ss) PPST_LAUNCH((conv_wino_kernel<1>), grid, dim3(512), 0, st, k);
+  else PPST_LAUNCH((conv_wino_kernel<0>), grid, dim3(512), 0, st, k);
   return PPST_LAUNCH_CHECK();
 }
 

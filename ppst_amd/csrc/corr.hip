@@ -389,9 +389,6 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void gemm_split
   // iteration earlier) waits in the other set -- a full iteration of MFMAs between a request and its first use
   float4 ra0[FA], rb0[FB], ra1[FA], rb1[FB];
   auto g_load = [&](float4 (&ra)[FA], float4 (&rb)[FB], int k0) {
-#if defined(GEMM_ABL) && (GEMM_ABL & 4)
-    if (kb >= 0) return;
-#endif
     const int sa_off = k0 * 4, sb_off = B_NT ? k0 * 4 : k0 * ldb * 4;
 #pragma unroll
     for (int it = 0; it < FA; ++it)
@@ -417,9 +414,6 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void gemm_split
     }
   };
   auto s_store = [&](const float4 (&ra)[FA], const float4 (&rb)[FB], int buf) {
-#if defined(GEMM_ABL) && (GEMM_ABL & 2)
-    if (kb >= 0) return;
-#endif
     unsigned char* const sa = smem + buf * STAGE;
     unsigned char* const sb = sa + NP * PL_A;
 #pragma unroll
@@ -457,9 +451,6 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void gemm_split
   const int g = lane >> 4, qd = (lane & 15) >> 2, pp = lane & 3;
   const int tr_off = (8 * (g >> 1) + qd) * 64 + (16 * (g & 1) + 4 * pp) * 2;
   auto compute = [&](int buf) {
-#if defined(GEMM_ABL) && (GEMM_ABL & 1)
-    if (kb >= 0) return;
-#endif
     const unsigned char* const sa = smem + buf * STAGE;
     const unsigned char* const sb = sa + NP * PL_A;
 #pragma unroll

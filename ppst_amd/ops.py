@@ -21,11 +21,8 @@ RES_BEFORE_ACT = 1 << 8
 
 PRECISION = {"value": 0}  # 0 = bf16x3 (fp32-class), 1 = single-pass bf16
 TILE_ROWS = {"value": 16}  # conv tile rows: 8 (2 blocks per CU) or 16 (1 block per CU)
-# 1: layers whose step table allows it run on the fat-wave kernel (conv_mfma2.hip: 4 waves, 128-px x 64/128-ch wave
-# tiles, N tile 128 or 256); 0 (default): everything on the 8-wave kernel.  Measured on MI355X (round 2, same process
-# class of runs, tests/conv_table.py): the fat-wave kernel is bit-identical but SLOWER -- 256->256@256^2 395 vs 417 TF/s
-# with the 256-channel tile, 128->128@512^2 261 vs 356 with the 128-channel tile; whole step 284-294 vs 330 TF/s: one
-# in-order wave per SIMD exposes its own LDS / wait latency, which two co-resident waves hide for each other.
+# 0: everything on the 8-wave tile kernel (conv_mfma.hip).  (1 and 3 were the one-wave-per-SIMD and the two-block forms of
+# conv_mfma2.hip: measured slower -- DESIGN.md section 4 -- and removed; choose_kernel refuses them.)
 # 2 (default since round 2): layers with Cout % 256 == 0 whose grid still covers the chip run on the 8-wave kernel with
 # 128 px x 64 ch wave tiles and a 256-channel N tile (conv_mfma2.hip, WNW = 4): bit-identical to the 64x64-wave-tile kernel
 # and 10-16 % faster on those layers (256->256 @256^2 459 vs 417 TFLOP/s, 512->512 @128^2 494 vs 440).
@@ -43,9 +40,6 @@ DIRECT_MAX = {"cout": 64, "nsteps": 40, "cout3x3": 64}   # cout3x3 = 128 was mea
 WGRAD_SPLIT = {"blocks": 1024, "min_tiles": 4}   # conv_wgrad: target block count of a launch, fewest pixel tiles per block
 WGRAD_X3 = {"value": True}         # conv weight gradients on the bf16 matrix pipe (hi/lo split), exact fp32 with precision 2
 STREAM_1X1 = {"value": True}       # 1x1 convs (halo 0) on the streaming kernel of conv1x1.hip
-# variant 8 (conv_ksplit.hip: the block's waves split K in two, 128 px x 64 ch wave tiles, two activation slots) for the
-# Cout = 128-class layers when one image gives >= min_blocks: measured 3-7 % SLOWER than the tile kernel (128->128 @512^2
-# 342-348 vs 358-368 TFLOP/s; in-kernel trace: step pair 5 750 cycles against an issue floor of 3 072) and not bit-identical -- off
 # round 5: across-block K split (ppst_conv_args.ksplit) of launches whose grid fills a fraction of the chip while every block runs
 # one long serial chain of steps -- the 64^2 ... 4^2 layers of a train step at batch 2 (4-128 blocks of 72-160 steps: ~0.9 us per
 # step whatever the grid).  S = the largest of 8 / 4 / 2 with S x blocks <= max_blocks, chunk count divisible by S and >= min_steps
@@ -55,20 +49,12 @@ KSPLIT = {"value": os.environ.get("PPST_KSPLIT", "1") != "0", "max_blocks": 256,
 # the workspace every stream that runs a K-split launch owns (PPST_KSPLIT_SCRATCH_BYTES / PPST_KSPLIT_FLAG_WORDS of include/ppst_hip.h)
 KSPLIT_SCRATCH_BYTES = 256 * 512 * 128 * 4
 KSPLIT_FLAG_WORDS = 4096
-KSPLIT_128 = {"value": False, "min_blocks": 32}
-# variant 7 (32 x 16 px x 128 ch blocks, conv_mfma2.hip WMW = 4) when one image gives >= min_blocks: measured 3-5 % SLOWER than
-# the tile kernel on the Cout = 128 layers (one activation slot: the chunk store sits between two barriers; 33-44 spills) -- off
-TALL_TILE_128 = {"value": False, "min_blocks": 32}
-# the same geometry in the single-pass modes (two activation slots fit there): the Cout = 128-class 3x3 layers, which the tile
-# kernel runs at 0.22 of the single-pass ceiling (128 -> 128 @1024^2 fp16)
+# variant 7 (32 x 16 px x 128 ch blocks, conv_mfma2.hip WMW = 4) in the single-pass modes (two activation slots fit there): the
+# Cout = 128-class 3x3 layers, which the tile kernel runs at 0.22 of the single-pass ceiling (128 -> 128 @1024^2 fp16)
 TALL_TILE_SINGLE = {"value": True, "min_blocks": 64}
 # single-pass modes on half-stored activations: 64 input channels per step on the N-256 kernel family (ppst_conv_args.k64) -- half the
 # steps (barriers, fragment waits, DMA issues) per MFMA; the Cout = 128-class layers then take 24 x 16 px tiles (variant 9)
 K64 = {"value": True}
-# variant 9 (24 x 16 px x 128 ch blocks, wave tile 96 px x 64 ch, TWO activation slots: conv_mfma2.hip MT_ = 6) for the Cout = 128-class
-# layers whose tile height wastes <= max_waste of the rows (512 -> 528, 256 -> 264: 3.1 %; 128 -> 144 would be 12.5 %)
-TILE24_128 = {"value": False, "min_blocks": 32, "max_waste": 0.04}
-TWO_BLOCK_128 = {"value": False}   # experiment: variant 3 (see __call__) for the Cout = 128-class layers
 # round 3: the tile kernel itself as two 4-wave blocks per CU (8 x 16 px x 128 ch tiles, 64 px x 64 ch waves, TWO activation slots,
 # 77 KB of LDS each) for the Cout = 128-class layers: one block's prologue / epilogue / barrier waits overlap the other's MFMAs
 TWO_BLOCK_8ROW = {"value": False, "min_blocks": 64}
@@ -106,22 +92,17 @@ FUSE_TAIL = {"value": os.environ.get("PPST_FUSE_TAIL", "1") != "0", "torgb": os.
 FAT_MIN_BLOCKS = 32         # take the 256-channel tile only when ONE image still gives >= this many blocks (B = 8: one per CU)
 
 
-# the measured-and-off conv forms exist only in a PPST_EXPERIMENTS=1 build of the library (ppst_amd/build.py)
-EXPERIMENTS = bool(lib.ppst_has_experiments())
-
-
-def _need_experiments(what):
-    if not EXPERIMENTS:
-        raise RuntimeError("%s is an experiment kernel: rebuild the library with PPST_EXPERIMENTS=1 (python -m ppst_amd.build)" % what)
+def _removed(what):
+    """The measured-and-off conv forms are gone from the library."""
+    raise RuntimeError("%s was a measured experiment and has been removed; 79feb53 is the last commit that has it" % what)
 
 
 def set_precision(p):
     """0: bf16x3 (fp32-class, the measured path); 1: single-pass bf16; 2: exact fp32 MFMA (verification only, slow);
-    3: single-pass fp16 (the "fp16 generator" of BASELINE configs[4]; fp32 accumulate / statistics / StyleMod);
-    4: two-pass fp16 (activation hi + lo, weight rounded once to fp16): a measured experiment, 2/3 of the MFMAs of mode 0."""
-    assert p in (0, 1, 2, 3, 4)
+    3: single-pass fp16 (the "fp16 generator" of BASELINE configs[4]; fp32 accumulate / statistics / StyleMod)."""
     if p == 4:
-        _need_experiments("precision 4 (two-pass fp16)")
+        _removed("precision 4 (two-pass fp16)")
+    assert p in (0, 1, 2, 3)
     PRECISION["value"] = p
 
 
@@ -312,7 +293,7 @@ class ConvPlan:
     # changed), ~150 per D + G iteration: the tables are shared between plans of one geometry, only the weights are new.
     _GEOMETRY = {}
     _GEOM_ATTRS = ("kind", "cout", "cin", "k", "bn", "n_groups", "halo", "src", "max_chan", "wstrides", "nsteps", "flop_steps",
-                   "early_a", "ksplit_ok", "chunk_starts0", "chunk_starts0_k64", "steps", "src_dev", "chunk_start", "chunks_per_group", "w4_shape", "max_chunk_steps",
+                   "early_a", "chunk_starts0", "chunk_starts0_k64", "steps", "src_dev", "chunk_start", "chunks_per_group", "w4_shape", "max_chunk_steps",
                    "min_chunk_steps", "full_cover", "steps_dual", "src_dual", "steps_up9", "steps_k64", "src_k64", "steps_dual_k64",
                    "src_dual_k64")
 
@@ -541,14 +522,10 @@ class ConvPlan:
         ns_ = self.nsteps
 
         def encode(steps_):
-            enc, chunk_idx = [], -1
+            enc = []
             for i, (c_, dy_, dx_, f_) in enumerate(steps_):
-                if i % ns_ == 0:
-                    chunk_idx = -1                   # the chunk count restarts with every group
-                chunk_idx += 1 if f_ else 0
                 nxt = steps_[i + 1] if (i + 1) % ns_ != 0 else None
-                # bit 2 = parity of this step's chunk index within its group (the activation-ring slot of conv_ksplit.hip)
-                w_ = f_ | ((2 | (nxt[0] << 8)) if (nxt is not None and nxt[3]) else 0) | ((chunk_idx & 1) << 2)
+                w_ = f_ | ((2 | (nxt[0] << 8)) if (nxt is not None and nxt[3]) else 0)
                 enc.append((c_, dy_, dx_, w_))
             return enc
         enc = encode(steps)
@@ -559,8 +536,6 @@ class ConvPlan:
         self.early_a = 1 if (min(lens) >= 2 and ns_ >= 3) else 0
         self.max_chunk_steps = max(lens)
         self.min_chunk_steps = min(lens)
-        # conv_ksplit.hip stores a chunk one step PAIR before its first use: a 2-step chunk must not straddle two pairs
-        self.ksplit_ok = bool(self.early_a and all(l_ >= 3 or (a_ % ns_) % 2 == 0 for a_, l_ in zip(starts[:-1], lens)))
         # 4 padding rows: the kernel prefetches the descriptor of step s+3 without a bounds test
         self.steps = torch.tensor(enc + [(0, 0, 0, 0)] * 4, dtype=torch.int32, device=dev).contiguous()
         self.steps_dual = self.src_dual = None
@@ -705,35 +680,35 @@ class ConvPlan:
                 and (th, tw) == (oh, ow) == (H, W)
                 and ((th + 15) // 16) * ((tw + 15) // 16) * ((self.cout + 127) // 128) >= WINO["min_blocks"])
 
-    def choose_kernel(self, th, tw, oh, ow, H, W, osy, B=None, allow_up9=True):
+    def choose_kernel(self, th, tw, oh, ow, H, W, osy, B=None, allow_up9=True, allow_wino=True):
         """(variant, N tile, tile rows) of ppst_conv_args for one launch of this plan -- a function of the plan and of ONE
         image's geometry only.  The batch size is deliberately not an argument: every variant gives bit-identical outputs,
         but their tile statistics differ in the last bit (other summation tree), and a shard of a batch has to reproduce the
         whole batch bit for bit (evaluation.grid_exchange; "2 simulated ranks == 1 rank"; tests/test_abi_cpu.py).
           0  tile kernel (64 px x 64 ch waves), bn 64 / 128;      2  its N-256 form (128 px x 64 ch waves) for Cout % 256 == 0
           4  1x1 streaming kernel;   5  direct form for thin stride-2 tables;   6  3x3 register-reuse form (thin layers)
-          1 / 3 / 7 and variant 6 with bn 128: measured experiments, off unless a test switches them on."""
+          7  32-row tiles for the Cout = 128-class layers of the single-pass modes;   10  Winograd;   "dual" / "up9"  fused upscale."""
+        cv = CONV_VARIANT["value"]
+        if cv in (1, 3):
+            _removed("conv variant %d" % cv)
         rows = TILE_ROWS["value"]
         variant, bn = 0, self.bn
         single = self.precision in (1, 3)
         if self.precision not in (0, 1, 3):
-            return variant, bn, rows                     # fp16x2 experiment / exact-fp32 verification: the tile kernel only
-        if WINO["value"] and self.wino_ok(th, tw, oh, ow, H, W, osy):
+            return variant, bn, rows                     # exact-fp32 verification: the tile kernel only
+        if allow_wino and WINO["value"] and self.wino_ok(th, tw, oh, ow, H, W, osy):
             wblocks = ((th + 15) // 16) * ((tw + 15) // 16) * ((self.cout + 127) // 128) * (B or 1)
             aware_b = BATCH_AWARE["value"] and B is not None
             if not (aware_b and (wblocks < WINO["fill"] or (KSPLIT["value"] and 0 in KSPLIT["variants"] and self.cout <= 256
                                                              and wblocks <= WINO["ksplit_fill"]))):
                 return 10, 128, 16
         tiles16 = ((th + 15) // 16) * ((tw + 15) // 16) * self.n_groups          # blocks PER IMAGE per N tile
-        cv = CONV_VARIANT["value"]
-        if cv in (1, 3) or TWO_BLOCK_128["value"] or KSPLIT_128["value"] or TILE24_128["value"] or TALL_TILE_128["value"]:
-            _need_experiments("the requested conv variant")
         if (UP9["value"] and allow_up9 and self.kind == "convT" and self.precision == 0 and getattr(self, "steps_up9", None) is not None
                 and self.early_a and ((th + 14) // 15) * ((tw + 14) // 15) * (self.cout // 64) >= UP9["min_blocks"]
                 and th * tw >= UP9["min_fill"] * (((th + 14) // 15) * 15) * (((tw + 14) // 15) * 15)):
             return "up9", 256, 15
         if (DUAL_CONVT["value"] and self.kind == "convT" and getattr(self, "steps_dual", None) is not None
-                and self.cout % 256 != 0 and CONV_VARIANT["value"] == 2 and self.early_a
+                and self.cout % 256 != 0 and cv == 2 and self.early_a
                 and ((th + 15) // 16) * ((tw + 15) // 16) * 2 * (self.cout // 128) >= DUAL_CONVT["min_blocks"]):
             return "dual", 256, 16
         n256_ok = self.cout % 256 == 0 and tiles16 * (self.cout // 256) >= FAT_MIN_BLOCKS
@@ -744,32 +719,17 @@ class ConvPlan:
         #  38 us with S = 4 against 69 us on 8-row tiles with S = 2)
         small = (aware and tiles16 * ((self.cout + 127) // 128) * B < BATCH_AWARE["fill"]
                  and not (KSPLIT["value"] and 0 in KSPLIT["variants"]))
-        if cv == 1 and not single and self.early_a and self.cout >= 128:
-            variant, bn = 1, (256 if n256_ok else 128)
-        elif cv in (2, 3) and self.early_a:
-            force3 = cv == 3                             # (tests) every eligible plan on the two-block kernel
-            if n256_ok and not force3:
+        if cv == 2 and self.early_a:
+            if n256_ok:
                 variant, bn = 2, 256                     # 8 waves x (128 px x 64 ch), N tile 256 (conv_mfma2.hip, WNW = 4)
             elif single:
                 # single-pass modes: the N-256 geometry, and for Cout = 128-class layers with a halo the 32 x 16 px x 128 ch tile
                 if (self.bn == 128 and self.halo == 1 and self.n_groups == 1 and TALL_TILE_SINGLE["value"] and
                         ((th + 31) // 32) * ((tw + 15) // 16) * ((self.cout + 127) // 128) >= TALL_TILE_SINGLE["min_blocks"]):
                     variant, rows = 7, 32
-            elif self.bn == 128 and (force3 or (TWO_BLOCK_128["value"] and
-                                                tiles16 * ((self.cout + 127) // 128) >= 2 * FAT_MIN_BLOCKS)):
-                variant = 3                              # two 4-wave blocks per CU, N tile 128, one activation slot
             elif (self.bn == 128 and self.halo == 1 and (small or (TWO_BLOCK_8ROW["value"] and
                   ((th + 7) // 8) * ((tw + 15) // 16) * self.n_groups * ((self.cout + 127) // 128) >= TWO_BLOCK_8ROW["min_blocks"]))):
                 rows = 8                                 # tile kernel, two 4-wave blocks per CU
-            elif (self.bn == 128 and KSPLIT_128["value"] and getattr(self, "ksplit_ok", False)
-                  and tiles16 * ((self.cout + 127) // 128) >= KSPLIT_128["min_blocks"]):
-                variant = 8                              # two K-groups of 128 px x 64 ch waves, N tile 128 (conv_ksplit.hip)
-            elif (self.bn == 128 and TILE24_128["value"] and ((th + 23) // 24) * 24 <= th * (1.0 + TILE24_128["max_waste"]) and
-                  ((th + 23) // 24) * ((tw + 15) // 16) * self.n_groups * ((self.cout + 127) // 128) >= TILE24_128["min_blocks"]):
-                variant, rows = 9, 24                    # block tile 24 x 16 px x 128 ch, two activation slots (WMW = 4, MT_ = 6)
-            elif (self.bn == 128 and TALL_TILE_128["value"] and
-                  ((th + 31) // 32) * ((tw + 15) // 16) * self.n_groups * ((self.cout + 127) // 128) >= TALL_TILE_128["min_blocks"]):
-                variant, rows = 7, 32                    # block tile 32 x 16 px x 128 ch, one activation slot (WMW = 4)
         same = (th, tw) == (oh, ow)
         if STREAM_1X1["value"] and self.halo == 0 and self.n_groups == 1 and osy == 1 and same and (oh, ow) == (H, W):
             variant, bn, rows = 4, 64, TILE_ROWS["value"]            # 1x1 convs: streaming kernel, no activation staging
@@ -784,7 +744,7 @@ class ConvPlan:
 
     def _ksplit(self, variant, a, skip):
         """ppst_conv_args.ksplit of the launch described by ``a`` (0: none) -- ops.KSPLIT."""
-        if (skip or variant not in KSPLIT["variants"] or a.in_presplit
+        if (skip or variant not in KSPLIT["variants"]
                 or not (a.tile_rows == 16 or (variant == 0 and a.tile_rows == 8))):
             return 0, None
         cs = self.chunk_starts0_k64 if a.k64 else self.chunk_starts0       # chunk starts of one group of the launch's table
@@ -802,7 +762,7 @@ class ConvPlan:
 
     def __call__(self, x, bias=None, noise=None, noise_weight=0.0, act=ACT_NONE, prelu=None, stats=False,
                  residual=None, out=None, out_scale=1.0, pad_mode=PAD_ZERO, out_hw=None, res_after_act=False,
-                 in_ss=None, in_act=ACT_NONE, in_prelu=None, presplit=False, in_res=None):
+                 in_ss=None, in_act=ACT_NONE, in_prelu=None, in_res=None):
         in_ld = _nhwc_ld(x, "conv input", half_ok=True)
         B, H, W, xc = x.shape
         if x.dtype != torch.float32 and {torch.float16: 3, torch.bfloat16: 1}[x.dtype] != self.precision:
@@ -844,13 +804,9 @@ class ConvPlan:
         # falls back to the phase-pair / four-phase forms (which take all of them) instead of failing (round-4 ADVICE)
         up9_ok = in_ss is None and residual is None and act != ACT_PRELU and pad_mode == PAD_ZERO
         variant, bn, rows = self.choose_kernel(th, tw, oh, ow, H, W, osy, B, allow_up9=up9_ok)
+        if variant == 10 and in_ss is not None and self.cin > 1024:      # (the Winograd kernel's LDS copy of the table: wino_ok)
+            variant, bn, rows = self.choose_kernel(th, tw, oh, ow, H, W, osy, B, allow_up9=up9_ok, allow_wino=False)
         # single-pass modes on half-stored activations: 64 input channels per step where the N-256 kernel family runs the layer
-        if variant == 10 and in_ss is not None and self.cin > 1024:
-            WINO["value"], prev = False, WINO["value"]
-            try:
-                variant, bn, rows = self.choose_kernel(th, tw, oh, ow, H, W, osy, B, allow_up9=up9_ok)
-            finally:
-                WINO["value"] = prev
         k64 = (K64["value"] and x.dtype != torch.float32 and self.precision in (1, 3) and variant in (2, 7, "dual")
                and (self.steps_dual_k64 if variant == "dual" else self.steps_k64) is not None)
         if k64 and variant == 7:
@@ -901,11 +857,6 @@ class ConvPlan:
         a.flop_steps = self.flop_steps
         a.a_slots = min(3, self.chunks_per_group)
         a.early_a = self.early_a
-        if presplit:         # experiment: x holds the pre-split layout (ops.presplit); the tile kernel stages it by LDS-DMA
-            _need_experiments("pre-split conv input")
-            if variant != 0 or bn != 128 or in_ss is not None or self.nsteps // max(1, self.chunks_per_group) < 4:
-                raise RuntimeError("pre-split input: tile kernel (bn 128) plans with chunks of >= 4 steps and no in_ss only")
-            a.in_presplit = 1
         # (batch-aware passes only: the split depends on the batch in the launch and changes the summation order -- a shard of an
         #  inference batch has to reproduce the whole batch bit for bit)
         ks_S, ks_cuts = self._ksplit(variant, a, self.precision == 2) if (KSPLIT["value"] and BATCH_AWARE["value"]) else (0, None)
@@ -1039,7 +990,7 @@ def repack_plans(plans):
             n_tiles = (pl.cout + bn - 1) // bn
             pk.append((pl.wsrc.data_ptr(), sn, sc, sy, sx, c_.data_ptr(), ky_.data_ptr(), kx_.data_ptr(), wpack.data_ptr(),
                        pl.n_groups * n_tiles * pl.nsteps * 4 * bn, float(pl.scale), pl.cout, bn, pl.nsteps, pl.n_groups,
-                       1 if pl.precision == 0 else 0, 1 if pl.precision in (3, 4) else 0, 0))
+                       1 if pl.precision == 0 else 0, 1 if pl.precision == 3 else 0, 0))
     dev = plans[0].steps.device if plans else None
 
     def table(cls, rows, fill):
@@ -1106,16 +1057,6 @@ def _grad_out(out, shape, like):
 # form 2: two 256-thread blocks per CU; bf16_single_pass: in precision mode 1 (bf16 compute, fp32 master weights -- BASELINE
 # configs[3]) the weight gradient multiplies the hi halves only (one MFMA pass instead of three)
 WGRAD_TR = {"value": True, "blocks": 256, "min_tiles": 8, "form": 2, "blocks2": 512, "pair": True, "bf16_single_pass": True, "exact": True, "nohalo": True}
-
-
-def presplit(x):
-    """fp32 NHWC -> the pre-split layout (experiment, ppst_conv_args.in_presplit): same shape / dtype container, per pixel and
-    8-channel group 32 bytes [hi x 8 | lo x 8] bf16."""
-    ld = _nhwc_ld(x)
-    B, H, W, C = x.shape
-    y = torch.empty((B, H, W, C), device=x.device, dtype=torch.float32)
-    check(lib.ppst_presplit(_p(x), _p(y), B * H * W, C, ld, C, _stream()), "ppst_presplit")
-    return y
 
 
 def conv_wgrad(plan, x, dy, splits=None, out=None, accumulate=False, bias_out=None, bias_accumulate=False, want_bias=False, dy_scale=1.0):

@@ -1,5 +1,5 @@
 """Tuning aid (GPU): time the plain conv for a few shapes with the library named by PPST_HIP_LIB
-(ablation builds from tests/build_variant.sh; their results are numerically wrong on purpose)."""
+(variant builds from tests/build_variant.sh)."""
 import os, sys, math
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,4 +1,7 @@
-"""Tuning aid (GPU): per-shape table of the fused conv launches of one swap step."""
+"""Tuning aid (GPU): per-shape table of the fused conv launches of one swap step.
+   python tests/conv_table.py [batch] [precision] [CONV_VARIANT] [FAT_MIN_BLOCKS] [DIRECT_MAX cout] [nsteps] [cout3x3] [TWO_BLOCK_8ROW]
+(Up to 79feb53 the positions were different: 5 and 9-11 held the switches of kernel forms that have been removed, DIRECT_MAX was
+6-8 and TWO_BLOCK_8ROW 12 -- command lines recorded in DESIGN.md and older notes use that numbering.)"""
 import os, sys, collections
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -10,25 +13,17 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 prec = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 ops.set_precision(prec)
 if len(sys.argv) > 3:
-    ops.CONV_VARIANT["value"] = int(sys.argv[3])        # 0: 8-wave kernel everywhere; 1: fat-wave kernel where eligible
+    ops.CONV_VARIANT["value"] = int(sys.argv[3])        # 0: 8-wave kernel everywhere; 2: its N-256 form where eligible
 if len(sys.argv) > 4:
     ops.FAT_MIN_BLOCKS = int(sys.argv[4])
 if len(sys.argv) > 5:
-    ops.TWO_BLOCK_128["value"] = bool(int(sys.argv[5]))
+    ops.DIRECT_MAX["cout"] = int(sys.argv[5])
 if len(sys.argv) > 6:
-    ops.DIRECT_MAX["cout"] = int(sys.argv[6])
+    ops.DIRECT_MAX["nsteps"] = int(sys.argv[6])
 if len(sys.argv) > 7:
-    ops.DIRECT_MAX["nsteps"] = int(sys.argv[7])
+    ops.DIRECT_MAX["cout3x3"] = int(sys.argv[7])
 if len(sys.argv) > 8:
-    ops.DIRECT_MAX["cout3x3"] = int(sys.argv[8])
-if len(sys.argv) > 9:
-    ops.TALL_TILE_128["value"] = bool(int(sys.argv[9]))
-if len(sys.argv) > 10:
-    ops.KSPLIT_128["value"] = bool(int(sys.argv[10]))
-if len(sys.argv) > 11:
-    ops.TILE24_128["value"] = bool(int(sys.argv[11]))
-if len(sys.argv) > 12:
-    ops.TWO_BLOCK_8ROW["value"] = bool(int(sys.argv[12]))
+    ops.TWO_BLOCK_8ROW["value"] = bool(int(sys.argv[8]))
 dev = torch.device("cuda", 0)
 sd = W.make_state_dict(0, with_D=False, with_nce=False, bias_std=0.1, noise_weight=0.1)
 m = create_model(state_dict=sd, device=dev)

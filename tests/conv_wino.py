@@ -143,7 +143,7 @@ def time_shapes(B):
 
 
 def time_wino_only(B):
-    """one line per library (PPST_HIP_LIB = an ablation build of tests/build_wino_variant.sh): Winograd kernel only"""
+    """one line per library (PPST_HIP_LIB = another build of the library): Winograd kernel only"""
     torch.manual_seed(1)
     ops.WINO["value"] = True
     out = []

@@ -106,15 +106,19 @@ def test_conv_entry_rejects_images_beyond_32bit_offsets():
     a.in_h = a.in_w = a.out_h = a.out_w = a.tile_h = a.tile_w = 64
     assert _lib.lib.ppst_conv2d_mfma(ctypes.byref(a), None) == -1
     a.tile_rows = 24
-    # ... and is an experiment kernel: accepted only by a PPST_EXPERIMENTS=1 build, refused by the production library
-    assert _lib.lib.ppst_conv2d_mfma(ctypes.byref(a), None) == (0 if _lib.lib.ppst_has_experiments() else -1)
+    # ... and, without k64, is a retired form: refused
+    assert _lib.lib.ppst_conv2d_mfma(ctypes.byref(a), None) == -1
     a.variant, a.tile_rows, a.precision, a.halo = 0, 8, 0, 1          # the 8-row two-block form is a production kernel
     assert _lib.lib.ppst_conv2d_mfma(ctypes.byref(a), None) == 0
     for variant, rows, prec in ((1, 16, 0), (3, 16, 0), (7, 32, 0), (8, 16, 0), (0, 16, 4)):
         a.variant, a.tile_rows, a.precision, a.halo = variant, rows, prec, 1
         rc = _lib.lib.ppst_conv2d_mfma(ctypes.byref(a), None)
-        assert rc == (0 if _lib.lib.ppst_has_experiments() else -1), (variant, rows, prec, rc)
+        assert rc == -1, (variant, rows, prec, rc)
     a.variant, a.tile_rows, a.precision = 0, 16, 0
+    assert _lib.lib.ppst_conv2d_mfma(ctypes.byref(a), None) == 0
+    a.reserved0 = 1                                                   # the slot of a removed experiment: must be 0
+    assert _lib.lib.ppst_conv2d_mfma(ctypes.byref(a), None) == -1
+    a.reserved0 = 0
     assert _lib.lib.ppst_conv2d_mfma(ctypes.byref(a), None) == 0
 
 
@@ -462,10 +466,20 @@ def _direct_kernel_table(ops, plan, ck):
     # single-pass modes: the N-256 and streaming kernels are built for them, the experiments are not
     assert ck(plan("conv", 256, 256, 3, 72, 1, precision=3), 256) == (2, 256, 16)
     assert ck(plan("conv", 32, 32, 3, 9, 1, precision=1), 512) == (6, 64, 16)
-    # fp16x2 experiment and the exact-fp32 verification mode: tile kernel only
-    assert ck(plan("conv", 256, 256, 3, 72, 1, precision=4), 256) == (0, 128, 16)
+    # the exact-fp32 verification mode: tile kernel only
     assert ck(plan("conv", 32, 32, 3, 9, 1, precision=2), 512) == (0, 64, 16)
-    assert not ops.TWO_BLOCK_128["value"] and not ops.TALL_TILE_128["value"] and ops.DIRECT_MAX["cout3x3"] == 64
+    assert ops.DIRECT_MAX["cout3x3"] == 64
+    # the removed forms are refused by name: conv variants 1 / 3 by the choice function, the two-pass fp16 mode by set_precision
+    for cv in (1, 3):
+        ops.CONV_VARIANT["value"] = cv
+        try:
+            with pytest.raises(RuntimeError, match="removed.*79feb53"):
+                ck(plan("conv", 128, 128, 3, 36, 1), 64)
+        finally:
+            ops.CONV_VARIANT["value"] = 2
+    with pytest.raises(RuntimeError, match="removed.*79feb53"):
+        ops.set_precision(4)
+    assert ops.PRECISION["value"] == 0
 
 
 def test_gemm_mode_selection():
