@@ -14,6 +14,13 @@
  * timing ablation ppst_wgrad_ablate of the weight-gradient kernel.  Each declaration cites the
  * reference interface (file:line under wangxb29/PPST) it replaces.
  *
+ * Grouped entry points (ppst_linear_grouped, ppst_l2norm_rows_grouped, ppst_lerp_grouped,
+ * ppst_gap_gmp_multi_level): up to PPST_GROUP_MAX INDEPENDENT problems of one small op -- no
+ * problem reads what another of the same call writes -- run as one launch (two for the pooling).
+ * The problem table travels in the kernel arguments: nothing is uploaded, the array is the
+ * caller's and is not kept.  Every problem runs the code of its single-problem entry point, so
+ * its result is that call's, bit for bit.
+ *
  * Tensor layouts: "NCHW" = the reference's contiguous torch layout;
  * "NHWC" = channels-last [B][H][W][C], the internal layout of the fused path.
  * All tensors are fp32 unless stated.  Activation tensors of the single-pass precision
@@ -439,6 +446,21 @@ int ppst_gap_gmp(const void* x, const void* mask, void* out, void* ws, int B, in
                  int C, int ld, void* stream);
 int ppst_gap_gmp_st(const void* x, const void* mask, void* out, void* ws, int B, int H, int W,
                     int C, int ld, int x_st, void* stream);
+/* Grouped calls take at most this many problems; more: PPST_EINVAL, 0: PPST_OK without a launch. */
+#define PPST_GROUP_MAX 32
+/* ppst_gap_gmp_st of n feature maps of one batch (the four pyramid levels of an E2 pass, encoder_col.py:159-161, plain / warped /
+ * masked) as ONE reduction launch and ONE finalize launch.  Every level keeps the chunking and the summation order it has alone:
+ * out of level i == ppst_gap_gmp_st on level i, bit for bit, for any batch.  All levels share B and the storage type x_st;
+ * C % 4 == 0, ld % 4 == 0, x 16-byte aligned (8 for a half type), else PPST_EINVAL; a null x / out / ws: PPST_ENULL.
+ * ws: ppst_gap_gmp_multi_level_ws bytes (the levels' ppst_gap_gmp_ws, summed). */
+typedef struct {
+  const void* x;     /* [B][H][W][ld] */
+  const void* mask;  /* optional [B][H][W] */
+  void* out;         /* [B][2C] */
+  int32_t H, W, C, ld;
+} ppst_gap_gmp_level;
+int64_t ppst_gap_gmp_multi_level_ws(const ppst_gap_gmp_level* levels, int n, int B);
+int ppst_gap_gmp_multi_level(const ppst_gap_gmp_level* levels, int n, int B, void* ws, int x_st, void* stream);
 /* integer-factor average pool (adaptive_avg_pool2d to H/f) NHWC -> dst slice */
 int ppst_avgpool(const void* x, void* y, int B, int H, int W, int C, int x_ld, int f,
                  int y_ld, void* stream);
@@ -469,6 +491,23 @@ int ppst_linear(const void* x, const void* w, const void* bias, void* y,
 int ppst_l2norm_rows(const void* x, void* y, int B, int K, float eps, int mode, void* stream);
 /* y = a*(1-r) + b*r (util.lerp, util/util.py:32-35) */
 int ppst_lerp(const void* a, const void* b, void* y, int64_t n, float r, void* stream);
+/* n <= PPST_GROUP_MAX independent problems of the three ops above in ONE launch each (the E2 projector levels of a pass, the
+ * generator's StyleMod / GeneratorModulation linears, the four code vectors of a swap).  A problem is the argument list of the
+ * single call; it runs the kernel form that call would pick (a linear of more than 16 rows stays the 16-row pieces it is there;
+ * pieces beyond the 32 one launch holds go out in a further launch) and gives its result bit for bit.  An empty problem (B or n
+ * of 0) is skipped; a bad size in any problem: PPST_EINVAL, a null pointer in any non-empty problem: PPST_ENULL -- checked for
+ * the whole table before anything is launched. */
+typedef struct {
+  const void* x; const void* w; const void* bias /* may be NULL */; void* y;
+  int32_t B, K, N;
+  float wscale, bscale;
+  int32_t relu_in, act;
+} ppst_linear_problem;
+typedef struct { const void* x; void* y; int32_t B, K; float eps; int32_t mode; } ppst_l2norm_problem;
+typedef struct { const void* a; const void* b; void* y; int64_t n; float r; } ppst_lerp_problem;
+int ppst_linear_grouped(const ppst_linear_problem* problems, int n, void* stream);
+int ppst_l2norm_rows_grouped(const ppst_l2norm_problem* problems, int n, void* stream);
+int ppst_lerp_grouped(const ppst_lerp_problem* problems, int n, void* stream);
 /* GeneratorModulation (generator.py:80-91): y[b,p,c] = x[b,p,c]*scale[b,c] + bias[b,c] */
 int ppst_spatial_modulation(const void* x, const void* scale, const void* bias, void* y,
                             int B, int64_t hw, int C, void* stream);

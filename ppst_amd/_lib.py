@@ -40,6 +40,30 @@ class UpscaleJob(ctypes.Structure):
     _fields_ = [("w", vp), ("out", vp), ("total", i64), ("block0", i64), ("scale", f32), ("cout", i32), ("cin", i32), ("nblocks", i32)]
 
 
+class LinearProblem(ctypes.Structure):
+    """ppst_linear_problem (include/ppst_hip.h)."""
+    _fields_ = [("x", vp), ("w", vp), ("bias", vp), ("y", vp), ("B", i32), ("K", i32), ("N", i32), ("wscale", f32), ("bscale", f32),
+                ("relu_in", i32), ("act", i32)]
+
+
+class L2normProblem(ctypes.Structure):
+    """ppst_l2norm_problem (include/ppst_hip.h)."""
+    _fields_ = [("x", vp), ("y", vp), ("B", i32), ("K", i32), ("eps", f32), ("mode", i32)]
+
+
+class LerpProblem(ctypes.Structure):
+    """ppst_lerp_problem (include/ppst_hip.h)."""
+    _fields_ = [("a", vp), ("b", vp), ("y", vp), ("n", i64), ("r", f32)]
+
+
+class GapGmpLevel(ctypes.Structure):
+    """ppst_gap_gmp_level (include/ppst_hip.h)."""
+    _fields_ = [("x", vp), ("mask", vp), ("out", vp), ("H", i32), ("W", i32), ("C", i32), ("ld", i32)]
+
+
+GROUP_MAX = 32           # PPST_GROUP_MAX
+
+
 class ConvArgs(ctypes.Structure):
     """ppst_conv_args (include/ppst_hip.h)."""
     _fields_ = [
@@ -105,6 +129,11 @@ _SIGS = {
     "ppst_linear": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, vp]),
     "ppst_l2norm_rows": (i32, [vp, vp, i32, i32, f32, i32, vp]),
     "ppst_lerp": (i32, [vp, vp, vp, i64, f32, vp]),
+    "ppst_linear_grouped": (i32, [vp, i32, vp]),
+    "ppst_l2norm_rows_grouped": (i32, [vp, i32, vp]),
+    "ppst_lerp_grouped": (i32, [vp, i32, vp]),
+    "ppst_gap_gmp_multi_level_ws": (i64, [vp, i32, i32]),
+    "ppst_gap_gmp_multi_level": (i32, [vp, i32, i32, vp, i32, vp]),
     "ppst_spatial_modulation": (i32, [vp, vp, vp, vp, i32, i64, i32, vp]),
     "ppst_spatial_modulation_st": (i32, [vp, vp, vp, vp, i32, i64, i32, i32, vp]),
     "ppst_rselfcorr": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),

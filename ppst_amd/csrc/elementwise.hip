@@ -190,12 +190,13 @@ struct ApplyArgs {
   int res_ld, y_ld, actf; float out_scale;
   int res_up2;  // residual is half-resolution, bilinearly upsampled x2 on the fly
 };
-template <int MODE, bool APPLY, int XS = PPST_ST_F32>
-__global__ __launch_bounds__(256) void chan_reduce4_kernel(const void* __restrict__ x, const float* __restrict__ mask,
-                                                           float* __restrict__ partial, int H, int W, int C, int ld,
-                                                           int rep_pad, int nchunks, ApplyArgs ap, int PIX_CHUNK, FastDiv d_w) {
+// (the block's work as a function of (image b, pixel chunk): blockIdx of chan_reduce4_kernel, the level's own numbering inside the
+// multi-level GAP/GMP launch)
+template <int MODE, bool APPLY, int XS>
+__device__ __forceinline__ void chan_reduce4_body(const void* __restrict__ x, const float* __restrict__ mask,
+                                                  float* __restrict__ partial, int H, int W, int C, int ld, int rep_pad, int nchunks,
+                                                  const ApplyArgs& ap, int PIX_CHUNK, const FastDiv& d_w, int b, int chunk) {
   __shared__ float4 s0[256], s1[256];
-  const int b = blockIdx.y, chunk = blockIdx.x;
   const int P = H * W;
   const int pbeg = chunk * PIX_CHUNK;
   const int pend = (pbeg + PIX_CHUNK < P) ? pbeg + PIX_CHUNK : P;
@@ -278,6 +279,12 @@ __global__ __launch_bounds__(256) void chan_reduce4_kernel(const void* __restric
     }
     __syncthreads();
   }
+}
+template <int MODE, bool APPLY, int XS = PPST_ST_F32>
+__global__ __launch_bounds__(256) void chan_reduce4_kernel(const void* __restrict__ x, const float* __restrict__ mask,
+                                                           float* __restrict__ partial, int H, int W, int C, int ld,
+                                                           int rep_pad, int nchunks, ApplyArgs ap, int PIX_CHUNK, FastDiv d_w) {
+  chan_reduce4_body<MODE, APPLY, XS>(x, mask, partial, H, W, C, ld, rep_pad, nchunks, ap, PIX_CHUNK, d_w, blockIdx.y, blockIdx.x);
 }
 
 extern "C" int ppst_in_stats(const void* x, void* partial, int B, int H, int W, int C, int ld, int rep_pad,
@@ -533,12 +540,12 @@ extern "C" int ppst_affine_act_stats(const void* x, const void* scale_shift, con
 // ---------------------------------------------------------------- GAP/GMP --
 // One block per (image b, 8-channel group), 32 partial rows x 4 in flight (as in_finalize_kernel), double accumulation
 // of the sums in a fixed order, LDS tree at the end.
-__global__ __launch_bounds__(256) void gap_gmp_finalize_kernel(const float* __restrict__ partial, int n_partials,
-                                                               float* __restrict__ out, int B, int C, double count) {
+__device__ __forceinline__ void gap_gmp_finalize_body(const float* __restrict__ partial, int n_partials, float* __restrict__ out,
+                                                      int C, double count, int blk) {
   __shared__ double ss[FIN_ROWS][FIN_CH];
   __shared__ float sm[FIN_ROWS][FIN_CH];
   const int cgroups = (C + FIN_CH - 1) / FIN_CH;
-  const int b = blockIdx.x / cgroups, c0 = (blockIdx.x % cgroups) * FIN_CH;
+  const int b = blk / cgroups, c0 = (blk % cgroups) * FIN_CH;
   const int cl = threadIdx.x & (FIN_CH - 1), kk = threadIdx.x / FIN_CH;
   const int c = c0 + cl;
   double s = 0.0;
@@ -566,6 +573,11 @@ __global__ __launch_bounds__(256) void gap_gmp_finalize_kernel(const float* __re
     out[(int64_t)b * 2 * C + c] = (float)(s / count);
     out[(int64_t)b * 2 * C + C + c] = m;
   }
+}
+__global__ __launch_bounds__(256) void gap_gmp_finalize_kernel(const float* __restrict__ partial, int n_partials,
+                                                               float* __restrict__ out, int B, int C, double count) {
+  (void)B;
+  gap_gmp_finalize_body(partial, n_partials, out, C, count, blockIdx.x);
 }
 extern "C" int64_t ppst_gap_gmp_ws(int B, int64_t hw, int C) {
   if (B <= 0 || hw <= 0) return 0;
@@ -605,6 +617,84 @@ extern "C" int ppst_gap_gmp_st(const void* x, const void* mask, void* out, void*
 extern "C" int ppst_gap_gmp(const void* x, const void* mask, void* out, void* ws, int B, int H, int W, int C, int ld,
                              void* stream) {
   return ppst_gap_gmp_st(x, mask, out, ws, B, H, W, C, ld, PPST_ST_F32, stream);
+}
+
+// ---- GAP || GMP of SEVERAL feature maps in two launches (the four pyramid levels of an E2 pass, plain / warped / masked: each level
+// alone is 8 - 2048 blocks and two launches).  Level i owns blocks [blk0[i], blk0[i + 1]) of the reduction, numbered (image, chunk)
+// with ITS chunk size pix_chunk(hw_i), and runs chan_reduce4_kernel<1, false>'s body on them; its partials lie at its own offset of
+// the workspace; the second launch runs gap_gmp_finalize_kernel's body per level.  Same chunking, same lane map, same order of
+// every sum as ppst_gap_gmp_st on the level alone: the values are those, bit for bit, for any batch.
+struct GapLevelSeg { const void* x; const float* mask; float* partial; int H, W, C, ld, nchunks, chunk, pad_; };
+struct GapLevelGroup { GapLevelSeg seg[PPST_GROUP_MAX]; int blk0[PPST_GROUP_MAX]; };
+template <int XS>
+__global__ __launch_bounds__(256) void gap_gmp_levels_kernel(const GapLevelGroup g) {
+  int s = 0;
+#pragma unroll
+  for (int i = 1; i < PPST_GROUP_MAX; ++i)
+    if ((int)blockIdx.x >= g.blk0[i]) s = i;
+  const GapLevelSeg& q = g.seg[s];
+  const int blk = (int)blockIdx.x - g.blk0[s];
+  const int b = blk / q.nchunks;
+  const ApplyArgs ap = {};
+  const FastDiv d_w = {1u, 0u, 0u, 0u};  // (the GAP/GMP mode takes no pixel coordinates)
+  chan_reduce4_body<1, false, XS>(q.x, q.mask, q.partial, q.H, q.W, q.C, q.ld, 0, q.nchunks, ap, q.chunk, d_w, b, blk - b * q.nchunks);
+}
+struct GapFinSeg { const float* partial; float* out; double count; int n_partials, C; };
+struct GapFinGroup { GapFinSeg seg[PPST_GROUP_MAX]; int blk0[PPST_GROUP_MAX]; };
+__global__ __launch_bounds__(256) void gap_gmp_levels_finalize_kernel(const GapFinGroup g) {
+  int s = 0;
+#pragma unroll
+  for (int i = 1; i < PPST_GROUP_MAX; ++i)
+    if ((int)blockIdx.x >= g.blk0[i]) s = i;
+  const GapFinSeg& q = g.seg[s];
+  gap_gmp_finalize_body(q.partial, q.n_partials, q.out, q.C, q.count, (int)blockIdx.x - g.blk0[s]);
+}
+static int gap_level_check(const ppst_gap_gmp_level& l, int x_st) {
+  if (l.H <= 0 || l.W <= 0 || l.C <= 0 || l.ld < l.C || l.C % 4 || l.ld % 4 || (int64_t)l.H * l.W > 0x7fffffffll) return PPST_EINVAL;
+  if (!l.x || !l.out) return PPST_ENULL;
+  if ((uintptr_t)l.x % (x_st ? 8 : 16)) return PPST_EINVAL;
+  return PPST_OK;
+}
+extern "C" int64_t ppst_gap_gmp_multi_level_ws(const ppst_gap_gmp_level* lv, int n, int B) {
+  if (!lv || n <= 0 || n > PPST_GROUP_MAX || B <= 0) return 0;
+  int64_t bytes = 0;
+  for (int i = 0; i < n; ++i) bytes += ppst_gap_gmp_ws(B, (int64_t)lv[i].H * lv[i].W, lv[i].C);
+  return bytes;
+}
+extern "C" int ppst_gap_gmp_multi_level(const ppst_gap_gmp_level* lv, int n, int B, void* ws, int x_st, void* stream) {
+  if (n < 0 || n > PPST_GROUP_MAX || B < 0 || (unsigned)x_st > 2u) return PPST_EINVAL;
+  if (n == 0 || B == 0) return PPST_OK;
+  if (!lv || !ws) return PPST_ENULL;
+  for (int i = 0; i < n; ++i) {
+    int e = gap_level_check(lv[i], x_st);
+    if (e) return e;
+  }
+  GapLevelGroup g;
+  GapFinGroup f;
+  int64_t nblk = 0, fblk = 0, off = 0;
+  for (int i = 0; i < n; ++i) {
+    const ppst_gap_gmp_level& l = lv[i];
+    const int64_t hw = (int64_t)l.H * l.W;
+    const int chunk = pix_chunk(B, hw), nchunks = (int)cdiv64(hw, chunk);
+    float* part = (float*)ws + off;
+    GapLevelSeg& s = g.seg[i];
+    s.x = l.x; s.mask = (const float*)l.mask; s.partial = part;
+    s.H = l.H; s.W = l.W; s.C = l.C; s.ld = l.ld; s.nchunks = nchunks; s.chunk = chunk; s.pad_ = 0;
+    g.blk0[i] = (int)nblk;
+    nblk += (int64_t)nchunks * B;
+    GapFinSeg& t = f.seg[i];
+    t.partial = part; t.out = (float*)l.out; t.count = (double)l.H * l.W; t.n_partials = nchunks; t.C = l.C;
+    f.blk0[i] = (int)fblk;
+    fblk += (int64_t)B * cdiv(l.C, FIN_CH);
+    off += (int64_t)nchunks * l.C * 2 * B;
+    if (nblk > 0x7fffffffll || fblk > 0x7fffffffll) return PPST_EINVAL;
+  }
+  for (int i = n; i < PPST_GROUP_MAX; ++i) g.blk0[i] = f.blk0[i] = 0x7fffffff;
+  PPST_ST_SWITCH(x_st, PPST_LAUNCH(gap_gmp_levels_kernel<ST_>, dim3((unsigned)nblk), dim3(256), 0, as_stream(stream), g));
+  int e = PPST_LAUNCH_CHECK();
+  if (e) return e;
+  PPST_LAUNCH(gap_gmp_levels_finalize_kernel, dim3((unsigned)fblk), dim3(256), 0, as_stream(stream), f);
+  return PPST_LAUNCH_CHECK();
 }
 
 
@@ -1162,16 +1252,54 @@ extern "C" int ppst_torgb_apply_st(const void* x, const void* scale_shift, const
 }
 
 // --------------------------------------------------------------- misc glue --
+__device__ __forceinline__ void lerp_body(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ y, int64_t n,
+                                          float r, int blk, int nblk) {
+  for (int64_t i = (int64_t)blk * 256 + threadIdx.x; i < n; i += (int64_t)nblk * 256)
+    y[i] = a[i] * (1.f - r) + b[i] * r;  // util/util.py:35 (same operation order)
+}
 __global__ __launch_bounds__(256) void lerp_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ y,
                                                    int64_t n, float r) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-    y[i] = a[i] * (1.f - r) + b[i] * r;  // util/util.py:35 (same operation order)
+  lerp_body(a, b, y, n, r, blockIdx.x, gridDim.x);
 }
 extern "C" int ppst_lerp(const void* a, const void* b, void* y, int64_t n, float r, void* stream) {
   if (n < 0) return PPST_EINVAL;
   if (n == 0) return PPST_OK;
   if (!a || !b || !y) return PPST_ENULL;
   PPST_LAUNCH(lerp_kernel, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), (const float*)a, (const float*)b, (float*)y, n, r);
+  return PPST_LAUNCH_CHECK();
+}
+// several independent lerps in one launch (the four code vectors of a swap): problem i owns grid_for(n_i) blocks
+struct LerpSeg { const float* a; const float* b; float* y; int64_t n; float r; int nblk; };
+struct LerpGroup { LerpSeg seg[PPST_GROUP_MAX]; int blk0[PPST_GROUP_MAX]; };
+__global__ __launch_bounds__(256) void lerp_grouped_kernel(const LerpGroup g) {
+  int s = 0;
+#pragma unroll
+  for (int i = 1; i < PPST_GROUP_MAX; ++i)
+    if ((int)blockIdx.x >= g.blk0[i]) s = i;
+  const LerpSeg& q = g.seg[s];
+  lerp_body(q.a, q.b, q.y, q.n, q.r, (int)blockIdx.x - g.blk0[s], q.nblk);
+}
+extern "C" int ppst_lerp_grouped(const ppst_lerp_problem* p, int n, void* stream) {
+  if (n < 0 || n > PPST_GROUP_MAX) return PPST_EINVAL;
+  if (n == 0) return PPST_OK;
+  if (!p) return PPST_ENULL;
+  for (int i = 0; i < n; ++i) {
+    if (p[i].n < 0) return PPST_EINVAL;
+    if (p[i].n > 0 && (!p[i].a || !p[i].b || !p[i].y)) return PPST_ENULL;
+  }
+  LerpGroup g;
+  int nseg = 0, nblk = 0;
+  for (int i = 0; i < n; ++i) {
+    if (p[i].n == 0) continue;
+    LerpSeg& s = g.seg[nseg];
+    s.a = (const float*)p[i].a; s.b = (const float*)p[i].b; s.y = (float*)p[i].y; s.n = p[i].n; s.r = p[i].r;
+    s.nblk = (int)grid_for(p[i].n);
+    g.blk0[nseg++] = nblk;
+    nblk += s.nblk;
+  }
+  if (nseg == 0) return PPST_OK;
+  for (int i = nseg; i < PPST_GROUP_MAX; ++i) g.blk0[i] = 0x7fffffff;
+  PPST_LAUNCH(lerp_grouped_kernel, dim3(nblk), dim3(256), 0, as_stream(stream), g);
   return PPST_LAUNCH_CHECK();
 }
 

@@ -8,6 +8,8 @@ from . import ops
 def normalize(v):
     """util.normalize (util/util.py:18-22) via ppst_l2norm_rows."""
     if isinstance(v, (list, tuple)):
+        if all(isinstance(vv, torch.Tensor) and vv.dim() == 2 for vv in v):
+            return ops.l2norm_rows_grouped(list(v), 1e-8, 0)      # one launch for the list
         return [normalize(vv) for vv in v]
     return ops.l2norm_rows(v, 1e-8, 0)
 
@@ -15,6 +17,8 @@ def normalize(v):
 def lerp(a, b, r):
     """util.lerp (util/util.py:32-35): a*(1-r) + b*r, lists element-wise."""
     if isinstance(a, (list, tuple)):
+        if all(isinstance(t, torch.Tensor) for t in list(a) + list(b)):
+            return ops.lerp_grouped(list(zip(a, b)), r)           # one launch for the list
         return [lerp(aa, bb, r) for aa, bb in zip(a, b)]
     return ops.lerp(a, b, r)
 

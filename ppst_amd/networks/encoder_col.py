@@ -18,15 +18,25 @@ CH = [32, 64, 128, 256]
 class StyleGAN2ResnetEncodercol(BaseNetwork):
     prefix = "E2."
 
-    def _head(self, tag, x, mask=None):
-        v = ops.gap_gmp(x, mask)
-        w = self.p("conv1x1_%s.weight" % tag)
-        v = ops.linear(v, w.reshape(w.shape[0], -1), self.p("conv1x1_%s.bias" % tag))
-        q = "projector%s." % tag
-        v = ops.linear(v, self.p(q + "1.weight"), self.p(q + "1.bias"), relu_in=True)
-        v = ops.linear(v, self.p(q + "3.weight"), self.p(q + "3.bias"), relu_in=True)
-        v = ops.linear(v, self.p(q + "5.weight"), self.p(q + "5.bias"), relu_in=True)
-        return ops.l2norm_rows(v, 1e-12, 1)
+    def _heads(self, jobs):
+        """The code heads of several (tag, feature map, mask) jobs.  The jobs do not depend on each other, and each stage of the
+        chain -- GAP/GMP, the 1x1 conv, the three projector linears, F.normalize -- is a launch of 8 - 2048 blocks at the batch's
+        few rows: every stage runs as ONE grouped launch over the jobs (two for the pooling), each job's values being those of
+        its own chain of single calls."""
+        if not jobs:
+            return []
+        tags = [t for t, _, _ in jobs]
+        v = [None] * len(jobs)
+        for dt in dict.fromkeys(x.dtype for _, x, _ in jobs):     # (one pooling call per storage type)
+            idx = [i for i, (_, x, _) in enumerate(jobs) if x.dtype == dt]
+            for i, o in zip(idx, ops.gap_gmp_levels([jobs[i][1] for i in idx], [jobs[i][2] for i in idx])):
+                v[i] = o
+        ws = [self.p("conv1x1_%s.weight" % t) for t in tags]
+        v = ops.linear_grouped([(vi, w.reshape(w.shape[0], -1), self.p("conv1x1_%s.bias" % t)) for vi, w, t in zip(v, ws, tags)])
+        for layer in ("1", "3", "5"):
+            v = ops.linear_grouped([(vi, self.p("projector%s.%s.weight" % (t, layer)), self.p("projector%s.%s.bias" % (t, layer)),
+                                     1.0, 1.0, True) for vi, t in zip(v, tags)])
+        return ops.l2norm_rows_grouped(v, 1e-12, 1)
 
     def trunk(self, x, dtype=torch.float32):
         feats = [self.from_rgb(to_nhwc(x), "FromRGB.", out_dtype=dtype)]
@@ -66,22 +76,29 @@ class StyleGAN2ResnetEncodercol(BaseNetwork):
         # half-precision activation storage (ops.HALF_STORE) for the plain code pass; the warp / masked heads (pooling,
         # bilinear resize, the correspondence GEMM) read fp32 features
         feats = self.trunk(x, ops.act_dtype() if (corrmatrix is None and mask is None) else torch.float32)
-        vectors = [self._head(t, f) for t, f in zip(TAGS, feats)]
-        vectors_w, pm, pmw = [], [], []
+        # every head of the pass -- plain, warped, masked -- goes into the same grouped launches (_heads)
+        jobs = [(t, f, None) for t, f in zip(TAGS, feats)]
         warped = None
         if corrmatrix is not None:
             if isinstance(corrmatrix, (list, tuple)):  # simple_swapping_evaluator.py:53 wraps it in a list
                 corrmatrix = corrmatrix[0]
             warped = self.warp_levels(feats, corrmatrix.detach())
-            vectors_w = [self._head(t, f) for t, f in zip(TAGS, warped)]
+            jobs += [(t, f, None) for t, f in zip(TAGS, warped)]
+        n_w = len(jobs) - 4
+        pm_at, pmw_at = [], []
         if mask is not None:
             from .. import glue
             levels = self._mask_planes(mask)
             sw_levels = self._mask_planes(glue.swap(mask)) if warped is not None else None
             for lvl, (t, f) in enumerate(zip(TAGS, feats)):
                 for i in range(3):
-                    pm.append(self._head(t, f, levels[lvl][..., i].contiguous()))
+                    pm_at.append(len(jobs))
+                    jobs.append((t, f, levels[lvl][..., i].contiguous()))
                     if warped is not None:
-                        pmw.append(self._head(t, warped[lvl], sw_levels[lvl][..., i].contiguous()))
-            return vectors, pm, vectors_w, pmw
+                        pmw_at.append(len(jobs))
+                        jobs.append((t, warped[lvl], sw_levels[lvl][..., i].contiguous()))
+        out = self._heads(jobs)
+        vectors, vectors_w = out[:4], out[4:4 + n_w]
+        if mask is not None:
+            return vectors, [out[i] for i in pm_at], vectors_w, [out[i] for i in pmw_at]
         return vectors, vectors_w

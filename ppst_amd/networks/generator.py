@@ -39,7 +39,8 @@ class StyleGAN2ResnetGenerator(BaseNetwork):
             return b, float(ts[3].item())
         return self.cached(("sc", p), ts, build)
 
-    # -- all StyleMod GEMVs that share a style code run as ONE weight-streaming launch -----
+    # -- the StyleMod GEMVs that share a style code are ONE problem (weights concatenated); the four problems and the two
+    #    SpatialCodeModulation linears -- all read code vectors that exist before the first conv -- run as ONE grouped launch -----
     def _style_groups(self):
         groups = [["HeadResnetBlock%d.%s." % (i, c) for i in range(4) for c in ("conv1", "conv2")]]
         groups += [["UpsamplingResBlock%d.%s." % (key, c) for c in ("conv1", "conv2")] for key, _, _ in UP]
@@ -47,19 +48,29 @@ class StyleGAN2ResnetGenerator(BaseNetwork):
         return groups
 
     def _style_table(self, codes):
-        """{layer prefix: (B, 2C) StyleMod output} -- EqualizedLinear(2048 -> 2C, wscale) per layer
-        (stylegan2_layers.py:361-374), batched per style code: groups use codes[-1], [-2], [-3], [-4]."""
-        out = {}
-        for gi, names in enumerate(self._style_groups()):
+        """({layer prefix: (B, 2C) StyleMod output}, scale, shift) -- EqualizedLinear(2048 -> 2C, wscale) per layer
+        (stylegan2_layers.py:361-374), batched per style code: groups use codes[-1], [-2], [-3], [-4]; scale / shift = the two
+        EqualizedLinears of SpatialCodeModulation (generator.py:80-91) on codes[-1]."""
+        groups, problems = self._style_groups(), []
+        wsl = []
+        for gi, names in enumerate(groups):
             ws = [self.p(n + "epi1.style_mod.lin.weight") for n in names]
             bs = [self.p(n + "epi1.style_mod.lin.bias") for n in names]
             W, Bv = self.cached(("stylecat", gi), ws + bs, lambda: (torch.cat(ws, 0).contiguous(), torch.cat(bs, 0).contiguous()))
-            y = ops.linear(codes[-1 - gi], W, Bv, wscale=W.shape[1] ** -0.5)
+            problems.append((codes[-1 - gi], W, Bv, W.shape[1] ** -0.5))
+            wsl.append(ws)
+        wsc = self.p("SpatialCodeModulation.scale.weight")
+        inv = 1.0 / math.sqrt(wsc.shape[1])
+        problems.append((codes[-1], wsc, self.p("SpatialCodeModulation.scale.bias"), inv))
+        problems.append((codes[-1], self.p("SpatialCodeModulation.bias.weight"), self.p("SpatialCodeModulation.bias.bias"), inv))
+        ys = ops.linear_grouped(problems)
+        out = {}
+        for names, ws, y in zip(groups, wsl, ys):
             off = 0
             for n, w in zip(names, ws):
                 out[n] = y[:, off:off + w.shape[0]]
                 off += w.shape[0]
-        return out
+        return out, ys[-2], ys[-1]
 
     def styled_conv(self, x, p, style, key, noise, upsample=False, res=None, out_scale=1.0, in_ss=None, defer=False,
                     out_stats=None, res_up2=False):
@@ -168,13 +179,8 @@ class StyleGAN2ResnetGenerator(BaseNetwork):
         B, S = sp.shape[0], sp.shape[1]
         if isinstance(noise, str) and noise == "random":
             noise = self.make_noise(B, S, sp.device)
-        codes = [ops.l2norm_rows(c, 1e-8, 0) for c in global_codes]  # util.normalize (generator.py:246)
-        g = codes[-1]
-        styles = self._style_table(codes)
-        ws = self.p("SpatialCodeModulation.scale.weight")
-        inv = 1.0 / math.sqrt(ws.shape[1])
-        scale = ops.linear(g, ws, self.p("SpatialCodeModulation.scale.bias"), wscale=inv)
-        shift = ops.linear(g, self.p("SpatialCodeModulation.bias.weight"), self.p("SpatialCodeModulation.bias.bias"), wscale=inv)
+        codes = ops.l2norm_rows_grouped(list(global_codes), 1e-8, 0)  # util.normalize (generator.py:246)
+        styles, scale, shift = self._style_table(codes)
         # half-precision activation storage (ops.HALF_STORE): the plain image pass runs in ops.act_dtype(); the feature-extraction
         # pass (correspondence heads, pooled / resized copies) keeps fp32 storage
         adt = torch.float32 if extract_features else ops.act_dtype()

@@ -1707,6 +1707,34 @@ def gap_gmp(x, mask=None):
     return out
 
 
+def gap_gmp_levels(xs, masks=None):
+    """gap_gmp of several feature maps of one batch and one storage type (the pyramid levels of an E2 pass) as one reduction and
+    one finalize launch (ppst_gap_gmp_multi_level); more than GROUP_MAX maps go out GROUP_MAX at a time.  -> [(B, 2C)] per map,
+    each bit-equal to gap_gmp on the map alone."""
+    from ._lib import GROUP_MAX, GapGmpLevel
+    masks = list(masks) if masks is not None else [None] * len(xs)
+    assert len(masks) == len(xs)
+    if not xs:
+        return []
+    B, dt = xs[0].shape[0], xs[0].dtype
+    outs = []
+    for i0 in range(0, len(xs), GROUP_MAX):
+        grp = list(zip(xs[i0:i0 + GROUP_MAX], masks[i0:i0 + GROUP_MAX]))
+        lv = (GapGmpLevel * len(grp))()
+        for l, (x, m) in zip(lv, grp):
+            ld = _nhwc_ld(x, half_ok=True)
+            _chk(m, "mask")
+            if x.shape[0] != B or x.dtype != dt:
+                raise RuntimeError("gap_gmp_levels: the maps of one call share the batch and the storage type")
+            _, H, W, C = x.shape
+            out = torch.empty((B, 2 * C), device=x.device, dtype=torch.float32)
+            l.x, l.mask, l.out, l.H, l.W, l.C, l.ld = x.data_ptr(), (m.data_ptr() if m is not None else None), out.data_ptr(), H, W, C, ld
+            outs.append(out)
+        ws = torch.empty(max(lib.ppst_gap_gmp_multi_level_ws(lv, len(grp), B) // 4, 1), device=xs[0].device, dtype=torch.float32)
+        check(lib.ppst_gap_gmp_multi_level(lv, len(grp), B, _p(ws), _ST[dt], _stream()), "ppst_gap_gmp_multi_level")
+    return outs
+
+
 def avgpool(x, f, out=None):
     x_ld = _nhwc_ld(x)
     B, H, W, C = x.shape
@@ -1758,6 +1786,69 @@ def linear(x, w, bias=None, wscale=1.0, bscale=1.0, relu_in=False, act=ACT_NONE)
     check(lib.ppst_linear(_p(x), _p(w), _p(bias), _p(y), B, K, N, float(wscale), float(bscale), 1 if relu_in else 0, act,
                           _stream()), "ppst_linear")
     return y
+
+
+def linear_grouped(problems):
+    """[(x, w, bias, wscale, bscale, relu_in, act), ...] (the arguments of ``linear``; short tuples take its defaults) -> [y]:
+    INDEPENDENT linears in one launch per GROUP_MAX problems (ppst_linear_grouped), each bit-equal to ``linear`` on it."""
+    from ._lib import GROUP_MAX, LinearProblem
+    ys, hold = [], []
+    defaults = (None, 1.0, 1.0, False, ACT_NONE)
+    for i0 in range(0, len(problems), GROUP_MAX):
+        grp = problems[i0:i0 + GROUP_MAX]
+        arr = (LinearProblem * len(grp))()
+        for q, pr in zip(arr, grp):
+            x, w = pr[0], pr[1]
+            bias, wscale, bscale, relu_in, act = tuple(pr[2:]) + defaults[len(pr) - 2:]
+            _chk(x, "x"); _chk(w, "weight"); _chk(bias, "bias")
+            x = x.contiguous()
+            w = w.detach().contiguous()
+            B, K = x.shape
+            N = w.shape[0]
+            assert w.numel() == N * K
+            y = torch.empty((B, N), device=x.device, dtype=torch.float32)
+            q.x, q.w, q.bias, q.y = x.data_ptr(), w.data_ptr(), (bias.data_ptr() if bias is not None else None), y.data_ptr()
+            q.B, q.K, q.N, q.wscale, q.bscale, q.relu_in, q.act = B, K, N, float(wscale), float(bscale), 1 if relu_in else 0, act
+            ys.append(y)
+            hold.append((x, w))
+        check(lib.ppst_linear_grouped(arr, len(grp), _stream()), "ppst_linear_grouped")
+    return ys
+
+
+def l2norm_rows_grouped(xs, eps, mode):
+    """l2norm_rows of several (B, K) tensors in one launch per GROUP_MAX (ppst_l2norm_rows_grouped)."""
+    from ._lib import GROUP_MAX, L2normProblem
+    ys, hold = [], []
+    for i0 in range(0, len(xs), GROUP_MAX):
+        grp = xs[i0:i0 + GROUP_MAX]
+        arr = (L2normProblem * len(grp))()
+        for q, x in zip(arr, grp):
+            _chk(x)
+            x = x.contiguous()
+            y = torch.empty_like(x)
+            q.x, q.y, q.B, q.K, q.eps, q.mode = x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], float(eps), mode
+            ys.append(y)
+            hold.append(x)
+        check(lib.ppst_l2norm_rows_grouped(arr, len(grp), _stream()), "ppst_l2norm_rows_grouped")
+    return ys
+
+
+def lerp_grouped(pairs, r):
+    """lerp(a, b, r) of several (a, b) pairs in one launch per GROUP_MAX (ppst_lerp_grouped)."""
+    from ._lib import GROUP_MAX, LerpProblem
+    ys, hold = [], []
+    for i0 in range(0, len(pairs), GROUP_MAX):
+        grp = pairs[i0:i0 + GROUP_MAX]
+        arr = (LerpProblem * len(grp))()
+        for q, (a, b) in zip(arr, grp):
+            _chk(a); _chk(b)
+            a, b = a.contiguous(), b.contiguous()
+            y = torch.empty_like(a)
+            q.a, q.b, q.y, q.n, q.r = a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel(), float(r)
+            ys.append(y)
+            hold.append((a, b))
+        check(lib.ppst_lerp_grouped(arr, len(grp), _stream()), "ppst_lerp_grouped")
+    return ys
 
 
 def l2norm_rows(x, eps, mode):
