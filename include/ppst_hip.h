@@ -10,8 +10,7 @@
  * and keeps no state between calls: every buffer, workspaces included, is the
  * caller's.  The only process-wide settings are opt-in diagnostics: the profiling
  * event pool of ppst_prof_* (it creates its events) with its side channel
- * ppst_wgrad_flop_steps, the tuning aid ppst_guided_filter_tune, and the undeclared
- * timing ablation ppst_wgrad_ablate of the weight-gradient kernel.  Each declaration cites the
+ * ppst_wgrad_flop_steps, and the tuning aid ppst_guided_filter_tune.  Each declaration cites the
  * reference interface (file:line under wangxb29/PPST) it replaces.
  *
  * Grouped entry points (ppst_linear_grouped, ppst_l2norm_rows_grouped, ppst_lerp_grouped,
@@ -651,22 +650,13 @@ int ppst_smooth_local_affine(const void* output, const void* input, void* result
 int ppst_conv_wgrad_f32(const void* x, const void* dy, const void* steps, const void* chunk_start,
                         void* partial, int B, int in_h, int in_w, int in_ld, int oh, int ow,
                         int dy_ld, int cout, int nsteps, int nchunks, int splits, void* stream);
-/* the same gradient on the bf16 matrix pipe, fp32-class through the hi/lo split of both operands (the production path;
- * ppst_conv_wgrad_f32 stays the exact verification path).  Same arguments; rows must be 16-B aligned, taps in [-1,1]^2. */
-int ppst_conv_wgrad_bf16x3(const void* x, const void* dy, const void* steps, const void* chunk_start,
-                           void* partial, int B, int in_h, int in_w, int in_ld, int oh, int ow,
-                           int dy_ld, int cout, int nsteps, int nchunks, int splits, void* stream);
-/* the production form of round 3 (same arithmetic: bf16 hi / lo split, three MFMA passes, fp32 accumulation): raw fp32 tiles by
- * LDS-DMA one tile ahead, one conversion pass per tile, transposed LDS reads (ds_read_b64_tr_b16) for the MFMA operands.
- * ``splits`` must be even: the grid covers splits / 2 pixel ranges and every block writes two partial slots.  ``csum`` (NULL or
- * [splits / 2][cout]): partial fp32 column sums of dy, fused into the conversion pass -- summed over the rows (ppst_colsum) they
- * are the bias gradient. */
-int ppst_conv_wgrad_tr(const void* x, const void* dy, const void* steps, const void* chunk_start, void* partial, void* csum,
-                       int B, int in_h, int in_w, int in_ld, int oh, int ow, int dy_ld, int cout, int nsteps, int nchunks,
-                       int splits, void* stream);
-/* the two-blocks-per-CU form of it (256-thread blocks, fp32 -> bf16 hi | lo converted in place in LDS, 49 KB per block): the
+/* the same gradient on the bf16 matrix pipe (the production path; ppst_conv_wgrad_f32 stays the exact verification path):
+ * fp32-class through the bf16 hi / lo split of both operands, three MFMA passes, fp32 accumulation.  Rows must be 16-B aligned,
+ * taps in [-1,1]^2.  Raw fp32 tiles arrive by LDS-DMA and are converted to hi | lo in place in LDS (49 KB per 256-thread block),
+ * the MFMA operands come from transposed LDS reads (ds_read_b64_tr_b16); two blocks per CU: the
  * phases of one block (request, wait, convert, MFMA) overlap the other block's.  ``splits`` = partial slots = pixel ranges (any
- * positive count); csum NULL or [splits][cout].  max_taps / min_taps: longest / shortest chunk of the step table (0 = unknown):
+ * positive count); csum NULL or [splits][cout]: partial fp32 column sums of dy, fused into the conversion pass -- summed over
+ * the rows (ppst_wgrad_scatter) they are the bias gradient.  max_taps / min_taps: longest / shortest chunk of the step table (0 = unknown):
  * <= 4 and an even chunk count select the two-chunks-per-block form, min == max == 9 (or 4) the form without per-tap tests.
  * halo: 1 in general; 0 = every step has offset (0, 0) and the input has the output's extent (1x1 convs): with one step per
  * chunk the block then stages no halo and takes four (two) chunks per dY image.
@@ -680,7 +670,7 @@ int ppst_conv_wgrad_tr2(const void* x, const void* dy, const void* steps, const 
 int ppst_wgrad_scatter(const void* partial, const void* src_c, const void* src_ky, const void* src_kx,
                        void* dw, int64_t sn, int64_t sc, int64_t sy, int64_t sx, int cout, int nsteps,
                        int splits, float scale, int accumulate, const void* csum, void* db, int csum_rows, int db_accumulate,
-                       void* stream);   /* csum (NULL or [csum_rows][cout] from ppst_conv_wgrad_tr*): db[n] (+)= sum of its rows */
+                       void* stream);   /* csum (NULL or [csum_rows][cout] from ppst_conv_wgrad_tr2 / ppst_conv_wgrad_tr2_st): db[n] (+)= sum of its rows */
 /* FromRGB (Cin <= 4) weight gradient: dw[n][c] (+)= scale * sum_p dy[p][n]*x[p][c] */
 int64_t ppst_wgrad_small_cin_ws(int64_t npix, int cin, int cout);
 int ppst_wgrad_small_cin(const void* x, const void* dy, void* dw, void* ws, int64_t npix, int cin,
@@ -800,7 +790,7 @@ int ppst_prof_dropped(void);
 /* after a stream sync: total ms, launches, algorithmic flop of bracketed calls */
 int ppst_prof_collect(double* ms, int64_t* launches, double* flop);
 /* per-launch detail of bracketed call idx (before ppst_prof_collect resets the pool):
- * info = {B, tile_h, tile_w, nsteps, cout, n_groups, halo, bn}; a ppst_conv_wgrad_bf16x3 / ppst_conv_wgrad_tr launch is bracketed too, with
+ * info = {B, tile_h, tile_w, nsteps, cout, n_groups, halo, bn}; a ppst_conv_wgrad_tr2 / ppst_conv_wgrad_tr2_st launch is bracketed too, with
  * info = {B, oh, ow, nsteps, cout, nchunks, splits, 0} (bn = 0 marks it) */
 int ppst_prof_detail(int idx, double* ms, double* flop, int32_t* info);
 /* profiling only: number of steps of the NEXT weight-gradient launch that carry real weights (default: all of them) */

@@ -447,7 +447,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void gemm_split
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  // transposed-read lane geometry (train.hip, conv_wgrad_tr_kernel): lane -> row 8 kb + qd (+ 4), column group 16 (g & 1) + 4 pp
+  // transposed-read lane geometry (train.hip, the comment in front of conv_wgrad_tr2_kernel): lane -> row 8 kb + qd (+ 4), column group 16 (g & 1) + 4 pp
   const int g = lane >> 4, qd = (lane & 15) >> 2, pp = lane & 3;
   const int tr_off = (8 * (g >> 1) + qd) * 64 + (16 * (g & 1) + 4 * pp) * 2;
   auto compute = [&](int buf) {

@@ -184,360 +184,42 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_lds_kernel(const float* __r
   }
 }
 
-// bf16x3 weight gradient (round 2): the same partial layout, step tables and tiling as conv_wgrad_lds_kernel, on the bf16
-// matrix pipe (v_mfma_f32_32x32x16_bf16: 5.3x the fp32 MFMA's rate after the three passes of the hi/lo split).  The
-// reduction index of this GEMM is the PIXEL, so an MFMA operand lane needs 8 consecutive pixels of one channel: the staging
-// pass converts fp32 -> bf16 hi / lo and packs PIXEL PAIRS (x even, x odd) of one channel into a dword, laid out
-// [pair][channel]; a fragment is then 4 conflict-free ds_read_b32.  The input tile is kept twice -- pairs starting at an odd
-// and at an even column -- so that the dx = -1 / 0 / +1 taps all find their pixel pairs aligned.  67 KB of LDS, two blocks per
-// CU.  Rounding: every product carries the 2^-17 relative error of the split, the sums are the MFMA's fp32 accumulation as
-// before (the discriminator / generator gradient bars of tests/ are 5e-3).
-#define WX_ROWS (WG_TR + 2)
-#define WX_PAIRS (WG_TC / 2 + 1)
-__global__ __launch_bounds__(256, 2) void conv_wgrad_x3_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                             const int4* __restrict__ steps, const int* __restrict__ chunk_start,
-                                                             float* __restrict__ partial, int B, int in_h, int in_w, int in_ld,
-                                                             int oh, int ow, int dy_ld, int cout, int nsteps, int tiles_x,
-                                                             int tiles_per_image, int tiles_total, int tiles_per_split) {
-  // [hi | lo][pixel pair][channel]
-  __shared__ __attribute__((aligned(16))) unsigned sdy[2][WG_TR * WG_TC / 2][128];
-  __shared__ __attribute__((aligned(16))) unsigned sx[2][2][WX_ROWS * WX_PAIRS][32];     // [hi|lo][copy A (odd start) | B (even start)]
-  typedef unsigned __attribute__((ext_vector_type(4))) u4;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, kb = lane >> 5;
-  const int n0 = blockIdx.x * 128;
-  const int s0 = chunk_start[blockIdx.y], s1 = chunk_start[blockIdx.y + 1];
-  const int T = s1 - s0;
-  const int chan = steps[s0].x;
-  int tdy[WG_MAXT], tdx[WG_MAXT];
-#pragma unroll
-  for (int t = 0; t < WG_MAXT; ++t) {
-    int4 d = steps[s0 + (t < T ? t : 0)];
-    tdy[t] = d.y; tdx[t] = d.z;
-  }
-  f32x16 acc[WG_MAXT];
-#pragma unroll
-  for (int t = 0; t < WG_MAXT; ++t)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
-  const int t_begin = blockIdx.z * tiles_per_split;
-  const int t_end = min(t_begin + tiles_per_split, tiles_total);
-  const bool wave_live = n0 + wave * 32 < cout;
-  auto pack2 = [](float a, float b, unsigned& hi, unsigned& lo) {
-    unsigned short ah, al, bh, bl;
-    split_bf16(a, ah, al);
-    split_bf16(b, bh, bl);
-    hi = (unsigned)ah | ((unsigned)bh << 16);
-    lo = (unsigned)al | ((unsigned)bl << 16);
-  };
-  for (int tile = t_begin; tile < t_end; ++tile) {
-    const int b = tile / tiles_per_image;
-    const int r = tile - b * tiles_per_image;
-    const int ty0 = (r / tiles_x) * WG_TR, tx0 = (r - (r / tiles_x) * tiles_x) * WG_TC;
-    __syncthreads();                                       // previous tile's reads are done
-    // dY: pairs (x, x+1), x even, of the 2 x 32-pixel tile; 4 channels per thread-item
-    for (int i = tid; i < (WG_TR * WG_TC / 2) * 32; i += 256) {
-      const int q = i & 31, pr = i >> 5;
-      const int y = ty0 + pr / (WG_TC / 2), xx = tx0 + (pr % (WG_TC / 2)) * 2;
-      const int n = n0 + q * 4;
-      float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
-      if (y < oh && n < cout) {
-        const float* p = dy + (((int64_t)b * oh + y) * ow + xx) * dy_ld + n;
-        if (xx < ow) v0 = *(const float4*)p;
-        if (xx + 1 < ow) v1 = *(const float4*)(p + dy_ld);
-      }
-      unsigned h[4], l[4];
-      pack2(v0.x, v1.x, h[0], l[0]); pack2(v0.y, v1.y, h[1], l[1]); pack2(v0.z, v1.z, h[2], l[2]); pack2(v0.w, v1.w, h[3], l[3]);
-      *(u4*)&sdy[0][pr][q * 4] = (u4){h[0], h[1], h[2], h[3]};
-      *(u4*)&sdy[1][pr][q * 4] = (u4){l[0], l[1], l[2], l[3]};
-    }
-    // input halo tile, rows ty0 - 1 .. ty0 + 2: copy A pairs (tx0 + 2j - 1, tx0 + 2j), copy B pairs (tx0 + 2j, tx0 + 2j + 1)
-    for (int i = tid; i < 2 * WX_ROWS * WX_PAIRS * 8; i += 256) {
-      const int q = i & 7;
-      int rest = i >> 3;
-      const int j = rest % WX_PAIRS; rest /= WX_PAIRS;
-      const int row = rest % WX_ROWS, copy = rest / WX_ROWS;
-      const int iy = ty0 - 1 + row, ix = tx0 + 2 * j - (copy == 0 ? 1 : 0);
-      float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
-      if (iy >= 0 && iy < in_h) {
-        const float* p = x + (((int64_t)b * in_h + iy) * in_w + ix) * in_ld + chan + q * 4;
-        if (ix >= 0 && ix < in_w) v0 = *(const float4*)p;
-        if (ix + 1 >= 0 && ix + 1 < in_w) v1 = *(const float4*)(p + in_ld);
-      }
-      unsigned h[4], l[4];
-      pack2(v0.x, v1.x, h[0], l[0]); pack2(v0.y, v1.y, h[1], l[1]); pack2(v0.z, v1.z, h[2], l[2]); pack2(v0.w, v1.w, h[3], l[3]);
-      *(u4*)&sx[0][copy][row * WX_PAIRS + j][q * 4] = (u4){h[0], h[1], h[2], h[3]};
-      *(u4*)&sx[1][copy][row * WX_PAIRS + j][q * 4] = (u4){l[0], l[1], l[2], l[3]};
-    }
-    __syncthreads();
-    if (wave_live) {
-#pragma unroll
-      for (int ks = 0; ks < WG_TR * WG_TC / 16; ++ks) {      // 16 pixels of one tile row per MFMA
-        const int row = ks / (WG_TC / 16), xh = (ks % (WG_TC / 16)) * 16;
-        const int pa = row * (WG_TC / 2) + xh / 2 + kb * 4;
-        u4 ah, al;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { ah[e] = sdy[0][pa + e][wave * 32 + li]; al[e] = sdy[1][pa + e][wave * 32 + li]; }
-        const bf16x8 a_h = __builtin_bit_cast(bf16x8, ah), a_l = __builtin_bit_cast(bf16x8, al);
-#pragma unroll
-        for (int t = 0; t < WG_MAXT; ++t) {
-          if (t < T) {
-            const int copy = tdx[t] == 0 ? 1 : 0;
-            const int pj = (row + 1 + tdy[t]) * WX_PAIRS + xh / 2 + kb * 4 + (tdx[t] == 1 ? 1 : 0);
-            u4 bh, bl;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { bh[e] = sx[0][copy][pj + e][li]; bl[e] = sx[1][copy][pj + e][li]; }
-            const bf16x8 b_h = __builtin_bit_cast(bf16x8, bh), b_l = __builtin_bit_cast(bf16x8, bl);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_l, b_h, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, b_l, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, b_h, acc[t], 0, 0, 0);
-          }
-        }
-      }
-    }
-  }
-  if (!wave_live) return;
-#pragma unroll
-  for (int t = 0; t < WG_MAXT; ++t) {
-    if (t < T) {
-      float* o = partial + (((int64_t)blockIdx.z * nsteps + s0 + t) * cout) * 32;
-#pragma unroll
-      for (int rg = 0; rg < 16; ++rg) {
-        int nn = n0 + wave * 32 + (rg & 3) + 8 * (rg >> 2) + 4 * kb;
-        if (nn < cout) o[(int64_t)nn * 32 + li] = acc[t][rg];
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
-// Round 3: the bf16x3 weight gradient without exposed memory latency.  rocprofv3 + ISA of conv_wgrad_x3_kernel: its staging
-// loops were not unrolled (256 registers, 144 of them accumulators), so a tile cost ~9 SERIALISED global round trips
-// (load 2 x 16 B -> s_waitcnt vmcnt(0) -> convert -> ds_write), 10-12 k cycles per tile against 3.5 k of MFMA work: 0.16 of the
-// bf16x3 ceiling over the step.  This kernel:
-//   * raw fp32 tiles (dY 64 px x 128 n, input halo 4 x 34 px x 32 ch) arrive by LDS-DMA (global_load_lds_dwordx4: no registers,
-//     out-of-image / out-of-range lanes read a 16-byte zero word), requested one tile AHEAD, under the MFMA phase;
-//   * ONE conversion pass per tile (all 512 threads): fp32 -> bf16 hi / lo into plain [pixel][channel] images -- and, in the
-//     blocks of chunk 0, the fp32 column sums of dY (the bias gradient: the 304 colsum launches per train step re-read every dY
-//     the weight gradient had just read);
-//   * MFMA operands by ds_read_b64_tr_b16 (the K index of this GEMM is the PIXEL; the transposed read turns 4 pixel rows x 16
-//     channels into 4 k-values per lane): no pixel-pair packing, ONE input image for all nine taps, half the LDS cycles;
-//   * 8 waves = 4 (n slabs of 32) x 2 (tile rows): the two row groups accumulate separate partial sums, written as two split
-//     slots -- the existing scatter kernel adds them like any other split.
-// LDS: two raw buffers (the DMA runs TWO tiles ahead: a 49-KB fill takes longer than one tile's MFMA phase when every CU asks
-// at once) + the converted images = 147 KB (one block per CU, two waves per SIMD).
-#define WT_PX (WG_TR * WG_TC)                 // 64 pixels of dY per tile
-#define WT_XW (WG_TC + 2)
-#define WT_XPX ((WG_TR + 2) * WT_XW)          // 136 halo pixels of the input chunk
-__device__ __attribute__((aligned(16))) float g_wg_zero[4] = {0.f, 0.f, 0.f, 0.f};
-typedef short __attribute__((ext_vector_type(4))) wt_v4s;
-__device__ __forceinline__ bf16x8 wt_tr2(const unsigned char* p0) {
-  // two transposed reads, 4 pixel rows (64-B rows) apart: k = 0..3 and 4..7 of this lane's channel
-  const wt_v4s a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wt_v4s __attribute__((address_space(3)))*)(p0));
-  const wt_v4s b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wt_v4s __attribute__((address_space(3)))*)(p0 + 4 * 64));
-  return (bf16x8){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-__global__ __launch_bounds__(512, 1) void conv_wgrad_tr_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                             const int4* __restrict__ steps, const int* __restrict__ chunk_start,
-                                                             float* __restrict__ partial, float* __restrict__ csum, int B, int in_h,
-                                                             int in_w, int in_ld, int oh, int ow, int dy_ld, int cout, int nsteps,
-                                                             int tiles_x, int tiles_per_image, int tiles_total, int tiles_per_split, int abl) {
-  // abl (timing ablations, results WRONG, tests/wgrad_tr_check.py only): 1 no MFMA phase, 2 no conversion pass, 4 no DMA after the prologue
-  constexpr int RAW_DY = WT_PX * 128 * 4, RAW_X = WT_XPX * 32 * 4;          // 32768 + 17408 bytes
-  constexpr int CV_DY = WT_PX * 128 * 2, CV_X = WT_XPX * 32 * 2;            // per plane: 16384, 8704 bytes
-  constexpr int RAW = RAW_DY + RAW_X;                                         // 49 pieces of 1 KB
-  static_assert(RAW_X == 17 * 1024, "input halo = 17 DMA pieces");
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * RAW + 2 * CV_DY + 2 * CV_X];
-  unsigned char* const cvdy = smem + 2 * RAW;                 // [hi | lo][slab 0..3][64 px][32 ch] bf16
-  unsigned char* const cvx = cvdy + 2 * CV_DY;                // [hi | lo][136 px][32 ch] bf16
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nw = wave & 3, kh = wave >> 2;                     // n slab (32 channels), tile row this wave reduces over
-  const int li = lane & 31, kb = lane >> 5;
-  // XCD-aware block map.  Blocks go to the 8 XCDs round-robin by linear id, and the blocks that share a tile of dY (all chunks
-  // y of one pixel range z) or of the input (all n tiles x) had consecutive ids: every XCD's L2 fetched those tiles from HBM
-  // itself (the three 3x3 layers of the generator each moved 1.34 GB per launch instead of 0.54).  The bijective 8-way remap
-  // gives each XCD a contiguous range of the (z, y, x) order -- x fastest -- so co-resident blocks of one XCD walk the same tiles.
-  int bx, by, bz;
-  {
-    const int nb = gridDim.x * gridDim.y * gridDim.z;
-    const int id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const int q8 = nb >> 3, r8 = nb & 7, xcd = id & 7;
-    int v = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
-    bx = v % (int)gridDim.x; v /= (int)gridDim.x;
-    by = v % (int)gridDim.y; bz = v / (int)gridDim.y;
-  }
-  const int n0 = bx * 128;
-  const int s0 = chunk_start[by], s1 = chunk_start[by + 1];
-  const int T = s1 - s0;
-  const int chan = steps[s0].x;
-  int tdy[WG_MAXT], tdx[WG_MAXT];
-#pragma unroll
-  for (int t = 0; t < WG_MAXT; ++t) {
-    int4 d = steps[s0 + (t < T ? t : 0)];
-    tdy[t] = d.y; tdx[t] = d.z;
-  }
-  f32x16 acc[WG_MAXT];
-#pragma unroll
-  for (int t = 0; t < WG_MAXT; ++t)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
-  const int t_begin = bz * tiles_per_split;
-  const int t_end = min(t_begin + tiles_per_split, tiles_total);
-  const bool wave_live = n0 + nw * 32 < cout;
-  const bool want_csum = csum != nullptr && by == 0;
-  float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);               // this thread's 4 channels (tid & 31), its pixels of every tile
-
-  // ---- LDS-DMA of one tile's raw fp32 data: 32 pieces of dY (2 pixels x 512 B each) + 17 of the input (8 pixels x 128 B)
-  // one piece (wave-uniform index wi) of a tile's raw data
-  auto dma_piece = [&](int tile, int slot, int wi) {
-    unsigned char* const rawdy = smem + slot * RAW;
-    unsigned char* const rawx = rawdy + RAW_DY;
-    const int b = tile / tiles_per_image;
-    const int r = tile - b * tiles_per_image;
-    const int ty0 = (r / tiles_x) * WG_TR, tx0 = (r - (r / tiles_x) * tiles_x) * WG_TC;
-    {
-      const float* src = g_wg_zero;
-      unsigned char* dst;
-      if (wi < 32) {
-        const int p = 2 * wi + (lane >> 5), q = lane & 31;
-        const int y = ty0 + (p >> 5), xx = tx0 + (p & 31), n = n0 + q * 4;
-        if (y < oh && xx < ow && n < cout) src = dy + (((int64_t)b * oh + y) * ow + xx) * dy_ld + n;
-        dst = rawdy + wi * 1024;
-      } else {
-        const int P = 8 * (wi - 32) + (lane >> 3), q = lane & 7;
-        const int row = P / WT_XW, col = P - row * WT_XW;
-        const int iy = ty0 - 1 + row, ix = tx0 - 1 + col;
-        if (iy >= 0 && iy < in_h && ix >= 0 && ix < in_w) src = x + (((int64_t)b * in_h + iy) * in_w + ix) * in_ld + chan + q * 4;
-        dst = rawx + (wi - 32) * 1024;
-      }
-      __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src, (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
-    }
-  };
-  auto dma_tile = [&](int tile, int slot) {
-    for (int wi = wave; wi < 32 + 17; wi += 8) dma_piece(tile, slot, wi);
-  };
-  auto split4 = [](float4 v, uint2& hi, uint2& lo) { split_bf16x4(v, hi, lo); };
-  // transposed-read lane geometry: group g = lane / 16 reads 4 pixel rows x 16 channels; lane 4q + p of the group supplies the
-  // address of row q, channels 4p .. 4p+3; lane i receives channel i of the 4 rows.  Groups 0 / 1: channels 0-15 / 16-31 of
-  // k-half 0, groups 2 / 3 the same of k-half 1 -- i.e. channel li, k-half kb, as the 32x32x16 operand wants.
-  const int g = lane >> 4, qd = (lane & 15) >> 2, pp = lane & 3;
-  const int tr_off = (8 * (g >> 1) + qd) * 64 + (16 * (g & 1) + 4 * pp) * 2;      // bytes, relative to the operand's first pixel
-
-  if (t_begin < t_end) dma_tile(t_begin, 0);
-  if (t_begin + 1 < t_end) dma_tile(t_begin + 1, 1);
-  for (int tile = t_begin; tile < t_end; ++tile) {
-    const int slot = (tile - t_begin) & 1;
-    const unsigned char* const rawdy = smem + slot * RAW;
-    const unsigned char* const rawx = rawdy + RAW_DY;
-    // this tile's raw data have landed (hipcc adds no wait for LDS-DMA); the NEXT tile's pieces -- younger, 7 from wave 0 and
-    // 6 from the others -- may stay in flight: vmcnt retires in issue order
-    if (tile + 1 < t_end && !(abl & 4)) {
-      if (wave == 0) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();                                        // ... for every wave; and the previous tile's MFMA reads are done
-    // ---- conversion pass: raw fp32 -> bf16 hi / lo images
-    if (!(abl & 2)) {
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int i = tid + it * 512;
-      const int q = i & 31, p = i >> 5;
-      const float4 v = *(const float4*)(rawdy + (p * 128 + q * 4) * 4);
-      if (want_csum) { cs.x += v.x; cs.y += v.y; cs.z += v.z; cs.w += v.w; }
-      uint2 hi, lo;
-      split4(v, hi, lo);
-      unsigned char* o = cvdy + (q >> 3) * 4096 + p * 64 + (q & 7) * 8;
-      *(uint2*)o = hi;
-      *(uint2*)(o + CV_DY) = lo;
-    }
-#pragma unroll
-    for (int it = 0; it < 3; ++it) {
-      const int i = tid + it * 512;
-      if (i < WT_XPX * 8) {
-        const float4 v = *(const float4*)(rawx + i * 16);
-        uint2 hi, lo;
-        split4(v, hi, lo);
-        *(uint2*)(cvx + i * 8) = hi;
-        *(uint2*)(cvx + CV_X + i * 8) = lo;
-      }
-    }
-    }
-    __syncthreads();                                        // images complete; this raw slot is free again
-    // The raw data of tile + 2 go into the slot just converted, requested in one burst in front of the MFMA phase.  (Measured:
-    // handing the 6-7 pieces of a wave out between the taps of the MFMA loop instead is 30 % SLOWER, 0.68 -> 0.89 ms on
-    // 128->128 @512^2 -- an in-order wave that waits at the issue of a request does not issue its MFMAs either.  Timing
-    // ablations of that layer, ms: barriers only 0.08, + DMA 0.29, + conversion 0.19, + MFMA 0.39, everything 0.68-0.75: the
-    // three phases of a tile add up; 49 KB per tile and CU move at 7.5 TB/s chip-wide, as long as the tile's MFMA work.)
-    if (tile + 2 < t_end && !(abl & 4)) dma_tile(tile + 2, slot);
-    if (wave_live && !(abl & 1)) {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {                       // the two 16-pixel halves of this wave's tile row
-        const int xh = kk * 16;
-        const unsigned char* pa = cvdy + nw * 4096 + (kh * 32 + xh) * 64 + tr_off;
-        const bf16x8 a_h = wt_tr2(pa), a_l = wt_tr2(pa + CV_DY);
-        // software pipeline over the taps: the fragments of tap t + 1 are requested before the MFMAs of tap t
-        const unsigned char* pb0 = cvx + ((kh + 1 + tdy[0]) * WT_XW + xh + 1 + tdx[0]) * 64 + tr_off;
-        bf16x8 b_h = wt_tr2(pb0), b_l = wt_tr2(pb0 + CV_X);
-#pragma unroll
-        for (int t = 0; t < WG_MAXT; ++t) {
-          if (t < T) {
-            bf16x8 n_h = b_h, n_l = b_l;
-            if (t + 1 < WG_MAXT && t + 1 < T) {
-              const unsigned char* pb = cvx + ((kh + 1 + tdy[t + 1]) * WT_XW + xh + 1 + tdx[t + 1]) * 64 + tr_off;
-              n_h = wt_tr2(pb); n_l = wt_tr2(pb + CV_X);
-            }
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_l, b_h, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, b_l, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, b_h, acc[t], 0, 0, 0);
-            b_h = n_h; b_l = n_l;
-          }
-        }
-      }
-    }
-  }
-  // ---- column sums of dY (chunk-0 blocks): 16 threads share a channel quad -> one partial row per block
-  if (want_csum) {
-    __syncthreads();                                        // the images are dead: reuse the front of the raw buffer
-    float4* red = (float4*)smem;                            // [16][32] float4
-    red[(tid >> 5) * 32 + (tid & 31)] = cs;
-    __syncthreads();
-    if (tid < 32) {
-      float4 a = red[tid];
-#pragma unroll
-      for (int r = 1; r < 16; ++r) { const float4 v = red[r * 32 + tid]; a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
-      const int n = n0 + tid * 4;
-      float* o = csum + (int64_t)bz * cout + n;
-      if (n < cout) { o[0] = a.x; if (n + 1 < cout) o[1] = a.y; if (n + 2 < cout) o[2] = a.z; if (n + 3 < cout) o[3] = a.w; }
-    }
-  }
-  if (!wave_live) return;
-#pragma unroll
-  for (int t = 0; t < WG_MAXT; ++t) {
-    if (t < T) {
-      float* o = partial + ((((int64_t)bz * 2 + kh) * nsteps + s0 + t) * cout) * 32;
-#pragma unroll
-      for (int rg = 0; rg < 16; ++rg) {
-        int nn = n0 + nw * 32 + (rg & 3) + 8 * (rg >> 2) + 4 * kb;
-        if (nn < cout) o[(int64_t)nn * 32 + li] = acc[t][rg];
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The two-blocks-per-CU form of the same idea (the production weight gradient).  conv_wgrad_tr_kernel's phases ADD UP inside
-// its one block per CU (timing ablations at its DMA call site): the fix is not a deeper pipeline inside the block but a second
-// block on the CU that is in another phase.  For that the tile has to fit 80 KB:
-//   * the fp32 data are converted IN PLACE: a 16-byte unit (one pixel, four channels) becomes [hi x 4 | lo x 4] bf16 in the same
-//     16 bytes -- no second image.  ds_read_b64_tr_b16 takes a per-lane address, so any unit layout works; units of pixels p and
-//     p + 2 alias the same banks, so every other pixel PAIR stores [lo | hi] instead: the 32 eight-byte reads of a half-wave
-//     (4 pixels x 8 channel quads) then hit 64 distinct banks;
-//   * dY image: 4 slabs (32 channels) x 64 pixels x 128 B = 32 KB, input halo image 136 pixels x 128 B = 17 KB: 49 KB per block,
-//     256 threads, 4 waves = 4 n slabs, each wave reduces over the tile's four 16-pixel groups.
-// Per tile: request (LDS-DMA, 49 pieces) -> wait -> convert (+ the bias column sums) -> MFMA; nothing inside the block overlaps,
-// the co-resident block does.
+// The production weight gradient (every precision but 2, 16-byte aligned operands): the same partial layout, step tables and
+// 2 x 32-pixel tiles as conv_wgrad_lds_kernel, on the bf16 matrix pipe (v_mfma_f32_32x32x16_bf16) with the fp32 operands split
+// into bf16 hi / lo halves: three passes (lo x hi, hi x lo, hi x hi -- 5.3x the fp32 MFMA's rate after the three passes; every
+// product carries the 2^-17 relative error of the split, the sums are the MFMA's fp32 accumulation as before: the discriminator /
+// generator gradient bars of tests/ are 5e-3), or ONE pass over the hi halves (X1, below).
+//   * Feed: LDS-DMA.  The raw fp32 tile (dY 64 px x 128 n = 32 KB, input halo 4 x 34 px x 32 ch = 17 KB) goes global -> LDS by
+//     global_load_lds_dwordx4: no registers, one 1-KB piece (64 lanes x 16 B) per wave instruction.  A lane whose pixel lies outside
+//     the image or whose channels lie beyond cout reads the 16-byte ZERO WORD g_wg_zero instead of its own address: the image needs
+//     no zero fill and the request no branch.  hipcc adds no wait for LDS-DMA: s_waitcnt vmcnt(0) in front of the barrier.
+//   * Conversion IN PLACE, one pass of all threads per tile: a 16-byte unit (one pixel, four channels) becomes [hi x 4 | lo x 4]
+//     bf16 in the same 16 bytes -- no second image -- and, in the blocks of chunk 0, the fp32 column sums of dY are taken on the way
+//     (the bias gradient: the 304 colsum launches per train step re-read every dY the weight gradient had just read).  Units of
+//     pixels p and p + 2 alias the same banks, so every other pixel PAIR stores [lo | hi] instead: the 32 eight-byte reads of a
+//     half-wave (4 pixels x 8 channel quads) then hit 64 distinct banks.
+//   * MFMA operands by transposed reads (ds_read_b64_tr_b16).  The K index of this GEMM is the PIXEL, so an operand lane needs 8
+//     consecutive pixels of ONE channel while the image is [pixel][channel].  The instruction takes a per-lane address (any unit
+//     layout works) and transposes within groups of 16 lanes: group g = lane / 16 reads 4 pixel rows x 16 channels; lane 4q + p of
+//     the group supplies the address of pixel row q, channels 4p .. 4p+3; lane i of the group receives channel i of the 4 rows, i.e.
+//     4 k-values.  Groups 0 / 1: channels 0-15 / 16-31 of k-half 0, groups 2 / 3 the same of k-half 1 -- channel lane & 31, k-half
+//     lane >> 5, as the 32x32x16 operand wants; a second read 4 pixels on completes the 8 k-values.  No pixel-pair packing, and ONE
+//     input image serves all nine taps (a tap is an address offset).
+//   * XCD-aware block map.  Blocks go to the 8 XCDs round-robin by linear id, and the blocks that share a tile of dY (all chunks y
+//     of one pixel range z) or of the input (all n tiles x) had consecutive ids: every XCD's L2 fetched those tiles from HBM itself
+//     (the three 3x3 layers of the generator each moved 1.34 GB per launch instead of 0.54).  The bijective 8-way remap gives each
+//     XCD a contiguous range of the (z, y, x) order -- x fastest -- so co-resident blocks of one XCD walk the same tiles.
+//   * Two blocks per CU.  Per tile: request (49 pieces) -> wait -> convert (+ the bias column sums) -> MFMA; nothing inside the
+//     block overlaps, the co-resident block -- in another phase -- does.  For that the tile has to fit 80 KB: dY image 4 slabs
+//     (32 channels) x 64 pixels x 128 B = 32 KB, input halo image 136 pixels x 128 B = 17 KB: 49 KB per block, 256 threads, 4 waves
+//     = 4 n slabs, each wave reduces over the tile's four 16-pixel groups.
+// History (a4b3174 is the last commit with their code): conv_wgrad_x3_kernel (round 2) staged through registers, converting and
+// packing pixel pairs on the way to LDS; its staging loops serialised ~9 global round trips per tile, 10-12 k cycles against 3.5 k
+// of MFMA work: 0.16 of the bf16x3 ceiling over the step.  conv_wgrad_tr_kernel (round 3) brought the feed, the transposed reads
+// and the block map described here, as ONE 8-wave block per CU with 147 KB of LDS (DMA two tiles ahead, a second, converted image);
+// its phases ADDED UP inside the one block (128->128 @512^2, ms: DMA 0.29 + conversion 0.19 + MFMA 0.39 of 0.68-0.75; handing the
+// DMA pieces out between the taps was 30 % slower still), and the fix was not a deeper pipeline but the second block on the CU.
 // NCH chunks (32 input channels each) per block, at most TM taps per chunk: <1, 9> for 3x3 tables; <2, 4> for tables whose chunks
 // have <= 4 steps (transposed conv, stride-2 tables, 1x1): two input images share ONE dY image, i.e. a third fewer bytes per MFMA
 // where a 4-tap chunk would otherwise do 4/9 of the MFMA work of a 3x3 chunk per staged tile (blockIdx.y = pair of chunks).
@@ -548,6 +230,11 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_tr_kernel(const float* __re
 // LDS queue at every block entry, and the next tap's fragments could not be requested across it).
 // HALO = false (1x1 tables: one step per chunk, no offsets): the input image is the tile's own 2 x 32 pixels (8 KB per chunk
 // instead of the 17-KB halo image), so FOUR chunks share a block and one dY image at 64 KB of LDS.
+#define WT_PX (WG_TR * WG_TC)                 // 64 pixels of dY per tile
+#define WT_XW (WG_TC + 2)
+#define WT_XPX ((WG_TR + 2) * WT_XW)          // 136 halo pixels of the input chunk
+__device__ __attribute__((aligned(16))) float g_wg_zero[4] = {0.f, 0.f, 0.f, 0.f};
+typedef short __attribute__((ext_vector_type(4))) wt_v4s;
 template <int NCH, int TM, bool X1, bool EXACT, bool HALO = true>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                               const int4* __restrict__ steps, const int* __restrict__ chunk_start,
@@ -563,7 +250,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2_kernel(const float* __r
   unsigned char* const imx = smem + IMG_DY;                   // NCH x [136 px][8 quads][16 B]
   const int tid = threadIdx.x, lane = tid & 63, nw = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, kb = lane >> 5;
-  int bx, by, bz;                                             // XCD-aware block map (conv_wgrad_tr_kernel)
+  int bx, by, bz;                                             // XCD-aware block map (the comment in front of conv_wgrad_tr2_kernel)
   {
     const int nb = gridDim.x * gridDim.y * gridDim.z;
     const int id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
@@ -605,7 +292,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2_kernel(const float* __r
   const int nslab = min(4, (cout - n0 + 31) >> 5);            // 32-channel slabs of dY this block has any use for
   const bool want_csum = csum != nullptr && by == 0;
   float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);               // this thread's 4 channels (quad tid % (8 nslab)) over its pixels of every tile
-  // transposed-read lane geometry (conv_wgrad_tr_kernel): channel quad 4 (g & 1) + pp, pixel 8 kb + qd (+ 4 for the second read)
+  // transposed-read lane geometry (the comment above): channel quad 4 (g & 1) + pp, pixel 8 kb + qd (+ 4 for the second read)
   const int g = lane >> 4, qd = (lane & 15) >> 2, pp = lane & 3;
   const int tr_unit = (8 * (g >> 1) + qd) * 128 + (4 * (g & 1) + pp) * 16;
   auto split4 = [](float4 v, uint2& hi, uint2& lo) { split_bf16x4(v, hi, lo); };
@@ -789,7 +476,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2b_kernel(const unsigned 
   __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63, nw = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, kb = lane >> 5;
-  int bx, by, bz;                                             // XCD-aware block map (conv_wgrad_tr_kernel)
+  int bx, by, bz;                                             // XCD-aware block map (the comment in front of conv_wgrad_tr2_kernel)
   {
     const int nb = gridDim.x * gridDim.y * gridDim.z;
     const int id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
@@ -946,62 +633,35 @@ static int wgrad_prof_begin(int B, int oh, int ow, int cout, int nsteps, int flo
   const int inf[8] = {B, oh, ow, nsteps, cout, nchunks, splits, 0};
   return ppst_prof_begin_(2.0 * 32.0 * (flop_steps > 0 ? flop_steps : nsteps) * (double)cout * (double)B * oh * ow, inf, st);
 }
-static int g_wgrad_abl = 0;          // timing ablations of conv_wgrad_tr_kernel (diagnostic: results wrong while non-zero)
-extern "C" int ppst_wgrad_ablate(int mask) { g_wgrad_abl = mask; return PPST_OK; }
 static int g_wgrad_flop_steps = 0;   // set by ppst_wgrad_flop_steps for the NEXT weight-gradient launch (profiling only)
 extern "C" int ppst_wgrad_flop_steps(int flop_steps) { g_wgrad_flop_steps = flop_steps; return PPST_OK; }
 
-// same contract as ppst_conv_wgrad_f32 (which stays the exact-fp32 path of precision 2); needs the 16-B aligned rows every
-// caller on the train path has, taps in [-1, 1]^2 (every step table of the path)
-extern "C" int ppst_conv_wgrad_bf16x3(const void* x, const void* dy, const void* steps, const void* chunk_start, void* partial,
-                                      int B, int in_h, int in_w, int in_ld, int oh, int ow, int dy_ld, int cout, int nsteps,
-                                      int nchunks, int splits, void* stream) {
+// The argument checks of every weight-gradient launcher, in the order the return codes promise: sizes, the empty batch (PPST_OK and
+// nothing to launch: the caller tests B == 0 itself), null pointers.  *aligned: 16-byte rows and pointers (the LDS-staged and the
+// transposed-read kernels need them; every caller on the train path has them)
+static int wgrad_check(const void* x, const void* dy, const void* steps, const void* chunk_start, const void* partial, int B, int in_h,
+                       int in_w, int in_ld, int oh, int ow, int dy_ld, int cout, int nsteps, int nchunks, int splits, bool* aligned) {
   if (B < 0 || in_h <= 0 || in_w <= 0 || in_ld <= 0 || oh <= 0 || ow <= 0 || dy_ld < cout || cout <= 0 || nsteps <= 0 ||
       nchunks <= 0 || splits <= 0)
     return PPST_EINVAL;
   if (B == 0) return PPST_OK;
   if (!x || !dy || !steps || !chunk_start || !partial) return PPST_ENULL;
-  if (cout % 4 || dy_ld % 4 || in_ld % 4 || ((uintptr_t)x | (uintptr_t)dy) % 16) return PPST_EINVAL;
-  const int tiles_x = cdiv(ow, WG_TC), tiles_per_image = cdiv(oh, WG_TR) * tiles_x;
-  const int tiles_total = B * tiles_per_image;
-  const int tps = cdiv(tiles_total, splits);
-  dim3 grid(cdiv(cout, 128), nchunks, splits);
-  const int slot = wgrad_prof_begin(B, oh, ow, cout, nsteps, g_wgrad_flop_steps, nchunks, splits, as_stream(stream));
-  g_wgrad_flop_steps = 0;
-  PPST_LAUNCH(conv_wgrad_x3_kernel, grid, dim3(256), 0, as_stream(stream), (const float*)x, (const float*)dy, (const int4*)steps,
-              (const int*)chunk_start, (float*)partial, B, in_h, in_w, in_ld, oh, ow, dy_ld, cout, nsteps, tiles_x, tiles_per_image,
-              tiles_total, tps);
-  ppst_prof_end_(slot, as_stream(stream));
-  return PPST_LAUNCH_CHECK();
+  *aligned = cout % 4 == 0 && dy_ld % 4 == 0 && in_ld % 4 == 0 && ((uintptr_t)x | (uintptr_t)dy) % 16 == 0;
+  return PPST_OK;
+}
+// the 2 x 32-pixel tiles of the output, dealt out to ``splits`` pixel ranges
+struct WgradTiles { int tiles_x, per_image, total, per_split; };
+static WgradTiles wgrad_tiles(int B, int oh, int ow, int splits) {
+  WgradTiles t;
+  t.tiles_x = cdiv(ow, WG_TC);
+  t.per_image = cdiv(oh, WG_TR) * t.tiles_x;
+  t.total = B * t.per_image;
+  t.per_split = cdiv(t.total, splits);
+  return t;
 }
 
-// LDS-DMA + transposed-read form (conv_wgrad_tr_kernel).  ``splits`` (even) = partial slots: the grid has splits / 2 pixel ranges,
-// each block writes two slots (one per tile row).  ``csum`` (optional): [splits / 2][cout] partial column sums of dY, written by the
-// blocks of chunk 0 -- their column-wise sum is the bias gradient (ppst_colsum over those rows finishes it).
-extern "C" int ppst_conv_wgrad_tr(const void* x, const void* dy, const void* steps, const void* chunk_start, void* partial, void* csum,
-                                  int B, int in_h, int in_w, int in_ld, int oh, int ow, int dy_ld, int cout, int nsteps,
-                                  int nchunks, int splits, void* stream) {
-  if (B < 0 || in_h <= 0 || in_w <= 0 || in_ld <= 0 || oh <= 0 || ow <= 0 || dy_ld < cout || cout <= 0 || nsteps <= 0 ||
-      nchunks <= 0 || splits <= 0 || (splits & 1))
-    return PPST_EINVAL;
-  if (B == 0) return PPST_OK;
-  if (!x || !dy || !steps || !chunk_start || !partial) return PPST_ENULL;
-  if (cout % 4 || dy_ld % 4 || in_ld % 4 || ((uintptr_t)x | (uintptr_t)dy) % 16) return PPST_EINVAL;
-  const int tiles_x = cdiv(ow, WG_TC), tiles_per_image = cdiv(oh, WG_TR) * tiles_x;
-  const int tiles_total = B * tiles_per_image;
-  const int tps = cdiv(tiles_total, splits / 2);
-  dim3 grid(cdiv(cout, 128), nchunks, splits / 2);
-  const int slot = wgrad_prof_begin(B, oh, ow, cout, nsteps, g_wgrad_flop_steps, nchunks, splits, as_stream(stream));
-  g_wgrad_flop_steps = 0;
-  PPST_LAUNCH(conv_wgrad_tr_kernel, grid, dim3(512), 0, as_stream(stream), (const float*)x, (const float*)dy, (const int4*)steps,
-              (const int*)chunk_start, (float*)partial, (float*)csum, B, in_h, in_w, in_ld, oh, ow, dy_ld, cout, nsteps, tiles_x,
-              tiles_per_image, tiles_total, tps, g_wgrad_abl);
-  ppst_prof_end_(slot, as_stream(stream));
-  return PPST_LAUNCH_CHECK();
-}
-
-// two-blocks-per-CU form (conv_wgrad_tr2_kernel, in-place conversion): ``splits`` partial slots = pixel ranges; csum (optional):
-// [splits][cout] partial column sums of dy
+// conv_wgrad_tr2_kernel on fp32 operands: ``splits`` partial slots = pixel ranges; csum (optional): [splits][cout] partial column
+// sums of dy, written by the blocks of chunk 0 -- their column-wise sum is the bias gradient (ppst_wgrad_scatter finishes it)
 extern "C" int ppst_conv_wgrad_tr2_st(const void* x, const void* dy, const void* steps, const void* chunk_start, void* partial, void* csum,
                                       int B, int in_h, int in_w, int in_ld, int oh, int ow, int dy_ld, int cout, int nsteps,
                                       int nchunks, int splits, int max_taps, int min_taps, int halo, int passes, int st, void* stream);
@@ -1018,90 +678,62 @@ extern "C" int ppst_conv_wgrad_tr2_st(const void* x, const void* dy, const void*
                                       int nchunks, int splits, int max_taps, int min_taps, int halo, int passes, int st, void* stream) {
   if (st != PPST_ST_F32 && st != PPST_ST_BF16) return PPST_EINVAL;
   if (st == PPST_ST_BF16 && (passes != 1 || cout % 8 || dy_ld % 8 || in_ld % 8)) return PPST_EINVAL;
-  if (B < 0 || in_h <= 0 || in_w <= 0 || in_ld <= 0 || oh <= 0 || ow <= 0 || dy_ld < cout || cout <= 0 || nsteps <= 0 ||
-      nchunks <= 0 || splits <= 0 || (passes != 1 && passes != 3))
-    return PPST_EINVAL;
-  if (B == 0) return PPST_OK;
-  if (!x || !dy || !steps || !chunk_start || !partial) return PPST_ENULL;
-  if (cout % 4 || dy_ld % 4 || in_ld % 4 || ((uintptr_t)x | (uintptr_t)dy) % 16) return PPST_EINVAL;
-  const int tiles_x = cdiv(ow, WG_TC), tiles_per_image = cdiv(oh, WG_TR) * tiles_x;
-  const int tiles_total = B * tiles_per_image;
-  const int tps = cdiv(tiles_total, splits);
-  // max_taps: the caller's promise about the table (it lives on the device): <= 4 steps in every chunk and an even chunk count
-  // select the two-chunks-per-block form
+  if (passes != 1 && passes != 3) return PPST_EINVAL;
+  bool aligned = false;
+  const int rc = wgrad_check(x, dy, steps, chunk_start, partial, B, in_h, in_w, in_ld, oh, ow, dy_ld, cout, nsteps, nchunks, splits, &aligned);
+  if (rc != PPST_OK || B == 0) return rc;
+  if (!aligned) return PPST_EINVAL;
+  const WgradTiles t = wgrad_tiles(B, oh, ow, splits);
+  // max_taps / min_taps: the caller's promise about the table's chunk lengths (the table lives on the device): <= 4 steps in every
+  // chunk and an even chunk count select the two-chunks-per-block form
   const bool pair = max_taps > 0 && max_taps <= 4 && (nchunks & 1) == 0;
   // halo == 0: the caller's promise that every step has offset (0, 0) on an input of the output's extent (1x1 conv tables)
   const int one = (halo == 0 && max_taps == 1 && min_taps == 1 && in_h == oh && in_w == ow) ? ((nchunks & 3) == 0 ? 4 : ((nchunks & 1) == 0 ? 2 : 0)) : 0;
   dim3 grid(cdiv(cout, 128), one ? nchunks / one : (pair ? nchunks / 2 : nchunks), splits);
   const int slot = wgrad_prof_begin(B, oh, ow, cout, nsteps, g_wgrad_flop_steps, nchunks, splits, as_stream(stream));
   g_wgrad_flop_steps = 0;
-#define WG2(NCH, TM, X1, EX)                                                                                                          \
-  PPST_LAUNCH((conv_wgrad_tr2_kernel<NCH, TM, X1, EX>), grid, dim3(256), 0, as_stream(stream), (const float*)x, (const float*)dy,         \
-              (const int4*)steps, (const int*)chunk_start, (float*)partial, (float*)csum, B, in_h, in_w, in_ld, oh, ow, dy_ld, cout,     \
-              nsteps, tiles_x, tiles_per_image, tiles_total, tps)
-#define WG2X(NCH, TM, EX) do { if (passes == 1) WG2(NCH, TM, true, EX); else WG2(NCH, TM, false, EX); } while (0)
-#define WG2N(NCH)                                                                                                                     \
+  // the launch of one kernel instantiation (the variadic part: its name) on operands stored as T
+#define WG_KERNEL(T, ...)                                                                                                             \
+  PPST_LAUNCH((__VA_ARGS__), grid, dim3(256), 0, as_stream(stream), (const T*)x, (const T*)dy, (const int4*)steps,                      \
+              (const int*)chunk_start, (float*)partial, (float*)csum, B, in_h, in_w, in_ld, oh, ow, dy_ld, cout, nsteps, t.tiles_x,    \
+              t.per_image, t.total, t.per_split)
+  // <chunks per block, taps per chunk, EXACT, HALO> of the storage type's kernel; fp32 storage: X1 = single pass
+#define WG_LAUNCH(NCH, TM, EX, HALO)                                                                                                  \
   do {                                                                                                                                \
-    if (passes == 1)                                                                                                                  \
-      PPST_LAUNCH((conv_wgrad_tr2_kernel<NCH, 1, true, true, false>), grid, dim3(256), 0, as_stream(stream), (const float*)x,           \
-                  (const float*)dy, (const int4*)steps, (const int*)chunk_start, (float*)partial, (float*)csum, B, in_h, in_w, in_ld,  \
-                  oh, ow, dy_ld, cout, nsteps, tiles_x, tiles_per_image, tiles_total, tps);                                            \
-    else                                                                                                                              \
-      PPST_LAUNCH((conv_wgrad_tr2_kernel<NCH, 1, false, true, false>), grid, dim3(256), 0, as_stream(stream), (const float*)x,          \
-                  (const float*)dy, (const int4*)steps, (const int*)chunk_start, (float*)partial, (float*)csum, B, in_h, in_w, in_ld,  \
-                  oh, ow, dy_ld, cout, nsteps, tiles_x, tiles_per_image, tiles_total, tps);                                            \
+    if (st == PPST_ST_BF16) WG_KERNEL(unsigned short, conv_wgrad_tr2b_kernel<NCH, TM, EX, HALO>);                                     \
+    else if (passes == 1) WG_KERNEL(float, conv_wgrad_tr2_kernel<NCH, TM, true, EX, HALO>);                                           \
+    else WG_KERNEL(float, conv_wgrad_tr2_kernel<NCH, TM, false, EX, HALO>);                                                           \
   } while (0)
-  if (st == PPST_ST_BF16) {
-#define WGB(NCH, TM, EX, HALO)                                                                                                          \
-  PPST_LAUNCH((conv_wgrad_tr2b_kernel<NCH, TM, EX, HALO>), grid, dim3(256), 0, as_stream(stream), (const unsigned short*)x,               \
-              (const unsigned short*)dy, (const int4*)steps, (const int*)chunk_start, (float*)partial, (float*)csum, B, in_h, in_w, in_ld, \
-              oh, ow, dy_ld, cout, nsteps, tiles_x, tiles_per_image, tiles_total, tps)
-    if (one == 4) WGB(4, 1, true, false);
-    else if (one == 2) WGB(2, 1, true, false);
-    else if (pair) { if (min_taps == 4 && max_taps == 4) WGB(2, 4, true, true); else WGB(2, 4, false, true); }
-    else { if (min_taps == WG_MAXT && max_taps == WG_MAXT) WGB(1, WG_MAXT, true, true); else WGB(1, WG_MAXT, false, true); }
-#undef WGB
-    ppst_prof_end_(slot, as_stream(stream));
-    return PPST_LAUNCH_CHECK();
-  }
-  // max_taps / min_taps: the caller's promise about the table's chunk lengths (the table lives on the device)
-  if (one == 4) WG2N(4);
-  else if (one == 2) WG2N(2);
-  else if (pair) { if (min_taps == 4 && max_taps == 4) WG2X(2, 4, true); else WG2X(2, 4, false); }
-  else { if (min_taps == WG_MAXT && max_taps == WG_MAXT) WG2X(1, WG_MAXT, true); else WG2X(1, WG_MAXT, false); }
-#undef WG2N
-#undef WG2X
-#undef WG2
+  if (one == 4) WG_LAUNCH(4, 1, true, false);
+  else if (one == 2) WG_LAUNCH(2, 1, true, false);
+  else if (pair && min_taps == 4 && max_taps == 4) WG_LAUNCH(2, 4, true, true);
+  else if (pair) WG_LAUNCH(2, 4, false, true);
+  else if (min_taps == WG_MAXT && max_taps == WG_MAXT) WG_LAUNCH(1, WG_MAXT, true, true);
+  else WG_LAUNCH(1, WG_MAXT, false, true);
+#undef WG_LAUNCH
+#undef WG_KERNEL
   ppst_prof_end_(slot, as_stream(stream));
   return PPST_LAUNCH_CHECK();
 }
 
+// the exact-fp32 MFMA (precision 2: verification; and operands the kernels above cannot take)
 extern "C" int ppst_conv_wgrad_f32(const void* x, const void* dy, const void* steps, const void* chunk_start, void* partial,
                                    int B, int in_h, int in_w, int in_ld, int oh, int ow, int dy_ld, int cout, int nsteps,
                                    int nchunks, int splits, void* stream) {
-  if (B < 0 || in_h <= 0 || in_w <= 0 || in_ld <= 0 || oh <= 0 || ow <= 0 || dy_ld < cout || cout <= 0 || nsteps <= 0 ||
-      nchunks <= 0 || splits <= 0)
-    return PPST_EINVAL;
-  if (B == 0) return PPST_OK;
-  if (!x || !dy || !steps || !chunk_start || !partial) return PPST_ENULL;
-  // the LDS-staged kernel needs 16-B aligned rows (every caller on the train path has them); else the direct one
-  const bool lds_ok = cout % 4 == 0 && dy_ld % 4 == 0 && in_ld % 4 == 0 && ((uintptr_t)x | (uintptr_t)dy) % 16 == 0;
-  if (lds_ok) {
-    const int tiles_x = cdiv(ow, WG_TC), tiles_per_image = cdiv(oh, WG_TR) * tiles_x;
-    const int tiles_total = B * tiles_per_image;
-    const int tps = cdiv(tiles_total, splits);
-    // every split block must write its partial (the scatter sums all `splits` of them): an empty split writes zeros
-    dim3 grid(cdiv(cout, 128), nchunks, splits);
+  bool aligned = false;
+  const int rc = wgrad_check(x, dy, steps, chunk_start, partial, B, in_h, in_w, in_ld, oh, ow, dy_ld, cout, nsteps, nchunks, splits, &aligned);
+  if (rc != PPST_OK || B == 0) return rc;
+  // every split block must write its partial (the scatter sums all `splits` of them): an empty split writes zeros
+  dim3 grid(cdiv(cout, 128), nchunks, splits);
+  if (aligned) {                 // the LDS-staged kernel needs 16-B aligned rows; else the direct one
+    const WgradTiles t = wgrad_tiles(B, oh, ow, splits);
     PPST_LAUNCH(conv_wgrad_lds_kernel, grid, dim3(256), 0, as_stream(stream), (const float*)x, (const float*)dy, (const int4*)steps,
-                (const int*)chunk_start, (float*)partial, B, in_h, in_w, in_ld, oh, ow, dy_ld, cout, nsteps, tiles_x, tiles_per_image,
-                tiles_total, tps);
+                (const int*)chunk_start, (float*)partial, B, in_h, in_w, in_ld, oh, ow, dy_ld, cout, nsteps, t.tiles_x, t.per_image,
+                t.total, t.per_split);
     return PPST_LAUNCH_CHECK();
   }
-  int rows_total = B * oh;
-  int rps = cdiv(rows_total, splits);
-  dim3 grid(cdiv(cout, 128), nchunks, splits);
   PPST_LAUNCH(conv_wgrad_kernel, grid, dim3(256), 0, as_stream(stream), (const float*)x, (const float*)dy, (const int4*)steps,
-              (const int*)chunk_start, (float*)partial, B, in_h, in_w, in_ld, oh, ow, dy_ld, cout, nsteps, rps);
+              (const int*)chunk_start, (float*)partial, B, in_h, in_w, in_ld, oh, ow, dy_ld, cout, nsteps, cdiv(B * oh, splits));
   return PPST_LAUNCH_CHECK();
 }
 

@@ -5,10 +5,12 @@ operation of the path is a HIP kernel in libppst_hip.so.  Activations of the
 fused path are NHWC fp32 tensors of shape (B, H, W, C) (or channel-slice views
 of such tensors: pixel stride ``ld`` = stride(2)).
 """
+import collections
 import ctypes
 import math
 import os
 import threading
+import types
 
 import torch
 
@@ -37,8 +39,12 @@ DUAL_CONVT = {"value": True, "min_blocks": 32}
 UP9 = {"value": True, "min_blocks": 64, "min_fill": 0.85}
 DIRECT_MAX = {"cout": 64, "nsteps": 40, "cout3x3": 64}   # cout3x3 = 128 was measured: 128->128 @512^2 230 vs 357 TFLOP/s
 # thin layers (few channels in and out) on the direct form of that kernel
-WGRAD_SPLIT = {"blocks": 1024, "min_tiles": 4}   # conv_wgrad: target block count of a launch, fewest pixel tiles per block
-WGRAD_X3 = {"value": True}         # conv weight gradients on the bf16 matrix pipe (hi/lo split), exact fp32 with precision 2
+WGRAD_SPLIT = {"blocks": 1024, "min_tiles": 4}   # conv_wgrad, exact-fp32 kernels: target block count of a launch, fewest pixel tiles per block
+# conv_wgrad on the bf16 matrix pipe (conv_wgrad_tr2_kernel): one partial slot per block, two 256-thread blocks per CU -> ONE round of
+# <= 512 blocks (every further split is 49 KB more of partial sums per block written and re-read by the scatter), and >= 8 pixel
+# tiles (2 x 32 px) per block
+WGRAD_TR2_BLOCKS = 512
+WGRAD_TR2_MIN_TILES = 8
 STREAM_1X1 = {"value": True}       # 1x1 convs (halo 0) on the streaming kernel of conv1x1.hip
 # round 5: across-block K split (ppst_conv_args.ksplit) of launches whose grid fills a fraction of the chip while every block runs
 # one long serial chain of steps -- the 64^2 ... 4^2 layers of a train step at batch 2 (4-128 blocks of 72-160 steps: ~0.9 us per
@@ -1052,11 +1058,41 @@ def _grad_out(out, shape, like):
     return out
 
 
-# the LDS-DMA / transposed-read weight-gradient kernel (round 3): one 8-wave block per CU -> ONE round of <= 256 blocks (every
-# further split is 2 x 147 KB of partial sums written and re-read by the scatter), >= min_tiles pixel tiles per block
-# form 2: two 256-thread blocks per CU; bf16_single_pass: in precision mode 1 (bf16 compute, fp32 master weights -- BASELINE
-# configs[3]) the weight gradient multiplies the hi halves only (one MFMA pass instead of three)
-WGRAD_TR = {"value": True, "blocks": 256, "min_tiles": 8, "form": 2, "blocks2": 512, "pair": True, "bf16_single_pass": True, "exact": True, "nohalo": True}
+# read by bench.py's train line (which kernel and how many MFMA passes its roofline names); nothing sets it
+WGRAD_TR = types.MappingProxyType({"value": True, "form": 2, "bf16_single_pass": True})
+
+WgradChoice = collections.namedtuple("WgradChoice", "launcher family chunks_per_block splits promises")
+
+
+def wgrad_choose(kind, k, halo, max_chunk_steps, min_chunk_steps, nchunks, cout, B, hw, ohw, plan_precision, precision, aligned, splits=None):
+    """The launcher conv_wgrad calls for a step table (``kind``, ``k``, ``halo``, longest / shortest chunk, ``nchunks``) on operands
+    of these extents (``hw`` input, ``ohw`` output), and the pixel split: pure arithmetic, restating the launchers' own dispatch.
+    ``plan_precision`` 2 (exact fp32) or operands without 16-byte rows (``aligned``) -> ppst_conv_wgrad_f32, else the
+    transposed-read kernel with 4 ('quad') / 2 ('one2') chunks of a 1x1 table per block, 2 chunks of <= 4 steps ('pair'), or one
+    ('single'; '-exact': every chunk has 4 / 9 steps).  ``precision`` 1 (the process's mode): one MFMA pass instead of three.
+    ``splits``: the caller's, or blocks = n-tiles x chunk groups x splits filling the chip once (WGRAD_TR2_*) -- the exact-fp32
+    kernels run 3 blocks per CU (768 slots): ~2 rounds, >= WGRAD_SPLIT['min_tiles'] pixel tiles per block.  (Round 1 capped
+    splits at 64: the 512x512 layers with few channels ran on 64-256 blocks, a third of the chip or less.)
+    -> WgradChoice; promises = (max_taps, min_taps, halo, passes) of ppst_conv_wgrad_tr2_st, None for ppst_conv_wgrad_f32."""
+    ntiles = (cout + 127) // 128
+    tiles_total = B * ((ohw[0] + 1) // 2) * ((ohw[1] + 31) // 32)
+    if plan_precision == 2 or not aligned:
+        if splits is None:
+            per = nchunks * ntiles
+            splits = max(1, min((WGRAD_SPLIT["blocks"] + per - 1) // per, max(1, tiles_total // WGRAD_SPLIT["min_tiles"]), 2048))
+        return WgradChoice("ppst_conv_wgrad_f32", "f32-lds" if aligned else "f32-direct", 1, splits, None)
+    lo, hi = min_chunk_steps, max_chunk_steps
+    nohalo = kind == "conv" and k == 1 and halo == 0          # 1x1 tables: one step per chunk, offset (0, 0)
+    if nohalo and lo == hi == 1 and tuple(hw) == tuple(ohw) and nchunks % 2 == 0:
+        cpb, family = (4, "quad") if nchunks % 4 == 0 else (2, "one2")
+    elif hi <= 4 and nchunks % 2 == 0:
+        cpb, family = 2, "pair-exact" if lo == hi == 4 else "pair"
+    else:
+        cpb, family = 1, "single-exact" if lo == hi == 9 else "single"
+    if splits is None:
+        per = (nchunks // cpb) * ntiles
+        splits = max(1, min(max(1, WGRAD_TR2_BLOCKS // per), max(1, tiles_total // WGRAD_TR2_MIN_TILES), 2048))
+    return WgradChoice("ppst_conv_wgrad_tr2_st", family, cpb, splits, (hi, lo, 0 if nohalo else 1, 1 if precision == 1 else 3))
 
 
 def conv_wgrad(plan, x, dy, splits=None, out=None, accumulate=False, bias_out=None, bias_accumulate=False, want_bias=False, dy_scale=1.0):
@@ -1075,10 +1111,9 @@ def conv_wgrad(plan, x, dy, splits=None, out=None, accumulate=False, bias_out=No
     in_ld = _nhwc_ld(x, "x", half_ok=True)
     dy_ld = _nhwc_ld(dy, "dy", half_ok=True)
     half = x.dtype != torch.float32 or dy.dtype != torch.float32
-    if half and not (x.dtype == dy.dtype == torch.bfloat16 and PRECISION["value"] == 1 and WGRAD_X3["value"] and WGRAD_TR["value"]
-                     and WGRAD_TR["form"] == 2 and WGRAD_TR["bf16_single_pass"]):
-        raise RuntimeError("conv_wgrad on half-stored operands: both bfloat16, precision mode 1, the single-pass transposed-read kernel "
-                           "(got %s / %s, mode %d)" % (x.dtype, dy.dtype, PRECISION["value"]))
+    if half and not (x.dtype == dy.dtype == torch.bfloat16 and PRECISION["value"] == 1):
+        raise RuntimeError("conv_wgrad on half-stored operands: both bfloat16 and precision mode 1 (the single-pass kernel reads them "
+                           "as its MFMA operands; got %s / %s, mode %d)" % (x.dtype, dy.dtype, PRECISION["value"]))
     B, H, W, _ = x.shape
     _, oh, ow, cout = dy.shape
     assert cout == plan.cout
@@ -1087,52 +1122,21 @@ def conv_wgrad(plan, x, dy, splits=None, out=None, accumulate=False, bias_out=No
     aligned = cout % 4 == 0 and dy_ld % 4 == 0 and in_ld % 4 == 0 and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0
     if half and not (aligned and cout % 8 == 0 and dy_ld % 8 == 0 and in_ld % 8 == 0):
         raise RuntimeError("conv_wgrad on bfloat16 operands needs channel counts / strides divisible by 8 and 16-byte aligned tensors")
-    x3 = WGRAD_X3["value"] and plan.precision != 2 and aligned
-    use_tr = x3 and WGRAD_TR["value"]
-    per = nchunks * ((cout + 127) // 128)
-    tiles_total = B * ((oh + 1) // 2) * ((ow + 31) // 32)
-    csum = None
-    if use_tr:
-        # one 8-wave block per CU (256 slots): ~2 rounds of blocks, >= min_tiles pixel tiles (2 x 32 px) each; a block writes two
-        # partial slots (one per tile row)
-        form2 = WGRAD_TR["form"] == 2
-        if form2 and WGRAD_TR["pair"] and plan.max_chunk_steps <= 4 and nchunks % 2 == 0:
-            per = (nchunks // 2) * ((cout + 127) // 128)       # two chunks per block
-            if (WGRAD_TR["nohalo"] and WGRAD_TR["exact"] and plan.kind == "conv" and plan.k == 1 and plan.halo == 0 and nchunks % 4 == 0
-                    and (H, W) == (oh, ow)):
-                per = (nchunks // 4) * ((cout + 127) // 128)   # 1x1 tables: four chunks per block (no halo image)
-        if form2:       # one partial slot per block, two blocks per CU: one round of <= 512 blocks
-            gz = splits if splits is not None else max(1, min(max(1, WGRAD_TR["blocks2"] // per), max(1, tiles_total // WGRAD_TR["min_tiles"]), 2048))
-            splits = gz
-        else:
-            gz = splits // 2 if splits is not None else max(1, min(max(1, WGRAD_TR["blocks"] // per), max(1, tiles_total // WGRAD_TR["min_tiles"]), 1024))
-            splits = 2 * gz
-        if want_bias:
-            csum = torch.empty((gz, cout), device=x.device, dtype=torch.float32)
-    elif splits is None:
-        # blocks = n-tiles x chunks x splits; the LDS-staged kernel runs 3 blocks per CU (768 slots): aim for ~2 rounds, keep
-        # >= 2 pixel tiles (2 x 32 px) per block.  (Round 1 capped splits at 64: the 512x512 layers with few channels ran on
-        # 64-256 blocks, a third of the chip or less.)
-        splits = max(1, min((WGRAD_SPLIT["blocks"] + per - 1) // per, max(1, tiles_total // WGRAD_SPLIT["min_tiles"]), 2048))
+    ch = wgrad_choose(plan.kind, plan.k, plan.halo, plan.max_chunk_steps, plan.min_chunk_steps, nchunks, cout, B, (H, W), (oh, ow),
+                      plan.precision, PRECISION["value"], aligned, splits)
+    splits = ch.splits
+    tr2 = ch.promises is not None
+    # the transposed-read kernel's staging pass also takes the bias column sums: one row per pixel split
+    csum = torch.empty((splits, cout), device=x.device, dtype=torch.float32) if (tr2 and want_bias) else None
     partial = torch.empty((splits, plan.nsteps, cout, 32), device=x.device, dtype=torch.float32)
     if PROF_ON["value"]:
         lib.ppst_wgrad_flop_steps(int(plan.flop_steps))
-    if use_tr:
-        if WGRAD_TR["form"] == 2:
-            check(lib.ppst_conv_wgrad_tr2_st(_p(x), _p(dy), _p(plan.steps), _p(plan.chunk_start), _p(partial), _p(csum), B, H, W, in_ld, oh, ow,
-                                             dy_ld, cout, plan.nsteps, nchunks, splits, plan.max_chunk_steps if WGRAD_TR["pair"] else 0,
-                                             plan.min_chunk_steps if WGRAD_TR["exact"] else 0,
-                                             0 if (WGRAD_TR["nohalo"] and plan.kind == "conv" and plan.k == 1 and plan.halo == 0) else 1,
-                                             1 if (PRECISION["value"] == 1 and WGRAD_TR["bf16_single_pass"]) else 3,
-                                             _ST[x.dtype], _stream()), "ppst_conv_wgrad_tr2")
-        else:
-            check(lib.ppst_conv_wgrad_tr(_p(x), _p(dy), _p(plan.steps), _p(plan.chunk_start), _p(partial), _p(csum), B, H, W, in_ld, oh, ow,
-                                         dy_ld, cout, plan.nsteps, nchunks, splits, _stream()), "ppst_conv_wgrad_tr")
-    else:
-        # bf16x3 with register staging (round 2), or precision 2 (verification): the exact fp32 MFMA
-        fn, name = ((lib.ppst_conv_wgrad_bf16x3, "ppst_conv_wgrad_bf16x3") if x3 else (lib.ppst_conv_wgrad_f32, "ppst_conv_wgrad_f32"))
-        check(fn(_p(x), _p(dy), _p(plan.steps), _p(plan.chunk_start), _p(partial), B, H, W, in_ld, oh, ow, dy_ld,
-                 cout, plan.nsteps, nchunks, splits, _stream()), name)
+    if tr2:
+        check(lib.ppst_conv_wgrad_tr2_st(_p(x), _p(dy), _p(plan.steps), _p(plan.chunk_start), _p(partial), _p(csum), B, H, W, in_ld, oh, ow,
+                                         dy_ld, cout, plan.nsteps, nchunks, splits, *ch.promises, _ST[x.dtype], _stream()), "ppst_conv_wgrad_tr2")
+    else:        # precision 2 (verification) or unaligned operands: the exact fp32 MFMA
+        check(lib.ppst_conv_wgrad_f32(_p(x), _p(dy), _p(plan.steps), _p(plan.chunk_start), _p(partial), B, H, W, in_ld, oh, ow, dy_ld,
+                                      cout, plan.nsteps, nchunks, splits, _stream()), "ppst_conv_wgrad_f32")
     # 'dgradT': the plan's "weights" are the blurred 4x4 kernel (Cin,Cout,4,4) of the transposed conv
     shape = plan.w4_shape if plan.kind == "dgradT" else (plan.cout, plan.cin, plan.k, plan.k)
     cover = getattr(plan, "full_cover", False)

@@ -1342,7 +1342,8 @@ _case("transpose_last2", "3x64x64", b=3, M=64, N=64)
 #   'dgradT'  x = the space-to-depth copy (B,H,W,4 cout) of the gradient at the transposed conv's (2H, 2W) output, dy = that conv's
 #             INPUT (B,H,W,cin): dw = the gradient of the blurred 4x4 kernel w4 (cin,cout,4,4) of F.conv_transpose2d(., w4, stride = 2,
 #             padding = 1); dw3 = ops.upscale_weight_bwd of it, the gradient of the (cout,cin,3,3) parameter through the blur
-# Launchers (ops.conv_wgrad, then ppst_conv_wgrad_tr2_st / ppst_conv_wgrad_f32, csrc/train.hip):
+# Launchers (ops.conv_wgrad -- its choice is ops.wgrad_choose, which tests/test_abi_cpu.py holds against _cw_branch below -- then
+# ppst_conv_wgrad_tr2_st / ppst_conv_wgrad_f32, csrc/train.hip):
 #   cout % 4 == 0, both ld % 4 == 0, 16-byte pointers and plan precision != 2 -> conv_wgrad_tr2_kernel (bf16x3), instantiated by the
 #     table's chunk lengths: 1x1 tables (no halo) with chunks % 4 == 0 -> four chunks per block ('quad'), chunks % 2 == 0 -> two
 #     ('one2'); else every chunk <= 4 steps and an even chunk count -> 'pair' ('pair-exact': every chunk exactly 4 steps); else
@@ -1628,6 +1629,5 @@ FAMILIES = ["bilinear_bwd:gather", "bilinear_bwd:scatter", "pad2d:fwd-float4:bwd
             "conv_dgrad:k3:bf16x3", "conv_dgrad:k3:fp32", "conv_dgrad:k1:bf16x3", "conv_dgrad:k1:fp32", "conv_dgrad:four-group:bf16x3",
             "conv_dgrad:four-group:fp32", "conv_dgrad:stack:bf16x3", "conv_dgrad:stack:fp32", "conv_dgrad:entry-stack:bf16x3",
             "conv_dgrad:entry-four-group:bf16x3"]
-# In no case: the half-storage (`_st`) instances of every launcher (held bit-equal to these fp32 forms by gpu_diag.t_train_half), the
-# weight-gradient kernels that ops reaches only with its WGRAD_TR / WGRAD_X3 switches off their defaults (ppst_conv_wgrad_tr,
-# ppst_conv_wgrad_bf16x3), and the lpips entries (tests/test_gpu_lpips.py).
+# In no case: the half-storage (`_st`) instances of every launcher (held bit-equal to these fp32 forms by gpu_diag.t_train_half)
+# and the lpips entries (tests/test_gpu_lpips.py).

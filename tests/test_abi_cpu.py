@@ -505,3 +505,120 @@ def test_gemm_mode_selection():
         ops.GEMM_MODE["value"] = None
     with pytest.raises(ValueError):
         ops._gemm_passes("bf16", 64)
+
+
+WGRAD_GONE = ("ppst_conv_wgrad_tr", "ppst_conv_wgrad_bf16x3", "ppst_wgrad_ablate")
+WGRAD_KEPT = ("ppst_conv_wgrad_tr2", "ppst_conv_wgrad_tr2_st", "ppst_conv_wgrad_f32")
+
+
+def test_removed_weight_gradient_entry_points_are_gone_everywhere():
+    """The round-2 / round-3 weight-gradient launchers and the timing-ablation hook left the header, the binding and the library
+    together (a4b3174 is the last commit with them); the launchers of the production kernels are in all three."""
+    from ppst_amd import _lib
+    header = open(os.path.join(ROOT, "include", "ppst_hip.h")).read()
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for n in WGRAD_GONE:
+        assert not re.search(r"\b%s\b" % n, header), n
+        assert n not in _lib._SIGS and not hasattr(lib, n), n
+    for n in WGRAD_KEPT:
+        assert n in _declared() and n in _lib._SIGS and hasattr(lib, n), n
+
+
+def test_weight_gradient_refusals_need_no_gpu():
+    """ppst_conv_wgrad_tr2_st / ppst_conv_wgrad_f32 share their argument checks: bad sizes PPST_EINVAL, an empty batch PPST_OK
+    before the pointers are looked at, null pointers PPST_ENULL, then (tr2 only) rows or pointers off the 16-byte grid PPST_EINVAL.
+    Every call here returns before a launch."""
+    from ppst_amd._lib import lib
+    d, odd = ctypes.c_void_p(16), ctypes.c_void_p(20)
+    size = dict(B=1, in_h=8, in_w=8, in_ld=32, oh=8, ow=8, dy_ld=32, cout=32, nsteps=9, nchunks=1, splits=2)
+
+    def tr2(x=d, dy=d, steps=d, cs=d, partial=d, passes=3, st=0, **kw):
+        s = dict(size, **kw)
+        return lib.ppst_conv_wgrad_tr2_st(x, dy, steps, cs, partial, None, *[s[k] for k in size], 9, 9, 1, passes, st, None)
+
+    def f32(x=d, dy=d, steps=d, cs=d, partial=d, **kw):
+        s = dict(size, **kw)
+        return lib.ppst_conv_wgrad_f32(x, dy, steps, cs, partial, *[s[k] for k in size], None)
+
+    for bad in (dict(B=-1), dict(in_h=0), dict(in_w=0), dict(in_ld=0), dict(oh=0), dict(ow=0), dict(dy_ld=16), dict(cout=0), dict(nsteps=0),
+                dict(nchunks=0), dict(splits=0)):
+        assert tr2(**bad) == -1 and f32(**bad) == -1, bad
+        assert tr2(B=0, **{k: v for k, v in bad.items() if k != "B"}) == (0 if "B" in bad else -1), bad
+    assert tr2(passes=2) == -1 and tr2(passes=2, B=0) == -1 and tr2(st=3) == -1 and tr2(st=2, passes=3) == -1   # st 2 = PPST_ST_BF16
+    assert tr2(st=2, passes=1, cout=36, dy_ld=36) == -1 and tr2(st=2, passes=1, in_ld=36) == -1                  # bf16: multiples of 8
+    assert tr2(B=0, x=None, dy=None, steps=None, cs=None, partial=None) == 0 and f32(B=0, x=None, partial=None) == 0
+    for null in ("x", "dy", "steps", "cs", "partial"):
+        assert tr2(**{null: None}) == -3 and f32(**{null: None}) == -3, null
+    for off in (dict(cout=30, dy_ld=30), dict(dy_ld=34), dict(in_ld=34), dict(x=odd), dict(dy=odd)):
+        assert tr2(**off) == -1, off           # (ppst_conv_wgrad_f32 takes these: its direct kernel)
+
+
+def test_wgrad_tr_is_a_read_only_record():
+    """bench.py's train line reads these three keys; a tuning script that still writes one fails loudly."""
+    from ppst_amd import ops
+    assert dict(ops.WGRAD_TR) == {"value": True, "form": 2, "bf16_single_pass": True}
+    for key, v in (("value", False), ("form", 1), ("blocks2", 256)):
+        with pytest.raises(TypeError):
+            ops.WGRAD_TR[key] = v
+    assert not hasattr(ops, "WGRAD_X3")
+    assert (ops.WGRAD_TR2_BLOCKS, ops.WGRAD_TR2_MIN_TILES) == (512, 8) and ops.WGRAD_SPLIT == {"blocks": 1024, "min_tiles": 4}
+
+
+def _wgrad_table(kind, k, cin, cout):
+    """(chunk lengths of ops.ConvPlan's step table, channels of the kernel's dy operand) for a forward conv cin -> cout"""
+    if kind == "conv":
+        return [k * k] * (cin // 32), cout
+    if kind == "s2d":
+        return [n for n in (4, 2, 2, 2) for _ in range(cin // 32)], cout
+    return [4] * (4 * (cout // 32)), cin
+
+
+def _wgrad_choice(ops, kind, k, cin, cout, B, oh, ow, plan_precision=0, precision=0, aligned=True, splits=None):
+    lens, dc = _wgrad_table(kind, k, cin, cout)
+    hw = (oh + 1, ow + 1) if kind == "s2d" else (oh, ow)        # the space-to-depth copy of a (2 oh + 1, 2 ow + 1) tensor
+    return ops.wgrad_choose(kind, k, 0 if (kind == "conv" and k == 1) else 1, max(lens), min(lens), len(lens), dc, B, hw, (oh, ow),
+                            plan_precision, precision, aligned, splits)
+
+
+def test_wgrad_split_and_form_are_the_parents():
+    """ops.wgrad_choose against the values of a4b3174's expressions in ops.conv_wgrad (evaluated from a copy of those lines, not
+    from this function): the same splits mean the same summation order, i.e. bit-identical gradients."""
+    from ppst_amd import ops
+    tr2, f32 = "ppst_conv_wgrad_tr2_st", "ppst_conv_wgrad_f32"
+    rows = [  # kind, k, cin, cout, B, oh, ow, {other arguments} -> launcher, family, chunks per block, splits, promises
+        (("conv", 3, 128, 128, 2, 512, 512), {}, (tr2, "single-exact", 1, 128, (9, 9, 1, 3))),
+        (("conv", 1, 128, 64, 2, 512, 512), {}, (tr2, "quad", 4, 512, (1, 1, 0, 3))),
+        (("conv", 1, 64, 256, 2, 20, 36), {}, (tr2, "one2", 2, 5, (1, 1, 0, 3))),
+        (("s2d", 3, 32, 64, 2, 256, 256), {}, (tr2, "pair", 2, 256, (4, 2, 1, 3))),
+        (("conv", 3, 512, 512, 2, 64, 64), {}, (tr2, "single-exact", 1, 8, (9, 9, 1, 3))),
+        (("conv", 3, 32, 32, 1, 33, 70), {}, (tr2, "single-exact", 1, 6, (9, 9, 1, 3))),
+        (("conv", 3, 32, 32, 1, 33, 70), dict(precision=1), (tr2, "single-exact", 1, 6, (9, 9, 1, 1))),      # process mode 1: one pass
+        (("dgradT", 3, 64, 32, 2, 17, 19), {}, (tr2, "pair-exact", 2, 2, (4, 4, 1, 3))),
+        (("conv", 1, 32, 32, 3, 9, 11), {}, (tr2, "single", 1, 1, (1, 1, 0, 3))),                             # one chunk of one step
+        (("conv", 3, 32, 32, 1, 33, 70), dict(plan_precision=2), (f32, "f32-lds", 1, 12, None)),
+        (("conv", 3, 32, 30, 1, 33, 70), dict(aligned=False), (f32, "f32-direct", 1, 12, None)),            # WGRAD_SPLIT: ceil(1024 / 1), 51 // 4
+        (("conv", 3, 32, 64, 2, 33, 37), dict(splits=1), (tr2, "single-exact", 1, 1, (9, 9, 1, 3))),
+        (("conv", 3, 32, 64, 2, 33, 37), dict(splits=10000), (tr2, "single-exact", 1, 10000, (9, 9, 1, 3))),
+        (("conv", 3, 32, 64, 2, 33, 37), dict(splits=10000, plan_precision=2), (f32, "f32-lds", 1, 10000, None)),
+    ]
+    for shape, kw, want in rows:
+        assert tuple(_wgrad_choice(ops, *shape, **kw)) == want, (shape, kw)
+
+
+def test_wgrad_choice_names_the_family_bwd_cases_restates():
+    """For every conv_wgrad case of the backward-kernel tests, the family ops.wgrad_choose names is the one bwd_cases.branch_of
+    restates by hand from the launcher (which never calls into ops): the GPU tests' claim about which kernel a case reaches."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import bwd_cases as C
+    from ppst_amd import ops
+    seen = set()
+    for c in (c for c in C.CASES if c.op == "conv_wgrad"):
+        p, kind = c.p, C._cw_kind(c)
+        ch = _wgrad_choice(ops, kind, p["k"], p["cin"], p["cout"], p["B"], p["H"], p["W"], plan_precision=p["prec"],
+                           aligned=C._cw_aligned(c), splits=p.get("splits"))
+        tr2 = ch.launcher == "ppst_conv_wgrad_tr2_st"
+        bias = "nobias" if not p.get("bias") else ("csum" if tr2 else "colsum")
+        assert "conv_wgrad:%s:%s:%s" % (kind, ("tr2-" if tr2 else "") + ch.family, bias) == C.branch_of(c), c.id
+        assert ch.splits == p.get("splits", ch.splits)
+        seen.add(ch.family)
+    assert seen == {"quad", "one2", "pair", "pair-exact", "single", "single-exact", "f32-lds", "f32-direct"}

@@ -1,6 +1,6 @@
-"""Tuning aid (GPU): the LDS-DMA / transposed-read weight-gradient kernel (ops.WGRAD_TR) against the register-staged bf16x3
-kernel of round 2 and against float64 torch autograd, on every plan kind incl. ragged sizes; its fused column sums against
-ops.colsum; then a same-process timing of the heavy layers of the train step."""
+"""Tuning aid (GPU): the LDS-DMA / transposed-read weight-gradient kernel (conv_wgrad_tr2_kernel) against float64 torch autograd
+on every plan kind incl. ragged sizes; its fused column sums; accumulate and a NaN-filled destination; the single-pass mode
+(precision 1); then a same-process timing of the heavy layers of the train step in both precisions."""
 import math
 import os
 import sys
@@ -50,25 +50,20 @@ for name, kind, B, ci, co, H, Wd, k in cases:
         w4 = plan.wsrc.double().cpu().requires_grad_(True)           # (Cin, Cout, 4, 4)
         F.conv_transpose2d(xin.double(), w4, stride=2, padding=1).backward(dyf.double())
         ref = w4.grad
-    outs = {}
-    for key, on, form in ((False, False, 2), (True, True, 2), ("f1", True, 1)):
-        ops.WGRAD_TR["value"], ops.WGRAD_TR["form"] = on, form
-        dw, db = ops.conv_wgrad(plan, x, dy, want_bias=True)
-        outs[key] = (dw.cpu(), db.cpu())
-    ops.WGRAD_TR["value"], ops.WGRAD_TR["form"] = True, 2
-    e_ref = rel(outs[True][0] / plan.scale, ref)
-    e_old = max(rel(outs[True][0], outs[False][0]), rel(outs["f1"][0], outs[False][0]))
-    e_b = rel(outs[True][1], dy.reshape(-1, dy.shape[3]).double().sum(0).cpu())
+    dw, db = ops.conv_wgrad(plan, x, dy, want_bias=True)
+    dw, db = dw.cpu(), db.cpu()
+    e_ref = rel(dw / plan.scale, ref)
+    e_b = rel(db, dy.reshape(-1, dy.shape[3]).double().sum(0).cpu())
     # accumulate into a destination
-    dst = torch.full_like(outs[True][0], 0.5).to(dev)
+    dst = torch.full_like(dw, 0.5).to(dev)
     bdst = torch.full((dy.shape[3],), 0.25, device=dev)
     ops.conv_wgrad(plan, x, dy, out=dst, accumulate=True, bias_out=bdst, bias_accumulate=True)
-    e_acc = max(rel(dst.cpu() - 0.5, outs[True][0]), rel(bdst.cpu() - 0.25, outs[True][1]))
+    e_acc = max(rel(dst.cpu() - 0.5, dw), rel(bdst.cpu() - 0.25, db))
     # a destination full of NaN, accumulate off: every element must be WRITTEN (plans whose table covers the whole weight skip
     # the zero fill in front of the split reduction)
-    nan_dst = torch.full_like(outs[True][0], float("nan")).to(dev)
+    nan_dst = torch.full_like(dw, float("nan")).to(dev)
     ops.conv_wgrad(plan, x, dy, out=nan_dst)
-    e_cover = rel(nan_dst.cpu(), outs[True][0]) if torch.isfinite(nan_dst).all() else float("inf")
+    e_cover = rel(nan_dst.cpu(), dw) if torch.isfinite(nan_dst).all() else float("inf")
     e_acc = max(e_acc, e_cover)
     # precision mode 1 (bf16 compute, fp32 master weights): one MFMA pass over the hi halves; the bias sums stay fp32
     ops.set_precision(1)
@@ -77,10 +72,10 @@ for name, kind, B, ci, co, H, Wd, k in cases:
     finally:
         ops.set_precision(0)
     e_1 = rel(dw1.cpu() / plan.scale, ref)
-    e_b1 = rel(db1.cpu(), outs[True][1])
-    ok = e_ref <= 3e-5 and e_old <= 2e-5 and e_b <= 2e-6 and e_acc <= 1e-5 and 1e-4 < e_1 <= 1e-2 and e_b1 == 0.0
+    e_b1 = rel(db1.cpu(), db)
+    ok = e_ref <= 3e-5 and e_b <= 2e-6 and e_acc <= 1e-5 and 1e-4 < e_1 <= 1e-2 and e_b1 == 0.0
     bad += not ok
-    print("%-34s %s vs f64 autograd %.2e  vs round-2 kernel %.2e  fused bias %.2e  accumulate / NaN-filled destination %.2e  single-pass bf16 %.2e  (table covers the weight: %s)" % (name, "ok  " if ok else "FAIL", e_ref, e_old, e_b, e_acc, e_1, plan.full_cover), flush=True)
+    print("%-34s %s vs f64 autograd %.2e  fused bias %.2e  accumulate / NaN-filled destination %.2e  single-pass bf16 %.2e  (table covers the weight: %s)" % (name, "ok  " if ok else "FAIL", e_ref, e_b, e_acc, e_1, plan.full_cover), flush=True)
 
 print("timing (ms per weight gradient incl. the split reduction; median of 15)")
 for name, kind, B, ci, co, H, k in (("128->128 @512 3x3", "conv", 2, 128, 128, 512, 3), ("256->256 @256 3x3", "conv", 2, 256, 256, 256, 3),
@@ -97,55 +92,21 @@ for name, kind, B, ci, co, H, k in (("128->128 @512 3x3", "conv", 2, 128, 128, 5
         x, dy = g(torch.randn(B, H, H, 4 * co)), g(torch.randn(B, H, H, ci))
         fl = 2.0 * B * H * H * ci * co * 16
     res = []
-    for on, form in ((False, 2), (True, 2), (True, 1), (True, 2)):
-        ops.WGRAD_TR["value"], ops.WGRAD_TR["form"] = on, form
-        ts = []
-        for i in range(20):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            ops.conv_wgrad(plan, x, dy, want_bias=(kind == "conv"))
-            e1.record()
-            torch.cuda.synchronize()
-            if i >= 5:
-                ts.append(e0.elapsed_time(e1))
+    for prec in (0, 1):
+        ops.set_precision(prec)
+        try:
+            ts = []
+            for i in range(20):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                ops.conv_wgrad(plan, x, dy, want_bias=(kind == "conv"))
+                e1.record()
+                torch.cuda.synchronize()
+                if i >= 5:
+                    ts.append(e0.elapsed_time(e1))
+        finally:
+            ops.set_precision(0)
         ts.sort()
         res.append(ts[len(ts) // 2])
-    ops.WGRAD_TR["value"], ops.WGRAD_TR["form"] = True, 2
-    ops.set_precision(1)
-    ts = []
-    for i in range(20):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        ops.conv_wgrad(plan, x, dy, want_bias=(kind == "conv"))
-        e1.record()
-        torch.cuda.synchronize()
-        if i >= 5:
-            ts.append(e0.elapsed_time(e1))
-    ops.set_precision(0)
-    ts.sort()
-    print("  %-24s round-2 kernel (+ colsum) %.3f ms   one block / CU %.3f ms   two blocks / CU (in place) %.3f / %.3f ms   (%.0f -> %.0f TFLOP/s)   single-pass bf16 %.3f ms" % (
-        name, res[0], res[2], res[1], res[3], fl / res[0] / 1e9, fl / min(res[1], res[3]) / 1e9, ts[len(ts) // 2]), flush=True)
-# timing ablations of the new kernel (results wrong on purpose): what each phase of a tile costs
-import ctypes
-from ppst_amd._lib import lib
-lib.ppst_wgrad_ablate.restype = ctypes.c_int
-print("ablations, 128->128 @512 3x3 B=2 (ms incl. split reduction): ", end="")
-w = g(torch.randn(128, 128, 3, 3) / 34.0)
-plan = ops.ConvPlan(w)
-x, dy = g(torch.randn(2, 512, 512, 128)), g(torch.randn(2, 512, 512, 128))
-for mask, tag in ((0, "full"), (1, "no MFMA"), (2, "no conversion"), (4, "no DMA"), (3, "DMA only"), (6, "MFMA only"), (5, "conversion only"), (7, "barriers only")):
-    lib.ppst_wgrad_ablate(mask)
-    ts = []
-    for i in range(15):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        ops.conv_wgrad(plan, x, dy)
-        e1.record()
-        torch.cuda.synchronize()
-        if i >= 5:
-            ts.append(e0.elapsed_time(e1))
-    ts.sort()
-    print("%s %.3f | " % (tag, ts[len(ts) // 2]), end="")
-lib.ppst_wgrad_ablate(0)
-print()
+    print("  %-24s bf16x3 %.3f ms (%.0f TFLOP/s)   single-pass bf16 %.3f ms" % (name, res[0], fl / res[0] / 1e9, res[1]), flush=True)
 sys.exit(1 if bad else 0)
