@@ -7,14 +7,13 @@ of such tensors: pixel stride ``ld`` = stride(2)).
 """
 import collections
 import ctypes
-import math
 import os
 import threading
 import types
 
 import torch
 
-from . import _lib
+from . import _lib, conv_tables
 from ._lib import lib, check
 
 PAD_ZERO, PAD_REFLECT, PAD_REPLICATE = 0, 1, 2
@@ -286,393 +285,162 @@ def fused_bias_act_raw(x, b, ref, act, grad, alpha, scale):
 
 
 # ------------------------------------------------------------- fused conv ----
+def _tiles(th, tw, rows, cols=16):
+    """blocks that cover a (th, tw) extent with rows x cols pixel tiles"""
+    return ((th + rows - 1) // rows) * ((tw + cols - 1) // cols)
+
+
+def _upload(rec, dev):
+    """the plan attributes of a conv_tables record: scalars and host lists as they are, every table as an int32 tensor on ``dev``
+    (a source list as its three columns; the main one as ``src_dev`` next to the host list ``src``)"""
+    d = dict(vars(rec))
+
+    def tensor(rows):
+        return None if rows is None else torch.tensor(rows, dtype=torch.int32, device=dev).contiguous()
+    for n in ("steps", "steps_dual", "steps_up9", "steps_k64", "steps_dual_k64", "chunk_start"):
+        d[n] = tensor(d[n])
+    for n, attr in (("src", "src_dev"), ("src_dual", "src_dual"), ("src_k64", "src_k64"), ("src_dual_k64", "src_dual_k64")):
+        s = tensor(d[n])
+        d[attr] = None if s is None else (s[:, 0].contiguous(), s[:, 1].contiguous(), s[:, 2].contiguous())
+    return d
+
+
+def _weight_source(w, tag, scale):
+    """(the tensor a plan's ``wstrides`` index, the scale left to apply) for the (Cout, Cin, k, k) parameter ``w`` and the
+    ``wsource`` tag of its conv_tables record"""
+    cout, cin, k, _ = w.shape
+    if tag == "up4":            # the fused upscale's 4x4 kernel (Cin, Cout, 4, 4), scale folded in
+        wsrc = torch.empty((cin, cout, 4, 4), device=w.device, dtype=torch.float32)
+        check(lib.ppst_upscale_weight(_p(w), _p(wsrc), cout, cin, scale, _stream()), "ppst_upscale_weight")
+        return wsrc, 1.0
+    if tag == "flip":           # element (ky', kx') = (0, 0) is W[..][k-1][k-1]
+        return w.view(-1)[k * k - 1:], scale
+    if tag == "stack":          # the phase-stacked 2x2 kernel (4 Cin, Cout, 2, 2)
+        wsrc = torch.empty((4 * cin, cout, 2, 2), device=w.device, dtype=torch.float32)
+        check(lib.ppst_dgrad_s2d_stack_weight(_p(w), _p(wsrc), cout, cin, _stream()), "ppst_dgrad_s2d_stack_weight")
+        return wsrc, scale
+    assert tag == "param"
+    return w, scale
+
+
+# One pack of a plan, by its key in ``plan._packs``: 64 / 128 / 256 (N tile = the key), "dual" (the phase-pair form of the fused
+# upscale), "k64_<bn>" / "k64_dual" (64-channel steps), "up9" / "wino" (transforms of their own: ``src`` is None, one launch per
+# plan).  entry: the C function that fills it; w / strides / scale: what it reads; src: the (c, ky, kx) device columns; bn,
+# n_groups, nsteps, x3 (hi + lo planes; 2: the k64 layout), f16, dual, total: the fields of a ppst_pack_job; elems: int16 elements.
+_PackForm = collections.namedtuple("_PackForm", "entry w strides scale cout cin precision src bn n_groups nsteps x3 f16 dual total elems")
+
+
+def _pack_form(pl, key):
+    if key in ("up9", "wino"):
+        if key == "up9":        # from the layer's own (Cout, Cin, 3, 3) parameter
+            w, strides, scale, nbytes = pl.wparam, (pl.cin * 9, 9, 3, 1), pl.up_scale, lib.ppst_conv_pack_up9_bytes(pl.cout, pl.cin)
+        else:
+            w, strides, scale, nbytes = pl.wsrc, pl.wstrides, pl.scale, lib.ppst_conv_pack_wino_bytes(pl.cout, pl.cin)
+        return _PackForm("ppst_conv_pack_" + key, w, strides, float(scale), pl.cout, pl.cin, pl.precision, None, 0, 0, 0, 0, 0, 0, 0,
+                         nbytes // 2)
+    k64 = isinstance(key, str) and key.startswith("k64_")
+    dual = key in ("dual", "k64_dual")
+    bn = 256 if dual else int(key[4:]) if k64 else key
+    src = (pl.src_dual_k64 if dual else pl.src_k64) if k64 else (pl.src_dual if dual else pl.src_dev)
+    n_groups = 2 if dual else pl.n_groups
+    nsteps = src[0].numel() // n_groups
+    n_tiles = -(-pl.cout // (bn // 2 if dual else bn))          # (a dual N tile holds both column phases of 128 channels)
+    x3 = 2 if k64 else 1 if pl.precision == 0 else 0
+    total = n_groups * n_tiles * nsteps * 4 * bn
+    entry = "ppst_conv_pack_k64" if k64 else "ppst_conv_pack_dual" if dual else "ppst_conv_pack"
+    return _PackForm(entry, pl.wsrc, pl.wstrides, float(pl.scale), pl.cout, pl.cin, pl.precision, src, bn, n_groups, nsteps, x3,
+                     1 if pl.precision == 3 else 0, 1 if dual else 0, total, total * 8 * (2 if x3 else 1))
+
+
+def _pack_launch(f, out):
+    """fill the blob ``out`` of pack form ``f`` with the form's own C entry (one launch)"""
+    args = (_p(f.w),) + tuple(f.strides) + (f.scale, f.cout)
+    if f.src is None:
+        args += (f.cin,)
+    else:
+        args += () if f.entry == "ppst_conv_pack_dual" else (f.bn,)
+        args += tuple(_p(t) for t in f.src) + (f.nsteps, f.n_groups, f.precision)
+        args += (f.dual,) if f.entry == "ppst_conv_pack_k64" else ()
+    check(getattr(lib, f.entry)(*args, _p(out), _stream()), f.entry)
+
+
+# what one launch of a plan reads, from (choose_kernel's variant and N tile, k64): ppst_conv_args.variant / dual_b / steps / wpack /
+# n_groups / nsteps, and the groups its statistics have rows for
+_LaunchForm = collections.namedtuple("_LaunchForm", "variant dual_b steps pack n_groups nsteps stat_groups")
+
+
 class ConvPlan:
     """Packed weights + step table for ppst_conv2d_mfma.
 
     kind: 'conv' (k in {1,3}, stride 1), 's2d' (3x3 stride 2 over a space-to-depth
-    input), 'convT' (fused 4x4 stride-2 transposed conv = 4 output phases of 2x2 taps).
+    input), 'convT' (fused 4x4 stride-2 transposed conv = 4 output phases of 2x2 taps), and the input gradients 'dgrad',
+    'dgrad_s2d', 'dgrad_s2ds', 'dgradT' (conv_tables.py states every table).
     weight: (Cout, Cin, k, k) fp32 CUDA tensor; scale multiplies the weights.
     """
 
-    # Step tables are a function of (kind, weight shape, chan_base, device) only; building one is a Python loop over up to a few
-    # hundred steps plus three host-to-device copies from pageable memory.  A training step rebuilds every plan (the weights
-    # changed), ~150 per D + G iteration: the tables are shared between plans of one geometry, only the weights are new.
+    # Step tables are a function of (kind, weight shape) only (conv_tables.build); uploading one is up to nine host-to-device copies
+    # from pageable memory.  A training step rebuilds every plan whose weights it does not repack, ~150 per D + G iteration: the
+    # uploaded record is shared between the plans of one (kind, weight shape, device), only the weights are new.
     _GEOMETRY = {}
-    _GEOM_ATTRS = ("kind", "cout", "cin", "k", "bn", "n_groups", "halo", "src", "max_chan", "wstrides", "nsteps", "flop_steps",
-                   "early_a", "chunk_starts0", "chunk_starts0_k64", "steps", "src_dev", "chunk_start", "chunks_per_group", "w4_shape", "max_chunk_steps",
-                   "min_chunk_steps", "full_cover", "steps_dual", "src_dual", "steps_up9", "steps_k64", "src_k64", "steps_dual_k64",
-                   "src_dual_k64")
 
-    def __init__(self, weight, kind="conv", scale=1.0, chan_base=0, precision=None):
+    def __init__(self, weight, kind="conv", scale=1.0, precision=None):
         _chk(weight, "weight")
         w = weight.detach().contiguous()
-        gkey = (kind, tuple(w.shape), int(chan_base), str(w.device))
+        gkey = (kind, tuple(w.shape), str(w.device))
         geom = ConvPlan._GEOMETRY.get(gkey)
         if geom is None:
-            self._build(w, kind, scale, chan_base, precision)
-            ConvPlan._GEOMETRY[gkey] = {a: getattr(self, a) for a in ConvPlan._GEOM_ATTRS if hasattr(self, a)}
-            return
+            geom = ConvPlan._GEOMETRY[gkey] = _upload(conv_tables.build(kind, *w.shape[:3]), w.device)
         self.__dict__.update(geom)
         self.precision = PRECISION["value"] if precision is None else precision
         self.wparam, self.up_scale = w, float(scale)       # (repack_plans: the fp32 parameter storage this plan was packed from)
-        cout, cin, k, _ = w.shape
-        if kind in ("convT", "dgradT"):      # the fused upscale's 4x4 kernel (Cin, Cout, 4, 4), scale folded in
-            wsrc = torch.empty((cin, cout, 4, 4), device=w.device, dtype=torch.float32)
-            check(lib.ppst_upscale_weight(_p(w), _p(wsrc), cout, cin, float(scale), _stream()), "ppst_upscale_weight")
-            if kind == "dgradT":
-                self.fwd_scale = float(scale)
-            scale = 1.0
-        elif kind == "dgrad":
-            wsrc = w.view(-1)[k * k - 1:]
-        elif kind == "dgrad_s2ds":
-            wsrc = torch.empty((4 * cin, cout, 2, 2), device=w.device, dtype=torch.float32)
-            check(lib.ppst_dgrad_s2d_stack_weight(_p(w), _p(wsrc), cout, cin, _stream()), "ppst_dgrad_s2d_stack_weight")
-        else:
-            wsrc = w
-        self.scale = float(scale)
-        self.wsrc = wsrc
-        if self.precision == 2:
-            self.wpack = None
-            return
-        self._packs = {}
-        self.wpack = self.pack_for(self.bn)
-
-    def _build(self, w, kind, scale, chan_base, precision):
-        self.kind = kind
-        self.wparam, self.up_scale = w, float(scale)
-        self.precision = PRECISION["value"] if precision is None else precision
-        cout, cin, k, _ = w.shape
-        assert cin % 32 == 0, "fused conv needs Cin % 32 == 0 (got %d)" % cin
-        self.cout, self.cin, self.k = cout, cin, k
-        self.bn = 128 if cout >= 128 else 64
-        steps, src = [], []
-        nchunk = cin // 32
-        if kind == "conv":
-            assert k in (1, 3)
-            self.n_groups = 1
-            self.halo = 0 if k == 1 else 1
-            for c in range(nchunk):
-                first = True
-                for ky in range(k):
-                    for kx in range(k):
-                        steps.append((chan_base + 32 * c, ky - k // 2, kx - k // 2, 1 if first else 0))
-                        src.append((32 * c, ky, kx))
-                        first = False
-            sn, sc, sy, sx = cin * k * k, k * k, k, 1
-            wsrc = w
-        elif kind == "s2d":
-            assert k == 3
-            self.n_groups = 1
-            self.halo = 1
-            for py in range(2):
-                for px in range(2):
-                    for c in range(nchunk):
-                        first = True
-                        for ey in range(2):
-                            for ex in range(2):
-                                ky, kx = 2 * ey + py, 2 * ex + px
-                                if ky > 2 or kx > 2:
-                                    continue
-                                steps.append(((py * 2 + px) * cin + 32 * c, ey, ex, 1 if first else 0))
-                                src.append((32 * c, ky, kx))
-                                first = False
-                        if py == 1 and px == 1:
-                            # the (1,1) phase has a single tap: pad the chunk with a zero-weight step
-                            # (8-row tile kernels need >= 2 steps per chunk, ppst_hip.h tile_rows)
-                            steps.append(((py * 2 + px) * cin + 32 * c, 0, 0, 0))
-                            src.append((-1, 0, 0))
-            sn, sc, sy, sx = cin * 9, 9, 3, 1
-            wsrc = w
-        elif kind == "convT":
-            assert k == 3
-            self.n_groups = 4
-            self.halo = 1
-            # F.conv_transpose2d(x, w4, stride=2, padding=1): oy = 2*iy - 1 + ky
-            wsrc = torch.empty((cin, cout, 4, 4), device=w.device, dtype=torch.float32)
-            check(lib.ppst_upscale_weight(_p(w), _p(wsrc), cout, cin, float(scale), _stream()), "ppst_upscale_weight")
-            scale = 1.0
-            taps = {0: [(-1, 3), (0, 1)], 1: [(0, 2), (1, 0)]}
-            for a in range(2):
-                for b in range(2):
-                    for c in range(nchunk):
-                        first = True
-                        for dy, ky in taps[a]:
-                            for dx, kx in taps[b]:
-                                steps.append((chan_base + 32 * c, dy, dx, 1 if first else 0))
-                                src.append((32 * c, ky, kx))
-                                first = False
-            sn, sc, sy, sx = 16, cout * 16, 4, 1
-            if cout % 128 == 0 and chan_base % 1 == 0:
-                # the same conv as TWO row phases whose N tile holds both column phases (ppst_conv_args.dual_b): a step is a tap row
-                # dy with one tap column per column phase -- the per-element tap order stays (dy major), outputs bit-identical
-                dsteps, dsrc = [], []
-                for a in range(2):
-                    for c in range(nchunk):
-                        first = True
-                        for dy, ky in taps[a]:
-                            for j in range(2):
-                                (dx0, kx0), (dx1, kx1) = taps[0][j], taps[1][j]
-                                dsteps.append((chan_base + 32 * c, dy, (dx0 + 1) | ((dx1 + 1) << 8), 1 if first else 0))
-                                dsrc.append((32 * c, ky, kx0 | (kx1 << 8)))
-                                first = False
-                self._dual_tmp = (dsteps, dsrc)
-            if cout % 64 == 0:
-                # variant 11: per chunk the four input shifts; the u types each shift feeds are the kernel's (ppst_hip.h)
-                self._up9_tmp = [(chan_base + 32 * c, dy, dx, 1 if (dy, dx) == (0, 0) else 0)
-                                 for c in range(nchunk) for dy, dx in ((0, 0), (-1, 0), (0, -1), (-1, -1))]
-        elif kind == "dgrad":
-            # input gradient of a stride-1 conv (zero padding): a conv of dY with the transposed,
-            # flipped weights  Wd[c][n][ky][kx] = W[n][c][k-1-ky][k-1-kx]  -- same memory, other strides
-            assert k in (1, 3)
-            self.n_groups = 1
-            self.halo = 0 if k == 1 else 1
-            nchunk = cout // 32                      # the reduction now runs over the forward's Cout
-            assert cout % 32 == 0
-            for c in range(nchunk):
-                first = True
-                for ky in range(k):
-                    for kx in range(k):
-                        steps.append((32 * c, ky - k // 2, kx - k // 2, 1 if first else 0))
-                        src.append((32 * c, ky, kx))
-                        first = False
-            wsrc = w.view(-1)[k * k - 1:]            # element (ky', kx') = (0,0) is W[..][k-1][k-1]
-            sn, sc, sy, sx = k * k, cin * k * k, -k, -1
-            self.cout, self.cin = cin, cout          # roles swap
-            cout, cin = cin, cout
-            self.bn = 128 if cout >= 128 else 64
-        elif kind == "dgrad_s2d":
-            # input gradient of the stride-2 3x3 conv: element i = 2q+p of the (blurred) input grid
-            # receives  sum_{ky = p (mod 2)} W[.,.,ky,.]^T dY[q - ky//2]  -> 4 output phases scattered
-            # with stride 2, like the transposed conv; groups are padded to 4 steps per chunk.
-            assert k == 3 and cout % 32 == 0
-            self.n_groups = 4
-            self.halo = 1
-            taps = {0: [(0, 0), (-1, 2)], 1: [(0, 1)]}
-            for py in range(2):
-                for px in range(2):
-                    for c in range(cout // 32):
-                        tl = [(dy, dx, ky, kx) for dy, ky in taps[py] for dx, kx in taps[px]]
-                        for i in range(4):
-                            if i < len(tl):
-                                dy, dx, ky, kx = tl[i]
-                                steps.append((32 * c, dy, dx, 1 if i == 0 else 0))
-                                src.append((32 * c, ky, kx))
-                            else:
-                                steps.append((32 * c, 0, 0, 0))
-                                src.append((-1, 0, 0))
-            wsrc = w
-            sn, sc, sy, sx = 9, cin * 9, 3, 1     # n' = c (stride 9), c' = n (stride cin*9), no flip
-            self.cout, self.cin = cin, cout
-            cout, cin = cin, cout
-            self.bn = 128 if cout >= 128 else 64
-        elif kind == "dgrad_s2ds":
-            # round 5: the same input gradient with the four output phases STACKED as 4 x Cin output channels of ONE stride-1 conv
-            # with 2 x 2 taps (offsets 0 / -1 per axis), followed by ops.depth_to_space: one group, every step real (the four-group
-            # table pads 7 of its 16 steps per chunk), the tile staged once instead of once per phase, and 4 x Cin >= 128 output
-            # channels put a thin layer (Cin 32 / 64) on the 8-wave kernels -- its four-group launches ran 2 312-5 780 FOUR-wave
-            # blocks at 21-65 TFLOP/s.  Weights: ppst_dgrad_s2d_stack_weight (out (4 Cin, Cout, 2, 2) from the forward parameter).
-            assert k == 3 and cout % 32 == 0
-            self.n_groups = 1
-            self.halo = 1
-            for c in range(cout // 32):
-                for i, (ty, tx) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
-                    steps.append((32 * c, -ty, -tx, 1 if i == 0 else 0))
-                    src.append((32 * c, ty, tx))
-            wsrc = torch.empty((4 * cin, cout, 2, 2), device=w.device, dtype=torch.float32)
-            check(lib.ppst_dgrad_s2d_stack_weight(_p(w), _p(wsrc), cout, cin, _stream()), "ppst_dgrad_s2d_stack_weight")
-            sn, sc, sy, sx = cout * 4, 4, 2, 1
-            self.cout, self.cin = 4 * cin, cout
-            cout, cin = 4 * cin, cout
-            self.bn = 128 if cout >= 128 else 64
-        elif kind == "dgradT":
-            # input gradient of the fused 4x4 stride-2 transposed conv (kind 'convT'): a stride-2 4x4 conv (pad 1) of
-            # dY, run over the space-to-depth copy of dY:  oy = 2*iy - 1 + ky  ->  (dq, phase, ky) per axis in
-            # {(-1,1,0), (0,0,1), (0,1,2), (+1,0,3)}.  ``weight`` is the FORWARD (Cout,Cin,3,3) parameter.
-            assert k == 3 and cout % 32 == 0
-            self.n_groups = 1
-            self.halo = 1
-            wsrc = torch.empty((cin, cout, 4, 4), device=w.device, dtype=torch.float32)
-            check(lib.ppst_upscale_weight(_p(w), _p(wsrc), cout, cin, float(scale), _stream()), "ppst_upscale_weight")
+        self.wsrc, self.scale = _weight_source(w, self.wsource, float(scale))
+        if kind == "dgradT":
             self.fwd_scale = float(scale)
-            scale = 1.0
-            taps = {0: [(0, 1), (1, 3)], 1: [(-1, 0), (0, 2)]}
-            for py in range(2):
-                for px in range(2):
-                    for c in range(cout // 32):
-                        first = True
-                        for dqy, ky in taps[py]:
-                            for dqx, kx in taps[px]:
-                                steps.append(((py * 2 + px) * cout + 32 * c, dqy, dqx, 1 if first else 0))
-                                src.append((32 * c, ky, kx))
-                                first = False
-            sn, sc, sy, sx = cout * 16, 16, 4, 1      # w4[c][n][ky][kx]: output channel = c, reduction = n
-            self.w4_shape = (cin, cout, 4, 4)
-            self.cout, self.cin = cin, cout
-            cout, cin = cin, cout
-            self.bn = 128 if cout >= 128 else 64
-        else:
-            raise ValueError(kind)
-        self.src = src
-        self.max_chan = max(t[0] for t in steps)      # highest first-channel of any step (input needs max_chan + 32)
-        self.wstrides = (sn, sc, sy, sx)
-        self.nsteps = len(steps) // self.n_groups
-        self.flop_steps = sum(1 for t in src if t[0] >= 0) // self.n_groups
-        # every element of the weight tensor is the target of exactly one (step, output channel, k) of the table: the weight
-        # gradient's split reduction then WRITES all of dW and no zero fill has to run in front of it
-        live = [tuple(t[:3]) for t in src if t[0] >= 0]
-        target = math.prod(self.w4_shape) if kind == "dgradT" else w.numel()     # what conv_wgrad(plan, ...) returns
-        self.full_cover = bool(self.n_groups == 1 and len(set(live)) == len(live) and len(live) * 32 * cout == target)
-        dev = w.device
-        # flags: bit 0 = this step opens a chunk; bit 1 = the NEXT step of the group opens one, bits 8.. = its channel
-        # offset (lets the kernel request a chunk's activations a step early when every chunk spans >= 2 steps)
-        ns_ = self.nsteps
+        self.wpack = None
+        if self.precision != 2:      # (the exact-fp32 verification kernel reads the fp32 weights directly: nothing to pack)
+            self._packs = {}
+            self.wpack = self.pack_for(self.bn)
 
-        def encode(steps_):
-            enc = []
-            for i, (c_, dy_, dx_, f_) in enumerate(steps_):
-                nxt = steps_[i + 1] if (i + 1) % ns_ != 0 else None
-                w_ = f_ | ((2 | (nxt[0] << 8)) if (nxt is not None and nxt[3]) else 0)
-                enc.append((c_, dy_, dx_, w_))
-            return enc
-        enc = encode(steps)
-        starts = [i for i, t in enumerate(steps) if t[3] == 1] + [len(steps)]
-        lens = [b_ - a_ for a_, b_ in zip(starts[:-1], starts[1:])]
-        self.chunk_starts0 = [i for i in starts if i < ns_] + [ns_]          # chunk starts of ONE group (every group has the same)
-        self.chunk_starts0_k64 = None
-        self.early_a = 1 if (min(lens) >= 2 and ns_ >= 3) else 0
-        self.max_chunk_steps = max(lens)
-        self.min_chunk_steps = min(lens)
-        # 4 padding rows: the kernel prefetches the descriptor of step s+3 without a bounds test
-        self.steps = torch.tensor(enc + [(0, 0, 0, 0)] * 4, dtype=torch.int32, device=dev).contiguous()
-        self.steps_dual = self.src_dual = None
-        dual = self.__dict__.pop("_dual_tmp", None)
-        if dual is not None:
-            self.steps_dual = torch.tensor(encode(dual[0]) + [(0, 0, 0, 0)] * 4, dtype=torch.int32, device=dev).contiguous()
-            sd_ = torch.tensor(dual[1], dtype=torch.int32, device=dev)
-            self.src_dual = (sd_[:, 0].contiguous(), sd_[:, 1].contiguous(), sd_[:, 2].contiguous())
-        # K64 tables: every second 32-channel chunk of a group opens a 64-channel step group with the same taps (needs an even chunk
-        # count per group and plain 32-channel chunk order: conv k = 3, s2d, convT and its phase-pair form)
-        self.steps_k64 = self.src_k64 = self.steps_dual_k64 = self.src_dual_k64 = None
-
-        def k64_tables(steps_, src_, ngroups):
-            per = len(steps_) // ngroups
-            keep, chunk = [], -1
-            for i, t in enumerate(steps_):
-                if i % per == 0:
-                    chunk = -1
-                chunk += 1 if t[3] else 0
-                if chunk % 2 == 0:
-                    keep.append(i)
-            st = [steps_[i] for i in keep]
-            per2 = len(st) // ngroups
-            enc2, ci = [], -1
-            for i, (c_, dy_, dx_, f_) in enumerate(st):
-                if i % per2 == 0:
-                    ci = -1
-                ci += 1 if f_ else 0
-                nxt = st[i + 1] if (i + 1) % per2 != 0 else None
-                enc2.append((c_, dy_, dx_, f_ | ((2 | (nxt[0] << 8)) if (nxt is not None and nxt[3]) else 0) | ((ci & 1) << 2)))
-            if ngroups == self.n_groups:
-                self.chunk_starts0_k64 = [i for i, t in enumerate(st[:per2]) if t[3]] + [per2]
-            sr = torch.tensor([src_[i] for i in keep], dtype=torch.int32, device=dev)
-            return (torch.tensor(enc2 + [(0, 0, 0, 0)] * 4, dtype=torch.int32, device=dev).contiguous(),
-                    (sr[:, 0].contiguous(), sr[:, 1].contiguous(), sr[:, 2].contiguous()))
-        if kind in ("conv", "s2d", "convT") and self.halo == 1 and cin % 64 == 0 and cout >= 128 and self.early_a:
-            self.steps_k64, self.src_k64 = k64_tables(steps, src, self.n_groups)
-            if dual is not None:
-                self.steps_dual_k64, self.src_dual_k64 = k64_tables(dual[0], dual[1], 2)
-        up9 = self.__dict__.pop("_up9_tmp", None)
-        self.steps_up9 = None
-        if up9 is not None:
-            self.steps_up9 = torch.tensor(encode(up9) + [(0, 0, 0, 0)] * 4, dtype=torch.int32, device=dev).contiguous()
-        s = torch.tensor(src, dtype=torch.int32, device=dev)
-        src_c, src_ky, src_kx = s[:, 0].contiguous(), s[:, 1].contiguous(), s[:, 2].contiguous()
-        self.src_dev = (src_c, src_ky, src_kx)
-        cs = [i for i, t in enumerate(steps) if t[3] == 1] + [len(steps)]
-        self.chunk_start = torch.tensor(cs, dtype=torch.int32, device=dev)
-        # chunks per group (every group has the same count): ring depth hint for the kernel
-        self.chunks_per_group = (len(cs) - 1) // self.n_groups
-        self.scale = float(scale)
-        self.wsrc = wsrc
-        if self.precision == 2:      # exact-fp32 verification kernel reads the fp32 weights directly: nothing to pack
-            self.wpack = None
-            return
-        self._packs = {}
-        self.wpack = self.pack_for(self.bn)
+    def _pack(self, key):
+        """the packed weight blob ``key`` (see _PackForm), built on first use"""
+        hit = self._packs.get(key)
+        if hit is None:
+            f = _pack_form(self, key)
+            hit = torch.empty(f.elems, dtype=torch.int16, device=self.steps.device)
+            _pack_launch(f, hit)
+            self._packs[key] = hit
+        return hit
 
     def pack_for(self, bn):
-        """packed weight blob for N tile ``bn`` (built on first use: the fat-wave kernel wants 128 / 256)."""
-        hit = self._packs.get(bn)
-        if hit is not None:
-            return hit
-        cout = self.cout
-        sn, sc, sy, sx = self.wstrides
-        src_c, src_ky, src_kx = self.src_dev
-        n_tiles = (cout + bn - 1) // bn
-        npl = 8 if self.precision == 0 else 4
-        wpack = torch.empty(self.n_groups * n_tiles * self.nsteps * npl * bn * 8, dtype=torch.int16, device=self.steps.device)
-        check(lib.ppst_conv_pack(_p(self.wsrc), sn, sc, sy, sx, float(self.scale), cout, bn, _p(src_c), _p(src_ky), _p(src_kx),
-                                 self.nsteps, self.n_groups, self.precision, _p(wpack), _stream()), "ppst_conv_pack")
-        self._packs[bn] = wpack
-        return wpack
+        """packed weights for N tile ``bn`` (the fat-wave kernel wants 128 / 256)"""
+        return self._pack(bn)
 
     def pack_dual(self):
-        """weights for ppst_conv_args.dual_b (ppst_conv_pack_dual), built on first use."""
-        hit = self._packs.get("dual")
-        if hit is not None:
-            return hit
-        sn, sc, sy, sx = self.wstrides
-        c_, ky_, kx_ = self.src_dual
-        n_tiles = (self.cout + 127) // 128
-        npl = 8 if self.precision == 0 else 4                # hi + lo planes, or the hi planes of a single-pass mode
-        wpack = torch.empty(2 * n_tiles * self.nsteps * npl * 256 * 8, dtype=torch.int16, device=self.steps.device)
-        check(lib.ppst_conv_pack_dual(_p(self.wsrc), sn, sc, sy, sx, float(self.scale), self.cout, _p(c_), _p(ky_), _p(kx_),
-                                      self.nsteps, 2, self.precision, _p(wpack), _stream()), "ppst_conv_pack_dual")
-        self._packs["dual"] = wpack
-        return wpack
+        """weights for ppst_conv_args.dual_b"""
+        return self._pack("dual")
 
     def pack_k64(self, bn, dual=False):
-        """weights for ppst_conv_args.k64 (ppst_conv_pack_k64), built on first use."""
-        key = "k64_dual" if dual else "k64_%d" % bn
-        hit = self._packs.get(key)
-        if hit is not None:
-            return hit
-        sn, sc, sy, sx = self.wstrides
-        c_, ky_, kx_ = self.src_dual_k64 if dual else self.src_k64
-        ng = 2 if dual else self.n_groups
-        nst = c_.numel() // ng
-        n_tiles = (self.cout + (bn // 2 if dual else bn) - 1) // (bn // 2 if dual else bn)
-        wpack = torch.empty(ng * n_tiles * nst * 8 * bn * 8, dtype=torch.int16, device=self.steps.device)
-        check(lib.ppst_conv_pack_k64(_p(self.wsrc), sn, sc, sy, sx, float(self.scale), self.cout, bn, _p(c_), _p(ky_), _p(kx_), nst, ng,
-                                     self.precision, 1 if dual else 0, _p(wpack), _stream()), "ppst_conv_pack_k64")
-        self._packs[key] = wpack
-        return wpack
+        """weights for ppst_conv_args.k64"""
+        return self._pack("k64_dual" if dual else "k64_%d" % bn)
 
     def pack_up9(self):
-        """weights for variant 11 (ppst_conv_pack_up9: the un-blurred 3x3 kernel), built on first use."""
-        hit = self._packs.get("up9")
-        if hit is not None:
-            return hit
-        w = self.wparam                                          # (Cout, Cin, 3, 3) fp32, the layer's own parameter
-        nbytes = lib.ppst_conv_pack_up9_bytes(self.cout, self.cin)
-        wpack = torch.empty(nbytes // 2, dtype=torch.int16, device=self.steps.device)
-        check(lib.ppst_conv_pack_up9(_p(w), self.cin * 9, 9, 3, 1, float(self.up_scale), self.cout, self.cin, _p(wpack), _stream()),
-              "ppst_conv_pack_up9")
-        self._packs["up9"] = wpack
-        return wpack
+        """weights for variant 11 (the un-blurred 3x3 kernel)"""
+        return self._pack("up9")
 
     def pack_wino(self):
-        """transformed weights for variant 10 (ppst_conv_pack_wino), built on first use."""
-        hit = self._packs.get("wino")
-        if hit is not None:
-            return hit
-        sn, sc, sy, sx = self.wstrides
-        nbytes = lib.ppst_conv_pack_wino_bytes(self.cout, self.cin)
-        wpack = torch.empty(nbytes // 2, dtype=torch.int16, device=self.steps.device)
-        check(lib.ppst_conv_pack_wino(_p(self.wsrc), sn, sc, sy, sx, float(self.scale), self.cout, self.cin, _p(wpack), _stream()),
-              "ppst_conv_pack_wino")
-        self._packs["wino"] = wpack
-        return wpack
+        """transformed weights for variant 10"""
+        return self._pack("wino")
+
+    def _launch_form(self, variant, bn, k64):
+        dual, up9 = variant == "dual", variant == "up9"
+        if k64:
+            key, steps = ("k64_dual", self.steps_dual_k64) if dual else ("k64_%d" % bn, self.steps_k64)
+        else:
+            key = "wino" if variant == 10 else "up9" if up9 else "dual" if dual else bn
+            steps = self.steps_up9 if up9 else self.steps_dual if dual else self.steps
+        return _LaunchForm(11 if up9 else 2 if dual else variant, 1 if dual else 0, steps,
+                           None if self.precision == 2 else self._pack(key), 1 if up9 else 2 if dual else self.n_groups,
+                           self.nsteps // 2 if k64 else self.nsteps, 1 if up9 else self.n_groups)
 
     def takes_in_res(self, H, W):
         """True when a call of this plan on an (H, W) input may carry ``in_res`` (the 1x1 streaming kernel in the fp32-class mode)."""
@@ -684,7 +452,7 @@ class ConvPlan:
         # the (a, s) table is sized for 32 chunks)
         return (self.precision == 0 and self.kind in ("conv", "dgrad") and self.k == 3 and self.cout >= 128 and osy == 1
                 and (th, tw) == (oh, ow) == (H, W)
-                and ((th + 15) // 16) * ((tw + 15) // 16) * ((self.cout + 127) // 128) >= WINO["min_blocks"])
+                and _tiles(th, tw, 16) * ((self.cout + 127) // 128) >= WINO["min_blocks"])
 
     def choose_kernel(self, th, tw, oh, ow, H, W, osy, B=None, allow_up9=True, allow_wino=True):
         """(variant, N tile, tile rows) of ppst_conv_args for one launch of this plan -- a function of the plan and of ONE
@@ -703,19 +471,19 @@ class ConvPlan:
         if self.precision not in (0, 1, 3):
             return variant, bn, rows                     # exact-fp32 verification: the tile kernel only
         if allow_wino and WINO["value"] and self.wino_ok(th, tw, oh, ow, H, W, osy):
-            wblocks = ((th + 15) // 16) * ((tw + 15) // 16) * ((self.cout + 127) // 128) * (B or 1)
+            wblocks = _tiles(th, tw, 16) * ((self.cout + 127) // 128) * (B or 1)
             aware_b = BATCH_AWARE["value"] and B is not None
             if not (aware_b and (wblocks < WINO["fill"] or (KSPLIT["value"] and 0 in KSPLIT["variants"] and self.cout <= 256
                                                              and wblocks <= WINO["ksplit_fill"]))):
                 return 10, 128, 16
-        tiles16 = ((th + 15) // 16) * ((tw + 15) // 16) * self.n_groups          # blocks PER IMAGE per N tile
+        tiles16 = _tiles(th, tw, 16) * self.n_groups          # blocks PER IMAGE per N tile
         if (UP9["value"] and allow_up9 and self.kind == "convT" and self.precision == 0 and getattr(self, "steps_up9", None) is not None
-                and self.early_a and ((th + 14) // 15) * ((tw + 14) // 15) * (self.cout // 64) >= UP9["min_blocks"]
+                and self.early_a and _tiles(th, tw, 15, 15) * (self.cout // 64) >= UP9["min_blocks"]
                 and th * tw >= UP9["min_fill"] * (((th + 14) // 15) * 15) * (((tw + 14) // 15) * 15)):
             return "up9", 256, 15
         if (DUAL_CONVT["value"] and self.kind == "convT" and getattr(self, "steps_dual", None) is not None
                 and self.cout % 256 != 0 and cv == 2 and self.early_a
-                and ((th + 15) // 16) * ((tw + 15) // 16) * 2 * (self.cout // 128) >= DUAL_CONVT["min_blocks"]):
+                and _tiles(th, tw, 16) * 2 * (self.cout // 128) >= DUAL_CONVT["min_blocks"]):
             return "dual", 256, 16
         n256_ok = self.cout % 256 == 0 and tiles16 * (self.cout // 256) >= FAT_MIN_BLOCKS
         aware = BATCH_AWARE["value"] and B is not None and not single and self.bn == 128 and self.early_a and self.halo == 1
@@ -731,10 +499,10 @@ class ConvPlan:
             elif single:
                 # single-pass modes: the N-256 geometry, and for Cout = 128-class layers with a halo the 32 x 16 px x 128 ch tile
                 if (self.bn == 128 and self.halo == 1 and self.n_groups == 1 and TALL_TILE_SINGLE["value"] and
-                        ((th + 31) // 32) * ((tw + 15) // 16) * ((self.cout + 127) // 128) >= TALL_TILE_SINGLE["min_blocks"]):
+                        _tiles(th, tw, 32) * ((self.cout + 127) // 128) >= TALL_TILE_SINGLE["min_blocks"]):
                     variant, rows = 7, 32
             elif (self.bn == 128 and self.halo == 1 and (small or (TWO_BLOCK_8ROW["value"] and
-                  ((th + 7) // 8) * ((tw + 15) // 16) * self.n_groups * ((self.cout + 127) // 128) >= TWO_BLOCK_8ROW["min_blocks"]))):
+                  _tiles(th, tw, 8) * self.n_groups * ((self.cout + 127) // 128) >= TWO_BLOCK_8ROW["min_blocks"]))):
                 rows = 8                                 # tile kernel, two 4-wave blocks per CU
         same = (th, tw) == (oh, ow)
         if STREAM_1X1["value"] and self.halo == 0 and self.n_groups == 1 and osy == 1 and same and (oh, ow) == (H, W):
@@ -817,28 +585,16 @@ class ConvPlan:
                and (self.steps_dual_k64 if variant == "dual" else self.steps_k64) is not None)
         if k64 and variant == 7:
             variant, rows = 9, 24                # the Cout = 128-class layers: 24 x 16 px x 128 ch tiles (two activation slots fit)
+        form = self._launch_form(variant, bn, k64)
+        variant = form.variant
         st = None
         if stats:
-            tiles = lib.ppst_conv_tiles(th, tw, rows)
-            st = torch.empty((B, (1 if variant == "up9" else self.n_groups) * tiles, self.cout, 2), device=x.device, dtype=torch.float32)
+            st = torch.empty((B, form.stat_groups * lib.ppst_conv_tiles(th, tw, rows), self.cout, 2), device=x.device, dtype=torch.float32)
             # (a block of variant 11 writes its row only for channels it owns and every block of the grid writes: no zero fill needed)
         a = _lib.ConvArgs()
-        dual, up9 = variant == "dual", variant == "up9"
-        if dual:
-            variant = 2
-        if up9:
-            variant = 11
-        if k64:
-            wp = self.pack_k64(bn, dual)
-            steps_t = self.steps_dual_k64 if dual else self.steps_k64
-        else:
-            wp = None if self.precision == 2 else (self.pack_wino() if variant == 10 else self.pack_up9() if up9 else self.pack_dual() if dual
-                                                   else self.pack_for(bn))
-            steps_t = self.steps_up9 if up9 else self.steps_dual if dual else self.steps
-        a.x, a.wpack, a.steps, a.y = _p(x), _p(wp), _p(steps_t), _p(out)
+        a.x, a.wpack, a.steps, a.y = _p(x), _p(form.pack), _p(form.steps), _p(out)
         a.k64 = 1 if k64 else 0
-        a.variant = variant
-        a.dual_b = 1 if dual else 0
+        a.variant, a.dual_b = variant, form.dual_b
         a.bias, a.noise, a.prelu, a.stats = _p(bias), _p(noise), _p(prelu), _p(st)
         a.residual = _p(residual)
         a.res_ld = _nhwc_ld(residual, "residual", half_ok=True) if residual is not None else 0
@@ -846,7 +602,7 @@ class ConvPlan:
         a.noise_weight, a.out_scale = float(noise_weight), float(out_scale)
         a.B, a.in_h, a.in_w, a.in_ld = B, H, W, in_ld
         a.out_h, a.out_w, a.out_ld, a.cout = oh, ow, out_ld, self.cout
-        a.nsteps, a.n_groups, a.pad_mode = (self.nsteps // 2 if k64 else self.nsteps), (1 if up9 else 2 if dual else self.n_groups), pad_mode
+        a.nsteps, a.n_groups, a.pad_mode = form.nsteps, form.n_groups, pad_mode
         a.in_off_y = a.in_off_x = 0
         a.out_sy = a.out_sx = osy
         a.act, a.precision = act | (0x100 if res_after_act else 0), self.precision
@@ -953,96 +709,66 @@ def _ksplit_choice(blocks, chunk_starts, max_blocks, min_steps, max_s=8):
     return 0, None
 
 
+# what run_repack launches: two job tables (device arrays of ppst_upscale_job / ppst_pack_job, their job and block counts), the
+# phase-stacked kernels to refresh between them, and the packs that have a transform kernel of their own
+_JobTable = collections.namedtuple("_JobTable", "buf njobs nblocks")
+_StackJob = collections.namedtuple("_StackJob", "w out cout cin")
+_Repack = collections.namedtuple("_Repack", "upscale stack pack single")
+
+
+def _job_table(cls, rows, dev):
+    """``rows`` (field dicts of ``cls``) as a device array with every job's block range filled in"""
+    arr = (cls * len(rows))()
+    b0 = 0
+    for j, r in zip(arr, rows):
+        for name, v in r.items():
+            setattr(j, name, v)
+        j.block0, j.nblocks = b0, lib.ppst_pack_job_blocks(j.total)
+        b0 += j.nblocks
+    return _JobTable(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev) if rows else None, len(rows), b0)
+
+
 def repack_plans(plans):
     """Refresh the packed weights of ``plans`` (ConvPlan objects whose fp32 weights changed in place -- an Adam step) with TWO
-    launches: the fused-upscale 4x4 kernels of the 'convT' / 'dgradT' plans (ppst_upscale_weight_batch), then every pack of every
-    plan (ppst_conv_pack_batch).  Returns the job tables; pass them back as ``tables`` while the set of plans / packs is unchanged
-    (they hold device pointers only: nothing is rebuilt on the host)."""
-    import numpy as np
-    up, pk, wino = [], [], []
+    batched launches: the fused-upscale 4x4 kernels of the 'convT' / 'dgradT' plans (ppst_upscale_weight_batch), then every pack
+    with source columns of every plan (ppst_conv_pack_batch); the phase-stacked kernels and the "up9" / "wino" packs take one launch
+    each.  Every pack is described by _pack_form, as on its first use.  Returns the job tables; pass them to run_repack while the
+    set of plans / packs is unchanged (they hold device pointers only: nothing is rebuilt on the host)."""
+    up, stack, pk, single = [], [], [], []
     for pl in plans:
         if pl.precision == 2:
             continue
-        if pl.kind == "dgrad_s2ds":              # the phase-stacked 2 x 2 kernel: refreshed from the parameter before the packs read it
-            wino.append(("s2ds", pl.wparam, pl.wsrc, pl.wparam.shape[0], pl.wparam.shape[1], None))
-        if pl.kind in ("convT", "dgradT"):
+        if pl.wsource == "stack":                # refreshed from the parameter before the packs read it
+            stack.append(_StackJob(pl.wparam, pl.wsrc, pl.wparam.shape[0], pl.wparam.shape[1]))
+        if pl.wsource == "up4":
             cin4, cout4 = pl.wsrc.shape[0], pl.wsrc.shape[1]         # wsrc is the (Cin, Cout, 4, 4) kernel of the FORWARD conv
-            up.append((pl.wparam.data_ptr(), pl.wsrc.data_ptr(), cin4 * cout4 * 16, float(pl.up_scale), cout4, cin4))
-        sn, sc, sy, sx = pl.wstrides
-        c_, ky_, kx_ = pl.src_dev
-        for bn, wpack in pl._packs.items():
-            if bn == "wino":                     # variant-10 pack: its own transform kernel, one launch per plan
-                wino.append((pl.wsrc, pl.wstrides, float(pl.scale), pl.cout, pl.cin, wpack))
+            up.append(dict(w=pl.wparam.data_ptr(), out=pl.wsrc.data_ptr(), total=cin4 * cout4 * 16, scale=float(pl.up_scale),
+                           cout=cout4, cin=cin4))
+        for key, wpack in pl._packs.items():
+            f = _pack_form(pl, key)
+            if f.src is None:
+                single.append((f, wpack))
                 continue
-            if isinstance(bn, str) and bn.startswith("k64_"):     # 64-channel-step packs: jobs of the batched pack kernel (x3 = 2)
-                kd = bn == "k64_dual"
-                kc, kky, kkx = pl.src_dual_k64 if kd else pl.src_k64
-                kbn = 256 if kd else int(bn[4:])
-                kng = 2 if kd else pl.n_groups
-                knt = (pl.cout + (kbn // 2 if kd else kbn) - 1) // (kbn // 2 if kd else kbn)
-                pk.append((pl.wsrc.data_ptr(), sn, sc, sy, sx, kc.data_ptr(), kky.data_ptr(), kkx.data_ptr(), wpack.data_ptr(),
-                           kng * knt * (kc.numel() // kng) * 4 * kbn, float(pl.scale), pl.cout, kbn, kc.numel() // kng, kng,
-                           2, 1 if pl.precision == 3 else 0, 1 if kd else 0))
-                continue
-            if bn == "up9":                      # variant-11 pack: from the 3x3 parameter itself, one launch per plan
-                wino.append(("up9", pl.wparam, float(pl.up_scale), pl.cout, pl.cin, wpack))
-                continue
-            if bn == "dual":                     # two-phase-pair pack of the fused upscale: a job of the batched pack kernel
-                dc, dky, dkx = pl.src_dual
-                pk.append((pl.wsrc.data_ptr(), sn, sc, sy, sx, dc.data_ptr(), dky.data_ptr(), dkx.data_ptr(), wpack.data_ptr(),
-                           2 * ((pl.cout + 127) // 128) * pl.nsteps * 4 * 256, float(pl.scale), pl.cout, 256, pl.nsteps, 2,
-                           1 if pl.precision == 0 else 0, 1 if pl.precision == 3 else 0, 1))
-                continue
-            n_tiles = (pl.cout + bn - 1) // bn
-            pk.append((pl.wsrc.data_ptr(), sn, sc, sy, sx, c_.data_ptr(), ky_.data_ptr(), kx_.data_ptr(), wpack.data_ptr(),
-                       pl.n_groups * n_tiles * pl.nsteps * 4 * bn, float(pl.scale), pl.cout, bn, pl.nsteps, pl.n_groups,
-                       1 if pl.precision == 0 else 0, 1 if pl.precision == 3 else 0, 0))
+            sn, sc, sy, sx = f.strides
+            pk.append(dict(w=f.w.data_ptr(), sn=sn, sc=sc, sy=sy, sx=sx, src_c=f.src[0].data_ptr(), src_ky=f.src[1].data_ptr(),
+                           src_kx=f.src[2].data_ptr(), out=wpack.data_ptr(), total=f.total, scale=f.scale, cout=f.cout, bn=f.bn,
+                           nsteps=f.nsteps, n_groups=f.n_groups, x3=f.x3, f16=f.f16, dual=f.dual))
     dev = plans[0].steps.device if plans else None
-
-    def table(cls, rows, fill):
-        if not rows:
-            return None, 0
-        arr = (cls * len(rows))()
-        b0 = 0
-        for j, r in zip(arr, rows):
-            nb = lib.ppst_pack_job_blocks(fill(j, r))
-            j.block0, j.nblocks = b0, nb
-            b0 += nb
-        buf = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-        return buf, b0
-
-    def fill_up(j, r):
-        j.w, j.out, j.total, j.scale, j.cout, j.cin = r
-        return j.total
-
-    def fill_pk(j, r):
-        (j.w, j.sn, j.sc, j.sy, j.sx, j.src_c, j.src_ky, j.src_kx, j.out, j.total, j.scale, j.cout, j.bn, j.nsteps, j.n_groups,
-         j.x3, j.f16, j.dual) = r
-        return j.total
-    tu, nbu = table(_lib.UpscaleJob, up, fill_up)
-    tp, nbp = table(_lib.PackJob, pk, fill_pk)
-    tables = (tu, len(up), nbu, tp, len(pk), nbp, wino)
+    tables = _Repack(_job_table(_lib.UpscaleJob, up, dev), stack, _job_table(_lib.PackJob, pk, dev), single)
     run_repack(tables)
     return tables
 
 
 def run_repack(tables):
-    tu, nu, nbu, tp, npk, nbp, wino = tables
-    if nu:
-        check(lib.ppst_upscale_weight_batch(_p(tu), nu, nbu, _stream()), "ppst_upscale_weight_batch")
-    for e in wino:
-        if isinstance(e[0], str) and e[0] == "s2ds":
-            check(lib.ppst_dgrad_s2d_stack_weight(_p(e[1]), _p(e[2]), e[3], e[4], _stream()), "ppst_dgrad_s2d_stack_weight")
-    if npk:
-        check(lib.ppst_conv_pack_batch(_p(tp), npk, nbp, _stream()), "ppst_conv_pack_batch")
-    for wsrc, strides, scale, cout, cin, wpack in wino:
-        if isinstance(wsrc, str) and wsrc == "s2ds":
-            continue
-        if isinstance(wsrc, str):                # ("up9", the 3x3 parameter, ...): variant 11
-            check(lib.ppst_conv_pack_up9(_p(strides), cin * 9, 9, 3, 1, scale, cout, cin, _p(wpack), _stream()), "ppst_conv_pack_up9")
-            continue
-        sn, sc, sy, sx = strides
-        check(lib.ppst_conv_pack_wino(_p(wsrc), sn, sc, sy, sx, scale, cout, cin, _p(wpack), _stream()), "ppst_conv_pack_wino")
+    t = tables
+    if t.upscale.njobs:
+        check(lib.ppst_upscale_weight_batch(_p(t.upscale.buf), t.upscale.njobs, t.upscale.nblocks, _stream()), "ppst_upscale_weight_batch")
+    for e in t.stack:
+        check(lib.ppst_dgrad_s2d_stack_weight(_p(e.w), _p(e.out), e.cout, e.cin, _stream()), "ppst_dgrad_s2d_stack_weight")
+    if t.pack.njobs:
+        check(lib.ppst_conv_pack_batch(_p(t.pack.buf), t.pack.njobs, t.pack.nblocks, _stream()), "ppst_conv_pack_batch")
+    for f, wpack in t.single:
+        _pack_launch(f, wpack)
 
 
 def _grad_out(out, shape, like):
