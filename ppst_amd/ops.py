@@ -1673,8 +1673,10 @@ def gemm_nt(A, Bm, alpha=1.0, mode=None):
     A, Bm = A.contiguous(), Bm.contiguous()
     b, M, K = A.shape
     N = Bm.shape[1]
-    C = torch.empty((b, M, N), device=A.device, dtype=torch.float32)
     passes = _gemm_passes(mode, K)
+    if K % 16:
+        raise ValueError("gemm_nt: K = %d; every kernel (split and fp32) takes K %% 16 == 0 only" % K)
+    C = torch.empty((b, M, N), device=A.device, dtype=torch.float32)
     if passes:
         check(lib.ppst_gemm_nt_split(_p(A), _p(Bm), _p(C), b, M, N, K, float(alpha), passes, _stream()), "ppst_gemm_nt_split")
     else:
@@ -1688,8 +1690,10 @@ def gemm_nn(A, Bm, mode=None):
     A, Bm = A.contiguous(), Bm.contiguous()
     b, M, K = A.shape
     N = Bm.shape[2]
-    C = torch.empty((b, M, N), device=A.device, dtype=torch.float32)
     passes = _gemm_passes(mode, K) if N % 4 == 0 else 0
+    if N % 4 or K % 16:       # (the fp32 kernel these fall through to reads B four columns and K sixteen rows at a time as well)
+        raise ValueError("gemm_nn: N = %d, K = %d; every kernel (split and fp32) takes N %% 4 == 0 and K %% 16 == 0 only" % (N, K))
+    C = torch.empty((b, M, N), device=A.device, dtype=torch.float32)
     if passes:
         check(lib.ppst_gemm_nn_split(_p(A), _p(Bm), _p(C), b, M, N, K, N, N, passes, _stream()), "ppst_gemm_nn_split")
     else:
@@ -1701,6 +1705,8 @@ def softmax_rows_(x, div=1.0):
     _chk(x)
     assert x.is_contiguous()
     cols = x.shape[-1]
+    if cols % 4 or cols > 16384:
+        raise ValueError("softmax_rows_: cols = %d; the kernel holds a row of cols %% 4 == 0, cols <= 16384 in registers" % cols)
     check(lib.ppst_softmax_rows(_p(x), x.numel() // cols, cols, float(div), _stream()), "ppst_softmax_rows")
     return x
 
