@@ -562,6 +562,21 @@ int ppst_resample_u8(const void* x, void* y, int B, int in_h, int in_w, int C, i
 /* transforms.ToTensor + transforms.Normalize(mean, std) (base_dataset.py:133-138): uint8 HWC
  * [B][H][W][C] -> fp32 NCHW, (v/255 - mean)/std in that operation order. */
 int ppst_u8_to_tensor(const void* x, void* y, int B, int H, int W, int C, float mean, float stdv, void* stream);
+/* The same filter (Pillow's antialiased bicubic: Keys a = -0.5, support 2 * max(1, in / out), window bounds of
+ * precompute_coeffs) on fp32 planes, both axes in ONE launch: x [B][in_h][in_w] -> y [B][out_h][out_w], B = batch * channels.
+ * bounds_* int32 [out][2] = (first input sample, count <= ksize_*), coef_* fp32 [out][ksize_*] = weights that sum to 1 per
+ * output position (host logic, float64 rounded once: ppst_amd/imageio.py); the windows advance with the output index.  A
+ * block filters the input rows its 16 x 64 output tile needs horizontally into LDS and then vertically from LDS (fp32 fma,
+ * taps in ascending order): the half-filtered image never reaches memory.  An axis with in == out is copied: its tables are
+ * not read and may be null.  clamp != 0: the result is clamped to [lo, hi] at the store (a bicubic overshoots; Pillow's
+ * 8-bit path clips the same way).
+ * The vertical window of one tile must fit the LDS: min(in_h, 15 * in_h / out_h + ksize_v + 1) <= 192 rows (integer division;
+ * ksize_v = 1 for a copied axis), else PPST_EINVAL -- every reduction up to 8 : 1 fits.  B * in_h * in_w and B * out_h * out_w
+ * at most 2^32 - 1; clamp with lo > hi: PPST_EINVAL. */
+int ppst_resample_f32(const void* x, void* y, int B, int in_h, int in_w, int out_h, int out_w,
+                      const void* bounds_h, const void* coef_h, int ksize_h,
+                      const void* bounds_v, const void* coef_v, int ksize_v,
+                      int clamp, float lo, float hi, void* stream);
 
 /* PNG encode on the device (ppst_amd/csrc/png.hip): uint8 HWC [B][H][W][C], C = 1 (grey) or 3 (RGB), 8 bits per sample, ->
  * B complete PNG files.  Per row the filter with the smallest sum of absolute signed bytes (libpng's heuristic, ties to the

@@ -150,6 +150,7 @@ _SIGS = {
     "ppst_tensor2im_u8": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "ppst_resample_u8": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]),
     "ppst_u8_to_tensor": (i32, [vp, vp, i32, i32, i32, i32, f32, f32, vp]),
+    "ppst_resample_f32": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, f32, f32, vp]),
     "ppst_png_bound": (i64, [i32, i32, i32]),
     "ppst_png_ws": (i64, [i32, i32, i32, i32]),
     "ppst_png_encode": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),

@@ -78,3 +78,97 @@ extern "C" int ppst_u8_to_tensor(const void* x, void* y, int B, int H, int W, in
               (unsigned)P, (unsigned)total, mean, stdv, make_fastdiv((unsigned)P), make_fastdiv(C));
   return PPST_LAUNCH_CHECK();
 }
+
+// The same filter on fp32 planes, both axes in one launch (ppst_resample_f32).  A block owns an RS_TH x RS_TW tile of one output
+// plane.  Pass 1: each of the input rows [y0, y0 + nrows) under the tile's vertical windows is filtered horizontally at the tile's
+// RS_TW output columns into LDS (a wave = one row: lane l reads x[row][first(ox0 + l) + j]).  Pass 2: every output sample is the
+// vertical filter over its column of the LDS tile (lanes = consecutive columns: conflict-free).  A null bounds table = that axis is
+// copied.  Windows are clipped to the image and to the LDS tile, whatever the tables say: a bad table gives wrong values, never an
+// access outside x or the tile.
+#define RS_TH 16
+#define RS_TW 64
+#define RS_ROWS_MAX 192
+__global__ __launch_bounds__(256) void resample_f32_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                           const int* __restrict__ bnd_h, const float* __restrict__ coef_h, int ksize_h,
+                                                           const int* __restrict__ bnd_v, const float* __restrict__ coef_v, int ksize_v,
+                                                           int in_h, int in_w, int out_h, int out_w, int rows_cap, int clamp, float lo,
+                                                           float hi, FastDiv d_tx, FastDiv d_ty) {
+  extern __shared__ __attribute__((aligned(16))) float rs_tile[];  // [rows_cap][RS_TW]
+  unsigned tx, ty;
+  const unsigned plane = fd_divmod(fd_divmod(blockIdx.x, d_tx, tx), d_ty, ty);
+  const int lx = threadIdx.x & (RS_TW - 1), wy = threadIdx.x / RS_TW;
+  const int ox = (int)tx * RS_TW + lx, oy0 = (int)ty * RS_TH;
+  const int oy_last = min(oy0 + RS_TH, out_h) - 1;
+  int y0 = oy0, y1 = oy_last + 1;
+  if (bnd_v) { y0 = bnd_v[2 * oy0]; y1 = bnd_v[2 * oy_last] + bnd_v[2 * oy_last + 1]; }
+  y0 = min(max(y0, 0), in_h);
+  const int nrows = min(max(min(y1, in_h) - y0, 0), rows_cap);
+  if (ox < out_w) {
+    int first = ox, n = 1;
+    const float* k = coef_h;
+    if (bnd_h) {
+      first = min(max(bnd_h[2 * ox], 0), in_w);
+      n = min(bnd_h[2 * ox + 1], min(ksize_h, in_w - first));
+      k += (int64_t)ox * ksize_h;
+    }
+    const float* p = x + ((int64_t)plane * in_h + y0) * in_w + first;
+    for (int r = wy; r < nrows; r += 256 / RS_TW) {
+      const float* q = p + (int64_t)r * in_w;
+      float s;
+      if (bnd_h) {
+        s = 0.f;
+        for (int j = 0; j < n; ++j) s = fmaf(q[j], k[j], s);
+      } else {
+        s = q[0];
+      }
+      rs_tile[r * RS_TW + lx] = s;
+    }
+  }
+  __syncthreads();
+  if (ox >= out_w) return;
+  for (int oy = oy0 + wy; oy <= oy_last; oy += 256 / RS_TW) {
+    int r0 = oy - y0, n = 1;
+    const float* k = coef_v;
+    if (bnd_v) {
+      r0 = bnd_v[2 * oy] - y0;
+      n = min(bnd_v[2 * oy + 1], ksize_v);
+      k += (int64_t)oy * ksize_v;
+    }
+    if (r0 < 0) n = 0;
+    n = min(n, nrows - r0);
+    const float* t = rs_tile + r0 * RS_TW + lx;
+    float s;
+    if (bnd_v) {
+      s = 0.f;
+      for (int j = 0; j < n; ++j) s = fmaf(t[j * RS_TW], k[j], s);
+    } else {
+      s = n > 0 ? t[0] : 0.f;
+    }
+    if (clamp) s = fminf(fmaxf(s, lo), hi);
+    y[((int64_t)plane * out_h + oy) * out_w + ox] = s;
+  }
+}
+
+extern "C" int ppst_resample_f32(const void* x, void* y, int B, int in_h, int in_w, int out_h, int out_w, const void* bounds_h,
+                                 const void* coef_h, int ksize_h, const void* bounds_v, const void* coef_v, int ksize_v, int clamp,
+                                 float lo, float hi, void* stream) {
+  if (B < 0 || in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0) return PPST_EINVAL;
+  const bool copy_h = in_w == out_w, copy_v = in_h == out_h;
+  if ((!copy_h && ksize_h <= 0) || (!copy_v && ksize_v <= 0)) return PPST_EINVAL;
+  if (clamp && !(lo <= hi)) return PPST_EINVAL;
+  if ((int64_t)B * in_h * in_w > PPST_IDX32_MAX || (int64_t)B * out_h * out_w > PPST_IDX32_MAX) return PPST_EINVAL;
+  // rows under the vertical windows of RS_TH consecutive outputs: the window starts move by at most (RS_TH - 1) * in / out, the
+  // last window is at most ksize_v long
+  int64_t rows = (int64_t)(RS_TH - 1) * in_h / out_h + (copy_v ? 1 : ksize_v) + 1;
+  if (rows > in_h) rows = in_h;
+  if (rows > RS_ROWS_MAX) return PPST_EINVAL;
+  const int64_t tiles_x = cdiv64(out_w, RS_TW), tiles_y = cdiv64(out_h, RS_TH), blocks = (int64_t)B * tiles_x * tiles_y;
+  if (blocks > 0x7FFFFFFFll) return PPST_EINVAL;
+  if (B == 0) return PPST_OK;
+  if (!x || !y || (!copy_h && (!bounds_h || !coef_h)) || (!copy_v && (!bounds_v || !coef_v))) return PPST_ENULL;
+  PPST_LAUNCH(resample_f32_kernel, dim3((unsigned)blocks), dim3(256), (size_t)rows * RS_TW * sizeof(float), as_stream(stream),
+              (const float*)x, (float*)y, copy_h ? nullptr : (const int*)bounds_h, (const float*)coef_h, ksize_h,
+              copy_v ? nullptr : (const int*)bounds_v, (const float*)coef_v, ksize_v, in_h, in_w, out_h, out_w, (int)rows, clamp, lo, hi,
+              make_fastdiv((unsigned)tiles_x), make_fastdiv((unsigned)tiles_y));
+  return PPST_LAUNCH_CHECK();
+}

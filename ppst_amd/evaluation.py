@@ -10,6 +10,8 @@
        image) -- RCCL on the GPU, the only data-path collective of inference (SURVEY.md section 8e);
     3. per-PAIR passes (corrm, encode2, decode + guided filter), pair (i, j) on rank ((i * M + j) mod world), batched.
   An 8 x 8 grid on 8 ranks costs each rank 2 image passes + 8 pair passes (~5.9 TFLOP) against 16 + 64 on one GPU.
+Above 512 x 512 (square, side 1024 or 1536) both recipes compute the correspondence from a 512 x 512 resample of each image and apply
+it at full size (``simple_swap_full_size``; DESIGN.md "Swaps above 512^2"); the reference cannot run that.
 The recipes take and return tensors.  The folder-level front ends at the end of this file (``evaluate_swap_files``,
 ``evaluate_grid_folder``) add what the reference's evaluators do around them: decode (PIL, a thread pool), resize + normalise
 on the device (ppst_amd/imageio.py, Pillow-exact), the uint8 quantisation on the device (glue.tensor2im), PNG encode in the
@@ -21,8 +23,39 @@ import torch
 from . import glue
 
 
+def above_code_grid(*images):
+    """True when an image is larger than the 512 x 512 the 64 x 64 correspondence grid belongs to: the recipes then compute the
+    correspondence from ``model.correspondence_image`` and apply it at full size."""
+    from .ppst_model import CORR_SIDE
+    return any(max(int(t.shape[-2]), int(t.shape[-1])) > CORR_SIDE for t in images)
+
+
+def simple_swap_full_size(model, content, style, alphas=(1.0,)):
+    """``simple_swap`` above 512 x 512: spatial code, global codes and the decode at full size, the correspondence from the
+    512 x 512 resamples of both images (PPSTModel.correspondence_features); E2's warp pools every level of the full-size style
+    pass to the 64 x 64 grid, applies the matrix and resizes back."""
+    sp, gl_c = model(content, command="encode")
+    if content.shape == style.shape:
+        # both 512 x 512 passes as one batch: contents, then styles (bit-identical: nothing depends on the batch size)
+        B = content.shape[0]
+        small = torch.cat((model(content, command="correspondence_image"), model(style, command="correspondence_image")), 0)
+        fea = model(small, command="correspondence_features")
+        fea_c, fea_s = fea[:B], fea[B:]
+    else:
+        fea_c = model(content, command="correspondence_features")
+        fea_s = model(style, command="correspondence_features")
+    corr = model(fea_s, fea_c, command="corrm")
+    _, gl_w = model(style, corr, command="encode2")
+    out = {}
+    for alpha in alphas:
+        out[alpha] = model(sp, glue.lerp(gl_c, gl_w, alpha), target=None, command="decode")
+    return out
+
+
 def simple_swap(model, content, style, alphas=(1.0,)):
     """content, style: (B,3,H,W) in [-1,1] on the GPU.  Returns {alpha: image (B,3,H,W)}."""
+    if above_code_grid(content, style):
+        return simple_swap_full_size(model, content, style, alphas)
     if content.shape == style.shape:
         # the encoder passes of the recipe (encode(content) + the E1 / E2 inside the two extract_feat_from_image) as one batch of
         # 3B images, the two generator feature passes as one of 2B: the same work, bit-identical (nothing depends on the batch size)
@@ -70,11 +103,17 @@ def grid_image_pass(model, contents, styles, rank=0, world=1, image_batch=8):
     """Phase 1: the per-image passes of this rank's images, batched.  Returns
     (ci, sp (len(ci),256,h,w), fc (len(ci),512,h,w)), (si, fs (len(si),512,h,w)) -- NCHW-shaped like the commands return."""
     ci, si = shard_images(contents.shape[0], styles.shape[0], rank, world)
+    full_size = above_code_grid(contents, styles)
 
     def feats(imgs, want_sp):
         sps, fs = [], []
         for k in range(0, imgs.shape[0], image_batch):
             img = imgs[k:k + image_batch]
+            if full_size:       # sp on the image's own grid (a content only), the features from its 512 x 512 resample
+                fs.append(model(img, command="correspondence_features").contiguous())
+                if want_sp:
+                    sps.append(model.E1(img).contiguous())      # (encode would add an E2 pass nobody reads)
+                continue
             sp, gl = model(img, command="encode")
             f0, f1 = model(sp, gl, command="extract_feat")[1:]
             fs.append(torch.cat((f0, model(f1, command="Rselfcorr")), dim=1).contiguous())
@@ -159,7 +198,13 @@ def grid_pair_pass(model, contents, styles, table_c, table_s, rank=0, world=1, s
 
 def swapping_grid(model, contents, styles, rank=0, world=1, smooth=True, pair_batch=8, image_batch=8):
     """contents (N,3,H,W), styles (M,3,H,W) on this rank's GPU (every rank holds all images: they are small; the image
-    passes and the pair passes are sharded).  Returns {(i, j): image (3,H,W)} for the pairs this rank owns."""
+    passes and the pair passes are sharded).  Returns {(i, j): image (3,H,W)} for the pairs this rank owns.
+    Above 512 x 512 (one rank only): sp at full size, the features from PPSTModel.correspondence_features; the packed exchange
+    of several ranks assumes one grid for sp and the features, so every rank refuses from the shapes alone, before any collective."""
+    if world > 1 and above_code_grid(contents, styles):
+        raise ValueError("swapping_grid above 512 x 512 runs on one rank: the exchange packs the spatial code and the 64 x 64 "
+                         "correspondence features on one grid (got %s and %s on %d ranks)"
+                         % (tuple(contents.shape[2:]), tuple(styles.shape[2:]), world))
     local_c, local_s = grid_image_pass(model, contents, styles, rank, world, image_batch)
     table_c, table_s = grid_exchange(local_c, local_s, contents.shape[0], styles.shape[0], world,
                                      like=(contents.device, contents.shape[2] // 8, contents.shape[3] // 8))

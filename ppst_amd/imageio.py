@@ -31,19 +31,16 @@ def _bicubic(x):
     return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1, np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))
 
 
-def resample_tables(in_size, out_size, device):
-    """(ksize, bounds int32 [out][2], coef int32 [out][ksize]) on ``device`` for the bicubic filter."""
-    key = (in_size, out_size, str(device))
-    hit = _TABLES.get(key)
-    if hit is not None:
-        return hit
+def bicubic_windows(in_size, out_size):
+    """Pillow's precompute_coeffs for the bicubic filter, in float64: (ksize, bounds int32 [out][2] = (first, count),
+    weights float64 [out][ksize], each row normalised to sum 1 and zero behind its count)."""
     support = 2.0
     scale = in_size / out_size
     filterscale = max(scale, 1.0)
     sup = support * filterscale
     ksize = int(math.ceil(sup)) * 2 + 1
     bounds = np.zeros((out_size, 2), dtype=np.int32)
-    coef = np.zeros((out_size, ksize), dtype=np.int32)
+    weights = np.zeros((out_size, ksize), dtype=np.float64)
     ss = 1.0 / filterscale
     for xx in range(out_size):
         center = (xx + 0.5) * scale
@@ -55,12 +52,40 @@ def resample_tables(in_size, out_size, device):
             ww += float(v)
         if ww != 0.0:
             k = k / ww
-        fx = k * float(1 << PRECISION_BITS)
-        coef[xx, :xmax] = np.where(k < 0, np.trunc(-0.5 + fx), np.trunc(0.5 + fx)).astype(np.int64)
+        weights[xx, :xmax] = k
         bounds[xx] = (xmin, xmax)
+    return ksize, bounds, weights
+
+
+def resample_tables(in_size, out_size, device):
+    """(ksize, bounds int32 [out][2], coef int32 [out][ksize]) on ``device`` for the bicubic filter."""
+    key = (in_size, out_size, str(device))
+    hit = _TABLES.get(key)
+    if hit is not None:
+        return hit
+    ksize, bounds, k = bicubic_windows(in_size, out_size)
+    fx = k * float(1 << PRECISION_BITS)
+    coef = np.where(k < 0, np.trunc(-0.5 + fx), np.trunc(0.5 + fx)).astype(np.int64).astype(np.int32)
     out = (ksize, torch.from_numpy(bounds).to(device), torch.from_numpy(coef).to(device))
     _TABLES[key] = out
     return out
+
+
+def resample_weights_f32(in_size, out_size):
+    """The fp32 tables of ``resize_tensor`` on the host: (ksize, bounds int32 [out][2], coef float32 [out][ksize]) -- the
+    float64 weights of ``bicubic_windows`` rounded once."""
+    ksize, bounds, k = bicubic_windows(in_size, out_size)
+    return ksize, bounds, k.astype(np.float32)
+
+
+def resample_tables_f32(in_size, out_size, device):
+    """``resample_weights_f32`` on ``device``, cached per (in, out, device) like the integer tables."""
+    key = ("f32", in_size, out_size, str(device))
+    hit = _TABLES.get(key)
+    if hit is None:
+        ksize, bounds, coef = resample_weights_f32(in_size, out_size)
+        hit = _TABLES[key] = (ksize, torch.from_numpy(bounds).to(device), torch.from_numpy(coef).to(device))
+    return hit
 
 
 def resize_bicubic_u8(img, out_h, out_w):
@@ -81,6 +106,15 @@ def resize_bicubic_u8(img, out_h, out_w):
         check(lib.ppst_resample_u8(ops._p(x), ops._p(y), B, H, x.shape[2], C, out_h, 0, ops._p(bnd), ops._p(cf), ks, ops._stream()), "ppst_resample_u8")
         x = y
     return x
+
+
+def resize_tensor(x, out_h, out_w, clamp=None):
+    """x (B,C,H,W) float32 CUDA -> (B,C,out_h,out_w): the antialiased bicubic of ``resize_bicubic_u8`` (Pillow's filter) in
+    fp32, both axes in one launch (csrc/imageio.hip resample_f32_kernel).  ``clamp`` = (lo, hi) clips the result: a bicubic
+    overshoots the range of its input."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError("resize_tensor needs a CUDA float32 (B,C,H,W) tensor (no CPU fallback)")
+    return ops.resample_f32(x, out_h, out_w, clamp)
 
 
 def to_tensor_normalized(img, mean=0.5, std=0.5):

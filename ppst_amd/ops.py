@@ -1775,6 +1775,27 @@ def png_encode(u8):
     return files, sizes
 
 
+def resample_f32(x, out_h, out_w, clamp=None):
+    """x (..., H, W) float32 on the device -> (..., out_h, out_w): Pillow's antialiased bicubic on every plane, both axes in one
+    launch (ppst_resample_f32; the fp32 weight tables are imageio.resample_tables_f32).  ``clamp`` = (lo, hi) or None."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() < 2:
+        raise RuntimeError("resample_f32 needs a CUDA float32 (..., H, W) tensor (no CPU fallback)")
+    from . import imageio
+    out_h, out_w = int(out_h), int(out_w)
+    if out_h <= 0 or out_w <= 0:
+        raise ValueError("resample_f32: output size must be positive, got %d x %d" % (out_h, out_w))
+    x = x.contiguous()
+    H, W = x.shape[-2:]
+    planes = x.numel() // (H * W) if H * W else 0
+    kh, bh, ch = imageio.resample_tables_f32(W, out_w, x.device) if W != out_w else (1, None, None)
+    kv, bv, cv = imageio.resample_tables_f32(H, out_h, x.device) if H != out_h else (1, None, None)
+    lo, hi = (float(clamp[0]), float(clamp[1])) if clamp is not None else (0.0, 0.0)
+    y = torch.empty(tuple(x.shape[:-2]) + (out_h, out_w), device=x.device, dtype=torch.float32)
+    check(lib.ppst_resample_f32(_p(x), _p(y), planes, H, W, out_h, out_w, _p(bh), _p(ch), kh, _p(bv), _p(cv), kv,
+                                int(clamp is not None), lo, hi, _stream()), "ppst_resample_f32")
+    return y
+
+
 # ------------------------------------------------------- LPIPS-AlexNet metric ----
 LPIPS_CHANNELS = (64, 192, 384, 256, 256)
 

@@ -29,6 +29,23 @@ class Options:
         self.__dict__.update(d)
 
 
+# The correspondence (extract_feat -> Rselfcorr -> corrm -> E2.warp) lives on the reference's 64 x 64 code grid = a 512 x 512
+# image.  Larger swaps compute it from a 512 x 512 resample of the image and apply it at full size (DESIGN.md "Swaps above
+# 512^2").  The upper bound is derived: the conv entry addresses one input image with 32-bit byte offsets and the widest
+# full-resolution activation has 128 fp32 channels, so side^2 * 512 B < 2^31: side < 2048.
+CORR_SIDE = 512
+CORR_MAX_SIDE = 1536
+
+
+def correspondence_side(h, w):
+    """The size rule of ``PPSTModel.correspondence_image`` from shapes alone: CORR_SIDE for an accepted (h, w), else ValueError."""
+    if h != w or h % CORR_SIDE != 0 or not CORR_SIDE <= h <= CORR_MAX_SIDE:
+        raise ValueError("the correspondence is computed at %d x %d: images must be square with a side that is a multiple of %d "
+                         "and at most %d (one image's widest activation must stay below 2^31 bytes), got %d x %d"
+                         % (CORR_SIDE, CORR_SIDE, CORR_SIDE, CORR_MAX_SIDE, h, w))
+    return CORR_SIDE
+
+
 class RsclQueues(nn.Module):
     """State + forward of rsclLoss (networks/rscl.py:17-90): four (2048, 128) key queues with their write pointers
     (checkpoint keys ``criterionNCE.queue_data_A{i}`` / ``queue_ptr_A{i}``)."""
@@ -238,6 +255,21 @@ class PPSTModel(nn.Module):
         gl = self.E2(img)[0]
         _, fea, fea1 = self.G(sp, gl, extract_features=True, noise=self.noise, want_rgb=not self.skip_unused_rgb)
         return fea, fea1
+
+    def correspondence_image(self, img):
+        """The image the correspondence features are computed from: ``img`` itself (the same object) at 512 x 512; for a larger
+        square image whose side is a multiple of 512 (``correspondence_side``) its antialiased bicubic resample to 512 x 512,
+        clipped to the image range [-1, 1] like an 8-bit resize; ValueError otherwise."""
+        side = correspondence_side(int(img.shape[-2]), int(img.shape[-1]))
+        if img.shape[-1] == side:
+            return img
+        from . import imageio
+        return imageio.resize_tensor(img, side, side, clamp=(-1.0, 1.0))
+
+    def correspondence_features(self, img):
+        """(B,3,H,W) -> (B,512,64,64): cat(fea, Rselfcorr(fea1)) of ``correspondence_image(img)``, the operand of ``corrm``."""
+        fea, fea1 = self.extract_feat_from_image(self.correspondence_image(img))
+        return torch.cat((fea, self.Rselfcorr(fea1)), dim=1)
 
     def Rselfcorr(self, fea):
         """(B,64,256,256) -> (B,256,64,64) (ppst_model.py:330-339)."""
