@@ -637,12 +637,15 @@ int ppst_lpips_backward(const void* pack, const void* ws, const void* gout, int 
 int ppst_tensor2im_u8(const void* x, void* y, int B, int C, int H, int W, void* stream);
 /* colour-guided filter (photo_gif.py:43 cv2.ximgproc.guidedFilter): guide, src
  * uint8 HWC [B][H][W][3]; out fp32 NCHW = (q/255 - 0.5)*2 as
- * PPSTModel.decode does (ppst_model.py:296-305).  work: >= ppst_guided_filter_ws() bytes. */
+ * PPSTModel.decode does (ppst_model.py:296-305).  work: >= ppst_guided_filter_ws() bytes.
+ * r = 30, 60 and 90 (the radius of 512^2 images and its multiples for 1024^2 and 1536^2) run as two fused launches; every other
+ * r <= 64 runs five launches through fp32 planes in the workspace.  PPST_EINVAL, with nothing written: any other r > 64, r <= 0,
+ * r >= H, r >= W, W > 2048. */
 int64_t ppst_guided_filter_ws(int B, int H, int W);
 int ppst_guided_filter(const void* guide_u8, const void* src_u8, void* out, void* out_u8,
                        int B, int H, int W, int r, float eps, void* work, void* stream);
-/* tuning aid (process-wide, diagnostic like ppst_prof_enable): rows per block of the two fused launches of the radius-30 filter;
- * 0 = the library's rule, 32 / 64 (/ 128 for the second) = forced.  Results do not depend on it beyond the rounding of the sliding
+/* tuning aid (process-wide, diagnostic like ppst_prof_enable): rows per block of the two fused launches, for all three fused radii;
+ * 0 = the library's default for that radius, 32 / 64 / 128 = forced.  Results do not depend on it beyond the rounding of the sliding
  * fp32 sums of the second launch. */
 int ppst_guided_filter_tune(int vs1, int vs2);
 

@@ -7,10 +7,11 @@
 // OpenCV itself; pinned against oracle/ppst_oracle.py:guided_filter_color.
 //
 // Two pipelines, chosen by the radius (ppst_guided_filter at the end of the file):
-//   r == 30 (the path's radius, photo_gif.py:43): TWO fused launches that keep every box sum on the chip --
+//   r == 30 (the path's radius, photo_gif.py:43), r == 60 and r == 90 (30 * side / 512 for 1024^2 and 1536^2 images,
+//     ppst_model.guided_filter_radius): TWO fused launches that keep every box sum on the chip --
 //     gf_s1_fused (uint8 -> exact uint32 moment sums -> 3x3 solve -> 12 half planes (a, b)), gf_s2_fused (means of (a, b),
-//     q = sum a_k I_k + b, round; uint8 + fp32 NCHW (q/255-0.5)*2).  Described at the kernels.
-//   every other radius: FIVE launches of separable direct sums (no running sums: order-independent fp32 error) over
+//     q = sum a_k I_k + b, round; uint8 + fp32 NCHW (q/255-0.5)*2).  Described at the kernels; each radius has its own strip geometry.
+//   every other radius up to GF_MAXR: FIVE launches of separable direct sums (no running sums: order-independent fp32 error) over
 //     [B][plane][H][W] fp32 planes in the caller's workspace --
 //     gf_h<true>  (uint8 -> 21 h-sums: I(3), p(3), I_i*I_j(6), I_i*p_c(9); one block per image row, row staged in LDS, reflected)
 //     gf_v        (21 means; lanes along x (coalesced), 2r+1 row reads per output served by L1/L2)
@@ -181,31 +182,46 @@ __global__ __launch_bounds__(256) void gf_v_final_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// The radius-30 filter in TWO launches that keep every box sum on the chip (round 5; round-4 verdict: 439 B / pixel of HBM traffic
-// by counter against 9 B / pixel algorithmic -- the three-launch form handed 21 + 12 fp32 planes through HBM and re-read them).
-// The windows SLIDE: after a first direct sum of 2 RR + 1 = 61 values the next window adds the entering and subtracts the leaving one.
-//   * the 21 moment planes of stage 1 are INTEGERS: row and column sums run in uint32 (< 2^28) -- exact whatever the order, and the
+// The filter at the radii RR = 30, 60 and 90 in TWO launches that keep every box sum on the chip (round 5; round-4 verdict: 439 B /
+// pixel of HBM traffic by counter against 9 B / pixel algorithmic -- the three-launch form handed 21 + 12 fp32 planes through HBM and
+// re-read them).  The kernels are templates on RR; the strip geometry of each radius is GfGeom<RR> below (figures in this comment are
+// radius 30's where they name one).
+// The windows SLIDE: after a first direct sum of 2 RR + 1 values the next window adds the entering and subtracts the leaving one.
+//   * the 21 moment planes of stage 1 are INTEGERS: row and column sums run in uint32 -- a window sum is at most 255^2 (2 RR + 1)^2
+//     (< 2^28 at RR = 30, 2.13e9 < 2^32 at RR = 90; exact up to RR = 127, which the kernel asserts) -- exact whatever the order, and the
 //     mean is formed from the exact sum (the direct fp32 sums of the generic path, and of the oracle, carry ~1e-7 relative rounding there);
-//   * the (a, b) planes of stage 2 are floats: a horizontal window slides over at most GF_SEG - 1 = 15 steps before the next thread
-//     starts from a direct sum again, a vertical one over at most VS - 1 rows: the drift is bounded by that many roundings of a sum
-//     of 61 terms.
-// Bar: <= 1 uint8 LSB against the oracle (tests/gpu_diag.py:t_guided).
-//   gf_s1_fused_kernel: a block owns GS_WC = 192 output columns (+ RR on both sides = 252 of its 256 threads) and VS rows.  Thread =
-//     column: its 21 vertical window sums live in REGISTERS and slide down the rows (the entering / leaving row's moments formed from
-//     the 6 uint8 bytes of the pixel, exact uint32); per row the 252 column sums go to LDS, 21 x 12 threads slide the horizontal
-//     window over 16-output segments (exact uint32), the window sums go back to LDS and thread = pixel solves its 3x3 system.
-//     Only (a, b) leave the kernel -- as 12 IEEE-half planes (24 B / pixel; they feed a 61 x 61 mean): each thread carries the
+//   * the (a, b) planes of stage 2 are floats: a horizontal window slides over at most SEG - 1 = 15 steps (every geometry below has
+//     SEG = 16) before the next thread starts from a direct sum again, a vertical one over at most VS - 1 rows: the drift is bounded
+//     by that many roundings of a sum of 2 RR + 1 terms.
+// Bar: <= 1 uint8 LSB against the oracle (tests/gpu_diag.py:t_guided); against float64: tests/test_gpu_guided_filter*.py.
+//   gf_s1_fused_kernel: a block owns WC output columns (+ RR on both sides: 192 + 60 = 252 of its 256 threads at RR = 30) and VS rows.
+//     Thread = column: its 21 vertical window sums live in REGISTERS and slide down the rows (the entering / leaving row's moments formed
+//     from the 6 uint8 bytes of the pixel, exact uint32); per row the column sums go to LDS, 21 x WC / SEG threads slide the horizontal
+//     window over SEG-output segments (exact uint32), the window sums go back to LDS and thread = pixel solves its 3x3 system.
+//     Only (a, b) leave the kernel -- as 12 IEEE-half planes (24 B / pixel; they feed a (2 RR + 1)^2 mean): each thread carries the
 //     rounding residual of every value down its column (error diffusion), so a vertical window sum of the stored halves differs from
-//     the fp32 sum by at most the two end residuals -- not 61 correlated roundings (a flat image region rounds every b alike).
+//     the fp32 sum by at most the two end residuals of every run of VS rows it spans -- not 2 RR + 1 correlated roundings (a flat
+//     image region rounds every b alike).
 //   gf_s2_fused_kernel: the same structure over the 12 half planes (fp32 sums, sliding with the bounded drift above), ending in
 //     q = mean(a) . I + mean(b), rounded to uint8 like cv2 (saturate_cast<uchar>(cvRound)).
-// HBM traffic per pixel: 6 B x halo factors in, 24 out; 24 x (1.31 columns x (VS2 + 60) / VS2 rows) in, 3 guide, 12 (+ 3) out.
-#define GF_SEG 16
+// Borders: reflect_idx reflects ONCE, which is enough because the entry point requires r < H and r < W, for every radius.
+// Half overflow of b at small eps applies to RR = 60 and 90 exactly as to RR = 30: the stored half of a |b| > 65504 is
+// infinite.  The clamp is not part of these kernels at any radius.
+// HBM traffic per pixel: 6 B x halo factors in, 24 out; 24 x ((WC + 2 RR) / WC columns x (VS2 + 2 RR) / VS2 rows) in, 3 guide,
+// 12 (+ 3) out -- at RR = 30: 1.31 columns x (VS2 + 60) / VS2 rows.
+// Strip geometry per radius: NT threads per block (= columns a block reads: WC outputs + RR on both sides, the rest idle), WC
+// output columns per strip, SEG outputs per sliding segment.  WC + 2 RR <= NT, WC a multiple of SEG, one horizontal item per
+// (plane, segment) and thread: 21 WC / SEG <= NT.  UNR: unroll count of a segment's first direct sum, 0 = the compiler's choice.
+// Radius 30 keeps the compiler's choice (it unrolls all 61 reads; 168 VGPRs, three blocks of 256 per CU); left alone at RR = 60 it
+// unrolls all 121 and needs 219 / 223 VGPRs -- two waves per SIMD, ONE block of 384 per CU -- where UNR = 16 needs 145 / 100.
+// (How each geometry was chosen: the table at ppst_guided_filter.)
+template <int RR> struct GfGeom;
+template <> struct GfGeom<30> { static constexpr int NT = 256, WC = 192, SEG = 16, UNR = 0; };
+template <> struct GfGeom<60> { static constexpr int NT = 384, WC = 256, SEG = 16, UNR = 16; };
+template <> struct GfGeom<90> { static constexpr int NT = 512, WC = 320, SEG = 16, UNR = 16; };
 // LDS row index with one pad slot per 16 entries: lanes are 16 entries apart (one segment each) -- unpadded, all of a wave's
 // reads fall on two banks
 #define GF_ROW(i) ((i) + ((i) >> 4))
-#define GS_WC 192
-#define GS_NSEG (GS_WC / GF_SEG)
 
 // The horizontal pass of both fused kernels, stated once: thread (plane ipl, segment iseg) forms the window sums of the GF_SEG outputs
 // j0 .. j0 + 15 of its plane over the padded LDS rows col[ipl] -> win[ipl] (output j covers entries j .. j + 2 RR): the first is a
@@ -214,25 +230,31 @@ __global__ __launch_bounds__(256) void gf_v_final_kernel(const float* __restrict
 // (A macro, not a force-inlined function template: with hipcc 7.x such a function -- taking pointers, the LDS arrays by reference,
 //  or (col, win, ipl, iseg) -- compiles gf_s1_fused_kernel to 172 and gf_s2_fused_kernel to 170 VGPRs against 168, which costs the
 //  third resident block per CU; as text both kernels compile to the streams they had.)
-#define GF_SLIDE_SEGMENT(T, RR, col, win, ipl, iseg)                                   \
+#define GF_SLIDE_SEGMENT(T, RR, SEG, col, win, ipl, iseg)                              \
   do {                                                                                 \
     const T* r = col[ipl];                                                             \
     T* wv = win[ipl];                                                                  \
-    const int j0 = (iseg) * GF_SEG;                                                    \
+    const int j0 = (iseg) * SEG;                                                       \
     T sum = 0;                                                                         \
-    for (int k = 0; k <= 2 * RR; ++k) sum += r[GF_ROW(j0 + k)];                        \
+    if constexpr (GfGeom<RR>::UNR == 0) {                                              \
+      for (int k = 0; k <= 2 * RR; ++k) sum += r[GF_ROW(j0 + k)];                      \
+    } else {                                                                           \
+      _Pragma("unroll (GfGeom<RR>::UNR)") for (int k = 0; k <= 2 * RR; ++k) sum += r[GF_ROW(j0 + k)]; \
+    }                                                                                  \
     wv[GF_ROW(j0)] = sum;                                                              \
-    _Pragma("unroll") for (int j = 1; j < GF_SEG; ++j) {                               \
+    _Pragma("unroll") for (int j = 1; j < SEG; ++j) {                                  \
       sum += r[GF_ROW(j0 + j + 2 * RR)] - r[GF_ROW(j0 + j - 1)];                       \
       wv[GF_ROW(j0 + j)] = sum;                                                        \
     }                                                                                  \
   } while (0)
 
 template <int RR, int VS>
-__global__ __launch_bounds__(256) void gf_s1_fused_kernel(const unsigned char* __restrict__ guide, const unsigned char* __restrict__ src,
+__global__ __launch_bounds__(GfGeom<RR>::NT) void gf_s1_fused_kernel(const unsigned char* __restrict__ guide, const unsigned char* __restrict__ src,
                                                           unsigned short* __restrict__ ab, int H, int W, float eps) {
-  static_assert(GS_WC + 2 * RR <= 256 && GS_WC % GF_SEG == 0 && 21 * GS_NSEG <= 256, "strip geometry");
-  __shared__ unsigned col[21][GF_ROW(256) + 1];
+  constexpr int GS_NT = GfGeom<RR>::NT, GS_WC = GfGeom<RR>::WC, GF_SEG = GfGeom<RR>::SEG, GS_NSEG = GS_WC / GF_SEG;
+  static_assert(GS_WC + 2 * RR <= GS_NT && GS_WC % GF_SEG == 0 && 21 * GS_NSEG <= GS_NT, "strip geometry");
+  static_assert(RR <= 127, "a uint32 window sum holds 255^2 (2 RR + 1)^2 up to RR = 127");
+  __shared__ unsigned col[21][GF_ROW(GS_NT) + 1];
   __shared__ unsigned win[21][GF_ROW(GS_WC) + 1];
   const int t = threadIdx.x, x0 = blockIdx.x * GS_WC, y0 = blockIdx.y * VS, b = blockIdx.z;
   const int64_t P = (int64_t)H * W;
@@ -271,7 +293,7 @@ __global__ __launch_bounds__(256) void gf_s1_fused_kernel(const unsigned char* _
 #pragma unroll
     for (int pl = 0; pl < 21; ++pl) col[pl][GF_ROW(t)] = cs[pl];
     __syncthreads();
-    if (iseg < GS_NSEG) GF_SLIDE_SEGMENT(unsigned, RR, col, win, ipl, iseg);
+    if (iseg < GS_NSEG) GF_SLIDE_SEGMENT(unsigned, RR, GF_SEG, col, win, ipl, iseg);
     __syncthreads();
     if (pix_ok) {
       float m[21];
@@ -305,9 +327,11 @@ __global__ __launch_bounds__(256) void gf_s1_fused_kernel(const unsigned char* _
 }
 
 template <int RR, int VS>
-__global__ __launch_bounds__(256) void gf_s2_fused_kernel(const unsigned short* __restrict__ ab, const unsigned char* __restrict__ guide,
+__global__ __launch_bounds__(GfGeom<RR>::NT) void gf_s2_fused_kernel(const unsigned short* __restrict__ ab, const unsigned char* __restrict__ guide,
                                                           float* __restrict__ out, unsigned char* __restrict__ out_u8, int H, int W) {
-  __shared__ float col[12][GF_ROW(256) + 1];
+  constexpr int GS_NT = GfGeom<RR>::NT, GS_WC = GfGeom<RR>::WC, GF_SEG = GfGeom<RR>::SEG, GS_NSEG = GS_WC / GF_SEG;
+  static_assert(GS_WC + 2 * RR <= GS_NT && GS_WC % GF_SEG == 0 && 12 * GS_NSEG <= GS_NT, "strip geometry");
+  __shared__ float col[12][GF_ROW(GS_NT) + 1];
   __shared__ float win[12][GF_ROW(GS_WC) + 1];
   const int t = threadIdx.x, x0 = blockIdx.x * GS_WC, y0 = blockIdx.y * VS, b = blockIdx.z;
   const int64_t P = (int64_t)H * W;
@@ -336,7 +360,7 @@ __global__ __launch_bounds__(256) void gf_s2_fused_kernel(const unsigned short* 
 #pragma unroll
     for (int i = 0; i < 12; ++i) col[i][GF_ROW(t)] = s[i];
     __syncthreads();
-    if (iseg < GS_NSEG) GF_SLIDE_SEGMENT(float, RR, col, win, ipl, iseg);
+    if (iseg < GS_NSEG) GF_SLIDE_SEGMENT(float, RR, GF_SEG, col, win, ipl, iseg);
     __syncthreads();
     if (pix_ok) {
       const int x = x0 + t;
@@ -357,24 +381,44 @@ __global__ __launch_bounds__(256) void gf_s2_fused_kernel(const unsigned short* 
 }
 
 // one launch of each fused kernel with VS rows per block
-template <int VS>
+template <int RR, int VS>
 static void gf_s1_launch(hipStream_t st, const unsigned char* g, const unsigned char* s, unsigned short* abh, int B, int H, int W, float eps) {
-  PPST_LAUNCH((gf_s1_fused_kernel<30, VS>), dim3(cdiv(W, GS_WC), cdiv(H, VS), B), dim3(256), 0, st, g, s, abh, H, W, eps);
+  PPST_LAUNCH((gf_s1_fused_kernel<RR, VS>), dim3(cdiv(W, GfGeom<RR>::WC), cdiv(H, VS), B), dim3(GfGeom<RR>::NT), 0, st, g, s, abh, H, W, eps);
 }
-template <int VS>
+template <int RR, int VS>
 static void gf_s2_launch(hipStream_t st, const unsigned short* abh, const unsigned char* g, void* out, void* out_u8, int B, int H, int W) {
-  PPST_LAUNCH((gf_s2_fused_kernel<30, VS>), dim3(cdiv(W, GS_WC), cdiv(H, VS), B), dim3(256), 0, st, abh, g, (float*)out, (unsigned char*)out_u8, H, W);
+  PPST_LAUNCH((gf_s2_fused_kernel<RR, VS>), dim3(cdiv(W, GfGeom<RR>::WC), cdiv(H, VS), B), dim3(GfGeom<RR>::NT), 0, st, abh, g, (float*)out, (unsigned char*)out_u8, H, W);
 }
 
-static int g_gf_vs1 = 0, g_gf_vs2 = 0;      // tuning aid: rows per block of the two fused launches (0 = the rule below; 32 / 64 / 128 = forced)
+// tuning aid: rows per block of the two fused launches, for all three fused radii (0 = the default of that radius, from the table
+// below; 32 / 64 / 128 = forced).  Process-wide; after (0, 0) the defaults reproduce their bytes.
+static int g_gf_vs1 = 0, g_gf_vs2 = 0;
 extern "C" int ppst_guided_filter_tune(int vs1, int vs2) { g_gf_vs1 = vs1; g_gf_vs2 = vs2; return PPST_OK; }
 
-// (42 planes: the generic radius hands 21 + 21 fp32 planes through the workspace; the radius-30 path uses 12 half planes of it)
+// (42 planes: the generic radius hands 21 + 21 fp32 planes through the workspace; the fused radii use 12 half planes of it)
 extern "C" int64_t ppst_guided_filter_ws(int B, int H, int W) { return (int64_t)B * 42 * H * W * (int64_t)sizeof(float); }
+
+// the two fused launches of radius RR; DVS1 / DVS2 are that radius's default rows per block
+template <int RR, int DVS1, int DVS2>
+static int gf_fused(hipStream_t st, const unsigned char* g, const unsigned char* s, unsigned short* abh, void* out, void* out_u8, int B, int H,
+                    int W, float eps) {
+  int e;
+  const int vs1 = g_gf_vs1 ? g_gf_vs1 : DVS1;
+  if (vs1 == 32) gf_s1_launch<RR, 32>(st, g, s, abh, B, H, W, eps);
+  else if (vs1 == 128) gf_s1_launch<RR, 128>(st, g, s, abh, B, H, W, eps);
+  else gf_s1_launch<RR, 64>(st, g, s, abh, B, H, W, eps);
+  if ((e = PPST_LAUNCH_CHECK())) return e;
+  const int vs2 = g_gf_vs2 ? g_gf_vs2 : DVS2;
+  if (vs2 == 128) gf_s2_launch<RR, 128>(st, abh, g, out, out_u8, B, H, W);
+  else if (vs2 == 32) gf_s2_launch<RR, 32>(st, abh, g, out, out_u8, B, H, W);
+  else gf_s2_launch<RR, 64>(st, abh, g, out, out_u8, B, H, W);
+  return PPST_LAUNCH_CHECK();
+}
 
 extern "C" int ppst_guided_filter(const void* guide_u8, const void* src_u8, void* out, void* out_u8, int B, int H, int W, int r,
                                   float eps, void* work, void* stream) {
-  if (B < 0 || H <= 0 || W <= 0 || W > GF_MAXW || r <= 0 || r > GF_MAXR || r >= H || r >= W) return PPST_EINVAL;
+  // (r == 90 is the one radius above GF_MAXR: it has a fused form and never reaches the generic kernels, whose LDS row is GF_MAXR wide)
+  if (B < 0 || H <= 0 || W <= 0 || W > GF_MAXW || r <= 0 || (r > GF_MAXR && r != 90) || r >= H || r >= W) return PPST_EINVAL;
   if (B == 0) return PPST_OK;
   if (!guide_u8 || !src_u8 || !work || (!out && !out_u8)) return PPST_ENULL;
   hipStream_t st = as_stream(stream);
@@ -382,21 +426,35 @@ extern "C" int ppst_guided_filter(const void* guide_u8, const void* src_u8, void
   const unsigned char* g = (const unsigned char*)guide_u8;
   const unsigned char* s = (const unsigned char*)src_u8;
   int e;
-  if (r == 30) {       // the path's radius (photo_gif.py:43): two fused launches, box sums kept on the chip
-    unsigned short* abh = (unsigned short*)work;            // [B][12][P] IEEE half
-    // rows per block: 32 in the first launch (its halo re-reads are uint8 rows: 6 B / pixel each), 64 in the second (24 B / pixel each).
-    // Measured, batch of four 1024^2 images (tests/gf_prof.sh): (64, 64) 0.36 ms, (32, 64) 0.33 ms, (32, 32) 0.30 ms with 1.25x the traffic,
-    // (64, 128) 0.44 ms -- three co-resident blocks per CU (768 blocks) are what hides the per-row latency.
-    const int vs1 = g_gf_vs1 ? g_gf_vs1 : 32;
-    if (vs1 == 32) gf_s1_launch<32>(st, g, s, abh, B, H, W, eps);
-    else gf_s1_launch<64>(st, g, s, abh, B, H, W, eps);
-    if ((e = PPST_LAUNCH_CHECK())) return e;
-    const int vs2 = g_gf_vs2 ? g_gf_vs2 : 64;
-    if (vs2 == 128) gf_s2_launch<128>(st, abh, g, out, out_u8, B, H, W);
-    else if (vs2 == 32) gf_s2_launch<32>(st, abh, g, out, out_u8, B, H, W);
-    else gf_s2_launch<64>(st, abh, g, out, out_u8, B, H, W);
-    return PPST_LAUNCH_CHECK();
-  }
+  // The fused radii: 30 (the path's radius at 512^2, photo_gif.py:43) and its multiples for 1024^2 and 1536^2 images
+  // (ppst_model.guided_filter_radius): two fused launches, box sums kept on the chip.  abh = [B][12][P] IEEE half.
+  // r == 30, rows per block: 32 in the first launch (its halo re-reads are uint8 rows: 6 B / pixel each), 64 in the second (24 B / pixel each).
+  // Measured, batch of four 1024^2 images (tests/gf_prof.sh): (64, 64) 0.36 ms, (32, 64) 0.33 ms, (32, 32) 0.30 ms with 1.25x the traffic,
+  // (64, 128) 0.44 ms -- three co-resident blocks per CU (768 blocks) are what hides the per-row latency.
+  // r == 60 and r == 90, geometry and rows per block.  Measured on one MI355X (tests/gf_radius_time.py, ms per call, median of five
+  // groups of ten calls, groups within 1 %); (NT, WC, SEG, UNR): resident blocks per CU by registers and LDS (first, second launch):
+  // best rows per block -- also (32, 64) / (64, 64):
+  //   r = 60, four 1024^2 images (the five-launch generic path of this radius: 8.00 ms)
+  //     (256, 128, 16, 16): 3, 4 blocks:  0.56 at (32, 64) -- 0.56 / 0.56
+  //     (384, 256, 16, 16): 2, 2 blocks:  0.54 at (32, 32) -- 0.61 / 0.58                      <- adopted, with (32, 32)
+  //     (384, 256, 16,  8): 2, 2 blocks:  0.56 at (32, 32) -- 0.65 / 0.62
+  //     (384, 256, 32,  8): 2, 2 blocks:  0.52 at (32, 32) -- 0.62 / 0.58
+  //     (512, 384, 16, 16): 1, 2 blocks:  0.61 at (32, 32) -- 0.68 / 0.64   (three strips for 1024 columns: a quarter of them idle)
+  //     (768, 640, 32, 16): 1, 1 block:   0.45 at (32, 32) -- 0.56 / 0.75   (100 B / lane of scratch in the first launch)
+  //   r = 90, four 1536^2 images (the parent refuses this radius)
+  //     (256,  64, 16, 16): 3, 4 blocks:  2.79 at (64, 64) -- 2.96 / 2.79
+  //     (384, 192, 16, 16): 2, 2 blocks:  1.53 at (64, 128) -- 1.79 / 1.63
+  //     (384, 192, 16,  8): 2, 2 blocks:  1.80 at (64, 128) -- 2.02 / 1.87
+  //     (384, 192, 32,  8): 2, 2 blocks:  1.95 at (64, 128) -- 2.13 / 1.97
+  //     (512, 320, 16, 16): 1, 2 blocks:  1.39 at (64, 64) -- 1.51 / 1.39                      <- adopted, with (64, 64)
+  //     (768, 576, 32, 16): 1, 1 block:   1.78 at (32, 32) -- 1.82 / 1.97   (100 B / lane of scratch in the first launch)
+  // Not adopted at r = 60 although fastest at that batch: 768 threads.  Its 0.45 ms is the case of 2 strips x 32 row blocks x 4 images
+  // = 256 blocks on 256 CUs, one resident block each; a single 1024^2 image (what a swap decodes) is 64 such blocks on a quarter of
+  // the chip and takes 0.44 ms, where 384 threads give 128 blocks of half the waves and 0.33 ms; and its first launch spills.  The longer segment (SEG = 32: 7.6
+  // LDS reads per output and plane at r = 90 in place of 13) did not pay for the threads it idles during the horizontal pass.
+  if (r == 30) return gf_fused<30, 32, 64>(st, g, s, (unsigned short*)work, out, out_u8, B, H, W, eps);
+  if (r == 60) return gf_fused<60, 32, 32>(st, g, s, (unsigned short*)work, out, out_u8, B, H, W, eps);
+  if (r == 90) return gf_fused<90, 64, 64>(st, g, s, (unsigned short*)work, out, out_u8, B, H, W, eps);
   float* bufA = (float*)work;              // [B][21][P]
   float* bufB = bufA + (int64_t)B * 21 * P;  // [B][21][P]
   auto blocks_for = [](int64_t total) { int64_t b = cdiv64(total, 256); return (unsigned)(b > 256 * 32 ? 256 * 32 : b); };

@@ -200,7 +200,9 @@ def swapping_grid(model, contents, styles, rank=0, world=1, smooth=True, pair_ba
     """contents (N,3,H,W), styles (M,3,H,W) on this rank's GPU (every rank holds all images: they are small; the image
     passes and the pair passes are sharded).  Returns {(i, j): image (3,H,W)} for the pairs this rank owns.
     Above 512 x 512 (one rank only): sp at full size, the features from PPSTModel.correspondence_features; the packed exchange
-    of several ranks assumes one grid for sp and the features, so every rank refuses from the shapes alone, before any collective."""
+    of several ranks assumes one grid for sp and the features, so every rank refuses from the shapes alone, before any collective.
+    ``smooth``: the guided-filter post-process of PPSTModel.decode, with the radius of the model's option (Options.gf_radius: 30, or
+    "scaled" = 30 * side // 512); there is no parameter for it here."""
     if world > 1 and above_code_grid(contents, styles):
         raise ValueError("swapping_grid above 512 x 512 runs on one rank: the exchange packs the spatial code and the 64 x 64 "
                          "correspondence features on one grid (got %s and %s on %d ranks)"
@@ -295,7 +297,8 @@ def evaluate_swap_files(model, structure_path, texture_path, out_dir, alphas=(1.
 def evaluate_grid_folder(model, dataroot, out_dir, rank=0, world=1, smooth=True, load_size=512, device="cuda", workers=8,
                          pair_batch=8, image_batch=8, png="host"):
     """evaluation/content_style_grid_generation_evaluator.py:36-99 over <dataroot>/content/* and <dataroot>/style/*: every
-    (content, style) pair, guided-filter post-process with the content as guide; files land in <out_dir>/images/ under the
+    (content, style) pair, guided-filter post-process with the content as guide (radius: the model's Options.gf_radius -- decode
+    reads it, this function has no parameter for it); files land in <out_dir>/images/ under the
     reference's names (<content>_<style>.png, the inputs as <name>.png; util/html.py:51-75 -- the HTML index itself is not
     written).  All images must come out of the preprocessing at one size (the reference batches them the same way).
     Multi-GPU: every rank reads all inputs (they are small), computes its share (swapping_grid) and writes its own files.

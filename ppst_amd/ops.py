@@ -1741,7 +1741,9 @@ def tensor2im_u8(x):
 
 
 def guided_filter(guide_u8, src_u8, r=30, eps=(0.02 * 255) ** 2, want_u8=False):
-    """guide/src (B,H,W,3) uint8 -> fp32 NCHW in [-1,1] (and the uint8 HWC result)."""
+    """guide/src (B,H,W,3) uint8 -> fp32 NCHW in [-1,1] (and the uint8 HWC result).  r = 30, 60 and 90 run as two fused
+    launches (the radii of 512^2, 1024^2 and 1536^2 images, ppst_model.guided_filter_radius); every other r <= 64 runs the
+    five-launch generic path; any other r, r >= H, r >= W and W > 2048 are refused."""
     for t in (guide_u8, src_u8):
         if not t.is_cuda or t.dtype != torch.uint8:
             raise RuntimeError("guided_filter needs CUDA uint8 tensors")

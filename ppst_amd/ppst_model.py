@@ -17,14 +17,16 @@ from .networks.base_network import as_nchw, to_nhwc
 
 
 class Options:
-    """The flags that shape the hot path with the reference's defaults."""
+    """The flags that shape the hot path with the reference's defaults.  ``gf_radius`` is this project's:
+    the radius of decode's guided filter -- 30 (the reference's, at any size), another integer, or "scaled"
+    (``guided_filter_radius``)."""
 
     def __init__(self, **kw):
         d = dict(netE1="StyleGAN2Resnet", netE2="StyleGAN2Resnet", netG="StyleGAN2Resnet", netD="StyleGAN2",
                  spatial_code_ch=256, global_code_ch=2048, crop_size=512, lambda_GAN=1.0, match_kernel=1,
                  num_gpus=1, local_rank=1, isTrain=False, checkpoints_dir="./checkpoints", name="ppst",
                  resume_iter="latest", pretrained_name=None, training_stage=2, lambda_R1=10.0, lambda_L1=3.0,
-                 lambda_StyleCon=1.0, lambda_Maskwarp=10.0, lambda_Cycwarp=0.0, nce_T=0.07)
+                 lambda_StyleCon=1.0, lambda_Maskwarp=10.0, lambda_Cycwarp=0.0, nce_T=0.07, gf_radius=30)
         d.update(kw)
         self.__dict__.update(d)
 
@@ -44,6 +46,25 @@ def correspondence_side(h, w):
                          "and at most %d (one image's widest activation must stay below 2^31 bytes), got %d x %d"
                          % (CORR_SIDE, CORR_SIDE, CORR_SIDE, CORR_MAX_SIDE, h, w))
     return CORR_SIDE
+
+
+GF_RADIUS = 30          # GIFSmoothing(r=30, ...) of the reference (photo_gif.py:43), chosen for CORR_SIDE x CORR_SIDE images
+
+
+def guided_filter_radius(opt, h, w):
+    """The radius of decode's guided filter for an (h, w) image under ``opt.gf_radius``: an integer is used as is (the default,
+    30, is the reference's at every size); "scaled" keeps the window's share of the image -- 30 * h // 512 for the sizes
+    ``correspondence_side`` accepts (30 / 60 / 90 at 512 / 1024 / 1536, the radii ops.guided_filter runs fused) and 30 at or below
+    512.  An option object without the attribute means 30."""
+    g = getattr(opt, "gf_radius", GF_RADIUS)
+    if isinstance(g, str):
+        if g != "scaled":
+            raise ValueError("gf_radius is an integer or \"scaled\", got %r" % (g,))
+        if h <= CORR_SIDE and w <= CORR_SIDE:
+            return GF_RADIUS
+        correspondence_side(h, w)
+        return GF_RADIUS * h // CORR_SIDE
+    return int(g)
 
 
 class RsclQueues(nn.Module):
@@ -310,8 +331,9 @@ class PPSTModel(nn.Module):
     def decode(self, spatial_code, global_code, target=None):
         out = self.G(spatial_code, global_code, noise=self.noise)
         if target is not None:
-            # GIFSmoothing(r=30, eps=(0.02*255)^2) with guide = target (ppst_model.py:290-305)
-            return ops.guided_filter(glue.tensor2im(target), glue.tensor2im(out), 30, (0.02 * 255) ** 2)
+            # GIFSmoothing(r=30, eps=(0.02*255)^2) with guide = target (ppst_model.py:290-305); the radius follows opt.gf_radius
+            r = guided_filter_radius(self.opt, int(target.shape[-2]), int(target.shape[-1]))
+            return ops.guided_filter(glue.tensor2im(target), glue.tensor2im(out), r, (0.02 * 255) ** 2)
         return out
 
     def discriminate(self, x):
