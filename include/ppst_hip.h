@@ -419,7 +419,9 @@ int ppst_affine_act(const void* x, const void* scale_shift, const void* res,
                     int act /* | 0x100: res joins before act */, const void* prelu,
                     float out_scale,
                     int res_up2_w /* >0: res is a HALF-resolution tensor, upsampled x2 bilinearly on the
-                                     fly (resnet skip, generator.py:75); value = output width W */,
+                                     fly (resnet skip, generator.py:75); value = output width W.  Vector
+                                     forms only: C and every ld multiples of 4, x / res / y 16-byte aligned
+                                     (8 with a half type), else PPST_EINVAL */,
                     void* stream);
 /* x_st: storage of x and res; y_st: of y (either may be fp32 beside a half type; two different half types are refused) */
 int ppst_affine_act_st(const void* x, const void* scale_shift, const void* res, const void* res_scale_shift, void* y,

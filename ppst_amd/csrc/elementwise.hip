@@ -473,6 +473,7 @@ extern "C" int ppst_affine_act_st(const void* x, const void* scale_shift, const 
   bool vec = C % 4 == 0 && x_ld % 4 == 0 && y_ld % 4 == 0 && (!res || res_ld % 4 == 0) &&
              (((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) % (x_st || y_st ? 8 : 16) == 0);
   if ((x_st || y_st) && !vec) return PPST_EINVAL;     // half storage: the vector forms only
+  if (res_up2_w > 0 && !vec) return PPST_EINVAL;      // res_up2: the vector forms only (the one-channel form reads res at full resolution)
   // 8 channels per thread when a half tensor is involved and everything is 16-byte addressable
   const bool w8 = vec && (x_st || y_st) && C % 8 == 0 && x_ld % 8 == 0 && y_ld % 8 == 0 && (!res || res_ld % 8 == 0) &&
                   (((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) % 16 == 0);
@@ -1083,6 +1084,12 @@ __global__ __launch_bounds__(256) void conv1x1_small_cout_kernel(const void* __r
     }
   }
 }
+// The four products of a lane's channel slice as ONE stated chain of fused multiply-adds: left to the compiler's contraction, the
+// chain it chose for a half-stored x (the widening folded into the multiply) was not the one of the fp32 form, and the half launch
+// was not the fp32 launch on the widened input bit for bit (include/ppst_hip.h, PPST_ST_*).
+__device__ __forceinline__ float dot4(const float4& a, const float4& b) {
+  return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)));
+}
 // Cout == 3 (ToRGB): 32 lanes x 8 pixels per iteration.  Each lane keeps 8 x 3 partial dot products over its
 // channel slice; the cross-lane sum is a transposing butterfly that halves the value count at offsets 16, 8, 4
 // (24 -> 12 -> 6 -> 3 values) and finishes with a 2-stage butterfly: 27 shuffles per 8 pixels instead of 15 per pixel.
@@ -1108,9 +1115,9 @@ __global__ __launch_bounds__(256) void conv1x1_cout3_kernel(const void* __restri
       }
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        v[k * 3 + 0] += xv[k].x * w0.x + xv[k].y * w0.y + xv[k].z * w0.z + xv[k].w * w0.w;
-        v[k * 3 + 1] += xv[k].x * w1.x + xv[k].y * w1.y + xv[k].z * w1.z + xv[k].w * w1.w;
-        v[k * 3 + 2] += xv[k].x * w2.x + xv[k].y * w2.y + xv[k].z * w2.z + xv[k].w * w2.w;
+        v[k * 3 + 0] += dot4(xv[k], w0);
+        v[k * 3 + 1] += dot4(xv[k], w1);
+        v[k * 3 + 2] += dot4(xv[k], w2);
       }
     }
 #pragma unroll
@@ -1202,9 +1209,9 @@ __global__ __launch_bounds__(256) void conv1x1_cout3_apply_kernel(const void* __
       }
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        v[k * 3 + 0] += xv[k].x * w0.x + xv[k].y * w0.y + xv[k].z * w0.z + xv[k].w * w0.w;
-        v[k * 3 + 1] += xv[k].x * w1.x + xv[k].y * w1.y + xv[k].z * w1.z + xv[k].w * w1.w;
-        v[k * 3 + 2] += xv[k].x * w2.x + xv[k].y * w2.y + xv[k].z * w2.z + xv[k].w * w2.w;
+        v[k * 3 + 0] += dot4(xv[k], w0);
+        v[k * 3 + 1] += dot4(xv[k], w1);
+        v[k * 3 + 2] += dot4(xv[k], w2);
       }
     }
 #pragma unroll

@@ -12,6 +12,9 @@ Tolerances (rel = max|a-b| / max|b|):
   guided filter ......................... <= 1 uint8 LSB (parity unpinned vs OpenCV); the boundary-aware
                                           bar against float64, every radius, the edge extents and the tuned instances:
                                           tests/test_gpu_guided_filter.py
+  activation path ....................... every launch form and edge of the elementwise, statistics, pooling, resize and NHWC
+                                          blur kernels against float64 at the bars above, half storage bit-equal to the fp32
+                                          launch rounded once: tests/test_gpu_act.py
 """
 import os
 import sys
