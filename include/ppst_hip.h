@@ -593,6 +593,41 @@ int64_t ppst_png_bound(int H, int W, int C);
 int64_t ppst_png_ws(int B, int H, int W, int C);
 int ppst_png_encode(const void* img_u8, void* files, void* sizes, int B, int H, int W, int C, void* work, void* stream);
 
+/* JPEG encode on the device (ppst_amd/csrc/jpeg.hip): uint8 HWC [B][H][W][C], C = 1 (grey, one component) or 3 (RGB -> YCbCr), ->
+ * B complete baseline sequential JPEG files (ITU-T T.81, JFIF 1.01).  The format, so that a host model can restate it:
+ *   quality      1 .. 100, libjpeg's scaling of the Annex K tables: s = 5000 / q (q < 50) or 200 - 2 q, Q = clamp((base * s + 50) / 100,
+ *                1, 255) in integer arithmetic; DQT in zigzag order, table 0 luma, table 1 chroma
+ *   subsampling  PPST_JPEG_444 or PPST_JPEG_420 (Pillow's numbers); grey ignores which of the two
+ *   colour       Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+ *                Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16; partial MCUs repeat the last column / row of the
+ *                pixels; 4:2:0 chroma = (sum of the 2 x 2 + bias) >> 2, bias 1, 2, 1, 2 .. along x
+ *   DCT          level shift 128; integer fixed point: T[u][x] = round(2^14 c(u) / 2 cos((2 x + 1) u pi / 16)); rows
+ *                a = (sum s T + 128) >> 8, columns b = sum a T (scale 2^20), q = sign(b) ((|b| + (Q << 19)) / (Q << 20)): to nearest,
+ *                halves away from zero.  No floating point anywhere: the bytes are a pure function of the pixels
+ *   entropy      the four Annex K "typical" Huffman tables, written as DHT (DC 0, AC 0, DC 1, AC 1)
+ *   restarts     DRI = 96 MCUs (grey), 32 (4:4:4), 16 (4:2:0): 96 blocks, one workgroup's interval whatever the width; DC predictors
+ *                start at 0 in each, each is padded with 1-bits to a byte, FF is followed by 00, RSTm (m = 0 .. 7, cycling) between
+ *   segments     SOI, APP0 (JFIF, density 1:1), DQT x 1 | 2, SOF0, DHT x 2 | 4, DRI, SOS, the scan, EOI
+ *   ppst_jpeg_bound   bytes one file can take: a true worst case, a multiple of 16; PPST_EINVAL for bad arguments.  A block takes at
+ *                     most 11 + 11 bits (longest DC code, chroma; 11 magnitude bits) + 63 x (16 + 10) (longest AC code, 10 magnitude
+ *                     bits) = 1660 bits (EOB and ZRL only replace coefficients, by less); an interval of n blocks is padded to
+ *                     ceil(1660 n / 8) bytes, every one of which may be an FF with its 00: x 2; + 2 for the marker behind it (RSTm
+ *                     or EOI); + the header (SOI through SOS: 334 bytes grey, 629 colour)
+ *   ppst_jpeg_ws      bytes of the caller-owned workspace (> 0, also for B = 0)
+ *   ppst_jpeg_header  host code, no GPU: the bytes from SOI through SOS, written from the constant tables the kernels read; returns
+ *                     their count; out may be null (count only); cap < count: PPST_EINVAL, nothing written
+ *   ppst_jpeg_encode  files: [B][ppst_jpeg_bound(H, W, C, subsampling)] bytes, file i starts at i * bound; sizes: int64 [B], the
+ *                     file lengths.  Bytes of a slot behind its file's length are not written.  img_u8, files, work: 16-byte aligned.
+ * 1 <= H, W <= 65535; C other than 1 / 3, another subsampling or quality, or a worst-case file of 2^32 bytes or more (a file's scan
+ * offsets are 32-bit): PPST_EINVAL, reported ahead of null pointers (PPST_ENULL); B = 0: PPST_OK, nothing touched. */
+#define PPST_JPEG_444 0
+#define PPST_JPEG_420 2
+int64_t ppst_jpeg_bound(int H, int W, int C, int subsampling);
+int64_t ppst_jpeg_ws(int B, int H, int W, int C, int subsampling);
+int64_t ppst_jpeg_header(int H, int W, int C, int quality, int subsampling, void* out, int64_t cap);
+int ppst_jpeg_encode(const void* img_u8, void* files, void* sizes, int B, int H, int W, int C, int quality, int subsampling,
+                     void* work, void* stream);
+
 /* ------------------------------------------------ LPIPS-AlexNet metric ---- */
 /* LPIPS v0.1, net = 'alex', lpips = True, spatial = False, normalize = False, eval mode (csrc/lpips.hip): for two fp32 image
  * batches a, b (B, 3, H, W)

@@ -154,6 +154,10 @@ _SIGS = {
     "ppst_png_bound": (i64, [i32, i32, i32]),
     "ppst_png_ws": (i64, [i32, i32, i32, i32]),
     "ppst_png_encode": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "ppst_jpeg_bound": (i64, [i32, i32, i32, i32]),
+    "ppst_jpeg_ws": (i64, [i32, i32, i32, i32, i32]),
+    "ppst_jpeg_header": (i64, [i32, i32, i32, i32, i32, vp, i64]),
+    "ppst_jpeg_encode": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "ppst_lpips_pack_floats": (i64, []),
     "ppst_lpips_pack": (i32, [vp, vp, vp, vp, vp, vp, vp]),
     "ppst_lpips_dims": (i32, [i32, i32, ctypes.POINTER(i32)]),

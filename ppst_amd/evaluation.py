@@ -16,11 +16,12 @@ The recipes take and return tensors.  The folder-level front ends at the end of 
 ``evaluate_grid_folder``) add what the reference's evaluators do around them: decode (PIL, a thread pool), resize + normalise
 on the device (ppst_amd/imageio.py, Pillow-exact), the uint8 quantisation on the device (glue.tensor2im), PNG encode in the
 thread pool (zlib releases the GIL: the encode of one batch overlaps the next batch's kernels) or -- ``png="device"`` -- on
-the GPU (imageio.encode_png: the threads only write bytes), the reference's file names.
+the GPU (imageio.encode_png: the threads only write bytes), the reference's file names.  ``format="jpeg"`` writes baseline JPEG
+files instead, by the same switch: Pillow on the threads, or imageio.encode_jpeg on the GPU.
 """
 import torch
 
-from . import glue
+from . import glue, ops
 
 
 def above_code_grid(*images):
@@ -238,6 +239,13 @@ def _save_png(args):
     return path
 
 
+def _save_jpeg(args):
+    from PIL import Image
+    arr, path, quality, subsampling = args
+    Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr).save(path, format="JPEG", quality=quality, subsampling=subsampling)
+    return path
+
+
 def _write_file(args):
     blob, path = args
     with open(path, "wb") as f:
@@ -253,15 +261,32 @@ def _check_encoder(encoder):
         raise ValueError("PNG encoder must be one of %s, not %r" % (PNG_ENCODERS, encoder))
 
 
-def write_png_batch(u8, paths, pool=None, encoder="host"):
+FORMATS = {"png": ".png", "jpeg": ".jpg"}          # file format -> the extension of the names the front ends make up
+
+
+def _check_format(format, jpeg_quality, jpeg_subsampling):
+    """ValueError for an unknown format or JPEG setting (checked whatever the format: a typo shows at once)."""
+    if format not in FORMATS:
+        raise ValueError("file format must be one of %s, not %r" % (tuple(FORMATS), format))
+    ops.check_jpeg_settings(jpeg_quality, jpeg_subsampling)
+
+
+def write_png_batch(u8, paths, pool=None, encoder="host", format="png", jpeg_quality=90, jpeg_subsampling="4:2:0"):
     """u8: (B,H,W,C) uint8 on the device -> one PNG file per image, the half of the file output both front ends share.
     ``host``: one device-to-host copy of the batch, ``Image.fromarray(arr).save(path)`` per image; ``device``: the files are
     encoded on the GPU (imageio.encode_png) and only their bytes are copied and written.  The per-image jobs run on ``pool``'s
-    threads when one is given (the futures are returned: the caller overlaps them with the next batch and joins at the end)."""
+    threads when one is given (the futures are returned: the caller overlaps them with the next batch and joins at the end).
+    ``format="jpeg"``: baseline JPEG files instead -- ``host`` = Pillow's ``save(format="JPEG", quality=, subsampling=)``,
+    ``device`` = imageio.encode_jpeg.  ``paths`` are written as given, whatever the format."""
     _check_encoder(encoder)
+    _check_format(format, jpeg_quality, jpeg_subsampling)
     if encoder == "device":
         from . import imageio
-        job, jobs = _write_file, list(zip(imageio.encode_png(u8), paths))
+        blobs = imageio.encode_jpeg(u8, jpeg_quality, jpeg_subsampling) if format == "jpeg" else imageio.encode_png(u8)
+        job, jobs = _write_file, list(zip(blobs, paths))
+    elif format == "jpeg":
+        arr = u8.cpu().numpy()
+        job, jobs = _save_jpeg, [(arr[i], p, jpeg_quality, jpeg_subsampling) for i, p in enumerate(paths)]
     else:
         arr = u8.cpu().numpy()
         job, jobs = _save_png, [(arr[i], p) for i, p in enumerate(paths)]
@@ -270,41 +295,48 @@ def write_png_batch(u8, paths, pool=None, encoder="host"):
     return [pool.submit(job, j) for j in jobs]
 
 
-def save_images(images, paths, pool=None, encoder="host"):
+def save_images(images, paths, pool=None, encoder="host", format="png", jpeg_quality=90, jpeg_subsampling="4:2:0"):
     """images: (B,3,H,W) in [-1,1] on the device -> PNG files.  util.tensor2im quantisation (util/util.py:98-131) on the
-    device, then write_png_batch (``encoder``: "host" = Pillow on the pool's threads, "device" = the HIP encoder)."""
+    device, then write_png_batch (``encoder``: "host" = Pillow on the pool's threads, "device" = the HIP encoder;
+    ``format="jpeg"`` with its quality and subsampling: JPEG files)."""
     _check_encoder(encoder)
-    return write_png_batch(glue.tensor2im(images), paths, pool, encoder)
+    _check_format(format, jpeg_quality, jpeg_subsampling)
+    return write_png_batch(glue.tensor2im(images), paths, pool, encoder, format, jpeg_quality, jpeg_subsampling)
 
 
-def evaluate_swap_files(model, structure_path, texture_path, out_dir, alphas=(1.0,), load_size=512, device="cuda", png="host"):
+def evaluate_swap_files(model, structure_path, texture_path, out_dir, alphas=(1.0,), load_size=512, device="cuda", png="host",
+                        format="png", jpeg_quality=90, jpeg_subsampling="4:2:0"):
     """evaluation/simple_swapping_evaluator.py:38-76: one structure image, one texture image, one output per mix alpha named
     <structure>_<texture>_<alpha %.2f>.png (ToPILImage quantisation of the clamped image, :61-62).  ``png``: where the files are
-    encoded (write_png_batch).  Returns the paths."""
+    encoded (write_png_batch).  ``format="jpeg"``: JPEG files of that quality and subsampling, named .jpg.  Returns the paths."""
     import os
     _check_encoder(png)
+    _check_format(format, jpeg_quality, jpeg_subsampling)
     os.makedirs(out_dir, exist_ok=True)
     c, s_ = load_images([os.path.expanduser(structure_path), os.path.expanduser(texture_path)], load_size, device)
     outs = simple_swap(model, c, s_, alphas)
     stem = lambda p: os.path.splitext(os.path.basename(p))[0]
     paths = []
     for alpha in alphas:
-        path = os.path.join(out_dir, "%s_%s_%.2f.png" % (stem(structure_path), stem(texture_path), alpha))
-        paths += write_png_batch(to_uint8_image(outs[alpha])[:1], [path], None, png)
+        path = os.path.join(out_dir, "%s_%s_%.2f%s" % (stem(structure_path), stem(texture_path), alpha, FORMATS[format]))
+        paths += write_png_batch(to_uint8_image(outs[alpha])[:1], [path], None, png, format, jpeg_quality, jpeg_subsampling)
     return paths
 
 
 def evaluate_grid_folder(model, dataroot, out_dir, rank=0, world=1, smooth=True, load_size=512, device="cuda", workers=8,
-                         pair_batch=8, image_batch=8, png="host"):
+                         pair_batch=8, image_batch=8, png="host", format="png", jpeg_quality=90, jpeg_subsampling="4:2:0"):
     """evaluation/content_style_grid_generation_evaluator.py:36-99 over <dataroot>/content/* and <dataroot>/style/*: every
     (content, style) pair, guided-filter post-process with the content as guide (radius: the model's Options.gf_radius -- decode
     reads it, this function has no parameter for it); files land in <out_dir>/images/ under the
     reference's names (<content>_<style>.png, the inputs as <name>.png; util/html.py:51-75 -- the HTML index itself is not
     written).  All images must come out of the preprocessing at one size (the reference batches them the same way).
     Multi-GPU: every rank reads all inputs (they are small), computes its share (swapping_grid) and writes its own files.
-    ``png``: "host" = Pillow on the worker threads, "device" = the HIP encoder (the threads only write the bytes)."""
+    ``png``: "host" = Pillow on the worker threads, "device" = the HIP encoder (the threads only write the bytes).
+    ``format="jpeg"``: JPEG files of that quality and subsampling under the same names with .jpg, by the same switch."""
     import os
     _check_encoder(png)
+    _check_format(format, jpeg_quality, jpeg_subsampling)
+    ext, fmt = FORMATS[format], (format, jpeg_quality, jpeg_subsampling)
     from concurrent.futures import ThreadPoolExecutor
     cdir, sdir = os.path.join(dataroot, "content"), os.path.join(dataroot, "style")
     ls = lambda d: sorted(os.path.join(d, f) for f in os.listdir(d) if f.lower().endswith(_IMG_EXT))
@@ -321,12 +353,12 @@ def evaluate_grid_folder(model, dataroot, out_dir, rank=0, world=1, smooth=True,
         contents, styles = torch.cat(imgs[:len(cpaths)], 0), torch.cat(imgs[len(cpaths):], 0)
         futures = []
         if rank == 0:   # the top row / first column of the reference's page: the inputs themselves
-            futures += save_images(torch.cat((contents, styles), 0), [os.path.join(img_dir, stem(p) + ".png") for p in cpaths + spaths], pool, png)
+            futures += save_images(torch.cat((contents, styles), 0), [os.path.join(img_dir, stem(p) + ext) for p in cpaths + spaths], pool, png, *fmt)
         out = swapping_grid(model, contents, styles, rank, world, smooth, pair_batch, image_batch)
         keys = sorted(out)
         for k in range(0, len(keys), pair_batch):
             chunk = keys[k:k + pair_batch]
-            names = [os.path.join(img_dir, "%s_%s.png" % (stem(cpaths[i]), stem(spaths[j]))) for i, j in chunk]
-            futures += save_images(torch.stack([out[ij] for ij in chunk], 0), names, pool, png)
+            names = [os.path.join(img_dir, "%s_%s%s" % (stem(cpaths[i]), stem(spaths[j]), ext)) for i, j in chunk]
+            futures += save_images(torch.stack([out[ij] for ij in chunk], 0), names, pool, png, *fmt)
         written = [f.result() for f in futures]
     return written

@@ -11,7 +11,8 @@ bicubic weights, normalised, 22-bit fixed point); the pixel arithmetic is intege
 (csrc/imageio.hip), bit-identical to Pillow.
 
 The other end of the pipeline is here too: ``encode_png`` turns a uint8 batch on the device into PNG files (csrc/png.hip:
-row filters, deflate and checksums as HIP kernels) and brings only the file bytes to the host.
+row filters, deflate and checksums as HIP kernels) and brings only the file bytes to the host; ``encode_jpeg`` does the same
+for baseline JPEG files (csrc/jpeg.hip: colour conversion, integer DCT, Huffman coding and restart intervals as HIP kernels).
 """
 import math
 
@@ -165,7 +166,16 @@ def preprocess_resize(img, load_size=512):
 def encode_png(u8):
     """(B,H,W,C) uint8 on the device (C = 1: grey, 3: RGB) -> list of B ``bytes``, each a complete PNG file.
     Two device-to-host copies per batch: the B sizes, then the batch's file slots cut at the longest file."""
-    files, sizes = ops.png_encode(u8)
+    return _files_to_bytes(*ops.png_encode(u8))
+
+
+def encode_jpeg(u8, quality=90, subsampling="4:2:0"):
+    """(B,H,W,C) uint8 on the device (C = 1: grey, 3: RGB) -> list of B ``bytes``, each a complete baseline JPEG file
+    (csrc/jpeg.hip; quality 1 .. 100 with libjpeg's table scaling, subsampling "4:4:4" or "4:2:0").  The same two copies."""
+    return _files_to_bytes(*ops.jpeg_encode(u8, quality, subsampling))
+
+
+def _files_to_bytes(files, sizes):
     if files.shape[0] == 0:
         return []
     n = sizes.cpu().tolist()

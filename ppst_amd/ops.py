@@ -1777,6 +1777,37 @@ def png_encode(u8):
     return files, sizes
 
 
+JPEG_SUBSAMPLING = {"4:4:4": 0, "4:2:0": 2}        # PPST_JPEG_444 / PPST_JPEG_420 (Pillow's numbers)
+
+
+def check_jpeg_settings(quality, subsampling):
+    """ValueError unless quality is an integer 1 .. 100 and subsampling "4:4:4" or "4:2:0"; -> the library's subsampling number."""
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError("JPEG quality must be an integer 1 .. 100, not %r" % (quality,))
+    if not isinstance(subsampling, str) or subsampling not in JPEG_SUBSAMPLING:
+        raise ValueError("JPEG subsampling must be one of %s, not %r" % (tuple(JPEG_SUBSAMPLING), subsampling))
+    return JPEG_SUBSAMPLING[subsampling]
+
+
+def jpeg_encode(u8, quality=90, subsampling="4:2:0"):
+    """(B,H,W,C) uint8 on the device, C = 1 (grey) or 3 (RGB) -> (files (B, bound) uint8, sizes (B,) int64), both on the device:
+    file i is files[i, :sizes[i]], a baseline JPEG (csrc/jpeg.hip; the format: include/ppst_hip.h).  The workspace comes from
+    torch's allocator; nothing synchronises the host."""
+    ss = check_jpeg_settings(quality, subsampling)
+    if not isinstance(u8, torch.Tensor) or not u8.is_cuda or u8.dtype != torch.uint8 or u8.dim() != 4:
+        raise RuntimeError("jpeg_encode needs a CUDA uint8 (B,H,W,C) tensor (no CPU fallback)")
+    u8 = u8.contiguous()
+    B, H, W, C = u8.shape
+    bound = lib.ppst_jpeg_bound(H, W, C, ss)
+    if bound < 0:
+        raise RuntimeError("jpeg_encode: unsupported image shape %s (C must be 1 or 3, H and W at most 65535)" % (tuple(u8.shape),))
+    files = torch.empty((B, bound), device=u8.device, dtype=torch.uint8)
+    sizes = torch.empty((B,), device=u8.device, dtype=torch.int64)
+    work = torch.empty(lib.ppst_jpeg_ws(B, H, W, C, ss), device=u8.device, dtype=torch.uint8)
+    check(lib.ppst_jpeg_encode(_p(u8), _p(files), _p(sizes), B, H, W, C, quality, ss, _p(work), _stream()), "ppst_jpeg_encode")
+    return files, sizes
+
+
 def resample_f32(x, out_h, out_w, clamp=None):
     """x (..., H, W) float32 on the device -> (..., out_h, out_w): Pillow's antialiased bicubic on every plane, both axes in one
     launch (ppst_resample_f32; the fp32 weight tables are imageio.resample_tables_f32).  ``clamp`` = (lo, hi) or None."""
