@@ -628,6 +628,86 @@ int64_t ppst_jpeg_header(int H, int W, int C, int quality, int subsampling, void
 int ppst_jpeg_encode(const void* img_u8, void* files, void* sizes, int B, int H, int W, int C, int quality, int subsampling,
                      void* work, void* stream);
 
+/* JPEG decode on the device (ppst_amd/csrc/jpeg_parse.hip: host parser; ppst_amd/csrc/jpeg_decode.hip: kernels): B baseline JPEG
+ * files of DIFFERENT sizes and samplings, packed into one byte buffer, -> uint8 HWC images, equal byte for byte to libjpeg-turbo's
+ * default decoder (jidctint "islow", fancy upsampling), which is what Pillow runs.  Integer arithmetic only.
+ *   accepted     SOF0, 8 bits; one component (its sampling factors are ignored, T.81 A.2.2), or three with Y at 1x1 (4:4:4) or 2x2
+ *                (4:2:0) and both chroma at 1x1; ONE interleaved scan with Ss, Se, Ah/Al = 0, 63, 0; 8-bit DQT; DC / AC tables 0 and 1,
+ *                any contents (optimised files); DRI or none; APPn / COM are skipped
+ *   refused      by ppst_jpeg_parse with one PPST_JPEG_E* each (below); the parser bounds every read by n and trusts no length
+ *   descriptor   ppst_jpeg_dec_image, plain data: the parser fills everything but the caller's four fields (file_off: where the
+ *                file starts in the packed buffer; out_off: where image i starts in out_u8; mirror: columns reversed; expand_grey:
+ *                a one-component file is written as three equal channels).  scan_off / scan_len: the entropy-coded segment, from
+ *                behind SOS to the first FF D9 behind it.  qt: per component, 64 entries in the file's (zigzag) order.  bits / vals:
+ *                BITS[16] and HUFFVAL of the tables DC 0, DC 1, AC 0, AC 1; dc_tab / ac_tab: each component's table number.
+ *   stages       (a) clean: per 4096-byte chunk of the segment, the 00 behind an FF and both bytes of RSTm are dropped (a prefix
+ *                over the chunks' counts in a second launch places the bytes); the clean offset behind RSTm number r is the start
+ *                of interval r + 1; m must be r mod 8 and there must be ceil(MCUs / DRI) - 1 of them;
+ *                (b) entropy: one workgroup per restart interval (a file without DRI: one).  The interval's bits are cut into
+ *                subsequences of 32 * subseq_words bits (0: the default, 32 words; at least 2).  The state at a boundary is
+ *                (p, b, k): bit position of the first codeword at or behind it, block within the MCU, zigzag index.  Subsequence 0
+ *                enters at (0, 0, 0), every other one is guessed as (its boundary, 0, 0); a round decodes every subsequence whose
+ *                entry changed from its entry until p passes its end and hands (p, b, k) to its successor; rounds repeat until no
+ *                entry changes -- after round r the first r subsequences are final, so the fixed point is the sequential decode
+ *                and there are at most #subsequences rounds.  A code the tables do not define advances one bit, k beyond 63
+ *                starts a new block, bits behind the interval are zero.  Then a prefix over the blocks each subsequence completed
+ *                gives it its first block, a second decode stores the coefficients (int16 [blocks][64], zigzag; every store
+ *                checked against the interval's block count), and DC differences are summed per component within the interval;
+ *                (c) IDCT: coefficient x table, libjpeg's jidctint: CONST_BITS 13, PASS1_BITS 2, FIX 2446 3196 4433 6270 7373 9633
+ *                12299 15137 16069 16819 20995 25172; columns descaled by 11, rows by 18, + 128, clamped to 0 .. 255; planes padded to whole MCUs;
+ *                (d) 4:2:0 chroma by libjpeg's fancy h2v2: rows 3 near + far (the neighbour row replicated at the top and bottom
+ *                of the ceil(H / 2) rows), columns (3 this + left + 8) >> 4 and (3 this + right + 7) >> 4 (this for the missing
+ *                neighbour at both ends); a chroma plane at most 2 samples wide: plain 2 x 2 replication.  Colour, Cb' = Cb - 128:
+ *                R = Y + ((91881 Cr' + 32768) >> 16), B = Y + ((116130 Cb' + 32768) >> 16),
+ *                G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16), arithmetic shifts, clamped.
+ *   status       int32 [B], 0 = decoded; else a sum of PPST_JPEG_S_* (below): the image's pixels are then undefined (but written
+ *                within its own H x W x C bytes only) and every other image of the batch is unaffected
+ *   ppst_jpeg_parse      host code, no GPU
+ *   ppst_jpeg_decode_ws  host code: bytes of the caller-owned workspace for these B descriptors (> 0; grows with every file's size);
+ *                        PPST_EINVAL for B < 0, subseq_words of 1 or above 65536, or a descriptor the parser would not have made
+ *   ppst_jpeg_decode     bytes: the packed files on the device (nbytes of them); imgs_host: the descriptors (launch geometry);
+ *                        imgs_dev: a copy of the same B descriptors on the device (what the kernels read); out_u8: out_bytes
+ *                        bytes, image i is HWC at out_off, C = 1 (grey) or 3; every file and image must lie inside its buffer:
+ *                        PPST_EINVAL.  work, out_u8, imgs_dev: 16-byte aligned.  After the call the first B int32 of work hold, per
+ *                        image, the largest number of rounds one of its intervals took.  B = 0: PPST_OK, nothing touched. */
+#define PPST_JPEG_E_TRUNCATED (-101)   /* the file ends inside a segment, or has no EOI behind its scan */
+#define PPST_JPEG_E_NOT_JPEG (-102)    /* no SOI */
+#define PPST_JPEG_E_ORDER (-103)       /* a segment out of order, missing or unknown, or of an impossible length */
+#define PPST_JPEG_E_PROGRESSIVE (-104) /* SOF2 (or any other non-baseline Huffman process) */
+#define PPST_JPEG_E_ARITHMETIC (-105)  /* SOF9 .. SOF15 */
+#define PPST_JPEG_E_PRECISION (-106)   /* not 8 bits per sample */
+#define PPST_JPEG_E_SAMPLING (-107)    /* 4:2:2, 4:4:0, 4:1:1, ... */
+#define PPST_JPEG_E_COMPONENTS (-108)  /* two, four or more components */
+#define PPST_JPEG_E_ADOBE_RGB (-109)   /* RGB, not YCbCr, by libjpeg's rule: no JFIF APP0 and Adobe transform 0, or neither and ids 'R' 'G' 'B' */
+#define PPST_JPEG_E_MULTISCAN (-110)   /* a scan that does not hold every component */
+#define PPST_JPEG_E_DQT16 (-111)       /* 16-bit quantisation table */
+#define PPST_JPEG_E_SIZE (-112)        /* H or W 0 (or the file too large for 32-bit offsets) */
+#define PPST_JPEG_E_HUFFMAN (-113)     /* a Huffman table missing, over-subscribed or with an id above 1 */
+#define PPST_JPEG_E_SCAN (-114)        /* Ss, Se, Ah/Al other than 0, 63, 0 */
+#define PPST_JPEG_S_MARKER 1           /* status bits: an FF inside the scan followed by neither 00 nor RSTm */
+#define PPST_JPEG_S_RST_COUNT 2        /*   not ceil(MCUs / DRI) - 1 restart markers */
+#define PPST_JPEG_S_RST_ORDER 4        /*   RSTm out of its 0 .. 7 cycle */
+#define PPST_JPEG_S_CODE 8             /*   a code no table defines, or a run beyond the block */
+#define PPST_JPEG_S_BLOCKS 16          /*   an interval does not hold its number of blocks */
+typedef struct ppst_jpeg_dec_image {
+  int32_t H, W, ncomp;
+  int32_t ss;                 /* 1: grey and 4:4:4 (8 x 8 MCUs); 2: 4:2:0 (16 x 16 MCUs) */
+  int32_t hs[3], vs[3];       /* the sampling factors as the file states them */
+  int32_t dri;                /* MCUs per restart interval, 0: none */
+  int32_t scan_off, scan_len; /* within the file */
+  uint8_t qt[3][64];
+  uint8_t dc_tab[3], ac_tab[3];
+  uint8_t pad_[2];
+  uint8_t bits[4][16];
+  uint8_t vals[4][256];
+  int64_t file_off, out_off;  /* the caller's */
+  int32_t mirror, expand_grey;
+} ppst_jpeg_dec_image;
+int ppst_jpeg_parse(const void* file, int64_t n, ppst_jpeg_dec_image* out);
+int64_t ppst_jpeg_decode_ws(const ppst_jpeg_dec_image* imgs, int B, int subseq_words);
+int ppst_jpeg_decode(const void* bytes, int64_t nbytes, const ppst_jpeg_dec_image* imgs_host, const void* imgs_dev, void* out_u8,
+                     int64_t out_bytes, void* status, int B, int subseq_words, void* work, void* stream);
+
 /* ------------------------------------------------ LPIPS-AlexNet metric ---- */
 /* LPIPS v0.1, net = 'alex', lpips = True, spatial = False, normalize = False, eval mode (csrc/lpips.hip): for two fp32 image
  * batches a, b (B, 3, H, W)

@@ -61,6 +61,14 @@ class GapGmpLevel(ctypes.Structure):
     _fields_ = [("x", vp), ("mask", vp), ("out", vp), ("H", i32), ("W", i32), ("C", i32), ("ld", i32)]
 
 
+class JpegDecImage(ctypes.Structure):
+    """ppst_jpeg_dec_image (include/ppst_hip.h): one file's descriptor, filled by ppst_jpeg_parse but for the caller's last four fields."""
+    _u8 = ctypes.c_uint8
+    _fields_ = [("H", i32), ("W", i32), ("ncomp", i32), ("ss", i32), ("hs", i32 * 3), ("vs", i32 * 3), ("dri", i32),
+                ("scan_off", i32), ("scan_len", i32), ("qt", _u8 * 64 * 3), ("dc_tab", _u8 * 3), ("ac_tab", _u8 * 3), ("pad_", _u8 * 2),
+                ("bits", _u8 * 16 * 4), ("vals", _u8 * 256 * 4), ("file_off", i64), ("out_off", i64), ("mirror", i32), ("expand_grey", i32)]
+
+
 GROUP_MAX = 32           # PPST_GROUP_MAX
 
 
@@ -158,6 +166,9 @@ _SIGS = {
     "ppst_jpeg_ws": (i64, [i32, i32, i32, i32, i32]),
     "ppst_jpeg_header": (i64, [i32, i32, i32, i32, i32, vp, i64]),
     "ppst_jpeg_encode": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "ppst_jpeg_parse": (i32, [vp, i64, ctypes.POINTER(JpegDecImage)]),
+    "ppst_jpeg_decode_ws": (i64, [ctypes.POINTER(JpegDecImage), i32, i32]),
+    "ppst_jpeg_decode": (i32, [vp, i64, ctypes.POINTER(JpegDecImage), vp, vp, i64, vp, i32, i32, vp, vp]),
     "ppst_lpips_pack_floats": (i64, []),
     "ppst_lpips_pack": (i32, [vp, vp, vp, vp, vp, vp, vp]),
     "ppst_lpips_dims": (i32, [i32, i32, ctypes.POINTER(i32)]),
@@ -243,6 +254,16 @@ if lib.ppst_version() != ABI_VERSION:
                       "(python -m ppst_amd.build)" % (LIB_PATH, lib.ppst_version(), ABI_VERSION))
 
 _ERR = {-1: "PPST_EINVAL (bad size / flag combination)", -2: "PPST_EUNSUPPORTED", -3: "PPST_ENULL"}
+
+# ppst_jpeg_parse's refusals (PPST_JPEG_E_* of include/ppst_hip.h)
+JPEG_REFUSALS = {-101: "truncated file", -102: "not a JPEG file (no SOI)", -103: "segment out of order, missing or unknown",
+                 -104: "progressive or other non-baseline process", -105: "arithmetic coding", -106: "not 8 bits per sample",
+                 -107: "chroma subsampling other than 4:4:4 and 4:2:0", -108: "not one or three components",
+                 -109: "Adobe RGB (transform 0)", -110: "more than one scan", -111: "16-bit quantisation table",
+                 -112: "height or width 0, or file too large", -113: "Huffman table missing or invalid",
+                 -114: "spectral selection or approximation other than 0, 63, 0"}
+# the bits of ppst_jpeg_decode's status words (PPST_JPEG_S_*)
+JPEG_STATUS_BITS = {1: "marker inside the scan", 2: "restart marker count", 4: "restart marker order", 8: "undefined code", 16: "block count"}
 
 
 def check(rc, what):

@@ -19,6 +19,9 @@ thread pool (zlib releases the GIL: the encode of one batch overlaps the next ba
 the GPU (imageio.encode_png: the threads only write bytes), the reference's file names.  ``format="jpeg"`` writes baseline JPEG
 files instead, by the same switch: Pillow on the threads, or imageio.encode_jpeg on the GPU.
 """
+import contextlib
+import threading
+
 import torch
 
 from . import glue, ops
@@ -224,12 +227,76 @@ def _decode(path):
     return np.array(Image.open(path).convert("RGB"))
 
 
-def load_images(paths, load_size=512, device="cuda", pool=None):
+DECODERS = ("host", "device")
+# Where load_images decodes when its caller does not say: the switch of evaluate_swap_files and evaluate_grid_folder, whose
+# parameter lists are pinned (tests/test_jpeg_cases_cpu.py test_front_end_signatures_only_grew_at_the_end).  Per thread: two
+# evaluators running side by side do not see each other's setting.  Set it with ``with evaluation.decoder("device"): ...``.
+_DECODE = threading.local()
+
+
+def current_decoder():
+    return getattr(_DECODE, "value", "host")
+
+
+def _check_decoder(decode):
+    if decode not in DECODERS:
+        raise ValueError("decoder must be one of %s, not %r" % (DECODERS, decode))
+
+
+@contextlib.contextmanager
+def decoder(name):
+    """``with decoder("device"):`` -- load_images, evaluate_swap_files and evaluate_grid_folder called from THIS thread inside the
+    block decode JPEG files with the HIP decoder (load_images' ``decode=`` argument still wins).  ValueError for an unknown name,
+    before anything runs."""
+    _check_decoder(name)
+    prev = current_decoder()
+    _DECODE.value = name
+    try:
+        yield
+    finally:
+        _DECODE.value = prev
+
+
+def _read_file(path):
+    with open(path, "rb") as f:
+        return f.read()
+
+
+def decode_files_device(blobs, names, device="cuda", mirror=None):
+    """The device half of ``decode="device"``: blobs[i] = the bytes of file names[i].  -> list with a (H,W,3) uint8 device tensor
+    where the HIP decoder took the file and decoded it with status 0 (one batched call over all of them, imageio / ops.jpeg_decode),
+    None where the host has to: another extension, a file the parser refuses, a non-zero status."""
+    out = [None] * len(blobs)
+    parsed = {i: ops.jpeg_parse(b) for i, (b, n) in enumerate(zip(blobs, names)) if n.lower().endswith((".jpg", ".jpeg"))}
+    take = [i for i in sorted(parsed) if parsed[i][0] == 0]
+    if take:
+        views, status = ops.jpeg_decode([blobs[i] for i in take], expand_grey=True, device=device,
+                                        mirror=None if mirror is None else [mirror[i] for i in take],
+                                        parsed=[parsed[i][1] for i in take])
+        for i, v, st in zip(take, views, status.cpu().tolist()):
+            out[i] = v if st == 0 else None
+    return out
+
+
+def load_images(paths, load_size=512, device="cuda", pool=None, decode=None):
     """data/base_dataset.py:85-171 (scale_shortside + make_power_2 + ToTensor + Normalize) for a list of files: decode on
-    host threads, everything else on the device.  Returns a list of (1,3,H,W) tensors (sizes may differ per file)."""
+    host threads, everything else on the device.  Returns a list of (1,3,H,W) tensors (sizes may differ per file).
+    ``decode="device"``: the threads only read the files' bytes; the .jpg / .jpeg files the HIP decoder takes are decoded in ONE
+    batched call on the device (bit-identical to Pillow), every other file -- and any the device reports damaged -- goes through
+    Pillow as before, so a file fails here exactly when it fails with ``"host"``.  ``decode=None``: the module's setting (``decoder``)."""
     from . import imageio
-    arrs = list(pool.map(_decode, paths)) if pool is not None else [_decode(p) for p in paths]
-    return [imageio.preprocess(torch.from_numpy(a[None]).to(device), load_size) for a in arrs]
+    decode = current_decoder() if decode is None else decode
+    _check_decoder(decode)
+    if decode == "host":
+        arrs = list(pool.map(_decode, paths)) if pool is not None else [_decode(p) for p in paths]
+        return [imageio.preprocess(torch.from_numpy(a[None]).to(device), load_size) for a in arrs]
+    blobs = list(pool.map(_read_file, paths)) if pool is not None else [_read_file(p) for p in paths]
+    imgs = decode_files_device(blobs, paths, device)
+    rest = [i for i, v in enumerate(imgs) if v is None]
+    host = list(pool.map(_decode, [paths[i] for i in rest])) if pool is not None else [_decode(paths[i]) for i in rest]
+    for i, a in zip(rest, host):
+        imgs[i] = torch.from_numpy(a).to(device)
+    return [imageio.preprocess(v[None], load_size) for v in imgs]
 
 
 def _save_png(args):
@@ -308,10 +375,12 @@ def evaluate_swap_files(model, structure_path, texture_path, out_dir, alphas=(1.
                         format="png", jpeg_quality=90, jpeg_subsampling="4:2:0"):
     """evaluation/simple_swapping_evaluator.py:38-76: one structure image, one texture image, one output per mix alpha named
     <structure>_<texture>_<alpha %.2f>.png (ToPILImage quantisation of the clamped image, :61-62).  ``png``: where the files are
-    encoded (write_png_batch).  ``format="jpeg"``: JPEG files of that quality and subsampling, named .jpg.  Returns the paths."""
+    encoded (write_png_batch).  ``format="jpeg"``: JPEG files of that quality and subsampling, named .jpg.  The two inputs are decoded where
+    ``evaluation.decoder`` says (load_images).  Returns the paths."""
     import os
     _check_encoder(png)
     _check_format(format, jpeg_quality, jpeg_subsampling)
+    _check_decoder(current_decoder())
     os.makedirs(out_dir, exist_ok=True)
     c, s_ = load_images([os.path.expanduser(structure_path), os.path.expanduser(texture_path)], load_size, device)
     outs = simple_swap(model, c, s_, alphas)
@@ -332,10 +401,13 @@ def evaluate_grid_folder(model, dataroot, out_dir, rank=0, world=1, smooth=True,
     written).  All images must come out of the preprocessing at one size (the reference batches them the same way).
     Multi-GPU: every rank reads all inputs (they are small), computes its share (swapping_grid) and writes its own files.
     ``png``: "host" = Pillow on the worker threads, "device" = the HIP encoder (the threads only write the bytes).
-    ``format="jpeg"``: JPEG files of that quality and subsampling under the same names with .jpg, by the same switch."""
+    ``format="jpeg"``: JPEG files of that quality and subsampling under the same names with .jpg, by the same switch.
+    Inside ``with evaluation.decoder("device"):`` the threads read bytes and the HIP decoder takes the JPEG files it can in one
+    batched call (load_images); otherwise Pillow decodes on the worker threads."""
     import os
     _check_encoder(png)
     _check_format(format, jpeg_quality, jpeg_subsampling)
+    _check_decoder(current_decoder())
     ext, fmt = FORMATS[format], (format, jpeg_quality, jpeg_subsampling)
     from concurrent.futures import ThreadPoolExecutor
     cdir, sdir = os.path.join(dataroot, "content"), os.path.join(dataroot, "style")

@@ -13,6 +13,8 @@ bicubic weights, normalised, 22-bit fixed point); the pixel arithmetic is intege
 The other end of the pipeline is here too: ``encode_png`` turns a uint8 batch on the device into PNG files (csrc/png.hip:
 row filters, deflate and checksums as HIP kernels) and brings only the file bytes to the host; ``encode_jpeg`` does the same
 for baseline JPEG files (csrc/jpeg.hip: colour conversion, integer DCT, Huffman coding and restart intervals as HIP kernels).
+``decode_jpeg`` is the way in: baseline JPEG files of any origin -> uint8 tensors on the device, equal to Pillow's decode byte for
+byte (csrc/jpeg_decode.hip: a parallel Huffman decoder for one sequential stream, integer IDCT, upsampling and colour).
 """
 import math
 
@@ -173,6 +175,37 @@ def encode_jpeg(u8, quality=90, subsampling="4:2:0"):
     """(B,H,W,C) uint8 on the device (C = 1: grey, 3: RGB) -> list of B ``bytes``, each a complete baseline JPEG file
     (csrc/jpeg.hip; quality 1 .. 100 with libjpeg's table scaling, subsampling "4:4:4" or "4:2:0").  The same two copies."""
     return _files_to_bytes(*ops.jpeg_encode(u8, quality, subsampling))
+
+
+def jpeg_info(blob):
+    """What the device decoder would do with this file, without a GPU (ppst_jpeg_parse): {"supported": True, "height", "width",
+    "components", "sampling" [(h, v) per component], "subsampling" ("grey", "4:4:4" or "4:2:0"), "restart_interval" (MCUs, 0:
+    none), "scan_offset", "scan_length"} or {"supported": False, "code", "reason"}."""
+    from . import _lib
+    rc, d = ops.jpeg_parse(blob)
+    if rc != 0:
+        return {"supported": False, "code": rc, "reason": _lib.JPEG_REFUSALS.get(rc, "error %d" % rc)}
+    return {"supported": True, "height": d.H, "width": d.W, "components": d.ncomp,
+            "sampling": [(d.hs[c], d.vs[c]) for c in range(d.ncomp)],
+            "subsampling": "grey" if d.ncomp == 1 else ("4:2:0" if d.ss == 2 else "4:4:4"),
+            "restart_interval": d.dri, "scan_offset": d.scan_off, "scan_length": d.scan_len}
+
+
+def decode_jpeg(blobs, mode=None, device="cuda"):
+    """blobs: list of baseline JPEG files (bytes; sizes and samplings may differ) -> list of (H,W,C) uint8 tensors on the device,
+    each equal to ``numpy.asarray(PIL.Image.open(file))``: C = 1 for a grey file, 3 for a colour one.  ``mode="RGB"``: grey files
+    come out with three equal channels (Pillow's ``convert("RGB")``).  One batched call (ops.jpeg_decode).  ValueError with the
+    parser's reason for a file the decoder does not take (progressive, 4:2:2, CMYK, ...: ``jpeg_info`` tells without a GPU);
+    OSError for a file whose scan the device refused (damaged data)."""
+    from . import _lib
+    if mode not in (None, "RGB"):
+        raise ValueError("mode must be None or 'RGB', not %r" % (mode,))
+    views, status = ops.jpeg_decode(blobs, expand_grey=(mode == "RGB"), device=device)
+    for i, st in enumerate(status.cpu().tolist()):
+        if st:
+            why = ", ".join(v for k, v in sorted(_lib.JPEG_STATUS_BITS.items()) if st & k)
+            raise OSError("decode_jpeg: file %d is damaged (%s)" % (i, why))
+    return views
 
 
 def _files_to_bytes(files, sizes):

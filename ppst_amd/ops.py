@@ -1808,6 +1808,92 @@ def jpeg_encode(u8, quality=90, subsampling="4:2:0"):
     return files, sizes
 
 
+def jpeg_parse(blob):
+    """bytes of a JPEG file -> (ppst_jpeg_parse's return code, the descriptor it filled).  Host code: no GPU."""
+    d = _lib.JpegDecImage()
+    blob = blob if isinstance(blob, bytes) else bytes(blob)
+    return lib.ppst_jpeg_parse(blob, len(blob), ctypes.byref(d)), d
+
+
+class _JpegDecodeCall:
+    """One batched decode, prepared: the files parsed and packed into one pinned buffer, one host-to-device copy of bytes and one of
+    descriptors, output / status / workspace from torch's allocator.  ``launch()`` runs the kernels (again and again:
+    tests/jpeg_decode_time.py times them alone)."""
+
+    def __init__(self, blobs, expand_grey, mirror, subseq_words, dev, parsed=None):
+        blobs = [b if isinstance(b, bytes) else bytes(b) for b in blobs]
+        B = self.B = len(blobs)
+        if mirror is not None and len(mirror) != B:
+            raise ValueError("mirror must be None or one flag per file")
+        if parsed is not None and len(parsed) != B:
+            raise ValueError("parsed must be None or one descriptor per file")
+        self.subseq_words, self.dev = subseq_words, dev
+        descs = self.descs = (_lib.JpegDecImage * max(B, 1))()
+        file_off, out_off = 0, 0
+        for i, blob in enumerate(blobs):
+            if parsed is not None:
+                descs[i] = parsed[i]                             # (a copy: the caller's descriptor keeps its own four fields)
+            else:
+                rc = lib.ppst_jpeg_parse(blob, len(blob), ctypes.byref(descs[i]))
+                if rc != 0:
+                    raise ValueError("jpeg_decode: file %d: %s" % (i, _lib.JPEG_REFUSALS.get(rc, "error %d" % rc)))
+            d = descs[i]
+            d.file_off, d.out_off = file_off, out_off
+            d.mirror, d.expand_grey = int(bool(mirror[i])) if mirror is not None else 0, int(bool(expand_grey))
+            file_off += (len(blob) + 15) & ~15
+            out_off += (d.H * d.W * (3 if d.ncomp == 3 or expand_grey else 1) + 15) & ~15
+        self.nbytes, self.out_bytes = file_off, out_off
+        self.status = torch.zeros((B,), device=dev, dtype=torch.int32)
+        if B == 0:
+            return
+        ws = lib.ppst_jpeg_decode_ws(descs, B, subseq_words)
+        if ws < 0:
+            raise ValueError("jpeg_decode: subseq_words must be 0 (the default) or 2 .. 65536, got %r" % (subseq_words,))
+        nd = ctypes.sizeof(_lib.JpegDecImage) * B
+        host = torch.empty((file_off + nd,), dtype=torch.uint8).pin_memory()
+        hv = host.numpy()
+        for i, blob in enumerate(blobs):
+            hv[descs[i].file_off:descs[i].file_off + len(blob)] = memoryview(blob)
+        ctypes.memmove(host.data_ptr() + file_off, ctypes.addressof(descs), nd)       # the descriptors ride behind the files
+        # (torch's caching host allocator keeps a pinned block from reuse until the copies recorded on it are done)
+        self.packed = host[:file_off].to(dev, non_blocking=True)
+        self.ddesc = host[file_off:].to(dev, non_blocking=True)
+        self.out = torch.empty((out_off,), device=dev, dtype=torch.uint8)
+        self.work = torch.empty((ws,), device=dev, dtype=torch.uint8)
+
+    def launch(self):
+        if self.B:
+            with torch.cuda.device(self.dev):
+                check(lib.ppst_jpeg_decode(_p(self.packed), self.nbytes, self.descs, _p(self.ddesc), _p(self.out), self.out_bytes,
+                                           _p(self.status), self.B, self.subseq_words, _p(self.work), _stream()), "ppst_jpeg_decode")
+        return self
+
+    def views(self):
+        out = []
+        for i in range(self.B):
+            d = self.descs[i]
+            C = 3 if d.ncomp == 3 or d.expand_grey else 1
+            out.append(self.out[d.out_off:d.out_off + d.H * d.W * C].view(d.H, d.W, C))
+        return out
+
+    def rounds(self):
+        return self.work[:4 * self.B].view(torch.int32).clone() if self.B else self.status.clone()
+
+
+def jpeg_decode(blobs, expand_grey=False, mirror=None, subseq_words=0, device="cuda", rounds=False, parsed=None):
+    """blobs: B baseline JPEG files (bytes) of any sizes and samplings -> (list of B (H,W,C) uint8 views of one device buffer,
+    status (B,) int32 on the device; 0 = decoded: include/ppst_hip.h, csrc/jpeg_decode.hip).  C = 1 for a grey file, 3 for a colour
+    one and for a grey one with ``expand_grey``; ``mirror``: None or B flags, image i comes out with its columns reversed.  The files
+    are packed into one pinned buffer: one host-to-device copy of bytes, one of descriptors.  A file the parser refuses raises
+    ValueError with its reason.  ``rounds``: also return the (B,) int32 tensor of rounds the subsequence iteration took.
+    ``parsed``: the files' descriptors where the caller has them already (``jpeg_parse`` returned 0 for each): nothing is parsed twice."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("jpeg_decode needs a CUDA (HIP) device (no CPU fallback)")
+    call = _JpegDecodeCall(blobs, expand_grey, mirror, subseq_words, dev, parsed).launch()
+    return (call.views(), call.status, call.rounds()) if rounds else (call.views(), call.status)
+
+
 def resample_f32(x, out_h, out_w, clamp=None):
     """x (..., H, W) float32 on the device -> (..., out_h, out_w): Pillow's antialiased bicubic on every plane, both axes in one
     launch (ppst_resample_f32; the fp32 weight tables are imageio.resample_tables_f32).  ``clamp`` = (lo, hi) or None."""

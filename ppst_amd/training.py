@@ -13,7 +13,7 @@ import time
 import numpy as np
 import torch
 
-from . import glue
+from . import glue, ops
 
 
 class IterationCounter:
@@ -111,11 +111,17 @@ class CelebAMaskDataset:
     (base_dataset.py:130-132, CelebAMask_dataset.py:17-18); here ONE draw flips both.  (2) the reference resizes the 'L' label
     image with its BICUBIC transform and then compares ``mask_np == i``; at the dataset's native 512 that is the identity, off
     size it invents label values -- here labels are resized NEAREST.  The next batch is decoded on a worker thread while the
-    current step runs (the reference: DataLoader workers)."""
+    current step runs (the reference: DataLoader workers).  ``decode="device"``: the worker thread only reads the image files and
+    parses their headers; ``next()`` decodes the batch's JPEG files in one call of the HIP decoder (imageio / ops.jpeg_decode), the
+    flip as its ``mirror`` -- the same batches, bit for bit.  Files the decoder does not take go through Pillow as before; labels
+    stay PNG on the host."""
 
     def __init__(self, dataroot, size=512, batch_size=2, rank=0, world=1, device="cuda", seed=0, preprocess="resize",
-                 flip=True, prefetch=True):
+                 flip=True, prefetch=True, decode="host"):
         assert preprocess in ("resize", "scale_shortside")
+        if decode not in ("host", "device"):
+            raise ValueError("decoder must be one of ('host', 'device'), not %r" % (decode,))
+        self.decode = decode
         self.size, self.batch_size, self.rank, self.world, self.device = size, batch_size, rank, world, device
         self.preprocess, self.flip, self.prefetch = preprocess, flip, prefetch
         img_dir, lab_dir = os.path.join(dataroot, "images"), os.path.join(dataroot, "labels")
@@ -138,31 +144,66 @@ class CelebAMaskDataset:
         return order[self.rank::self.world] or order[:1]
 
     def _decode(self, idx):
-        """host side: file -> (uint8 HWC image, PIL 'L' label), optionally mirrored together."""
+        """host side: file -> (uint8 HWC image, PIL 'L' label), optionally mirrored together.  With the device decoder a JPEG file
+        it takes stays bytes here: the image is then (bytes, mirror flag, path, parsed descriptor)."""
         from PIL import Image
         ip, lp = self.pairs[idx]
         try:
-            img = np.asarray(Image.open(ip).convert("RGB"))
+            blob = None
+            if self.decode == "device" and ip.lower().endswith((".jpg", ".jpeg")):
+                with open(ip, "rb") as f:
+                    blob = f.read()
+                rc, desc = ops.jpeg_parse(blob)
+                if rc != 0:
+                    blob = None
+            img = np.asarray(Image.open(ip).convert("RGB")) if blob is None else None
             lab = Image.open(lp).convert("L")
         except OSError as err:                                   # CelebAMask_dataset.py:33-38: retry a random index
             print(err)
             return self._decode(self.rng.randrange(len(self.pairs)))
-        if self.flip and self.rng.random() < 0.5:
-            img = np.ascontiguousarray(img[:, ::-1])
+        flip = bool(self.flip and self.rng.random() < 0.5)
+        if flip:
+            img = np.ascontiguousarray(img[:, ::-1]) if img is not None else None
             lab = lab.transpose(Image.FLIP_LEFT_RIGHT)
-        return img, lab
+        return (img if blob is None else (blob, flip, ip, desc)), lab
+
+    def _decode_on_device(self, batch):
+        """[(image | (bytes, flip, path, descriptor), label)] -> the same with every image a uint8 HWC array or device tensor: one
+        batched call.  A file that comes back with a status goes to Pillow; if Pillow raises OSError too, the sample is replaced by
+        a random index as in ``_decode`` (that draw is then made on the consumer's thread: the order of draws, and so the batches
+        that follow, differ from ``decode="host"`` from such a file on -- with sound files the two give the same batches)."""
+        from PIL import Image
+        todo = [n for n, (img, _) in enumerate(batch) if isinstance(img, tuple)]
+        if not todo:
+            return batch
+        views, status = ops.jpeg_decode([batch[n][0][0] for n in todo], expand_grey=True, mirror=[batch[n][0][1] for n in todo],
+                                        device=self.device, parsed=[batch[n][0][3] for n in todo])
+        batch = list(batch)
+        for n, v, st in zip(todo, views, status.cpu().tolist()):
+            (_, flip, path, _), lab = batch[n]
+            if st != 0:                                          # damaged scan: what the host decoder makes of it
+                try:
+                    v = np.asarray(Image.open(path).convert("RGB"))
+                except OSError as err:                           # CelebAMask_dataset.py:33-38: retry a random index
+                    print(err)
+                    batch[n] = self._decode_on_device([self._decode(self.rng.randrange(len(self.pairs)))])[0]
+                    continue
+                v = np.ascontiguousarray(v[:, ::-1]) if flip else v
+            batch[n] = (v, lab)
+        return batch
 
     def _to_device(self, img, lab):
         from PIL import Image
         from . import imageio
         fn = imageio.preprocess_resize if self.preprocess == "resize" else imageio.preprocess
-        x = fn(torch.from_numpy(img[None]).to(self.device), self.size)[0]
+        img = img if isinstance(img, torch.Tensor) else torch.from_numpy(img).to(self.device)
+        x = fn(img[None], self.size)[0]
         H, W = x.shape[1], x.shape[2]
         lab = torch.from_numpy(np.asarray(lab.resize((W, H), Image.NEAREST)).astype(np.int64))
         return x, lab
 
     def _load(self, idx):
-        return self._to_device(*self._decode(idx))
+        return self._to_device(*self._decode_on_device([self._decode(idx)])[0])
 
     def _decode_batch(self):
         out = []
@@ -200,7 +241,7 @@ class CelebAMaskDataset:
             self._next = (th, box)
         else:
             cur = self._decode_batch()
-        xs, labs = zip(*(self._to_device(img, lab) for img, lab in cur))
+        xs, labs = zip(*(self._to_device(img, lab) for img, lab in self._decode_on_device(cur)))
         labels = torch.stack(labs).to(self.device)
         return {"real_A": torch.stack(xs).contiguous(), "mask_A": glue.one_hot_mask(labels)}
 
