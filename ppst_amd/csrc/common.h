@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 #include "../../include/ppst_hip.h"
 
 // hipGetLastError() is sticky across libraries: clear stale errors (e.g. from the caller's own
@@ -119,6 +120,27 @@ __device__ __forceinline__ void ks_wait(const KSplitDev& k, int tile, int tid) {
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// grid of a grid-stride launch over `work` items
+#define GRID_CAP (256 * 16)
+static inline unsigned grid_for(int64_t work, int threads = 256) {
+  int64_t b = cdiv64(work, threads);
+  if (b > GRID_CAP) b = GRID_CAP;
+  if (b < 1) b = 1;
+  return (unsigned)b;
+}
+// Pixels per block of the per-(b, c) reductions (instance-norm statistics and their backward, GAP/GMP): 1024 for big images, fewer
+// when that would leave CUs idle (>= 2048 blocks wanted, >= 64 pixels per block).  n_partials = ceil(H*W / pix_chunk(B, H*W))
+// everywhere.
+// The chunk depends on the image size ONLY (not on the batch): the grouping of the partial sums -- and so every
+// bit of the statistics -- is the same whether an image is processed alone or inside any batch (the image-sharded grid
+// evaluator relies on it: N ranks reproduce one rank bit for bit).
+static inline int pix_chunk(int B, int64_t hw) {
+  (void)B;
+  int chunk = 1024;
+  while (chunk > 64 && cdiv64(hw, chunk) < 2048) chunk >>= 1;
+  return chunk;
+}
 
 // Division of a 32-bit index by a launch constant without the 64-bit divide sequence hipcc emits
 // for `int64 / int` (about 100 instructions per quotient: it made the elementwise kernels
@@ -241,6 +263,52 @@ template <int ST> __device__ __forceinline__ void st_st1(void* base, int64_t i, 
   if (ST == PPST_ST_F32) ((float*)base)[i] = v;
   else if (ST == PPST_ST_F16) ((unsigned short*)base)[i] = __builtin_bit_cast(unsigned short, (_Float16)v);
   else ((unsigned short*)base)[i] = f2bf(v);
+}
+// V consecutive channels of one pixel, as fp32: V = 4 (16 bytes of an fp32 tensor, 8 of a half one) or V = 1 (the fp32 fallback of a
+// launch that may not go four-wide: the same kernel body, its per-channel arithmetic written once through CV_EACH).  An fp32
+// side tensor (coefficients, pooled vectors, partial sums) is read and written as `*(ChanVec<V>*)p`: one 16-byte access at V = 4.
+template <int V, typename T = float> using ChanVec = HIP_vector_type<T, V>;   // float1 / float4 / int4: elements by [i]
+template <int V, int ST> __device__ __forceinline__ ChanVec<V> cv_ld(const void* base, int64_t i) {
+  static_assert(V == 4 || (V == 1 && ST == PPST_ST_F32), "one channel per thread: fp32 storage only");
+  if constexpr (V == 1) return make_float1(st_ld1<ST>(base, i));
+  else return st_ld4<ST>(base, i);
+}
+template <int V, int ST> __device__ __forceinline__ void cv_st(void* base, int64_t i, const ChanVec<V>& a) {
+  static_assert(V == 4 || (V == 1 && ST == PPST_ST_F32), "one channel per thread: fp32 storage only");
+  if constexpr (V == 1) st_st1<ST>(base, i, a[0]);
+  else st_st4<ST>(base, i, a);
+}
+// run `BODY` once per channel of a V-channel item with the compile-time constant i = 0 .. V-1 (the idiom of PPST_ST_SWITCH below).
+// Expanded as text on purpose: written as `#pragma unroll` loops, or as a lambda called V times, every instance of these kernels
+// compiled to another instruction stream than its hand-written .x/.y/.z/.w form; this gives the same one.
+#define CV_EACH(V, ...)                                                                               \
+  do {                                                                                                \
+    { constexpr int i = 0; __VA_ARGS__; }                                                             \
+    if constexpr ((V) == 4) {                                                                         \
+      { constexpr int i = 1; __VA_ARGS__; }                                                           \
+      { constexpr int i = 2; __VA_ARGS__; }                                                           \
+      { constexpr int i = 3; __VA_ARGS__; }                                                           \
+    }                                                                                                 \
+  } while (0)
+// the (a0, a1) pairs of V channels as a partial-sum tensor [..][C][2] holds them, interleaved per channel
+template <int V> __device__ __forceinline__ void cv_st_pairs(float* o, const ChanVec<V>& a0, const ChanVec<V>& a1) {
+  if constexpr (V == 1) { o[0] = a0[0]; o[1] = a1[0]; }
+  else {
+    ((float4*)o)[0] = make_float4(a0[0], a1[0], a0[1], a1[1]);
+    ((float4*)o)[1] = make_float4(a0[2], a1[2], a0[3], a1[3]);
+  }
+}
+// May a launch go four channels per thread?  `counts`: the channel count and every pixel stride (all multiples of 4); `act`: the
+// tensors of storage type st (4 elements = 16 bytes of fp32, 8 of a half type); `f32`: the fp32 side tensors (16 bytes whatever st
+// is).  Null pointers pass.
+static inline bool four_wide_ok(int st, std::initializer_list<int> counts, std::initializer_list<const void*> act,
+                                std::initializer_list<const void*> f32 = {}) {
+  uintptr_t a = 0, f = 0;
+  for (const void* p : act) a |= (uintptr_t)p;
+  for (const void* p : f32) f |= (uintptr_t)p;
+  for (int n : counts)
+    if (n % 4) return false;
+  return a % (st ? 8 : 16) == 0 && f % 16 == 0;
 }
 static inline int st_bytes(int st) { return st == PPST_ST_F32 ? 4 : 2; }
 // run `BODY` with the compile-time constant ST_ = st (host-side dispatch of the templated launches)

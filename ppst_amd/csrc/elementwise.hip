@@ -4,14 +4,6 @@
 // Each is a single pass at 16 B per lane; algorithmic bytes are listed in DESIGN.md.
 #include "common.h"
 
-#define GRID_CAP (256 * 16)
-static inline unsigned grid_for(int64_t work, int threads = 256) {
-  int64_t b = cdiv64(work, threads);
-  if (b > GRID_CAP) b = GRID_CAP;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
 __device__ __forceinline__ float act_apply(float t, int act, float slope);
 
 // residual that is a half-resolution tensor, bilinearly upsampled x2 on the fly
@@ -114,105 +106,42 @@ extern "C" int ppst_nhwc_to_nchw(const void* x, void* y, int B, int C, int H, in
 }
 
 // --------------------------------------------------- per-(b,c) reductions --
-// One block reduces PIX_CHUNK pixels of one image for all channels and writes a
+// One block reduces PIX_CHUNK = pix_chunk(B, H*W) pixels (common.h) of one image for all channels and writes a
 // partial (v0, v1) per channel: MODE 0 = (sum w*x, sum w*x^2) [instance norm; w = border
 // multiplicity when the statistics are those of the ReplicationPad2d(1)-padded tensor],
 // MODE 1 = (sum m*x, max m*x) [GAP/GMP with optional mask].
-// Pixels per block: 1024 for big images, fewer when that would leave CUs idle (>= 2048 blocks
-// wanted, >= 64 pixels per block).  n_partials = ceil(H*W / pix_chunk(B, H*W)) everywhere.
-// The chunk depends on the image size ONLY (not on the batch): the grouping of the partial sums -- and so every
-// bit of the statistics -- is the same whether an image is processed alone or inside any batch (the image-sharded grid
-// evaluator relies on it: N ranks reproduce one rank bit for bit).
-static inline int pix_chunk(int B, int64_t hw) {
-  (void)B;
-  int chunk = 1024;
-  while (chunk > 64 && cdiv64(hw, chunk) < 2048) chunk >>= 1;
-  return chunk;
-}
-template <int MODE>
-__global__ __launch_bounds__(256) void chan_reduce_kernel(const float* __restrict__ x, const float* __restrict__ mask,
-                                                          float* __restrict__ partial, int H, int W, int C, int ld,
-                                                          int rep_pad, int nchunks, int PIX_CHUNK) {
-  __shared__ float s0[256], s1[256];
-  const int b = blockIdx.y, chunk = blockIdx.x;
-  const int P = H * W;
-  const int pbeg = chunk * PIX_CHUNK;
-  const int pend = (pbeg + PIX_CHUNK < P) ? pbeg + PIX_CHUNK : P;
-  int lanesC = 1;
-  while (lanesC < C && lanesC < 256) lanesC <<= 1;
-  const int rows = 256 / lanesC;
-  const int cl = threadIdx.x % lanesC, pr = threadIdx.x / lanesC;
-  const float* xb = x + (int64_t)b * P * ld;
-  const float* mb = mask ? mask + (int64_t)b * P : nullptr;
-  for (int cbase = 0; cbase < C; cbase += lanesC) {
-    int c = cbase + cl;
-    float a0 = 0.f, a1 = (MODE == 1) ? -INFINITY : 0.f;
-    if (c < C) {
-      for (int p = pbeg + pr; p < pend; p += rows) {
-        float v = xb[(int64_t)p * ld + c];
-        if (MODE == 0) {
-          float w = 1.f;
-          if (rep_pad) {
-            int py = p / W, px = p - py * W;
-            w = (float)((1 + (py == 0) + (py == H - 1)) * (1 + (px == 0) + (px == W - 1)));
-          }
-          a0 += w * v;
-          a1 += w * v * v;
-        } else {
-          if (mb) v *= mb[p];
-          a0 += v;
-          a1 = fmaxf(a1, v);
-        }
-      }
-    }
-    s0[threadIdx.x] = a0;
-    s1[threadIdx.x] = a1;
-    __syncthreads();
-    if (pr == 0 && c < C) {
-      for (int r = 1; r < rows; ++r) {
-        a0 += s0[r * lanesC + cl];
-        a1 = (MODE == 1) ? fmaxf(a1, s1[r * lanesC + cl]) : a1 + s1[r * lanesC + cl];
-      }
-      float* o = partial + (((int64_t)b * nchunks + chunk) * C + c) * 2;
-      o[0] = a0;
-      o[1] = a1;
-    }
-    __syncthreads();
-  }
-}
-
-// 16-B-per-lane version of the reduction (C % 4 == 0): lane = 4 channels, the block's other
-// threads walk different pixel rows; optionally (APPLY) the elements are first transformed
-// like ppst_affine_act and stored, so a producer's apply pass also yields the statistics of
-// its output (no separate read pass for the instance norm that follows).
+// A lane holds V channels (4: 16 B per lane, C % 4 == 0; 1: any C, fp32), the block's other threads walk different pixel
+// rows; optionally (APPLY, four-wide only) the elements are first transformed like ppst_affine_act and stored, so a producer's
+// apply pass also yields the statistics of its output (no separate read pass for the instance norm that follows).
 struct ApplyArgs {
   const float* ss; const float* res; const float* rss; float* y; const float* prelu;
   int res_ld, y_ld, actf; float out_scale;
   int res_up2;  // residual is half-resolution, bilinearly upsampled x2 on the fly
 };
-// (the block's work as a function of (image b, pixel chunk): blockIdx of chan_reduce4_kernel, the level's own numbering inside the
+// (the block's work as a function of (image b, pixel chunk): blockIdx of chan_reduce_kernel, the level's own numbering inside the
 // multi-level GAP/GMP launch)
-template <int MODE, bool APPLY, int XS>
-__device__ __forceinline__ void chan_reduce4_body(const void* __restrict__ x, const float* __restrict__ mask,
-                                                  float* __restrict__ partial, int H, int W, int C, int ld, int rep_pad, int nchunks,
-                                                  const ApplyArgs& ap, int PIX_CHUNK, const FastDiv& d_w, int b, int chunk) {
-  __shared__ float4 s0[256], s1[256];
+template <int MODE, bool APPLY, int V, int XS>
+__device__ __forceinline__ void chan_reduce_body(const void* __restrict__ x, const float* __restrict__ mask,
+                                                 float* __restrict__ partial, int H, int W, int C, int ld, int rep_pad, int nchunks,
+                                                 const ApplyArgs& ap, int PIX_CHUNK, const FastDiv& d_w, int b, int chunk) {
+  static_assert(!APPLY || V == 4, "the apply pass is four-wide only");
+  __shared__ ChanVec<V> s0[256], s1[256];
   const int P = H * W;
   const int pbeg = chunk * PIX_CHUNK;
   const int pend = (pbeg + PIX_CHUNK < P) ? pbeg + PIX_CHUNK : P;
-  const int c4n = C >> 2;
+  const int cvn = C >> (V == 4 ? 2 : 0);
   int lanes = 1;
-  while (lanes < c4n && lanes < 256) lanes <<= 1;
+  while (lanes < cvn && lanes < 256) lanes <<= 1;
   const int rows = 256 / lanes;
   const int cl = threadIdx.x % lanes, pr = threadIdx.x / lanes;
   const float* mb = mask ? mask + (int64_t)b * P : nullptr;
   const int act = ap.actf & 0xff;
   const bool res_first = (ap.actf >> 8) & 1;
   const float slope = (APPLY && act == PPST_ACT_PRELU && ap.prelu) ? ap.prelu[0] : 0.f;
-  for (int cbase = 0; cbase < c4n; cbase += lanes) {
-    const int c = (cbase + cl) * 4;
-    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 a1 = (MODE == 1) ? make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY) : a0;
+  for (int cbase = 0; cbase < cvn; cbase += lanes) {
+    const int c = (cbase + cl) * V;
+    ChanVec<V> a0 = {}, a1 = {};
+    if (MODE == 1) CV_EACH(V, a1[i] = -INFINITY);
     if (c < C) {
       float4 sa = make_float4(1.f, 1.f, 1.f, 1.f), sb = make_float4(0.f, 0.f, 0.f, 0.f);
       float4 ra = sa, rb = sb;
@@ -230,9 +159,9 @@ __device__ __forceinline__ void chan_reduce4_body(const void* __restrict__ x, co
         const int64_t bp = (int64_t)b * P + p;
         unsigned pxu = 0;
         const int py = (APPLY || MODE == 0) ? (int)fd_divmod((unsigned)p, d_w, pxu) : 0, px = (int)pxu;
-        float4 v = st_ld4<XS>(x, bp * ld + c);
-        if (APPLY) {
-          float t[4] = {sa.x * v.x + sb.x, sa.y * v.y + sb.y, sa.z * v.z + sb.z, sa.w * v.w + sb.w};
+        ChanVec<V> v = cv_ld<V, XS>(x, bp * ld + c);
+        if constexpr (APPLY) {
+          float t[4] = {sa.x * v[0] + sb.x, sa.y * v[1] + sb.y, sa.z * v[2] + sb.z, sa.w * v[3] + sb.w};
           float r[4] = {0.f, 0.f, 0.f, 0.f};
           if (ap.res) {
             float4 rv;
@@ -246,20 +175,22 @@ __device__ __forceinline__ void chan_reduce4_body(const void* __restrict__ x, co
             if (res_first) tt += r[i];
             tt = act_apply(tt, act, slope);
             if (!res_first) tt += r[i];
-            t[i] = tt * ap.out_scale;
+            v[i] = tt * ap.out_scale;
           }
-          v = make_float4(t[0], t[1], t[2], t[3]);
-          *(float4*)(ap.y + bp * ap.y_ld + c) = v;
+          *(ChanVec<V>*)(ap.y + bp * ap.y_ld + c) = v;
         }
         if (MODE == 0) {
           float w = 1.f;
           if (rep_pad) w = (float)((1 + (py == 0) + (py == H - 1)) * (1 + (px == 0) + (px == W - 1)));
-          a0.x += w * v.x; a0.y += w * v.y; a0.z += w * v.z; a0.w += w * v.w;
-          a1.x += w * v.x * v.x; a1.y += w * v.y * v.y; a1.z += w * v.z * v.z; a1.w += w * v.w * v.w;
+          CV_EACH(V, a0[i] += w * v[i]);
+          CV_EACH(V, a1[i] += w * v[i] * v[i]);
         } else {
-          if (mb) { float m = mb[p]; v.x *= m; v.y *= m; v.z *= m; v.w *= m; }
-          a0.x += v.x; a0.y += v.y; a0.z += v.z; a0.w += v.w;
-          a1.x = fmaxf(a1.x, v.x); a1.y = fmaxf(a1.y, v.y); a1.z = fmaxf(a1.z, v.z); a1.w = fmaxf(a1.w, v.w);
+          if (mb) {
+            const float m = mb[p];
+            CV_EACH(V, v[i] *= m);
+          }
+          CV_EACH(V, a0[i] += v[i]);
+          CV_EACH(V, a1[i] = fmaxf(a1[i], v[i]));
         }
       }
     }
@@ -268,23 +199,20 @@ __device__ __forceinline__ void chan_reduce4_body(const void* __restrict__ x, co
     __syncthreads();
     if (pr == 0 && c < C) {
       for (int r = 1; r < rows; ++r) {
-        float4 u = s0[r * lanes + cl], w = s1[r * lanes + cl];
-        a0.x += u.x; a0.y += u.y; a0.z += u.z; a0.w += u.w;
-        if (MODE == 1) { a1.x = fmaxf(a1.x, w.x); a1.y = fmaxf(a1.y, w.y); a1.z = fmaxf(a1.z, w.z); a1.w = fmaxf(a1.w, w.w); }
-        else { a1.x += w.x; a1.y += w.y; a1.z += w.z; a1.w += w.w; }
+        const ChanVec<V> u = s0[r * lanes + cl], w = s1[r * lanes + cl];
+        CV_EACH(V, a0[i] += u[i]);
+        CV_EACH(V, a1[i] = (MODE == 1) ? fmaxf(a1[i], w[i]) : a1[i] + w[i]);
       }
-      float4* o = (float4*)(partial + (((int64_t)b * nchunks + chunk) * C + c) * 2);
-      o[0] = make_float4(a0.x, a1.x, a0.y, a1.y);
-      o[1] = make_float4(a0.z, a1.z, a0.w, a1.w);
+      cv_st_pairs<V>(partial + (((int64_t)b * nchunks + chunk) * C + c) * 2, a0, a1);
     }
     __syncthreads();
   }
 }
-template <int MODE, bool APPLY, int XS = PPST_ST_F32>
-__global__ __launch_bounds__(256) void chan_reduce4_kernel(const void* __restrict__ x, const float* __restrict__ mask,
-                                                           float* __restrict__ partial, int H, int W, int C, int ld,
-                                                           int rep_pad, int nchunks, ApplyArgs ap, int PIX_CHUNK, FastDiv d_w) {
-  chan_reduce4_body<MODE, APPLY, XS>(x, mask, partial, H, W, C, ld, rep_pad, nchunks, ap, PIX_CHUNK, d_w, blockIdx.y, blockIdx.x);
+template <int MODE, bool APPLY, int V, int XS = PPST_ST_F32>
+__global__ __launch_bounds__(256) void chan_reduce_kernel(const void* __restrict__ x, const float* __restrict__ mask,
+                                                          float* __restrict__ partial, int H, int W, int C, int ld,
+                                                          int rep_pad, int nchunks, ApplyArgs ap, int PIX_CHUNK, FastDiv d_w) {
+  chan_reduce_body<MODE, APPLY, V, XS>(x, mask, partial, H, W, C, ld, rep_pad, nchunks, ap, PIX_CHUNK, d_w, blockIdx.y, blockIdx.x);
 }
 
 extern "C" int ppst_in_stats(const void* x, void* partial, int B, int H, int W, int C, int ld, int rep_pad,
@@ -296,14 +224,13 @@ extern "C" int ppst_in_stats(const void* x, void* partial, int B, int H, int W, 
   if (!x && !partial) return PPST_OK;  // size query
   if (B == 0) return PPST_OK;
   if (!x || !partial) return PPST_ENULL;
-  if (C % 4 == 0 && ld % 4 == 0 && ((uintptr_t)x % 16) == 0) {
-    ApplyArgs ap = {};
-    PPST_LAUNCH((chan_reduce4_kernel<0, false>), dim3(nchunks, B), dim3(256), 0, as_stream(stream), x,
+  const ApplyArgs ap = {};
+  if (four_wide_ok(PPST_ST_F32, {C, ld}, {x}))
+    PPST_LAUNCH((chan_reduce_kernel<0, false, 4>), dim3(nchunks, B), dim3(256), 0, as_stream(stream), x,
                 (const float*)nullptr, (float*)partial, H, W, C, ld, rep_pad, nchunks, ap, chunk, make_fastdiv(W));
-  } else {
-    PPST_LAUNCH(chan_reduce_kernel<0>, dim3(nchunks, B), dim3(256), 0, as_stream(stream), (const float*)x,
-                (const float*)nullptr, (float*)partial, H, W, C, ld, rep_pad, nchunks, chunk);
-  }
+  else
+    PPST_LAUNCH((chan_reduce_kernel<0, false, 1>), dim3(nchunks, B), dim3(256), 0, as_stream(stream), x,
+                (const float*)nullptr, (float*)partial, H, W, C, ld, rep_pad, nchunks, ap, chunk, make_fastdiv(W));
   return PPST_LAUNCH_CHECK();
 }
 
@@ -470,8 +397,7 @@ extern "C" int ppst_affine_act_st(const void* x, const void* scale_shift, const 
   if (B == 0) return PPST_OK;
   if (!x || !y) return PPST_ENULL;
   if (res_up2_w > 0 && (x_ld % 4 || y_ld % 4 || res_ld % 4)) return PPST_EINVAL;
-  bool vec = C % 4 == 0 && x_ld % 4 == 0 && y_ld % 4 == 0 && (!res || res_ld % 4 == 0) &&
-             (((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) % (x_st || y_st ? 8 : 16) == 0);
+  const bool vec = four_wide_ok(x_st | y_st, {C, x_ld, y_ld, res ? res_ld : 0}, {x, y, res});
   if ((x_st || y_st) && !vec) return PPST_EINVAL;     // half storage: the vector forms only
   if (res_up2_w > 0 && !vec) return PPST_EINVAL;      // res_up2: the vector forms only (the one-channel form reads res at full resolution)
   // 8 channels per thread when a half tensor is involved and everything is 16-byte addressable
@@ -533,7 +459,7 @@ extern "C" int ppst_affine_act_stats(const void* x, const void* scale_shift, con
   ap.prelu = (const float*)prelu; ap.res_ld = res_ld; ap.y_ld = y_ld; ap.actf = act; ap.out_scale = out_scale;
   ap.res_up2 = (res && res_up2) ? 1 : 0;
   if (ap.res_up2 && (H % 2 || W % 2)) return PPST_EINVAL;
-  PPST_LAUNCH((chan_reduce4_kernel<0, true>), dim3(nchunks, B), dim3(256), 0, as_stream(stream), x,
+  PPST_LAUNCH((chan_reduce_kernel<0, true, 4>), dim3(nchunks, B), dim3(256), 0, as_stream(stream), x,
               (const float*)nullptr, (float*)partial, H, W, C, x_ld, rep_pad, nchunks, ap, chunk, make_fastdiv(W));
   return PPST_LAUNCH_CHECK();
 }
@@ -593,22 +519,13 @@ extern "C" int ppst_gap_gmp_st(const void* x, const void* mask, void* out, void*
   if ((int64_t)H * W > 0x7fffffffll) return PPST_EINVAL;
   const int chunk = pix_chunk(B, (int64_t)H * W);
   int nchunks = (int)cdiv64((int64_t)H * W, chunk);
-  if (x_st) {
-    ApplyArgs ap = {};
-    if (x_st == PPST_ST_F16)
-      PPST_LAUNCH((chan_reduce4_kernel<1, false, PPST_ST_F16>), dim3(nchunks, B), dim3(256), 0, as_stream(stream), x,
-                  (const float*)mask, (float*)ws, H, W, C, ld, 0, nchunks, ap, chunk, make_fastdiv(W));
-    else
-      PPST_LAUNCH((chan_reduce4_kernel<1, false, PPST_ST_BF16>), dim3(nchunks, B), dim3(256), 0, as_stream(stream), x,
-                  (const float*)mask, (float*)ws, H, W, C, ld, 0, nchunks, ap, chunk, make_fastdiv(W));
-  } else if (C % 4 == 0 && ld % 4 == 0 && ((uintptr_t)x % 16) == 0) {
-    ApplyArgs ap = {};
-    PPST_LAUNCH((chan_reduce4_kernel<1, false>), dim3(nchunks, B), dim3(256), 0, as_stream(stream), x,
+  const ApplyArgs ap = {};
+  if (four_wide_ok(x_st, {C, ld}, {x}))      // (a half tensor that fails this was refused above)
+    PPST_ST_SWITCH(x_st, PPST_LAUNCH((chan_reduce_kernel<1, false, 4, ST_>), dim3(nchunks, B), dim3(256), 0, as_stream(stream), x,
+                                     (const float*)mask, (float*)ws, H, W, C, ld, 0, nchunks, ap, chunk, make_fastdiv(W)));
+  else
+    PPST_LAUNCH((chan_reduce_kernel<1, false, 1>), dim3(nchunks, B), dim3(256), 0, as_stream(stream), x,
                 (const float*)mask, (float*)ws, H, W, C, ld, 0, nchunks, ap, chunk, make_fastdiv(W));
-  } else {
-    PPST_LAUNCH(chan_reduce_kernel<1>, dim3(nchunks, B), dim3(256), 0, as_stream(stream), (const float*)x,
-                (const float*)mask, (float*)ws, H, W, C, ld, 0, nchunks, chunk);
-  }
   int e = PPST_LAUNCH_CHECK();
   if (e) return e;
   PPST_LAUNCH(gap_gmp_finalize_kernel, dim3(B * cdiv(C, FIN_CH)), dim3(256), 0, as_stream(stream),
@@ -622,7 +539,7 @@ extern "C" int ppst_gap_gmp(const void* x, const void* mask, void* out, void* ws
 
 // ---- GAP || GMP of SEVERAL feature maps in two launches (the four pyramid levels of an E2 pass, plain / warped / masked: each level
 // alone is 8 - 2048 blocks and two launches).  Level i owns blocks [blk0[i], blk0[i + 1]) of the reduction, numbered (image, chunk)
-// with ITS chunk size pix_chunk(hw_i), and runs chan_reduce4_kernel<1, false>'s body on them; its partials lie at its own offset of
+// with ITS chunk size pix_chunk(hw_i), and runs chan_reduce_kernel<1, false, 4>'s body on them; its partials lie at its own offset of
 // the workspace; the second launch runs gap_gmp_finalize_kernel's body per level.  Same chunking, same lane map, same order of
 // every sum as ppst_gap_gmp_st on the level alone: the values are those, bit for bit, for any batch.
 struct GapLevelSeg { const void* x; const float* mask; float* partial; int H, W, C, ld, nchunks, chunk, pad_; };
@@ -638,7 +555,7 @@ __global__ __launch_bounds__(256) void gap_gmp_levels_kernel(const GapLevelGroup
   const int b = blk / q.nchunks;
   const ApplyArgs ap = {};
   const FastDiv d_w = {1u, 0u, 0u, 0u};  // (the GAP/GMP mode takes no pixel coordinates)
-  chan_reduce4_body<1, false, XS>(q.x, q.mask, q.partial, q.H, q.W, q.C, q.ld, 0, q.nchunks, ap, q.chunk, d_w, b, blk - b * q.nchunks);
+  chan_reduce_body<1, false, 4, XS>(q.x, q.mask, q.partial, q.H, q.W, q.C, q.ld, 0, q.nchunks, ap, q.chunk, d_w, b, blk - b * q.nchunks);
 }
 struct GapFinSeg { const float* partial; float* out; double count; int n_partials, C; };
 struct GapFinGroup { GapFinSeg seg[PPST_GROUP_MAX]; int blk0[PPST_GROUP_MAX]; };
@@ -702,7 +619,7 @@ extern "C" int ppst_gap_gmp_multi_level(const ppst_gap_gmp_level* lv, int n, int
 // ---- GAP || GMP of x * mask for SEVERAL masks in one read of x (round 5; the masked E2 heads of encoder_col.py:217-245 pool every
 // feature map four times -- unmasked and under each of the three class masks).  heads: h = 0 the plain pooling (with_plain), then one
 // per mask channel; masks [B][hw][nm] (the NHWC planes of the one-hot pyramid), nm <= 3.  Same block geometry, lane map and summation
-// order per head as chan_reduce4_kernel<1>: a head's values equal the single-head launch's bit for bit.
+// order per head as chan_reduce_kernel<1, false, 4>: a head's values equal the single-head launch's bit for bit.
 // partial [(h * B + b)][nchunks][C][2] -> gap_gmp_finalize_kernel over heads * B rows.
 #define GGM_MAXH 4
 template <int XS = PPST_ST_F32>

@@ -646,7 +646,7 @@ static int wgrad_check(const void* x, const void* dy, const void* steps, const v
     return PPST_EINVAL;
   if (B == 0) return PPST_OK;
   if (!x || !dy || !steps || !chunk_start || !partial) return PPST_ENULL;
-  *aligned = cout % 4 == 0 && dy_ld % 4 == 0 && in_ld % 4 == 0 && ((uintptr_t)x | (uintptr_t)dy) % 16 == 0;
+  *aligned = four_wide_ok(PPST_ST_F32, {cout, dy_ld, in_ld}, {x, dy});
   return PPST_OK;
 }
 // the 2 x 32-pixel tiles of the output, dealt out to ``splits`` pixel ranges
@@ -830,6 +830,7 @@ __global__ __launch_bounds__(256) void wgrad_small_cin_kernel(const float* __res
 }
 // float4 form for cout = 4 Q with Q a divisor of 256 (FromRGB: cout = 32 -> the scalar form above ran half its lanes, 128 B per
 // wave load): thread = (pixel slot tid / Q, channel quad tid % Q); 256 / Q pixels per block pass, four passes in flight.
+// (Another thread-to-pixel map and so another order of the sums than the scalar form: not a V = 4 copy of it.)
 template <int ST = PPST_ST_F32>     // storage type of dy (x: the fp32 image / RGB gradient)
 __global__ __launch_bounds__(256) void wgrad_small_cin4_kernel(const float* __restrict__ x, const void* __restrict__ dy,
                                                                float* __restrict__ partial, int64_t npix, int cin, int in_ld, int Q,
@@ -918,7 +919,7 @@ extern "C" int ppst_wgrad_small_cin_st(const void* x, const void* dy, void* dw, 
   if (npix <= 0 || cin <= 0 || cin > 4 || in_ld < cin || cout <= 0) return PPST_EINVAL;
   if (!x || !dy || !dw || !ws) return PPST_ENULL;
   int nblocks = (int)cdiv64(npix, WSC_PIX);
-  if (cout % 4 == 0 && cout / 4 <= 256 && 256 % (cout / 4) == 0 && (uintptr_t)dy % (dy_st ? 8 : 16) == 0)
+  if (four_wide_ok(dy_st, {cout}, {dy}) && cout / 4 <= 256 && 256 % (cout / 4) == 0)
     PPST_ST_SWITCH(dy_st, PPST_LAUNCH(wgrad_small_cin4_kernel<ST_>, dim3(nblocks), dim3(256), 0, as_stream(stream), (const float*)x, dy,
                                       (float*)ws, npix, cin, in_ld, cout / 4, (int64_t)WSC_PIX));
   else if (dy_st)
@@ -957,6 +958,7 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
   }
 }
 // 16-B-per-lane version (C % 4 == 0, ld % 4 == 0): lane = 4 columns, 4 rows in flight per thread
+// (four accumulators per column: another order of the sums than colsum_partial_kernel, not a V = 4 copy of it)
 template <int ST = PPST_ST_F32>
 __global__ __launch_bounds__(256) void colsum4_partial_kernel(const void* __restrict__ x, float* __restrict__ partial, int64_t rows,
                                                               int C, int ld, int64_t rows_per_block) {
@@ -1005,7 +1007,7 @@ extern "C" int ppst_colsum_st(const void* x, void* out, void* ws, int64_t rows, 
   if (rows <= 0 || C <= 0 || ld < C) return PPST_EINVAL;
   if (!x || !out || !ws) return PPST_ENULL;
   int nblocks = (int)cdiv64(rows, 2048);
-  if (C % 4 == 0 && ld % 4 == 0 && ((uintptr_t)x % (st ? 8 : 16)) == 0 && ((uintptr_t)ws % 16) == 0)
+  if (four_wide_ok(st, {C, ld}, {x}, {ws}))
     PPST_ST_SWITCH(st, PPST_LAUNCH(colsum4_partial_kernel<ST_>, dim3(nblocks), dim3(256), 0, as_stream(stream), x, (float*)ws, rows, C, ld,
                                    (int64_t)2048));
   else if (st)

@@ -7,106 +7,55 @@
 // conv_mfma.hip / train.hip driven by other step tables.
 #include "common.h"
 
-#define TG_GRID_CAP (256 * 16)
-static inline unsigned tg_grid(int64_t work, int threads = 256) {
-  int64_t b = cdiv64(work, threads);
-  if (b > TG_GRID_CAP) b = TG_GRID_CAP;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
 __device__ __forceinline__ float lrelu_gate(float ref) { return (ref > 0.f ? 1.f : 0.2f) * 1.41421356237309515f; }
-
-static inline int tg_pix_chunk(int B, int64_t hw) {   // batch-independent, like pix_chunk (elementwise.hip)
-  (void)B;
-  int chunk = 1024;
-  while (chunk > 64 && cdiv64(hw, chunk) < 2048) chunk >>= 1;
-  return chunk;
-}
 
 // ---------------------------------------------------- instance norm backward --
 // out = n * A + s1,  n = (y - mean) * rstd  (A = style s0 + 1 or 1).  With g = dL/dout:
 //   dy = rstd*A * (g - mean(g) - n * mean(g*n)),  ds0 = sum g*n,  ds1 = sum g.
 // Pass 1 (this kernel): per-(b, c) partial sums (sum g', sum g'*y) over pixel chunks, g' = g or, with `gate`
 // (ConvLayer norm='in': the norm precedes the activation), g * lrelu'(gate).
-__global__ __launch_bounds__(256) void dual_stats_kernel(const float* __restrict__ g, const float* __restrict__ y,
-                                                         const float* __restrict__ gate, float* __restrict__ partial, int P, int C,
-                                                         int g_ld, int y_ld, int gate_ld, int nchunks, int PIX_CHUNK) {
-  __shared__ float s0[256], s1[256];
-  const int b = blockIdx.y, chunk = blockIdx.x;
-  const int pbeg = chunk * PIX_CHUNK;
-  const int pend = (pbeg + PIX_CHUNK < P) ? pbeg + PIX_CHUNK : P;
-  int lanesC = 1;
-  while (lanesC < C && lanesC < 256) lanesC <<= 1;
-  const int rows = 256 / lanesC;
-  const int cl = threadIdx.x % lanesC, pr = threadIdx.x / lanesC;
-  for (int cbase = 0; cbase < C; cbase += lanesC) {
-    const int c = cbase + cl;
-    float a0 = 0.f, a1 = 0.f;
-    if (c < C) {
-      for (int p = pbeg + pr; p < pend; p += rows) {
-        const int64_t bp = (int64_t)b * P + p;
-        float gv = g[bp * g_ld + c];
-        const float yv = y[bp * y_ld + c];
-        if (gate) gv *= lrelu_gate(gate[bp * gate_ld + c]);
-        a0 += gv;
-        a1 += gv * yv;
-      }
-    }
-    s0[threadIdx.x] = a0;
-    s1[threadIdx.x] = a1;
-    __syncthreads();
-    if (pr == 0 && c < C) {
-      for (int r = 1; r < rows; ++r) { a0 += s0[r * lanesC + cl]; a1 += s1[r * lanesC + cl]; }
-      float* o = partial + (((int64_t)b * nchunks + chunk) * C + c) * 2;
-      o[0] = a0;
-      o[1] = a1;
-    }
-    __syncthreads();
-  }
-}
-// four channels per thread (C and the pixel strides multiples of 4, 16-byte aligned tensors: every tensor of the train step)
+// V channels per thread (common.h): 4 where C and the pixel strides are multiples of 4 and the tensors aligned (every tensor of the
+// train step), else 1; CV and the strides are counted in V-channel items.
 // ST (round 5: half-precision storage of the TRAINING activations and their gradients in precision mode 1): storage type of g, y and
 // gate; the sums are fp32 either way
-template <int ST = PPST_ST_F32>
-__global__ __launch_bounds__(256) void dual_stats4_kernel(const void* __restrict__ g, const void* __restrict__ y,
-                                                          const void* __restrict__ gate, float* __restrict__ partial, int P, int C4,
-                                                          int g_ld4, int y_ld4, int gate_ld4, int nchunks, int PIX_CHUNK) {
-  __shared__ float4 s0[256], s1[256];
+template <int V, int ST>
+__global__ __launch_bounds__(256) void dual_stats_kernel(const void* __restrict__ g, const void* __restrict__ y,
+                                                         const void* __restrict__ gate, float* __restrict__ partial, int P, int CV,
+                                                         int g_ldv, int y_ldv, int gate_ldv, int nchunks, int PIX_CHUNK) {
+  __shared__ ChanVec<V> s0[256], s1[256];
   const int b = blockIdx.y, chunk = blockIdx.x;
   const int pbeg = chunk * PIX_CHUNK;
   const int pend = (pbeg + PIX_CHUNK < P) ? pbeg + PIX_CHUNK : P;
   int lanesC = 1;
-  while (lanesC < C4 && lanesC < 256) lanesC <<= 1;
+  while (lanesC < CV && lanesC < 256) lanesC <<= 1;
   const int rows = 256 / lanesC;
   const int cl = threadIdx.x % lanesC, pr = threadIdx.x / lanesC;
-  for (int cbase = 0; cbase < C4; cbase += lanesC) {
+  for (int cbase = 0; cbase < CV; cbase += lanesC) {
     const int c = cbase + cl;
-    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-    if (c < C4) {
+    ChanVec<V> a0 = {}, a1 = {};
+    if (c < CV) {
       for (int p = pbeg + pr; p < pend; p += rows) {
         const int64_t bp = (int64_t)b * P + p;
-        float4 gv = st_ld4<ST>(g, (bp * g_ld4 + c) * 4);
-        const float4 yv = st_ld4<ST>(y, (bp * y_ld4 + c) * 4);
+        ChanVec<V> gv = cv_ld<V, ST>(g, (bp * g_ldv + c) * V);
+        const ChanVec<V> yv = cv_ld<V, ST>(y, (bp * y_ldv + c) * V);
         if (gate) {
-          const float4 t = st_ld4<ST>(gate, (bp * gate_ld4 + c) * 4);
-          gv.x *= lrelu_gate(t.x); gv.y *= lrelu_gate(t.y); gv.z *= lrelu_gate(t.z); gv.w *= lrelu_gate(t.w);
+          const ChanVec<V> t = cv_ld<V, ST>(gate, (bp * gate_ldv + c) * V);
+          CV_EACH(V, gv[i] *= lrelu_gate(t[i]));
         }
-        a0.x += gv.x; a0.y += gv.y; a0.z += gv.z; a0.w += gv.w;
-        a1.x += gv.x * yv.x; a1.y += gv.y * yv.y; a1.z += gv.z * yv.z; a1.w += gv.w * yv.w;
+        CV_EACH(V, a0[i] += gv[i]);
+        CV_EACH(V, a1[i] += gv[i] * yv[i]);
       }
     }
     s0[threadIdx.x] = a0;
     s1[threadIdx.x] = a1;
     __syncthreads();
-    if (pr == 0 && c < C4) {
+    if (pr == 0 && c < CV) {
       for (int r = 1; r < rows; ++r) {
-        const float4 u = s0[r * lanesC + cl], w = s1[r * lanesC + cl];
-        a0.x += u.x; a0.y += u.y; a0.z += u.z; a0.w += u.w;
-        a1.x += w.x; a1.y += w.y; a1.z += w.z; a1.w += w.w;
+        const ChanVec<V> u = s0[r * lanesC + cl], w = s1[r * lanesC + cl];
+        CV_EACH(V, a0[i] += u[i]);
+        CV_EACH(V, a1[i] += w[i]);
       }
-      float4* o = (float4*)(partial + (((int64_t)b * nchunks + chunk) * C4 * 4 + c * 4) * 2);
-      o[0] = make_float4(a0.x, a1.x, a0.y, a1.y);
-      o[1] = make_float4(a0.z, a1.z, a0.w, a1.w);
+      cv_st_pairs<V>(partial + (((int64_t)b * nchunks + chunk) * CV * V + c * V) * 2, a0, a1);
     }
     __syncthreads();
   }
@@ -115,21 +64,20 @@ extern "C" int ppst_dual_stats_st(const void* g, const void* y, const void* gate
                                   int y_ld, int gate_ld, int* n_partials, int st, void* stream) {
   if ((unsigned)st > 2u) return PPST_EINVAL;
   if (B < 0 || hw <= 0 || hw > 0x7fffffffll || C <= 0 || g_ld < C || y_ld < C || (gate && gate_ld < C)) return PPST_EINVAL;
-  const int chunk = tg_pix_chunk(B, hw);
+  const int chunk = pix_chunk(B, hw);
   const int nchunks = (int)cdiv64(hw, chunk);
   if (n_partials) *n_partials = nchunks;
   if (!g && !partial) return PPST_OK;  // size query
   if (B == 0) return PPST_OK;
   if (!g || !y || !partial) return PPST_ENULL;
-  if (C % 4 == 0 && g_ld % 4 == 0 && y_ld % 4 == 0 && (!gate || gate_ld % 4 == 0) &&
-      ((uintptr_t)g | (uintptr_t)y | (uintptr_t)gate) % (st ? 8 : 16) == 0 && (uintptr_t)partial % 16 == 0) {
-    PPST_ST_SWITCH(st, PPST_LAUNCH(dual_stats4_kernel<ST_>, dim3(nchunks, B), dim3(256), 0, as_stream(stream), g, y, gate, (float*)partial,
-                                   (int)hw, C / 4, g_ld / 4, y_ld / 4, gate_ld / 4, nchunks, chunk));
+  if (four_wide_ok(st, {C, g_ld, y_ld, gate ? gate_ld : 0}, {g, y, gate}, {partial})) {
+    PPST_ST_SWITCH(st, PPST_LAUNCH((dual_stats_kernel<4, ST_>), dim3(nchunks, B), dim3(256), 0, as_stream(stream), g, y, gate,
+                                   (float*)partial, (int)hw, C / 4, g_ld / 4, y_ld / 4, gate_ld / 4, nchunks, chunk));
     return PPST_LAUNCH_CHECK();
   }
   if (st) return PPST_EINVAL;      // half storage: the four-channel form only
-  PPST_LAUNCH(dual_stats_kernel, dim3(nchunks, B), dim3(256), 0, as_stream(stream), (const float*)g, (const float*)y,
-              (const float*)gate, (float*)partial, (int)hw, C, g_ld, y_ld, gate_ld, nchunks, chunk);
+  PPST_LAUNCH((dual_stats_kernel<1, PPST_ST_F32>), dim3(nchunks, B), dim3(256), 0, as_stream(stream), g, y, gate, (float*)partial,
+              (int)hw, C, g_ld, y_ld, gate_ld, nchunks, chunk);
   return PPST_LAUNCH_CHECK();
 }
 
@@ -207,49 +155,40 @@ extern "C" int ppst_in_bwd_finalize(const void* partial, int n_partials, const v
 
 // Pass 3: dx = post * (k0 * g' + k1 * y + k2);  g' = g * lrelu'(gate) if gate (norm before activation);
 // post = lrelu'(y) if post_gate (StyledConv: the activation precedes the norm, so y is its output) else 1.
-__global__ __launch_bounds__(256) void in_bwd_apply_kernel(const float* __restrict__ g, const float* __restrict__ y,
-                                                           const float* __restrict__ gate, const float* __restrict__ coef,
-                                                           float* __restrict__ dx, unsigned hw, int C, int g_ld, int y_ld, int gate_ld,
-                                                           int dx_ld, int post_gate, unsigned total, FastDiv d_c, FastDiv d_hw) {
+template <int V, int ST>
+__global__ __launch_bounds__(256) void in_bwd_apply_kernel(const void* __restrict__ g, const void* __restrict__ y,
+                                                           const void* __restrict__ gate, const float* __restrict__ coef,
+                                                           void* __restrict__ dx, unsigned hw, int CV, int g_ldv, int y_ldv,
+                                                           int gate_ldv, int dx_ldv, int post_gate, unsigned total, FastDiv d_c,
+                                                           FastDiv d_hw) {
   for (uint64_t t64 = (uint64_t)blockIdx.x * 256 + threadIdx.x; t64 < total; t64 += (uint64_t)gridDim.x * 256) {
     unsigned cq;
     const unsigned bpu = fd_divmod((unsigned)t64, d_c, cq);
     const int c = (int)cq;
     const int b = (int)fd_div(bpu, d_hw);
     const int64_t bp = bpu;
-    const float* k = coef + ((int64_t)b * C + c) * 4;
-    float gv = g[bp * g_ld + c];
-    const float yv = y[bp * y_ld + c];
-    if (gate) gv *= lrelu_gate(gate[bp * gate_ld + c]);
-    float o = k[0] * gv + k[1] * yv + k[2];
-    if (post_gate) o *= lrelu_gate(yv);
-    dx[bp * dx_ld + c] = o;
-  }
-}
-template <int ST = PPST_ST_F32>
-__global__ __launch_bounds__(256) void in_bwd_apply4_kernel(const void* __restrict__ g, const void* __restrict__ y,
-                                                            const void* __restrict__ gate, const float4* __restrict__ coef,
-                                                            void* __restrict__ dx, unsigned hw, int C4, int g_ld4, int y_ld4,
-                                                            int gate_ld4, int dx_ld4, int post_gate, unsigned total, FastDiv d_c,
-                                                            FastDiv d_hw) {
-  for (uint64_t t64 = (uint64_t)blockIdx.x * 256 + threadIdx.x; t64 < total; t64 += (uint64_t)gridDim.x * 256) {
-    unsigned cq;
-    const unsigned bpu = fd_divmod((unsigned)t64, d_c, cq);
-    const int c = (int)cq;
-    const int b = (int)fd_div(bpu, d_hw);
-    const int64_t bp = bpu;
-    const float4* k = coef + ((int64_t)b * C4 + c) * 4;      // (k0, k1, k2, -) of the thread's four channels
-    const float4 k0 = k[0], k1 = k[1], k2 = k[2], k3 = k[3];
-    float4 gv = st_ld4<ST>(g, (bp * g_ld4 + c) * 4);
-    const float4 yv = st_ld4<ST>(y, (bp * y_ld4 + c) * 4);
+    const float* kp = coef + ((int64_t)b * CV + c) * V * 4;      // (k0, k1, k2, -) of each of the thread's channels
+    float k[V][3];
+    if constexpr (V == 4) CV_EACH(V, const float4 q = ((const float4*)kp)[i]; k[i][0] = q.x; k[i][1] = q.y; k[i][2] = q.z);   // (coef 16-byte aligned)
+    else CV_EACH(V, k[i][0] = kp[0]; k[i][1] = kp[1]; k[i][2] = kp[2]);
+    ChanVec<V> gv = cv_ld<V, ST>(g, (bp * g_ldv + c) * V);
+    const ChanVec<V> yv = cv_ld<V, ST>(y, (bp * y_ldv + c) * V);
     if (gate) {
-      const float4 t = st_ld4<ST>(gate, (bp * gate_ld4 + c) * 4);
-      gv.x *= lrelu_gate(t.x); gv.y *= lrelu_gate(t.y); gv.z *= lrelu_gate(t.z); gv.w *= lrelu_gate(t.w);
+      const ChanVec<V> t = cv_ld<V, ST>(gate, (bp * gate_ldv + c) * V);
+      CV_EACH(V, gv[i] *= lrelu_gate(t[i]));
     }
-    float4 o = make_float4(k0.x * gv.x + k0.y * yv.x + k0.z, k1.x * gv.y + k1.y * yv.y + k1.z, k2.x * gv.z + k2.y * yv.z + k2.z,
-                           k3.x * gv.w + k3.y * yv.w + k3.z);
-    if (post_gate) { o.x *= lrelu_gate(yv.x); o.y *= lrelu_gate(yv.y); o.z *= lrelu_gate(yv.z); o.w *= lrelu_gate(yv.w); }
-    st_st4<ST>(dx, (bp * dx_ld4 + c) * 4, o);
+    ChanVec<V> o;
+    // The two widths have always rounded k0 g' + k1 y differently: hipcc fused the second product of the four-wide form and packed
+    // the two products of the one-channel form into one multiply.  Both roundings are spelled out so that neither moves (left to
+    // the compiler, the merged body kept them for fp32 and fused the other product in the half-storage instances).
+    if constexpr (V == 4) {
+      CV_EACH(V, o[i] = fmaf(k[i][1], yv[i], k[i][0] * gv[i]) + k[i][2]);
+    } else {
+#pragma clang fp contract(off)
+      o[0] = k[0][0] * gv[0] + k[0][1] * yv[0] + k[0][2];
+    }
+    if (post_gate) CV_EACH(V, o[i] *= lrelu_gate(yv[i]));
+    cv_st<V, ST>(dx, (bp * dx_ldv + c) * V, o);
   }
 }
 extern "C" int ppst_in_bwd_apply_st(const void* g, const void* y, const void* gate, const void* coef, void* dx, int B, int64_t hw, int C,
@@ -260,16 +199,15 @@ extern "C" int ppst_in_bwd_apply_st(const void* g, const void* y, const void* ga
   if (!g || !y || !coef || !dx) return PPST_ENULL;
   const int64_t total = (int64_t)B * hw * C;
   if (total > PPST_IDX32_MAX) return PPST_EINVAL;
-  if (C % 4 == 0 && g_ld % 4 == 0 && y_ld % 4 == 0 && dx_ld % 4 == 0 && (!gate || gate_ld % 4 == 0) &&
-      ((uintptr_t)g | (uintptr_t)y | (uintptr_t)gate | (uintptr_t)dx) % (st ? 8 : 16) == 0 && (uintptr_t)coef % 16 == 0) {
-    PPST_ST_SWITCH(st, PPST_LAUNCH(in_bwd_apply4_kernel<ST_>, dim3(tg_grid(total / 4)), dim3(256), 0, as_stream(stream), g, y, gate,
-                                   (const float4*)coef, dx, (unsigned)hw, C / 4, g_ld / 4, y_ld / 4, gate_ld / 4, dx_ld / 4, post_gate,
+  if (four_wide_ok(st, {C, g_ld, y_ld, dx_ld, gate ? gate_ld : 0}, {g, y, gate, dx}, {coef})) {
+    PPST_ST_SWITCH(st, PPST_LAUNCH((in_bwd_apply_kernel<4, ST_>), dim3(grid_for(total / 4)), dim3(256), 0, as_stream(stream), g, y, gate,
+                                   (const float*)coef, dx, (unsigned)hw, C / 4, g_ld / 4, y_ld / 4, gate_ld / 4, dx_ld / 4, post_gate,
                                    (unsigned)(total / 4), make_fastdiv((unsigned)(C / 4)), make_fastdiv((unsigned)hw)));
     return PPST_LAUNCH_CHECK();
   }
   if (st) return PPST_EINVAL;
-  PPST_LAUNCH(in_bwd_apply_kernel, dim3(tg_grid(total)), dim3(256), 0, as_stream(stream), (const float*)g, (const float*)y,
-              (const float*)gate, (const float*)coef, (float*)dx, (unsigned)hw, C, g_ld, y_ld, gate_ld, dx_ld, post_gate,
+  PPST_LAUNCH((in_bwd_apply_kernel<1, PPST_ST_F32>), dim3(grid_for(total)), dim3(256), 0, as_stream(stream), g, y, gate,
+              (const float*)coef, dx, (unsigned)hw, C, g_ld, y_ld, gate_ld, dx_ld, post_gate,
               (unsigned)total, make_fastdiv((unsigned)C), make_fastdiv((unsigned)hw));
   return PPST_LAUNCH_CHECK();
 }
@@ -308,7 +246,7 @@ __global__ __launch_bounds__(256) void prelu_bwd_kernel(const float* __restrict_
   __syncthreads();
   if (threadIdx.x == 0) dslope_partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
-extern "C" int64_t ppst_prelu_bwd_ws(int64_t total) { return (int64_t)tg_grid(total) * (int64_t)sizeof(float); }
+extern "C" int64_t ppst_prelu_bwd_ws(int64_t total) { return (int64_t)grid_for(total) * (int64_t)sizeof(float); }
 extern "C" int ppst_prelu_bwd(const void* g, const void* y, const void* scale_shift, const void* res, const void* prelu, void* gpre,
                               void* ws, int B, int64_t hw, int C, int g_ld, int y_ld, int res_ld, void* stream) {
   if (B < 0 || hw <= 0 || C <= 0 || g_ld < C || y_ld < C || (res && res_ld < C)) return PPST_EINVAL;
@@ -316,7 +254,7 @@ extern "C" int ppst_prelu_bwd(const void* g, const void* y, const void* scale_sh
   if (!g || !y || !prelu || !gpre || !ws) return PPST_ENULL;
   const int64_t total = (int64_t)B * hw * C;
   if (total > PPST_IDX32_MAX) return PPST_EINVAL;
-  PPST_LAUNCH(prelu_bwd_kernel, dim3(tg_grid(total)), dim3(256), 0, as_stream(stream), (const float*)g, (const float*)y,
+  PPST_LAUNCH(prelu_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), (const float*)g, (const float*)y,
               (const float*)scale_shift, (const float*)res, (const float*)prelu, (float*)gpre, (float*)ws, (unsigned)hw, C, g_ld,
               y_ld, res_ld, (unsigned)total, make_fastdiv((unsigned)C), make_fastdiv((unsigned)hw));
   return PPST_LAUNCH_CHECK();
@@ -369,27 +307,27 @@ extern "C" int ppst_pad2d_st(const void* x, void* y, int B, int H, int W, int C,
   if (total > PPST_IDX32_MAX) return PPST_EINVAL;
   if (st) {
     if (C % 4 || x_ld % 4 || ((uintptr_t)x | (uintptr_t)y) % 8) return PPST_EINVAL;
-    PPST_LAUNCH(pad2d_kernel<uint2>, dim3(tg_grid(total / 4)), dim3(256), 0, as_stream(stream), (const uint2*)x, (uint2*)y, H, W, C / 4,
+    PPST_LAUNCH(pad2d_kernel<uint2>, dim3(grid_for(total / 4)), dim3(256), 0, as_stream(stream), (const uint2*)x, (uint2*)y, H, W, C / 4,
                 x_ld / 4, OH, OW, py0, px0, mode, (unsigned)(total / 4), make_fastdiv((unsigned)(C / 4)), make_fastdiv((unsigned)OW),
                 make_fastdiv((unsigned)OH));
     return PPST_LAUNCH_CHECK();
   }
-  if (C % 4 == 0 && x_ld % 4 == 0 && ((uintptr_t)x | (uintptr_t)y) % 16 == 0) {
-    PPST_LAUNCH(pad2d_kernel<float4>, dim3(tg_grid(total / 4)), dim3(256), 0, as_stream(stream), (const float4*)x, (float4*)y, H, W, C / 4,
+  if (four_wide_ok(PPST_ST_F32, {C, x_ld}, {x, y})) {
+    PPST_LAUNCH(pad2d_kernel<float4>, dim3(grid_for(total / 4)), dim3(256), 0, as_stream(stream), (const float4*)x, (float4*)y, H, W, C / 4,
                 x_ld / 4, OH, OW, py0, px0, mode, (unsigned)(total / 4), make_fastdiv((unsigned)(C / 4)), make_fastdiv((unsigned)OW),
                 make_fastdiv((unsigned)OH));
     return PPST_LAUNCH_CHECK();
   }
-  PPST_LAUNCH(pad2d_kernel<float>, dim3(tg_grid(total)), dim3(256), 0, as_stream(stream), (const float*)x, (float*)y, H, W, C, x_ld, OH, OW,
+  PPST_LAUNCH(pad2d_kernel<float>, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), (const float*)x, (float*)y, H, W, C, x_ld, OH, OW,
               py0, px0, mode, (unsigned)total, make_fastdiv((unsigned)C), make_fastdiv((unsigned)OW), make_fastdiv((unsigned)OH));
   return PPST_LAUNCH_CHECK();
 }
 // adjoint of ppst_pad2d: dx[b][y][x][c] = sum of dy over every padded position whose source is (y, x).
 // Candidates per axis: the interior copy plus the (py0 + py1) border positions -- tested, not enumerated in closed form.
-__device__ __forceinline__ void pad_acc(float& a, float v) { a += v; }
-__device__ __forceinline__ void pad_acc(float4& a, float4 v) { a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
-template <typename VT>
-__global__ __launch_bounds__(256) void pad2d_bwd_kernel(const VT* __restrict__ dy, VT* __restrict__ dx, int H, int W, int C,
+// V channels per thread (CV = C / V items per pixel): the same sums in the same order at either width; a half tensor's sums are fp32,
+// rounded once at the store.
+template <int V, int ST>
+__global__ __launch_bounds__(256) void pad2d_bwd_kernel(const void* __restrict__ dy, void* __restrict__ dx, int H, int W, int CV,
                                                         int OH, int OW, int py0, int py1, int px0, int px1, int mode, unsigned total,
                                                         FastDiv d_c, FastDiv d_w, FastDiv d_h) {
   const int ny = 1 + (py0 > 0 ? py0 : 0) + (py1 > 0 ? py1 : 0), nx = 1 + (px0 > 0 ? px0 : 0) + (px1 > 0 ? px1 : 0);
@@ -398,8 +336,9 @@ __global__ __launch_bounds__(256) void pad2d_bwd_kernel(const VT* __restrict__ d
     unsigned r = fd_divmod((unsigned)t64, d_c, c);
     r = fd_divmod(r, d_w, xx);
     const unsigned b = fd_divmod(r, d_h, yy);
-    const VT* base = dy + (int64_t)b * OH * OW * C + c;
-    VT acc = {};
+    // (this thread's channel item of image b as a pointer: one address register pair less than an element index carried through the loops)
+    const void* base = (const char*)dy + ((int64_t)b * OH * OW * CV + c) * (V * (ST == PPST_ST_F32 ? 4 : 2));
+    ChanVec<V> acc = {};
     for (int iy = 0; iy < ny; ++iy) {
       // candidate padded row (coordinates relative to the unpadded origin): itself, the top border rows, the bottom ones
       int ty = iy == 0 ? (int)yy : (iy <= (py0 > 0 ? py0 : 0) ? -iy : H - 1 + (iy - (py0 > 0 ? py0 : 0)));
@@ -409,37 +348,11 @@ __global__ __launch_bounds__(256) void pad2d_bwd_kernel(const VT* __restrict__ d
         int tx = ix == 0 ? (int)xx : (ix <= (px0 > 0 ? px0 : 0) ? -ix : W - 1 + (ix - (px0 > 0 ? px0 : 0)));
         if (tx + px0 < 0 || tx + px0 >= OW) continue;
         if (pad_src(tx, W, mode) != (int)xx) continue;
-        pad_acc(acc, base[((int64_t)(ty + py0) * OW + (tx + px0)) * C]);
+        const ChanVec<V> v = cv_ld<V, ST>(base, ((int64_t)(ty + py0) * OW + (tx + px0)) * CV * V);
+        CV_EACH(V, acc[i] += v[i]);
       }
     }
-    dx[t64] = acc;
-  }
-}
-// half storage: the same sums (fp32) over four channels per thread, one rounding at the store
-template <int ST>
-__global__ __launch_bounds__(256) void pad2d_bwd_st_kernel(const void* __restrict__ dy, void* __restrict__ dx, int H, int W, int C4,
-                                                           int OH, int OW, int py0, int py1, int px0, int px1, int mode, unsigned total,
-                                                           FastDiv d_c, FastDiv d_w, FastDiv d_h) {
-  const int ny = 1 + (py0 > 0 ? py0 : 0) + (py1 > 0 ? py1 : 0), nx = 1 + (px0 > 0 ? px0 : 0) + (px1 > 0 ? px1 : 0);
-  for (uint64_t t64 = (uint64_t)blockIdx.x * 256 + threadIdx.x; t64 < total; t64 += (uint64_t)gridDim.x * 256) {
-    unsigned c, xx, yy;
-    unsigned r = fd_divmod((unsigned)t64, d_c, c);
-    r = fd_divmod(r, d_w, xx);
-    const unsigned b = fd_divmod(r, d_h, yy);
-    const int64_t base = (int64_t)b * OH * OW * C4 + c;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int iy = 0; iy < ny; ++iy) {
-      int ty = iy == 0 ? (int)yy : (iy <= (py0 > 0 ? py0 : 0) ? -iy : H - 1 + (iy - (py0 > 0 ? py0 : 0)));
-      if (ty + py0 < 0 || ty + py0 >= OH) continue;
-      if (pad_src(ty, H, mode) != (int)yy) continue;
-      for (int ix = 0; ix < nx; ++ix) {
-        int tx = ix == 0 ? (int)xx : (ix <= (px0 > 0 ? px0 : 0) ? -ix : W - 1 + (ix - (px0 > 0 ? px0 : 0)));
-        if (tx + px0 < 0 || tx + px0 >= OW) continue;
-        if (pad_src(tx, W, mode) != (int)xx) continue;
-        pad_acc(acc, st_ld4<ST>(dy, (base + ((int64_t)(ty + py0) * OW + (tx + px0)) * C4) * 4));
-      }
-    }
-    st_st4<ST>(dx, (int64_t)t64 * 4, acc);
+    cv_st<V, ST>(dx, (int64_t)t64 * V, acc);
   }
 }
 extern "C" int ppst_pad2d_bwd_st(const void* dy, void* dx, int B, int H, int W, int C, int py0, int py1, int px0, int px1, int mode,
@@ -458,20 +371,14 @@ extern "C" int ppst_pad2d_bwd_st(const void* dy, void* dx, int B, int H, int W, 
   if (!dy || !dx) return PPST_ENULL;
   const int64_t total = (int64_t)B * H * W * C;
   if (total > PPST_IDX32_MAX || (int64_t)B * OH * OW * C > PPST_IDX32_MAX) return PPST_EINVAL;
-  if (st) {
-    if (C % 4 || ((uintptr_t)dy | (uintptr_t)dx) % 8) return PPST_EINVAL;
-    PPST_ST_SWITCH(st, PPST_LAUNCH(pad2d_bwd_st_kernel<ST_>, dim3(tg_grid(total / 4)), dim3(256), 0, as_stream(stream), dy, dx, H, W, C / 4, OH,
-                                   OW, py0, py1, px0, px1, mode, (unsigned)(total / 4), make_fastdiv((unsigned)(C / 4)),
+  if (four_wide_ok(st, {C}, {dy, dx})) {
+    PPST_ST_SWITCH(st, PPST_LAUNCH((pad2d_bwd_kernel<4, ST_>), dim3(grid_for(total / 4)), dim3(256), 0, as_stream(stream), dy, dx, H, W, C / 4,
+                                   OH, OW, py0, py1, px0, px1, mode, (unsigned)(total / 4), make_fastdiv((unsigned)(C / 4)),
                                    make_fastdiv((unsigned)W), make_fastdiv((unsigned)H)));
     return PPST_LAUNCH_CHECK();
   }
-  if (C % 4 == 0 && ((uintptr_t)dy | (uintptr_t)dx) % 16 == 0) {     // four channels per thread (same sums, same order)
-    PPST_LAUNCH(pad2d_bwd_kernel<float4>, dim3(tg_grid(total / 4)), dim3(256), 0, as_stream(stream), (const float4*)dy, (float4*)dx, H, W,
-                C / 4, OH, OW, py0, py1, px0, px1, mode, (unsigned)(total / 4), make_fastdiv((unsigned)(C / 4)), make_fastdiv((unsigned)W),
-                make_fastdiv((unsigned)H));
-    return PPST_LAUNCH_CHECK();
-  }
-  PPST_LAUNCH(pad2d_bwd_kernel<float>, dim3(tg_grid(total)), dim3(256), 0, as_stream(stream), (const float*)dy, (float*)dx, H, W, C, OH, OW,
+  if (st) return PPST_EINVAL;      // half storage: the four-channel form only
+  PPST_LAUNCH((pad2d_bwd_kernel<1, PPST_ST_F32>), dim3(grid_for(total)), dim3(256), 0, as_stream(stream), dy, dx, H, W, C, OH, OW,
               py0, py1, px0, px1, mode, (unsigned)total, make_fastdiv((unsigned)C), make_fastdiv((unsigned)W),
               make_fastdiv((unsigned)H));
   return PPST_LAUNCH_CHECK();
@@ -558,10 +465,9 @@ extern "C" int ppst_bilinear_bwd_st(const void* dy, void* dx, int B, int H, int 
   if (B < 0 || H <= 0 || W <= 0 || C <= 0 || OH <= 0 || OW <= 0 || dx_ld < C || dy_ld < C) return PPST_EINVAL;
   if (B == 0) return PPST_OK;
   if (!dy || !dx) return PPST_ENULL;
-  if (C % 4 == 0 && dx_ld % 4 == 0 && dy_ld % 4 == 0 && (((uintptr_t)dy | (uintptr_t)dx) % (st ? 8 : 16)) == 0 &&
-      (int64_t)B * H * W * (C / 4) <= PPST_IDX32_MAX) {
+  if (four_wide_ok(st, {C, dx_ld, dy_ld}, {dy, dx}) && (int64_t)B * H * W * (C / 4) <= PPST_IDX32_MAX) {
     const int64_t t4 = (int64_t)B * H * W * (C / 4);
-    PPST_ST_SWITCH(st, PPST_LAUNCH(bilinear_bwd_gather_kernel<ST_>, dim3(tg_grid(t4)), dim3(256), 0, as_stream(stream), dy, dx, H, W,
+    PPST_ST_SWITCH(st, PPST_LAUNCH(bilinear_bwd_gather_kernel<ST_>, dim3(grid_for(t4)), dim3(256), 0, as_stream(stream), dy, dx, H, W,
                                    C / 4, OH, OW, dy_ld / 4, dx_ld / 4, (float)H / (float)OH, (float)W / (float)OW, (unsigned)t4,
                                    make_fastdiv((unsigned)(C / 4)), make_fastdiv((unsigned)W), make_fastdiv((unsigned)H)));
     return PPST_LAUNCH_CHECK();
@@ -569,7 +475,7 @@ extern "C" int ppst_bilinear_bwd_st(const void* dy, void* dx, int B, int H, int 
   if (st) return PPST_EINVAL;
   const int64_t total = (int64_t)B * OH * OW * C;
   if (total > PPST_IDX32_MAX) return PPST_EINVAL;
-  PPST_LAUNCH(bilinear_bwd_kernel, dim3(tg_grid(total)), dim3(256), 0, as_stream(stream), (const float*)dy, (float*)dx, H, W, C, OH, OW,
+  PPST_LAUNCH(bilinear_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), (const float*)dy, (float*)dx, H, W, C, OH, OW,
               dy_ld, dx_ld, (float)H / (float)OH, (float)W / (float)OW, (unsigned)total, make_fastdiv((unsigned)C),
               make_fastdiv((unsigned)OW), make_fastdiv((unsigned)OH));
   return PPST_LAUNCH_CHECK();
@@ -596,7 +502,7 @@ extern "C" int ppst_avgpool_bwd(const void* dy, void* dx, int B, int H, int W, i
   if (!dy || !dx) return PPST_ENULL;
   const int64_t total = (int64_t)B * H * W * C;
   if (total > PPST_IDX32_MAX) return PPST_EINVAL;
-  PPST_LAUNCH(avgpool_bwd_kernel, dim3(tg_grid(total)), dim3(256), 0, as_stream(stream), (const float*)dy, (float*)dx, H, W, C, f, dy_ld,
+  PPST_LAUNCH(avgpool_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), (const float*)dy, (float*)dx, H, W, C, f, dy_ld,
               dx_ld, (unsigned)total, make_fastdiv((unsigned)C), make_fastdiv((unsigned)W), make_fastdiv((unsigned)H),
               make_fastdiv((unsigned)f));
   return PPST_LAUNCH_CHECK();
@@ -607,35 +513,52 @@ extern "C" int ppst_avgpool_bwd(const void* dy, void* dx, int B, int H, int W, i
 // the x8 bilinear upsampling of the warped features has 4x4 plateaus at the image border).  Pass 1 finds it with an
 // atomicMin over the pixels equal to the forward's maximum; pass 2 applies.
 // (accumulate != 0: dx += ...; several heads pool the same feature map, encoder_col.py:162-245)
+// The per-element form of pass 1 (any hw): one thread = V channels of one pixel (4: C % 4 == 0, 16-B aligned rows; ldv = ld / V).
+// fp32 only: a half tensor reaches the strip form below or is refused.
+template <int V>
 __global__ __launch_bounds__(256) void gmp_argmax_kernel(const float* __restrict__ x, const float* __restrict__ mask,
-                                                         const float* __restrict__ v, int* __restrict__ arg, unsigned hw, int C, int ld,
-                                                         unsigned total, FastDiv d_c, FastDiv d_hw) {
+                                                         const float* __restrict__ v, int* __restrict__ arg, unsigned hw, int C, int ldv,
+                                                         unsigned total, FastDiv d_cv, FastDiv d_hw) {
   for (uint64_t t64 = (uint64_t)blockIdx.x * 256 + threadIdx.x; t64 < total; t64 += (uint64_t)gridDim.x * 256) {
-    unsigned c;
-    const unsigned bpu = fd_divmod((unsigned)t64, d_c, c);
+    unsigned cv;
+    const unsigned bpu = fd_divmod((unsigned)t64, d_cv, cv);
     const unsigned b = fd_div(bpu, d_hw);
     const float m = mask ? mask[bpu] : 1.f;
-    int* ap = arg + (int64_t)b * C + c;
+    const ChanVec<V> xv = cv_ld<V, PPST_ST_F32>(x, ((int64_t)bpu * ldv + cv) * V);
+    const ChanVec<V> mv = *(const ChanVec<V>*)(v + (int64_t)b * 2 * C + C + cv * V);
+    int* ap = arg + (int64_t)b * C + cv * V;
     const int pix = (int)(bpu - b * hw);
-    if (x[(int64_t)bpu * ld + c] * m == v[(int64_t)b * 2 * C + C + c] && pix < *(const volatile int*)ap) atomicMin(ap, pix);
+    // masked pooling makes ties massive (every masked-out pixel is 0 = the maximum of an all-negative channel): read the current
+    // winner first -- a stale value is only larger, so at worst an unnecessary atomic -- instead of 10^5 atomics on one address
+    const volatile int* cur = ap;
+    CV_EACH(V, if (xv[i] * m == mv[i] && pix < cur[i]) atomicMin(ap + i, pix));
   }
 }
+// pass 2, V channels of one pixel per thread
+template <int V, int ST>
 __global__ __launch_bounds__(256) void gap_gmp_bwd_kernel(const float* __restrict__ mask, const int* __restrict__ arg,
-                                                          const float* __restrict__ g, float* __restrict__ dx, unsigned hw, int C,
-                                                          int accumulate, unsigned total, FastDiv d_c, FastDiv d_hw) {
+                                                          const float* __restrict__ g, void* __restrict__ dx, unsigned hw, int C,
+                                                          int accumulate, unsigned total, FastDiv d_cv, FastDiv d_hw) {
   const float invP = 1.f / (float)hw;
   for (uint64_t t64 = (uint64_t)blockIdx.x * 256 + threadIdx.x; t64 < total; t64 += (uint64_t)gridDim.x * 256) {
-    unsigned c;
-    const unsigned bpu = fd_divmod((unsigned)t64, d_c, c);
+    unsigned cv;
+    const unsigned bpu = fd_divmod((unsigned)t64, d_cv, cv);
     const unsigned b = fd_div(bpu, d_hw);
     const float m = mask ? mask[bpu] : 1.f;
-    const bool top = (int)(bpu - b * hw) == arg[(int64_t)b * C + c];
-    float o = m * (g[(int64_t)b * 2 * C + c] * invP + (top ? g[(int64_t)b * 2 * C + C + c] : 0.f));
-    float* d = dx + (int64_t)bpu * C + c;
-    *d = accumulate ? *d + o : o;
+    const int pix = (int)(bpu - b * hw);
+    const ChanVec<V, int> ar = *(const ChanVec<V, int>*)(arg + (int64_t)b * C + cv * V);
+    const ChanVec<V> ga = *(const ChanVec<V>*)(g + (int64_t)b * 2 * C + cv * V), gm = *(const ChanVec<V>*)(g + (int64_t)b * 2 * C + C + cv * V);
+    ChanVec<V> o;
+    CV_EACH(V, o[i] = m * (ga[i] * invP + (pix == ar[i] ? gm[i] : 0.f)));
+    const int64_t d = ((int64_t)bpu * (C >> (V == 4 ? 2 : 0)) + cv) * V;
+    if (accumulate) {
+      const ChanVec<V> p = cv_ld<V, ST>(dx, d);
+      CV_EACH(V, o[i] += p[i]);
+    }
+    cv_st<V, ST>(dx, d, o);
   }
 }
-// 16-B forms of the two passes (C % 4 == 0, 16-B aligned rows): one thread = 4 channels of one pixel
+// The strip form of pass 1, a different algorithm from the per-element one above.
 // One thread = 4 channels of GMP_NP consecutive pixels: the first matching pixel of its strip is found in registers, then ONE
 // guarded atomicMin per channel (round 2 did the guard read + atomic per ELEMENT: four volatile loads per pixel, 140 us for a
 // (4, 512, 512, 32) tensor that a plain read moves in 30).  Needs hw % GMP_NP == 0 (a strip stays inside one image).
@@ -671,46 +594,6 @@ __global__ __launch_bounds__(256) void gmp_argmax4_kernel(const void* __restrict
     if (f3 >= 0 && pix0 + f3 < cur[3]) atomicMin(ap + 3, pix0 + f3);
   }
 }
-// (the per-element form: any hw)
-__global__ __launch_bounds__(256) void gmp_argmax4e_kernel(const float4* __restrict__ x, const float* __restrict__ mask,
-                                                           const float* __restrict__ v, int* __restrict__ arg, unsigned hw, int C, int ld4,
-                                                           unsigned total, FastDiv d_c4, FastDiv d_hw) {
-  for (uint64_t t64 = (uint64_t)blockIdx.x * 256 + threadIdx.x; t64 < total; t64 += (uint64_t)gridDim.x * 256) {
-    unsigned c4;
-    const unsigned bpu = fd_divmod((unsigned)t64, d_c4, c4);
-    const unsigned b = fd_div(bpu, d_hw);
-    const float m = mask ? mask[bpu] : 1.f;
-    const float4 xv = x[(int64_t)bpu * ld4 + c4];
-    const float4 mv = *(const float4*)(v + (int64_t)b * 2 * C + C + c4 * 4);
-    int* ap = arg + (int64_t)b * C + c4 * 4;
-    const int pix = (int)(bpu - b * hw);
-    const volatile int* cur = ap;
-    if (xv.x * m == mv.x && pix < cur[0]) atomicMin(ap, pix);
-    if (xv.y * m == mv.y && pix < cur[1]) atomicMin(ap + 1, pix);
-    if (xv.z * m == mv.z && pix < cur[2]) atomicMin(ap + 2, pix);
-    if (xv.w * m == mv.w && pix < cur[3]) atomicMin(ap + 3, pix);
-  }
-}
-template <int ST = PPST_ST_F32>
-__global__ __launch_bounds__(256) void gap_gmp_bwd4_kernel(const float* __restrict__ mask, const int* __restrict__ arg,
-                                                           const float* __restrict__ g, void* __restrict__ dx, unsigned hw, int C,
-                                                           int accumulate, unsigned total, FastDiv d_c4, FastDiv d_hw) {
-  const float invP = 1.f / (float)hw;
-  for (uint64_t t64 = (uint64_t)blockIdx.x * 256 + threadIdx.x; t64 < total; t64 += (uint64_t)gridDim.x * 256) {
-    unsigned c4;
-    const unsigned bpu = fd_divmod((unsigned)t64, d_c4, c4);
-    const unsigned b = fd_div(bpu, d_hw);
-    const float m = mask ? mask[bpu] : 1.f;
-    const int pix = (int)(bpu - b * hw);
-    const int4 ar = *(const int4*)(arg + (int64_t)b * C + c4 * 4);
-    const float4 ga = *(const float4*)(g + (int64_t)b * 2 * C + c4 * 4), gm = *(const float4*)(g + (int64_t)b * 2 * C + C + c4 * 4);
-    float4 o = make_float4(m * (ga.x * invP + (pix == ar.x ? gm.x : 0.f)), m * (ga.y * invP + (pix == ar.y ? gm.y : 0.f)),
-                           m * (ga.z * invP + (pix == ar.z ? gm.z : 0.f)), m * (ga.w * invP + (pix == ar.w ? gm.w : 0.f)));
-    const int64_t d = ((int64_t)bpu * (C >> 2) + c4) * 4;
-    if (accumulate) { const float4 p = st_ld4<ST>(dx, d); o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w; }
-    st_st4<ST>(dx, d, o);
-  }
-}
 extern "C" int ppst_gap_gmp_bwd_st(const void* x, const void* mask, const void* v, const void* g, void* dx, void* arg_ws, int B,
                                    int64_t hw, int C, int ld, int accumulate, int st, void* stream);
 extern "C" int ppst_gap_gmp_bwd(const void* x, const void* mask, const void* v, const void* g, void* dx, void* arg_ws, int B,
@@ -730,27 +613,26 @@ extern "C" int ppst_gap_gmp_bwd_st(const void* x, const void* mask, const void* 
   if (e != hipSuccess) return (int)e;
   if (st && (C % 4 || ld % 4 || hw % GMP_NP || ((uintptr_t)x | (uintptr_t)dx) % 8 || ((uintptr_t)v | (uintptr_t)g | (uintptr_t)arg_ws) % 16))
     return PPST_EINVAL;          // half storage: the strip form only
-  if (C % 4 == 0 && ld % 4 == 0 && (((uintptr_t)v | (uintptr_t)g | (uintptr_t)arg_ws) % 16) == 0 &&
-      (((uintptr_t)x | (uintptr_t)dx) % (st ? 8 : 16)) == 0) {
+  if (four_wide_ok(st, {C, ld}, {x, dx}, {v, g, arg_ws})) {
     const int64_t t4 = total / 4;
     if (hw % GMP_NP == 0) {
       const int64_t strips = t4 / GMP_NP;
-      PPST_ST_SWITCH(st, PPST_LAUNCH(gmp_argmax4_kernel<ST_>, dim3(tg_grid(strips)), dim3(256), 0, as_stream(stream), x, (const float*)mask,
+      PPST_ST_SWITCH(st, PPST_LAUNCH(gmp_argmax4_kernel<ST_>, dim3(grid_for(strips)), dim3(256), 0, as_stream(stream), x, (const float*)mask,
                                      (const float*)v, (int*)arg_ws, (unsigned)hw, C, ld / 4, (unsigned)strips,
                                      make_fastdiv((unsigned)(C / 4)), make_fastdiv((unsigned)(hw / GMP_NP))));
     } else {
-      PPST_LAUNCH(gmp_argmax4e_kernel, dim3(tg_grid(t4)), dim3(256), 0, as_stream(stream), (const float4*)x, (const float*)mask,
+      PPST_LAUNCH(gmp_argmax_kernel<4>, dim3(grid_for(t4)), dim3(256), 0, as_stream(stream), (const float*)x, (const float*)mask,
                   (const float*)v, (int*)arg_ws, (unsigned)hw, C, ld / 4, (unsigned)t4, make_fastdiv((unsigned)(C / 4)), make_fastdiv((unsigned)hw));
     }
-    PPST_ST_SWITCH(st, PPST_LAUNCH(gap_gmp_bwd4_kernel<ST_>, dim3(tg_grid(t4)), dim3(256), 0, as_stream(stream), (const float*)mask,
+    PPST_ST_SWITCH(st, PPST_LAUNCH((gap_gmp_bwd_kernel<4, ST_>), dim3(grid_for(t4)), dim3(256), 0, as_stream(stream), (const float*)mask,
                                    (const int*)arg_ws, (const float*)g, dx, (unsigned)hw, C, accumulate, (unsigned)t4,
                                    make_fastdiv((unsigned)(C / 4)), make_fastdiv((unsigned)hw)));
     return PPST_LAUNCH_CHECK();
   }
-  PPST_LAUNCH(gmp_argmax_kernel, dim3(tg_grid(total)), dim3(256), 0, as_stream(stream), (const float*)x, (const float*)mask,
+  PPST_LAUNCH(gmp_argmax_kernel<1>, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), (const float*)x, (const float*)mask,
               (const float*)v, (int*)arg_ws, (unsigned)hw, C, ld, (unsigned)total, make_fastdiv((unsigned)C), make_fastdiv((unsigned)hw));
-  PPST_LAUNCH(gap_gmp_bwd_kernel, dim3(tg_grid(total)), dim3(256), 0, as_stream(stream), (const float*)mask, (const int*)arg_ws,
-              (const float*)g, (float*)dx, (unsigned)hw, C, accumulate, (unsigned)total, make_fastdiv((unsigned)C),
+  PPST_LAUNCH((gap_gmp_bwd_kernel<1, PPST_ST_F32>), dim3(grid_for(total)), dim3(256), 0, as_stream(stream), (const float*)mask, (const int*)arg_ws,
+              (const float*)g, dx, (unsigned)hw, C, accumulate, (unsigned)total, make_fastdiv((unsigned)C),
               make_fastdiv((unsigned)hw));
   return PPST_LAUNCH_CHECK();
 }
@@ -851,15 +733,15 @@ extern "C" int ppst_gap_gmp_multi_bwd(const void* x, const void* masks, const vo
   if (!x || !masks || !v || !g || !dx || !arg_ws) return PPST_ENULL;
   const int64_t total = (int64_t)B * hw * C;
   if (total > PPST_IDX32_MAX) return PPST_EINVAL;
-  if ((((uintptr_t)v | (uintptr_t)g | (uintptr_t)arg_ws) % 16) != 0 || (((uintptr_t)x | (uintptr_t)dx) % (st ? 8 : 16)) != 0) return PPST_EINVAL;
+  if (!four_wide_ok(st, {C, ld}, {x, dx}, {v, g, arg_ws})) return PPST_EINVAL;
   const int heads = nm + with_plain;
   hipError_t e = hipMemsetAsync(arg_ws, 0x7f, (size_t)heads * B * C * sizeof(int), as_stream(stream));
   if (e != hipSuccess) return (int)e;
   const int64_t t4 = total / 4, strips = t4 / GMP_NP;
-  PPST_ST_SWITCH(st, PPST_LAUNCH(gmp_argmax_multi4_kernel<ST_>, dim3(tg_grid(strips)), dim3(256), 0, as_stream(stream), x, (const float*)masks,
+  PPST_ST_SWITCH(st, PPST_LAUNCH(gmp_argmax_multi4_kernel<ST_>, dim3(grid_for(strips)), dim3(256), 0, as_stream(stream), x, (const float*)masks,
                                  (const float*)v, (int*)arg_ws, (unsigned)hw, C, ld / 4, nm, with_plain, B, (unsigned)strips,
                                  make_fastdiv((unsigned)(C / 4)), make_fastdiv((unsigned)(hw / GMP_NP))));
-  PPST_ST_SWITCH(st, PPST_LAUNCH(gap_gmp_bwd_multi4_kernel<ST_>, dim3(tg_grid(t4)), dim3(256), 0, as_stream(stream), (const float*)masks,
+  PPST_ST_SWITCH(st, PPST_LAUNCH(gap_gmp_bwd_multi4_kernel<ST_>, dim3(grid_for(t4)), dim3(256), 0, as_stream(stream), (const float*)masks,
                                  (const int*)arg_ws, (const float*)g, dx, (unsigned)hw, C, nm, with_plain, B, accumulate, (unsigned)t4,
                                  make_fastdiv((unsigned)(C / 4)), make_fastdiv((unsigned)hw)));
   return PPST_LAUNCH_CHECK();
@@ -970,7 +852,7 @@ extern "C" int ppst_l1_grad(const void* a, const void* b, void* da, int64_t n, f
   if (n < 0) return PPST_EINVAL;
   if (n == 0) return PPST_OK;
   if (!a || !b || !da) return PPST_ENULL;
-  PPST_LAUNCH(l1_grad_kernel, dim3(tg_grid(n)), dim3(256), 0, as_stream(stream), (const float*)a, (const float*)b, (float*)da, n,
+  PPST_LAUNCH(l1_grad_kernel, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), (const float*)a, (const float*)b, (float*)da, n,
               weight / (float)n);
   return PPST_LAUNCH_CHECK();
 }
@@ -993,6 +875,7 @@ __global__ __launch_bounds__(256) void noise_wgrad_kernel(const float* __restric
   if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 // float4 form (C, ld multiples of 4, aligned): a wave covers 256 / C4 ... whole pixels per pass -- lane -> (pixel, channel quad)
+// (another order of the sums than noise_wgrad_kernel: not a V = 4 copy of it)
 template <int ST = PPST_ST_F32>
 __global__ __launch_bounds__(256) void noise_wgrad4_kernel(const void* __restrict__ dpre, const float* __restrict__ noise,
                                                            float* __restrict__ partial, int64_t npix, int C4, int ld4) {
@@ -1046,7 +929,7 @@ extern "C" int ppst_noise_wgrad_st(const void* dpre, const void* noise, void* ou
   const int blocks = (int)(ppst_noise_wgrad_ws(npix) / (int64_t)sizeof(float));
   // (C / 4 not a divisor of 256, e.g. 96: the last 256 % (C / 4) threads of a block idle -- the fp32 path keeps its scalar form for
   //  those widths, bit for bit as before; a half tensor takes the four-channel form at every width)
-  if (C % 4 == 0 && ld % 4 == 0 && (uintptr_t)dpre % (st ? 8 : 16) == 0 && (st || C / 4 >= 256 || 256 % (C / 4) == 0))
+  if (four_wide_ok(st, {C, ld}, {dpre}) && (st || C / 4 >= 256 || 256 % (C / 4) == 0))
     PPST_ST_SWITCH(st, PPST_LAUNCH(noise_wgrad4_kernel<ST_>, dim3(blocks), dim3(256), 0, as_stream(stream), dpre, (const float*)noise,
                                    (float*)ws, npix, C / 4, ld / 4));
   else if (st)
@@ -1083,7 +966,7 @@ extern "C" int ppst_upscale_weight_bwd(const void* dw4, void* dw, int cout, int 
   if (cout <= 0 || cin <= 0) return PPST_EINVAL;
   if (!dw4 || !dw) return PPST_ENULL;
   const int64_t total = (int64_t)cout * cin * 9;
-  PPST_LAUNCH(upscale_weight_bwd_kernel, dim3(tg_grid(total)), dim3(256), 0, as_stream(stream), (const float*)dw4, (float*)dw, cout, cin,
+  PPST_LAUNCH(upscale_weight_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), (const float*)dw4, (float*)dw, cout, cin,
               scale, total, accumulate);
   return PPST_LAUNCH_CHECK();
 }
@@ -1119,17 +1002,17 @@ extern "C" int ppst_space_to_depth_st(const void* x, void* y, int B, int H, int 
   if (total > PPST_IDX32_MAX) return PPST_EINVAL;
   if (st) {       // half storage: four channels = one 8-byte element (pure data movement)
     if (C % 4 || x_ld % 4 || ((uintptr_t)x | (uintptr_t)y) % 8) return PPST_EINVAL;
-    PPST_LAUNCH(s2d_kernel<uint2>, dim3(tg_grid(total / 4)), dim3(256), 0, as_stream(stream), (const uint2*)x, (uint2*)y, H, W, C / 4,
+    PPST_LAUNCH(s2d_kernel<uint2>, dim3(grid_for(total / 4)), dim3(256), 0, as_stream(stream), (const uint2*)x, (uint2*)y, H, W, C / 4,
                 x_ld / 4, H2, W2, (unsigned)(total / 4), make_fastdiv((unsigned)(C / 4)), make_fastdiv(4u), make_fastdiv((unsigned)W2),
                 make_fastdiv((unsigned)H2));
     return PPST_LAUNCH_CHECK();
   }
-  if (C % 4 == 0 && x_ld % 4 == 0 && ((uintptr_t)x | (uintptr_t)y) % 16 == 0)
-    PPST_LAUNCH(s2d_kernel<float4>, dim3(tg_grid(total / 4)), dim3(256), 0, as_stream(stream), (const float4*)x, (float4*)y, H, W, C / 4,
+  if (four_wide_ok(PPST_ST_F32, {C, x_ld}, {x, y}))
+    PPST_LAUNCH(s2d_kernel<float4>, dim3(grid_for(total / 4)), dim3(256), 0, as_stream(stream), (const float4*)x, (float4*)y, H, W, C / 4,
                 x_ld / 4, H2, W2, (unsigned)(total / 4), make_fastdiv((unsigned)(C / 4)), make_fastdiv(4u), make_fastdiv((unsigned)W2),
                 make_fastdiv((unsigned)H2));
   else
-    PPST_LAUNCH(s2d_kernel<float>, dim3(tg_grid(total)), dim3(256), 0, as_stream(stream), (const float*)x, (float*)y, H, W, C, x_ld, H2, W2,
+    PPST_LAUNCH(s2d_kernel<float>, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), (const float*)x, (float*)y, H, W, C, x_ld, H2, W2,
                 (unsigned)total, make_fastdiv((unsigned)C), make_fastdiv(4u), make_fastdiv((unsigned)W2), make_fastdiv((unsigned)H2));
   return PPST_LAUNCH_CHECK();
 }
@@ -1144,7 +1027,7 @@ extern "C" int ppst_scale_by(const void* x, const void* s, void* y, int64_t n, v
   if (n < 0) return PPST_EINVAL;
   if (n == 0) return PPST_OK;
   if (!x || !s || !y) return PPST_ENULL;
-  PPST_LAUNCH(scale_by_kernel, dim3(tg_grid(n)), dim3(256), 0, as_stream(stream), (const float*)x, (const float*)s, (float*)y, n);
+  PPST_LAUNCH(scale_by_kernel, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), (const float*)x, (const float*)s, (float*)y, n);
   return PPST_LAUNCH_CHECK();
 }
 
@@ -1268,7 +1151,7 @@ extern "C" int ppst_depth_to_space_st(const void* x, void* y, int B, int th, int
   const int cq = C / per;
   const int64_t total = (int64_t)B * oh * ow * cq;
   if (total > PPST_IDX32_MAX) return PPST_EINVAL;
-  PPST_LAUNCH(depth_to_space_kernel, dim3(tg_grid(total)), dim3(256), 0, as_stream(stream), (const uint4*)x, (uint4*)y, th, tw, oh, ow, cq,
+  PPST_LAUNCH(depth_to_space_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), (const uint4*)x, (uint4*)y, th, tw, oh, ow, cq,
               (unsigned)total, make_fastdiv(cq), make_fastdiv(ow), make_fastdiv(oh));
   return PPST_LAUNCH_CHECK();
 }

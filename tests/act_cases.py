@@ -129,8 +129,8 @@ def _pool(f, k):
 
 
 # ====================================================================================== in_stats + in_finalize, statistics
-# launcher (ppst_in_stats): C % 4 == 0 and ld % 4 == 0 and 16-byte x -> chan_reduce4_kernel<0> (lane = 4 channels, lanes = C / 4
-# rounded up to a power of two <= 256 and masked, one pass per 1024 channels) else chan_reduce_kernel<0> (lane = 1 channel, one
+# launcher (ppst_in_stats): C % 4 == 0 and ld % 4 == 0 and 16-byte x -> chan_reduce_kernel<0, false, 4> (lane = 4 channels, lanes
+# = C / 4 rounded up to a power of two <= 256 and masked, one pass per 1024 channels) else <0, false, 1> (lane = 1 channel, one
 # pass per 256 channels); pix_chunk(hw) pixels per block, n_partials = ceil(hw / chunk); in_finalize_kernel walks the partials 32
 # rows at a time, four-way unrolled from 128 rows on.
 def pix_chunk(hw):
@@ -436,7 +436,7 @@ _case("affine_act", "V4-C8-f16-slices-off4", B=2, C=8, H=5, W=7, st="f16", ss=Tr
 _case("affine_act", "V4-C8-f16-up2-6x4-rss", B=2, C=8, H=6, W=4, st="f16", yst="f32", ss=True, res="up2", rss=True, res_ld=12, res_off=4)
 
 
-# ppst_affine_act_stats: chan_reduce4_kernel<0, true> only (C, every ld multiples of 4); the statistics are those of the OUTPUT
+# ppst_affine_act_stats: chan_reduce_kernel<0, true, 4> only (C, every ld multiples of 4); the statistics are those of the OUTPUT
 def _as_eval(c, inp, dt, y=None, drop=0, corner=4):
     y = _aa_y(c, inp, dt) if y is None else y.to(dt)
     s, q = _moments(y, dt, c.p.get("rep_pad"), drop, corner)
@@ -472,8 +472,8 @@ _case("affine_act_stats", "C4-96x96-ss", B=1, C=4, H=96, W=96, ss=True)         
 
 
 # ============================================================================ gap_gmp, gap_gmp_multi, gap_gmp_levels
-# launcher (ppst_gap_gmp_st): a half tensor -> chan_reduce4_kernel<1, false, f16 | bf16> (C % 4, ld % 4, 8-byte x or refused);
-# fp32: C % 4 == 0, ld % 4 == 0, 16-byte x -> chan_reduce4_kernel<1> else chan_reduce_kernel<1>.  The mean divides by H W; the
+# launcher (ppst_gap_gmp_st): a half tensor -> chan_reduce_kernel<1, false, 4, f16 | bf16> (C % 4, ld % 4, 8-byte x or refused);
+# fp32: C % 4 == 0, ld % 4 == 0, 16-byte x -> chan_reduce_kernel<1, false, 4> else <1, false, 1>.  The mean divides by H W; the
 # maximum is that of the products m x (a masked-out pixel counts as 0).
 def _pool_x(c, g, shape, st):
     x = _randn(g, *shape)

@@ -245,7 +245,7 @@ _case("bilinear_bwd", "C8-slice-ld16-off2", B=1, C=8, H=5, W=7, OH=12, OW=9, dy_
 
 
 # ================================================================================================== pad2d, pad2d_bwd
-# launchers (ppst_pad2d_st / ppst_pad2d_bwd_st, fp32): C % 4 == 0 (and x_ld % 4 == 0, 16-byte pointers) -> float4, else float
+# launchers (ppst_pad2d_st / ppst_pad2d_bwd_st, fp32): C % 4 == 0 (and x_ld % 4 == 0, 16-byte pointers) -> four channels per thread (pad2d_kernel<float4>, pad2d_bwd_kernel<4>), else one (<float>, <1>)
 def pad_src(n, p0, p1, mode):
     """source index of every padded position (-1: zero), F.pad semantics; negative pads crop"""
     t = np.arange(n + p0 + p1) - p0
@@ -376,8 +376,8 @@ _case("avgpool_bwd", "f2-C8-slice-ld13-off5", B=2, C=8, oh=5, ow=7, f=2, dy_ld=1
 
 
 # ================================================================================== gap_gmp_bwd, gap_gmp_multi_bwd
-# launcher (ppst_gap_gmp_bwd_st, fp32): C % 4 == 0 and ld % 4 == 0 and 16-byte pointers -> (hw % 16 == 0 ? strip : 4e) + bwd4,
-# else the scalar pair.  ppst_gap_gmp_multi_bwd: the strip form only (refuses everything else).
+# launcher (ppst_gap_gmp_bwd_st, fp32): C % 4 == 0 and ld % 4 == 0 and 16-byte pointers -> (hw % 16 == 0 ? the strip kernel :
+# gmp_argmax_kernel<4>) + gap_gmp_bwd_kernel<4>, else the <1> pair.  ppst_gap_gmp_multi_bwd: the strip form only (refuses everything else).
 def _quant(g, kind, *shape):
     """float32 values on a 0.5 grid in [-2, 2] ('quant'), or that with constant 4 x 4 plateaus ('plateau'): ties in most channels"""
     B, H, W, C = shape
@@ -992,8 +992,8 @@ for _C in (3, 32):
 _case("prelu_bwd", "C8-ss-res-slices", B=2, C=8, H=5, W=7, ss=True, res=True, g_ld=12, g_off=4, y_ld=11, y_off=3, res_ld=16, res_off=8)
 
 # ===================================================================================================== instance norm
-# ppst_dual_stats_st / ppst_in_bwd_apply_st (fp32): C % 4 == 0, every ld % 4 == 0, 16-byte pointers -> four-channel, else scalar;
-# pixel chunks of tg_pix_chunk(hw) (64 at these sizes).  ppst_in_bwd_finalize: one kernel; mean_rstd == null is the no-norm path.
+# ppst_dual_stats_st / ppst_in_bwd_apply_st (fp32): C % 4 == 0, every ld % 4 == 0, 16-byte pointers -> dual_stats_kernel<4> /
+# in_bwd_apply_kernel<4>, else <1>; pixel chunks of pix_chunk(hw) (64 at these sizes).  ppst_in_bwd_finalize: one kernel; mean_rstd == null is the no-norm path.
 SQRT2 = 2.0 ** 0.5
 
 
@@ -1088,6 +1088,10 @@ def _in_mut(c, inp):
         out.append(("slice offset of y ignored", f(off=0)))
     if p["C"] % 4:
         out.append(("scalar tail channels zero", {k: (_zero_tail(v, p["C"] % 4) if k != "dstyle" else v) for k, v in f().items()}))
+    first = 1024 if _in_branch(c).startswith("in_bwd:four") else 256      # channels of one pass of the statistics kernel's channel loop
+    if p["C"] > first:
+        out.append(("channels beyond the first channel pass zero",
+                    {k: (_zero_tail(v, p["C"] - first) if k != "dstyle" else v) for k, v in f().items()}))
     return out
 
 
@@ -1108,6 +1112,9 @@ _case("in_bwd", "hw480-C8-slices-gate-style-dstyle", B=2, hw=480, C=8, gate=True
       gate_ld=8 + 4, gate_off=0)
 _case("in_bwd", "hw35-C8-slices-ld-odd-gate", B=2, hw=35, C=8, gate=True, g_ld=11, g_off=3, y_ld=9, y_off=1, gate_ld=10, gate_off=2)
 _case("in_bwd", "hw480-C32-big-mean-style-dstyle", B=2, hw=480, C=32, style=True, want_dstyle=True, big_mean=True)
+# dual_stats_kernel<V> walks the channels 256 lanes of V at a time: more than one pass only for C > 256 (V = 1) and C > 1024 (V = 4)
+_case("in_bwd", "hw15-C258-gate-style-dstyle", B=2, hw=15, C=258, gate=True, style=True, want_dstyle=True)      # scalar, two channel passes
+_case("in_bwd", "hw15-C1032-gate-style-dstyle", B=2, hw=15, C=1032, gate=True, style=True, want_dstyle=True)    # 258 lanes of 4: two passes
 
 
 # ppst_in_finalize_train: one kernel; partial rows of (sum, sum of squares) -> scale_shift, mean_rstd.  The judge takes the float32
