@@ -29,7 +29,8 @@ def _hipcc():
     return "hipcc"
 
 
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "rscl_common.h"), os.path.join(HERE, "..", "include", "ppst_hip.h")]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "rscl_common.h"),
+           os.path.join(HERE, "..", "include", "ppst_hip.h")]
 
 
 def _stale(target, deps):

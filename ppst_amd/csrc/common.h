@@ -18,11 +18,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 #define PPST_EPI_STORE(ptr, o) (*(float4*)(ptr) = make_float4((o)[0], (o)[1], (o)[2], (o)[3]))
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-// Tags for the conv epilogues' (activation, residual mode): EpiC = compile-time (the production kernels: the pass loops are
-// instantiated per combination), EpiR = run-time (experiment / reduced-precision kernels: one generic instance, shorter build).
-template <int V> struct EpiC { static constexpr int value = V; };
-struct EpiR { int value; };
-
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 
 // ---- across-block K split of a conv launch (ppst_conv_args.ksplit; the caller owns the workspace).  The S blocks of an output

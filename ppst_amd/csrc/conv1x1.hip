@@ -19,7 +19,7 @@
 //   * same MFMA sequence per output element as conv_mfma.hip (al*bh, ah*bl, ah*bh per step, steps in table order), so the
 //     outputs are bit-identical to it (tests/gpu_diag.py t_conv_variants); tile statistics: one (sum, sumsq) row per
 //     256-pixel block, fixed summation order (depends on H*W only, not on the batch).
-#include "common.h"
+#include "conv_common.h"
 
 struct C1Args {
   const float* x;
@@ -96,99 +96,56 @@ __device__ __forceinline__ f32x4 c1_mfma(bf16x8 bh, bf16x8 bl, bf16x8 xh, bf16x8
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, xh, acc, 0, 0, 0);
 }
 
-__device__ __forceinline__ int c1_pad(int i, int n, int mode) {
-  if (mode == PPST_PAD_REFLECT) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * (n - 1) - i;
-  }
-  return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
-
 // Epilogue shared by the kernels of this file: lane = pixel r16 of each m-tile, channels n0 + 4g .. 4g+3 of each n-tile
 // (operands swapped in the MFMAs), everything a 16-B access straight from the accumulators; tile statistics through `red`.
 template <int MT, int NT, bool TAPS, bool SPEC = true, int IOS = PPST_ST_F32>
 __device__ __forceinline__ void c1_epilogue(const C1Args& a, f32x4 (&acc)[MT][NT], float (&red)[8][NT > 4 ? 128 : 64][2], int b, int mblk,
                                             int ntile, int pbase, int oy0, int ox, int tid, int wave, int r16, int g) {
   const int act = a.act & 0xff;
-  const bool res_after = (a.act >> 8) & 1;
+  const int resm = a.residual ? (((a.act >> 8) & 1) ? 2 : 1) : 0;
   const float slope = (act == PPST_ACT_PRELU && a.prelu) ? a.prelu[0] : 0.f;
   float4 s1[NT], s2[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) { s1[nt] = make_float4(0.f, 0.f, 0.f, 0.f); s2[nt] = s1[nt]; }
   // Output addressing with 32-bit offsets inside image b; bias and noise of the whole wave tile are fetched before the first
-  // store (vmcnt counts stores and retires in order: a load behind a store waits for that store's acknowledgement) -- as in
-  // conv_mfma.hip.
+  // store (conv_common.h).
   const int64_t img = (int64_t)b * (TAPS ? a.out_h * a.out_w : a.hw);
   constexpr int ES = IOS == PPST_ST_F32 ? 4 : 2;     // storage type of residual / y: ppst_conv_args.io_st
   unsigned char* const yb = (unsigned char*)a.y + img * a.out_ld * ES;
   const float* const nzb = a.noise ? a.noise + img : nullptr;
   const unsigned char* const rb = a.residual ? (const unsigned char*)a.residual + img * a.res_ld * ES : nullptr;
   const int nbase = ntile * (NT > 4 ? 128 : 64) + g * 4;
-  // (buffer loads, every request unconditional -- a pixel outside the tile / image and a launch without noise read out of range and
-  //  get zero: as conditional global loads hipcc issued them one by one, each with its own wait; conv_mfma2.hip's UP9 epilogue)
   float nzv[MT];
   float4 bva[NT];
-  const __amdgpu_buffer_rsrc_t nrs = __builtin_amdgcn_make_buffer_rsrc((void*)(nzb ? (const void*)nzb : (const void*)yb), 0,
-                                                                       nzb ? (TAPS ? a.out_h * a.out_w : a.hw) * 4 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t nrs = conv_epi_noise_rsrc(nzb, yb, TAPS ? a.out_h * a.out_w : a.hw);
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
     const int p = pbase + mt * 16 + r16;
-    const bool ok = TAPS ? (oy0 + mt < a.out_h && ox < a.out_w) : p < a.hw;
-    nzv[mt] = a.noise_weight * __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                   nrs, ok ? (TAPS ? (oy0 + mt) * a.out_w + ox : p) * 4 : (int)0x80000000, 0, 0));
+    nzv[mt] = a.noise_weight * conv_epi_noise(nrs, TAPS ? (oy0 + mt < a.out_h && ox < a.out_w) : p < a.hw, TAPS ? (oy0 + mt) * a.out_w + ox : p);
   }
 #pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-    bva[nt] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(__builtin_amdgcn_make_buffer_rsrc((void*)(a.bias ? (const void*)a.bias : (const void*)a.y), 0, a.bias ? a.cout * 4 : 0, 0x00020000), (nbase + nt * 16) * 4, 0, 0));   // (out of range -> zeros)
-  // instantiated per (activation, residual mode), as in conv_mfma.hip / conv_mfma2.hip (same arithmetic, no FMA contraction)
+  for (int nt = 0; nt < NT; ++nt) bva[nt] = conv_epi_bias4(a.bias, a.y, a.cout, nbase + nt * 16);
   auto epi_passes = [&](auto act_c, auto res_c) {
-#pragma clang fp contract(off)
-    const int ACT = act_c.value, RES = res_c.value;
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
     const int p = pbase + mt * 16 + r16;
     if (TAPS ? (oy0 + mt >= a.out_h || ox >= a.out_w) : p >= a.hw) continue;
     const int pin = TAPS ? (oy0 + mt) * a.out_w + ox : p;      // pixel index inside the image
     const int yo = pin * a.out_ld, ro = pin * a.res_ld;
-    const float nz = nzv[mt];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
       const int n0 = nbase + nt * 16;
       if (n0 >= a.cout) continue;
       float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
-      const float4 bv = bva[nt];
-      if (RES) rv = st_ld4<IOS>(rb, ro + n0);
-      float o[4] = {acc[mt][nt][0] + bv.x + nz, acc[mt][nt][1] + bv.y + nz, acc[mt][nt][2] + bv.z + nz, acc[mt][nt][3] + bv.w + nz};
-      const float r4[4] = {rv.x, rv.y, rv.z, rv.w};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float t = o[c];
-        if (RES == 1) t += r4[c];
-        if (ACT == PPST_ACT_LRELU) t = (t > 0.f ? t : t * 0.2f) * 1.41421356237309515f;
-        else if (ACT == PPST_ACT_PRELU) t = t >= 0.f ? t : t * slope;
-        if (RES == 2) t += r4[c];
-        o[c] = t * a.out_scale;
-      }
+      if (res_c.value) rv = st_ld4<IOS>(rb, ro + n0);
+      float o[4];
+      conv_epi_value4(o, make_float4(acc[mt][nt][0], acc[mt][nt][1], acc[mt][nt][2], acc[mt][nt][3]), bva[nt], nzv[mt], rv, slope, a.out_scale, act_c, res_c);
       st_st4<IOS>(yb, yo + n0, make_float4(o[0], o[1], o[2], o[3]));
-      s1[nt].x += o[0]; s1[nt].y += o[1]; s1[nt].z += o[2]; s1[nt].w += o[3];
-      s2[nt].x += o[0] * o[0]; s2[nt].y += o[1] * o[1]; s2[nt].z += o[2] * o[2]; s2[nt].w += o[3] * o[3];
+      conv_epi_accum(s1[nt], s2[nt], o);
     }
   }
   };
-  {
-    const int resm = a.residual ? (res_after ? 2 : 1) : 0;
-#define EPI_GO(A_)                                                                                    \
-  do {                                                                                                \
-    if (resm == 0) epi_passes(EpiC<A_>{}, EpiC<0>{});                                                 \
-    else if (resm == 1) epi_passes(EpiC<A_>{}, EpiC<1>{});                                            \
-    else epi_passes(EpiC<A_>{}, EpiC<2>{});                                                           \
-  } while (0)
-    if (!SPEC) epi_passes(EpiR{act}, EpiR{resm});      // reduced-precision / experiment kernels: one generic instance
-    else if (act == PPST_ACT_LRELU) EPI_GO(PPST_ACT_LRELU);
-    else if (act == PPST_ACT_PRELU) EPI_GO(PPST_ACT_PRELU);
-    else EPI_GO(PPST_ACT_NONE);
-#undef EPI_GO
-  }
+  CONV_EPI_DISPATCH(SPEC, epi_passes, act, resm);
   if (a.stats) {
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -205,10 +162,7 @@ __device__ __forceinline__ void c1_epilogue(const C1Args& a, f32x4 (&acc)[MT][NT
         t += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, t), 0x140, 0xf, 0xf, true));   // row_mirror
         *uv[q] = t;
       }
-      if (r16 == 0) {
-        float* r = &red[wave][nt * 16 + g * 4][0];
-        r[0] = u.x; r[1] = w.x; r[2] = u.y; r[3] = w.y; r[4] = u.z; r[5] = w.z; r[6] = u.w; r[7] = w.w;
-      }
+      if (r16 == 0) conv_epi_put_sums(&red[wave][nt * 16 + g * 4][0], u, w);
     }
     __syncthreads();
     if (tid < (NT > 4 ? 128 : 64)) {
@@ -247,13 +201,8 @@ __global__ __launch_bounds__(512, 4) void conv1x1_stream_kernel(C1Args a) {
   __shared__ uint4 sB[C1_GROUP * BLOB1 / 16];
   __shared__ float red[8][64][2];
 
-  // XCD-aware order: each XCD gets a contiguous range of work ids; inside it the N tiles of one pixel block are adjacent
-  const int nwg = gridDim.x;
-  int wid;
-  {
-    int id = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = id & 7;
-    wid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-  }
+  // XCD-aware order (conv_common.h); inside an XCD's range the N tiles of one pixel block are adjacent
+  const int wid = xcd_block_id(blockIdx.x, gridDim.x);
   const int ntile = wid % a.n_tiles;
   int mblk = wid / a.n_tiles;
   const int b = mblk / a.tiles;
@@ -281,11 +230,7 @@ __global__ __launch_bounds__(512, 4) void conv1x1_stream_kernel(C1Args a) {
     aoff[mt] = TAPS ? 0 : (int64_t)(pok[mt] ? p : 0) * a.in_ld + g * 8;
   }
   const float in_slope = (INSS && a.in_act == PPST_ACT_PRELU && a.in_prelu) ? a.in_prelu[0] : 0.f;
-  auto in_act = [&](float t) -> float {
-    if (a.in_act == PPST_ACT_LRELU) return (t > 0.f ? t : t * 0.2f) * 1.41421356237309515f;
-    if (a.in_act == PPST_ACT_PRELU) return t >= 0.f ? t : t * in_slope;
-    return t;
-  };
+  auto in_act = [&](float t) -> float { return conv_in_act(t, a.in_act, in_slope); };
 
   f32x4 acc[MT][NT];
 #pragma unroll
@@ -300,12 +245,12 @@ __global__ __launch_bounds__(512, 4) void conv1x1_stream_kernel(C1Args a) {
     if (TAPS) {
       int ix = ox + d.z;
       bool xok = ix >= 0 && ix < a.in_w;
-      ix = c1_pad(ix, a.in_w, a.pad_mode);
+      ix = conv_pad_index(ix, a.in_w, a.pad_mode);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         int iy = oy0 + mt + d.y;
         const bool yok = iy >= 0 && iy < a.in_h;
-        iy = c1_pad(iy, a.in_h, a.pad_mode);
+        iy = conv_pad_index(iy, a.in_h, a.pad_mode);
         pok[mt] = a.pad_mode != PPST_PAD_ZERO || (xok && yok);
         aoff[mt] = ((int64_t)iy * a.in_w + ix) * a.in_ld + g * 8;
       }
@@ -443,15 +388,11 @@ __global__ __launch_bounds__(512, NT_ > 4 ? 2 : 4) void conv3x3_direct_kernel(C1
 #endif
   StepPtr steps = (StepPtr)a.steps;
   const float in_slope = (INSS && a.in_act == PPST_ACT_PRELU && a.in_prelu) ? a.in_prelu[0] : 0.f;
-  auto in_act = [&](float t) -> float {
-    if (a.in_act == PPST_ACT_LRELU) return (t > 0.f ? t : t * 0.2f) * 1.41421356237309515f;
-    if (a.in_act == PPST_ACT_PRELU) return t >= 0.f ? t : t * in_slope;
-    return t;
-  };
+  auto in_act = [&](float t) -> float { return conv_in_act(t, a.in_act, in_slope); };
   // column of the centre pixel and of this lane's edge pixel (lane 0: x0 - 1, lane 15: x0 + 16; other lanes: unused copy)
   const int xe_raw = r16 == 0 ? ox - 1 : (r16 == 15 ? ox + 1 : ox);
   const bool cx_ok = ox < a.in_w, ex_ok = xe_raw >= 0 && xe_raw < a.in_w;
-  const int cx = c1_pad(ox, a.in_w, a.pad_mode), ex = c1_pad(xe_raw, a.in_w, a.pad_mode);
+  const int cx = conv_pad_index(ox, a.in_w, a.pad_mode), ex = conv_pad_index(xe_raw, a.in_w, a.pad_mode);
 
   f32x4 acc[MT][NT];
 #pragma unroll
@@ -464,7 +405,7 @@ __global__ __launch_bounds__(512, NT_ > 4 ? 2 : 4) void conv3x3_direct_kernel(C1
   auto row_load = [&](int chan, int r) {     // input row oy0 - 1 + r of the chunk at channel `chan`
     int iy = oy0 - 1 + r;
     const bool yok = iy >= 0 && iy < a.in_h;
-    iy = c1_pad(iy, a.in_h, a.pad_mode);
+    iy = conv_pad_index(iy, a.in_h, a.pad_mode);
     okc = a.pad_mode != PPST_PAD_ZERO || (yok && cx_ok);
     oke = a.pad_mode != PPST_PAD_ZERO || (yok && ex_ok);
     const float4* pc = (const float4*)(xb + (((int64_t)iy * a.in_w + cx) * a.in_ld + chan + g * 8) * ES);

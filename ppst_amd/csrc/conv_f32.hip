@@ -8,7 +8,7 @@
 // PReLU slopes) amplify that to ~1e-2.  Running the SAME train step on this kernel separates rounding from defects:
 // with it the gradients meet the fp32 reference to its own float32 noise.  1/16 of the bf16 MFMA rate and no LDS
 // staging (operands come from L1/L2): 10-30x slower than conv_mfma_kernel -- never the measured path.
-#include "common.h"
+#include "conv_common.h"
 
 struct ConvF32Args {
   const float* x; const float* w; const int4* steps; float* y;
@@ -21,14 +21,6 @@ struct ConvF32Args {
   int tiles_y, tiles_x, n_tiles;
   const float* in_ss; const float* in_prelu; int in_c, in_act;
 };
-
-__device__ __forceinline__ int f32_pad_index(int i, int n, int mode) {
-  if (mode == PPST_PAD_REFLECT) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * (n - 1) - i;
-  }
-  return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
 
 // block = 256 threads = 4 waves; block tile = 16 x 16 output pixels x 32 output channels; wave w owns rows 4w..4w+3
 // as two 32-pixel M tiles (rows 4w+2m, 4w+2m+1).  MFMA 32x32x2: A lane l -> (pixel l%32, k l/32), B lane l -> (n l%32, k l/32).
@@ -68,8 +60,8 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32Args a) {
       int iy = prow[m] + d.y + a.in_off_y, ix = pcol + d.z + a.in_off_x;
       const bool inb = iy >= 0 && iy < a.in_h && ix >= 0 && ix < a.in_w;
       ok[m] = inb || a.pad_mode != PPST_PAD_ZERO;
-      iy = f32_pad_index(iy, a.in_h, a.pad_mode);
-      ix = f32_pad_index(ix, a.in_w, a.pad_mode);
+      iy = conv_pad_index(iy, a.in_h, a.pad_mode);
+      ix = conv_pad_index(ix, a.in_w, a.pad_mode);
       xp[m] = xb + ((int64_t)iy * a.in_w + ix) * a.in_ld + d.x;
     }
     for (int k = 0; k < 32; k += 2) {
@@ -80,9 +72,7 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32Args a) {
         float av = ok[m] ? xp[m][kk] : 0.f;
         if (a.in_ss && ok[m]) {
           const float* q = a.in_ss + ((int64_t)b * a.in_c + d.x + kk) * 2;
-          av = q[0] * av + q[1];
-          if (a.in_act == PPST_ACT_LRELU) av = (av > 0.f ? av : av * 0.2f) * 1.41421356237309515f;
-          else if (a.in_act == PPST_ACT_PRELU) av = av >= 0.f ? av : av * in_slope;
+          av = conv_in_act(q[0] * av + q[1], a.in_act, in_slope);
         }
         acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[m], 0, 0, 0);
       }
@@ -91,7 +81,7 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32Args a) {
   // epilogue: D tile col = li (channel), row = (reg&3) + 8*(reg>>2) + 4*lk (pixel of the M tile)
   const int gy = group >> 1, gx = group & 1;
   const int act = a.act & 0xff;
-  const bool res_after = (a.act >> 8) & 1;
+  const int resm = a.residual ? (((a.act >> 8) & 1) ? 2 : 1) : 0;
   const float slope = (act == PPST_ACT_PRELU && a.prelu) ? a.prelu[0] : 0.f;
   const float bv = (nok && a.bias) ? a.bias[n] : 0.f;
   float s1 = 0.f, s2 = 0.f;
@@ -105,13 +95,11 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32Args a) {
       const int oy = ty * a.out_sy + (a.n_groups > 1 ? gy : 0), ox = tx * a.out_sx + (a.n_groups > 1 ? gx : 0);
       if (oy >= a.out_h || ox >= a.out_w) continue;
       const int64_t opix = ((int64_t)b * a.out_h + oy) * a.out_w + ox;
-      float t = acc[m][rg] + bv + (a.noise ? a.noise_weight * a.noise[opix] : 0.f);
-      const float r = a.residual ? a.residual[opix * a.res_ld + n] : 0.f;
-      if (!res_after) t += r;
-      if (act == PPST_ACT_LRELU) t = (t > 0.f ? t : t * 0.2f) * 1.41421356237309515f;
-      else if (act == PPST_ACT_PRELU) t = t >= 0.f ? t : t * slope;
-      if (res_after) t += r;
-      t *= a.out_scale;
+      // (out_scale is applied here, with contraction allowed as everywhere in this kernel: its statistics have always summed
+      //  fma(out_scale, u, s1), and restating the arithmetic moves no bit of them)
+      const float u = conv_epi_value(acc[m][rg], bv, a.noise ? a.noise_weight * a.noise[opix] : 0.f,
+                                     a.residual ? a.residual[opix * a.res_ld + n] : 0.f, slope, 1.f, EpiR{act}, EpiR{resm});
+      float t = u * a.out_scale;
       a.y[opix * a.out_ld + n] = t;
       s1 += t;
       s2 += t * t;

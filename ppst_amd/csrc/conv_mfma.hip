@@ -23,42 +23,8 @@
 //    transposed conv as 4 output-phase groups of 2x2 taps; both are just step tables.
 //  * Block -> tile map is XCD-aware: the 8 XCDs each get a contiguous range of an N-major
 //    ordering so that co-resident blocks of one XCD stream the same weight blobs from its L2.
-#include "common.h"
+#include "conv_common.h"
 
-struct ConvKArgs {
-  const float* x;
-  const unsigned short* wpack;
-  const int4* steps;
-  float* y;
-  const float* bias;
-  const float* noise;
-  const float* prelu;
-  float* stats;
-  const float* residual;
-  float noise_weight, out_scale;
-  int B, in_h, in_w, in_ld, out_h, out_w, out_ld, cout;
-  int nsteps, n_groups, pad_mode, in_off_y, in_off_x, out_sy, out_sx, act, res_ld, tile_h, tile_w;
-  int tiles_y, tiles_x, n_tiles;
-  const float* in_ss;     // optional [B][in_c][2] (scale, shift) applied to the input while staging
-  const float* in_prelu;  // slope for in_act == PRELU
-  int in_c, in_act;
-  int early_a;              // step table guarantees chunks of >= 2 steps: a chunk's global loads go out one step early
-  unsigned long long* dbg;  // stamp build: [block][wave][8] cycle sums (else unused)
-  KSplitDev ks;             // ks.S > 1: grid row y runs steps [ks.start[y], ks.start[y + 1]) of every group (common.h)
-  int prefetch_w;           // small grid (<= 512 blocks): a block requests its weight blobs up front (see the kernel's prologue)
-};
-// (the storage type of x / residual / y -- ppst_conv_args.io_st, single-pass precision modes only -- is a template parameter IOS of
-// the kernels, not a field: the pointers above are then half / bfloat16 tensors behind their `float*` type)
-
-__device__ __forceinline__ int pad_index(int i, int n, int mode) {
-  if (mode == PPST_PAD_REFLECT) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * (n - 1) - i;
-  }
-  // replicate, and the safety clamp for reflect on far-out (masked) tile pixels
-  i = i < 0 ? 0 : (i >= n ? n - 1 : i);
-  return i;
-}
 
 // NAS: activation-tile ring depth (0 = default rule below).  1 or 2 only when no group has more
 // chunks than that; those variants also ask for two waves per SIMD so two blocks share a CU.
@@ -110,13 +76,8 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
   unsigned char* smA = smem;
   unsigned char* smB = smem + NA * ABUF;
 
-  // ---- XCD-aware block -> (n index, m tile) map (bijective remap, N-major order)
-  const int nwg = gridDim.x;
-  int wid;
-  {
-    int id = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = id & 7;
-    wid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-  }
+  // ---- XCD-aware block -> (n index, m tile) map, N-major order (conv_common.h)
+  const int wid = xcd_block_id(blockIdx.x, gridDim.x);
   const int m_count = a.B * a.tiles_y * a.tiles_x;
   const int nidx = wid / m_count;          // group * n_tiles + ntile
   int midx = wid - nidx * m_count;
@@ -178,8 +139,8 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
       int iy = ty0 + hy - HALO + a.in_off_y, ix = tx0 + hx - HALO + a.in_off_x;
       bool inb = iy >= 0 && iy < a.in_h && ix >= 0 && ix < a.in_w;
       if (inb || a.pad_mode != PPST_PAD_ZERO) {
-        iy = pad_index(iy, a.in_h, a.pad_mode);
-        ix = pad_index(ix, a.in_w, a.pad_mode);
+        iy = conv_pad_index(iy, a.in_h, a.pad_mode);
+        ix = conv_pad_index(ix, a.in_w, a.pad_mode);
         o = ((iy * a.in_w + ix) * a.in_ld + q4 * 4) * ES;  // bytes, < 2^31: the entry point rejects larger images
       }
     }
@@ -215,11 +176,7 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
       ras1 = p[1];
     }
   };
-  auto in_act = [&](float t) -> float {
-    if (a.in_act == PPST_ACT_LRELU) return (t > 0.f ? t : t * 0.2f) * 1.41421356237309515f;
-    if (a.in_act == PPST_ACT_PRELU) return t >= 0.f ? t : t * in_slope;
-    return t;
-  };
+  auto in_act = [&](float t) -> float { return conv_in_act(t, a.in_act, in_slope); };
   auto a_store = [&](int slot) {
     unsigned char* base = smA + slot * ABUF;
 #pragma unroll
@@ -486,132 +443,13 @@ __global__ __launch_bounds__(64 * WM * WN, NAS ? 2 : 1) void conv_mfma_kernel(Co
     KS_GATHER(acc, 4, 4, NT, S, slot0);
   }
 
-  // ---- epilogue: + bias + noise [+ residual] -> act -> * out_scale -> store, tile statistics.
-  // The accumulators (lane = channel, registers = pixels) are transposed through a per-wave
-  // LDS tile so that every lane stores 16 contiguous bytes of one pixel (128-B segments per
-  // pixel per wave-instruction instead of 64-B ones, 4x fewer store instructions, and the
-  // pixel address arithmetic runs once per float4).  Two passes of 32 channels each.
-  const int gy = group >> 1, gx = group & 1;  // output phase of the transposed conv
-  const int act = a.act & 0xff;
-  const bool res_after = (a.act >> 8) & 1;  // residual joins after the activation (resnet skip)
-  const float slope = (act == PPST_ACT_PRELU && a.prelu) ? a.prelu[0] : 0.f;
-  float* tw = (float*)smem + wave * EPI_TILE;            // main-loop buffers are dead: last barrier passed
-  float* red = (float*)smem + (NT / 64) * EPI_TILE;      // [WM][BN][2]
-  const int f8 = lane & 7, prow = lane >> 3;
-  // Output addressing: 32-bit element offsets inside image b (the entry point rejects images of >= 2^31 elements); the tile row
-  // and the column half of a store are wave-uniform, so their strides are scalar.  (With `opix` as a 64-bit product per store
-  // the epilogue was bound by v_mul_lo_u32 / v_mad_u64_u32: ~45 vector instructions per store, a third of them quarter-rate.)
-  const int egy = a.n_groups > 1 ? gy : 0, egx = a.n_groups > 1 ? gx : 0;
-  const int tyb = ty0 + wm * 4, oyb = tyb * a.out_sy + egy;               // first tile / output row of this wave (uniform)
-  const int txl = tx0 + prow, oxl = txl * a.out_sx + egx;                 // this lane's column for even `it` (odd: 8 further)
-  const bool okx0 = txl < a.tile_w && oxl < a.out_w, okx1 = txl + 8 < a.tile_w && oxl + 8 * a.out_sx < a.out_w;
-  const int pix0 = oyb * a.out_w + oxl, rs_pix = a.out_sy * a.out_w;
-  const int64_t img = (int64_t)b * a.out_h * a.out_w;
-  unsigned char* const yb = (unsigned char*)a.y + img * a.out_ld * ES;
-  const float* const nzb = a.noise ? a.noise + img : nullptr;
-  const unsigned char* const rb = a.residual ? (const unsigned char*)a.residual + img * a.res_ld * ES : nullptr;
-  // Bias and noise of the whole wave tile are fetched BEFORE the first store: vmcnt counts stores too and retires in order, so a
-  // load issued behind a pass's stores made its s_waitcnt sit out their acknowledgements (one HBM round trip per pass).
-  // (buffer loads, every request unconditional -- a pixel outside the tile / image and a launch without noise read out of range and
-  //  get zero: as conditional global loads hipcc issued them one by one, each with its own wait; conv_mfma2.hip's UP9 epilogue)
-  float nzv[8];
-  float4 bva[2];
-  const __amdgpu_buffer_rsrc_t nrs = __builtin_amdgcn_make_buffer_rsrc((void*)(nzb ? (const void*)nzb : (const void*)yb), 0,
-                                                                       nzb ? a.out_h * a.out_w * 4 : 0, 0x00020000);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int r = i >> 1, c8 = i & 1;
-    const bool ok = tyb + r < a.tile_h && oyb + r * a.out_sy < a.out_h && (c8 ? okx1 : okx0);
-    nzv[i] = a.noise_weight * __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                  nrs, ok ? (pix0 + r * rs_pix + c8 * 8 * a.out_sx) * 4 : (int)0x80000000, 0, 0));
-  }
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    const int n0 = ntile * BN + wn * 64 + pass * 32 + f8 * 4;
-    // (unconditional as the noise loads above: channels beyond cout and a launch without bias read out of range -> zeros)
-    bva[pass] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(__builtin_amdgcn_make_buffer_rsrc((void*)(a.bias ? (const void*)a.bias : (const void*)a.y), 0, a.bias ? a.cout * 4 : 0, 0x00020000), n0 * 4, 0, 0));
-  }
-  // The passes are instantiated per (activation, residual mode): as run-time values they cost ~30 VALU instructions per element
-  // (both activation branches evaluated and selected), ~10 when specialised (conv_mfma2.hip).
-  auto epi_passes = [&](auto act_c, auto res_c) {
-#pragma clang fp contract(off)   // no fused multiply-add here: every kernel family's epilogue must round like the others'
-    const int ACT = act_c.value, RES = res_c.value;   // RES: 0 none, 1 joins before the activation, 2 after
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int ntl = 0; ntl < 2; ++ntl)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tw[(mt * 16 + g * 4 + j) * 36 + ntl * 16 + r16] = acc[mt][pass * 2 + ntl][j];
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): only this wave touches its tile
-    __builtin_amdgcn_wave_barrier();
-    const int nl0 = wn * 64 + pass * 32 + f8 * 4;
-    const int n0 = ntile * BN + nl0;
-    const bool nok = n0 < a.cout;
-    const float4 bv = bva[pass];
-    float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int yo0 = pix0 * a.out_ld + n0, ro0 = pix0 * a.res_ld + n0;
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int p = it * 8 + prow;
-      const int r = it >> 1, c8 = it & 1;              // tile row p >> 4 and column half (p & 15) >> 3 of this store
-      float4 v = *(const float4*)(tw + p * 36 + f8 * 4);
-      // (oy / ox bounds: odd scattered extents -- the input gradient of a stride-2 conv)
-      const bool rowok = tyb + r < a.tile_h && oyb + r * a.out_sy < a.out_h;
-      if (nok && rowok && (c8 ? okx1 : okx0)) {
-        const int d = r * rs_pix + c8 * 8 * a.out_sx;  // uniform pixel step from (row 0, even column half)
-        const float nz = nzv[it];
-        float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (RES) rv = st_ld4<IOS>(rb, ro0 + d * a.res_ld);
-        float o[4] = {v.x + bv.x + nz, v.y + bv.y + nz, v.z + bv.z + nz, v.w + bv.w + nz};
-        const float r4[4] = {rv.x, rv.y, rv.z, rv.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          float t = o[c];
-          if (RES == 1) t += r4[c];
-          if (ACT == PPST_ACT_LRELU) t = (t > 0.f ? t : t * 0.2f) * 1.41421356237309515f;
-          else if (ACT == PPST_ACT_PRELU) t = t >= 0.f ? t : t * slope;
-          if (RES == 2) t += r4[c];
-          o[c] = t * a.out_scale;
-        }
-        if (IOS == PPST_ST_F32) PPST_EPI_STORE((float*)yb + (yo0 + d * a.out_ld), o);
-        else st_st4<IOS>(yb, yo0 + d * a.out_ld, make_float4(o[0], o[1], o[2], o[3]));
-        s1.x += o[0]; s1.y += o[1]; s1.z += o[2]; s1.w += o[3];
-        s2.x += o[0] * o[0]; s2.y += o[1] * o[1]; s2.z += o[2] * o[2]; s2.w += o[3] * o[3];
-      }
-    }
-    if (a.stats) {
-      // sum over the 8 pixel rows of the wave (lanes with equal f8): xor 8, 16, 32
-#pragma unroll
-      for (int o = 8; o < 64; o <<= 1) {
-        s1.x += __shfl_xor(s1.x, o, 64); s1.y += __shfl_xor(s1.y, o, 64); s1.z += __shfl_xor(s1.z, o, 64); s1.w += __shfl_xor(s1.w, o, 64);
-        s2.x += __shfl_xor(s2.x, o, 64); s2.y += __shfl_xor(s2.y, o, 64); s2.z += __shfl_xor(s2.z, o, 64); s2.w += __shfl_xor(s2.w, o, 64);
-      }
-      if (prow == 0) {
-        float* r = red + (wm * BN + nl0) * 2;
-        r[0] = s1.x; r[1] = s2.x; r[2] = s1.y; r[3] = s2.y; r[4] = s1.z; r[5] = s2.z; r[6] = s1.w; r[7] = s2.w;
-      }
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();  // tile reads done before the next pass overwrites it
-  }
-  };
-  {
-    const int resm = a.residual ? (res_after ? 2 : 1) : 0;
-#define EPI_GO(A_)                                                                                    \
-  do {                                                                                                \
-    if (resm == 0) epi_passes(EpiC<A_>{}, EpiC<0>{});                                                 \
-    else if (resm == 1) epi_passes(EpiC<A_>{}, EpiC<1>{});                                            \
-    else epi_passes(EpiC<A_>{}, EpiC<2>{});                                                           \
-  } while (0)
-    if (!X3) epi_passes(EpiR{act}, EpiR{resm});        // reduced-precision kernels: one generic instance
-    else if (act == PPST_ACT_LRELU) EPI_GO(PPST_ACT_LRELU);
-    else if (act == PPST_ACT_PRELU) EPI_GO(PPST_ACT_PRELU);
-    else EPI_GO(PPST_ACT_NONE);
-#undef EPI_GO
-  }
+  // ---- epilogue (conv_common.h): two passes of 32 channels through the wave's LDS transposition tile
+  float* red = (float*)smem + (NT / 64) * EPI_TILE;      // [WM][BN][2]; the main-loop buffers are dead: last barrier passed
+  float4 s1a[2], s2a[2];
+  conv_epi_transpose<4, 2, IOS, X3>(a, acc, b, ty0 + wm * 4, tx0, ntile * BN + wn * 64, a.n_groups > 1 ? group >> 1 : 0,
+                                    a.n_groups > 1 ? group & 1 : 0, (float*)smem + wave * EPI_TILE, s1a, s2a, lane);
   if (a.stats) {
+    conv_epi_transpose_sums(s1a, s2a, red + (wm * BN + wn * 64) * 2, lane);
     __syncthreads();
     const int tiles = a.tiles_y * a.tiles_x;
     for (int nl = tid; nl < BN; nl += NT) {
@@ -1072,26 +910,8 @@ extern "C" int ppst_conv2d_mfma(const ppst_conv_args* a, void* stream) {
   if ((a->tile_h - 1) * a->out_sy >= a->out_h || (a->tile_w - 1) * a->out_sx >= a->out_w) return PPST_EINVAL;
   if (a->B == 0) return PPST_OK;
   if (!a->x || !a->wpack || !a->steps || !a->y) return PPST_ENULL;
-  ConvKArgs k;
-  k.x = (const float*)a->x; k.wpack = (const unsigned short*)a->wpack; k.steps = (const int4*)a->steps; k.y = (float*)a->y;
-  k.bias = (const float*)a->bias; k.noise = (const float*)a->noise; k.prelu = (const float*)a->prelu;
-  k.stats = (float*)a->stats; k.residual = (const float*)a->residual;
-  k.noise_weight = a->noise_weight; k.out_scale = a->out_scale;
-  k.B = a->B; k.in_h = a->in_h; k.in_w = a->in_w; k.in_ld = a->in_ld; k.out_h = a->out_h; k.out_w = a->out_w;
-  k.out_ld = a->out_ld; k.cout = a->cout; k.nsteps = a->nsteps; k.n_groups = a->n_groups; k.pad_mode = a->pad_mode;
-  k.in_off_y = a->in_off_y; k.in_off_x = a->in_off_x; k.out_sy = a->out_sy; k.out_sx = a->out_sx; k.act = a->act;
-  k.res_ld = a->res_ld; k.tile_h = a->tile_h; k.tile_w = a->tile_w;
-  k.tiles_y = cdiv(a->tile_h, a->tile_rows); k.tiles_x = cdiv(a->tile_w, a->variant == 11 ? 15 : 16);
-  k.n_tiles = cdiv(a->cout, a->variant == 11 ? 64 : a->dual_b ? a->bn / 2 : a->bn);
-  k.in_ss = (const float*)a->in_scale_shift; k.in_prelu = (const float*)a->in_prelu;
-  k.in_c = a->in_c; k.in_act = a->in_act;
-  k.early_a = a->early_a ? 1 : 0;
-  k.dbg = nullptr;
-  k.ks.scratch = nullptr; k.ks.flags = nullptr; k.ks.epoch = 0; k.ks.S = 1;
-#ifdef PPST_CONV_TRACE
-  k.dbg = (unsigned long long*)a->prelu;  // diagnostic builds: the (unused) prelu slot carries the debug buffer
-  k.prelu = nullptr;
-#endif
+  ConvKArgs k = conv_kargs_fill(a, cdiv(a->cout, a->variant == 11 ? 64 : a->dual_b ? a->bn / 2 : a->bn), cdiv(a->tile_h, a->tile_rows),
+                                cdiv(a->tile_w, a->variant == 11 ? 15 : 16));
   int64_t blocks64 = (int64_t)a->n_groups * k.n_tiles * a->B * k.tiles_y * k.tiles_x;
   if (blocks64 > 0x7fffffff) return PPST_EINVAL;
   int blocks = (int)blocks64;

@@ -19,29 +19,7 @@
 //
 // LDS: activation ring of 2 slots (43 KB each; legal because every chunk of the step table spans >= 2 steps -- the
 // host only selects this kernel for such tables) + weight ring of 2 slots (16 / 32 KB each), one block per CU.
-#include "common.h"
-
-struct Conv2KArgs {
-  const float* x;
-  const unsigned short* wpack;
-  const int4* steps;
-  float* y;
-  const float* bias;
-  const float* noise;
-  const float* prelu;
-  float* stats;
-  const float* residual;
-  float noise_weight, out_scale;
-  int B, in_h, in_w, in_ld, out_h, out_w, out_ld, cout;
-  int nsteps, n_groups, pad_mode, in_off_y, in_off_x, out_sy, out_sx, act, res_ld, tile_h, tile_w;
-  int tiles_y, tiles_x, n_tiles;
-  const float* in_ss;
-  const float* in_prelu;
-  int in_c, in_act;
-  int early_a;
-  unsigned long long* dbg;   // -DPPST_CONV_TRACE builds only
-  KSplitDev ks;              // across-block K split (common.h): grid row y runs steps [ks.start[y], ks.start[y + 1])
-};
+#include "conv_common.h"
 
 // Diagnostic build -DPPST_CONV_TRACE (tests/build_variant.sh): the per-step timeline of conv_mfma.hip's trace, same buffer
 // layout [block < 8][wave][step < 160][8]: 0 absolute start; relative: 1 head (descriptor, DMA, activation loads) issued,
@@ -63,14 +41,6 @@ struct Conv2KArgs {
 #define TR2_FLUSH(s, flag)
 #endif
 
-__device__ __forceinline__ int pad_index2(int i, int n, int mode) {
-  if (mode == PPST_PAD_REFLECT) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * (n - 1) - i;
-  }
-  return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
-
 // WNW x WMW: waves along N x M, eight per block (two per SIMD), each with MT_ m-tiles (16-pixel rows) x 4 n-tiles (16 channels):
 //   4 x 2, MT_ = 8: block tile 16 x 16 px x 256 ch, wave tile 128 px x 64 ch -- the "8-phase template" geometry of the CDNA GEMM guide
 //                   (variant 2: Cout % 256 == 0);
@@ -89,7 +59,7 @@ __device__ __forceinline__ unsigned short f2h_2(float f) { return __builtin_bit_
 // the tile kernel's 64 x 64.  Per output element the MFMA sequence is the tile kernel's (dy-major taps): bit-identical outputs.
 template <int HALO, bool INSS, int WNW, int WMW = 2, int PREC = 0, int MT_ = 8, bool DUAL = false, int IOS = PPST_ST_F32, bool UP9 = false,
           bool K64 = false, bool KS = false>
-__global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : (WNW * WMW == 8 ? 2 : 1)) void conv_mfma2_kernel(Conv2KArgs a) {
+__global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : (WNW * WMW == 8 ? 2 : 1)) void conv_mfma2_kernel(ConvKArgs a) {
   constexpr int NT = 4;                                   // n-tiles (16 channels) per wave
   constexpr bool X3 = PREC == 0;
   // K64 (single-pass modes on half-stored activations): a step covers 64 input channels instead of 32 -- channels 0-31 of the chunk sit
@@ -126,13 +96,8 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : (WNW * WMW ==
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tr_c0)::"memory");
 #endif
 
-  // XCD-aware block -> (n index, m tile) map (bijective remap, N-major order): as conv_mfma.hip
-  const int nwg = gridDim.x;
-  int wid;
-  {
-    int id = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = id & 7;
-    wid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-  }
+  // XCD-aware block -> (n index, m tile) map, N-major order (conv_common.h)
+  const int wid = xcd_block_id(blockIdx.x, gridDim.x);
   const int m_count = a.B * a.tiles_y * a.tiles_x;
   const int nidx = wid / m_count;
   int midx = wid - nidx * m_count;
@@ -183,8 +148,8 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : (WNW * WMW ==
       int iy = ty0 + hy - HALO + a.in_off_y, ix = tx0 + hx - HALO + a.in_off_x;
       bool inb = iy >= 0 && iy < a.in_h && ix >= 0 && ix < a.in_w;
       if (inb || a.pad_mode != PPST_PAD_ZERO) {
-        iy = pad_index2(iy, a.in_h, a.pad_mode);
-        ix = pad_index2(ix, a.in_w, a.pad_mode);
+        iy = conv_pad_index(iy, a.in_h, a.pad_mode);
+        ix = conv_pad_index(ix, a.in_w, a.pad_mode);
         o = ((iy * a.in_w + ix) * a.in_ld + q4 * 4) * ES;  // bytes, < 2^31: the entry point rejects larger images
       }
     }
@@ -216,11 +181,7 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : (WNW * WMW ==
       if (K64) { ras2 = p[16]; ras3 = p[17]; }      // (32 channels = 16 float4 of (a, s) pairs further)
     }
   };
-  auto in_act = [&](float t) -> float {
-    if (a.in_act == PPST_ACT_LRELU) return (t > 0.f ? t : t * 0.2f) * 1.41421356237309515f;
-    if (a.in_act == PPST_ACT_PRELU) return t >= 0.f ? t : t * in_slope;
-    return t;
-  };
+  auto in_act = [&](float t) -> float { return conv_in_act(t, a.in_act, in_slope); };
   auto a_store = [&](int slot) {
     unsigned char* base = smA + slot * ABUF;
 #pragma unroll
@@ -478,37 +439,31 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : (WNW * WMW ==
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int j = 0; j < 4; ++j) e8[t][j] = wm == 0 ? xch[((wn * 2 + t) * 16 + g * 4 + j) * 16 + r16] : 0.f;
-    const int act = a.act & 0xff;
+    const int lrelu = (a.act & 0xff) == PPST_ACT_LRELU ? PPST_ACT_LRELU : PPST_ACT_NONE;
     // store pass: thread = (output column ox = tid >> 4, channel quad c4 = tid & 15); per pass 2 M-waves x 2 output rows
     const int c4 = tid & 15, sox = tid >> 4;
     const int n0 = ntile * 64 + c4 * 4;
-    const float4 bv = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(__builtin_amdgcn_make_buffer_rsrc((void*)(a.bias ? (const void*)a.bias : (const void*)a.y), 0, a.bias ? a.cout * 4 : 0, 0x00020000), n0 * 4, 0, 0));
+    const float4 bv = conv_epi_bias4(a.bias, a.y, a.cout, n0);
     const int64_t img = (int64_t)b * a.out_h * a.out_w;
     float* const yb = a.y + img * a.out_ld;
     const float* const nzb = a.noise ? a.noise + img : nullptr;
     const int oxg = 2 * tx0 + sox;                        // global output column of this thread
     const bool okx = (sox >> 1) < 15 && tx0 + (sox >> 1) < a.tile_w && oxg < a.out_w;
     float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
-    // the noise of this thread's 32 output pixels, all requested before the first store (vmcnt counts stores and retires in order:
-    // a load behind a pass's stores waits for their acknowledgement -- and a load per pass sat in front of its own use)
-    // (buffer loads: every request is unconditional -- pixels outside the tile / image and a launch without noise read out of range
-    //  and get zeros; as conditional global loads hipcc waited for each of the 32 in turn)
+    // the noise of this thread's 32 output pixels, all requested before the first store (conv_common.h)
     float nzv[8][4];
-    const __amdgpu_buffer_rsrc_t nrs = __builtin_amdgcn_make_buffer_rsrc((void*)(nzb ? nzb : (const float*)yb), 0,
-                                                                         nzb ? a.out_h * a.out_w * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t nrs = conv_epi_noise_rsrc(nzb, yb, a.out_h * a.out_w);
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int yl = (q >> 1) * 8 + mt, oy = 2 * (ty0 + yl) + (q & 1);
-        const bool ok = okx && yl < 15 && ty0 + yl < a.tile_h && oy < a.out_h;
-        nzv[mt][q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(nrs, ok ? (oy * a.out_w + oxg) * 4 : (int)0x80000000, 0, 0));
+        nzv[mt][q] = conv_epi_noise(nrs, okx && yl < 15 && ty0 + yl < a.tile_h && oy < a.out_h, oy * a.out_w + oxg);
       }
     // x + 1 neighbours of the first row
     float ee_n = __shfl_down(acc[0][0][0], 16, 64);       // ee[y][column 4 (g + 1)] for j = 3
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
-#pragma clang fp contract(off)
       float een[4], eon[4];                               // ee / eo of row y + 1
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -546,31 +501,18 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : (WNW * WMW ==
         if (okx && yl < 15 && ty0 + yl < a.tile_h && oy < a.out_h) {
           const float4 v = *(const float4*)(tile + (mt & 1) * TPASS + ((wq * 2 + aq) * 32 + sox) * TST + c4 * 4);
           const int pix = oy * a.out_w + oxg;
-          const float nz = a.noise_weight * nzv[mt][q];
-          float o[4] = {v.x + bv.x + nz, v.y + bv.y + nz, v.z + bv.z + nz, v.w + bv.w + nz};
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            float t = o[c];
-            if (act == PPST_ACT_LRELU) t = (t > 0.f ? t : t * 0.2f) * 1.41421356237309515f;
-            o[c] = t * a.out_scale;
-          }
+          // (noise_weight multiplied at use: the 32 loaded values stay as they came; no residual, no PReLU: the entry check)
+          float o[4];
+          conv_epi_value4(o, v, bv, a.noise_weight * nzv[mt][q], make_float4(0.f, 0.f, 0.f, 0.f), 0.f, a.out_scale, EpiR{lrelu}, EpiC<0>{});
           PPST_EPI_STORE(yb + ((int64_t)pix * a.out_ld + n0), o);
-          s1.x += o[0]; s1.y += o[1]; s1.z += o[2]; s1.w += o[3];
-          s2.x += o[0] * o[0]; s2.y += o[1] * o[1]; s2.z += o[2] * o[2]; s2.w += o[3] * o[3];
+          conv_epi_accum(s1, s2, o);
         }
       }
     }
     if (a.stats) {
       // lanes of a wave with equal c4 (lane & 15): xor 16, 32; then the eight waves through LDS
-#pragma unroll
-      for (int o = 16; o < 64; o <<= 1) {
-        s1.x += __shfl_xor(s1.x, o, 64); s1.y += __shfl_xor(s1.y, o, 64); s1.z += __shfl_xor(s1.z, o, 64); s1.w += __shfl_xor(s1.w, o, 64);
-        s2.x += __shfl_xor(s2.x, o, 64); s2.y += __shfl_xor(s2.y, o, 64); s2.z += __shfl_xor(s2.z, o, 64); s2.w += __shfl_xor(s2.w, o, 64);
-      }
-      if (lane < 16) {
-        float* r = red + (wave * 64 + c4 * 4) * 2;
-        r[0] = s1.x; r[1] = s2.x; r[2] = s1.y; r[3] = s2.y; r[4] = s1.z; r[5] = s2.z; r[6] = s1.w; r[7] = s2.w;
-      }
+      conv_epi_xor_sum<16>(s1, s2);
+      if (lane < 16) conv_epi_put_sums(red + (wave * 64 + c4 * 4) * 2, s1, s2);
       __syncthreads();
       if (tid < 64) {
         float t0 = 0.f, t1 = 0.f;
@@ -597,7 +539,8 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : (WNW * WMW ==
     ks_wait(a.ks, wid, tid);
     KS_GATHER(acc, MT, NT, NTHR, S, slot0);
   }
-  // ---- epilogue (as conv_mfma.hip): per wave, passes of 64 pixels x 32 channels through an LDS transposition tile
+  // ---- epilogue: conv_epi_transpose of conv_common.h, kept as this kernel's own copy -- called from here, the shared function costs
+  // the K64 normalise-on-load instances (at 256 registers, 40 bytes of scratch) 8 more bytes of scratch.  Same passes, same helpers.
   const int gy = DUAL ? group : group >> 1, gx = DUAL ? wn / (WNW / 2) : group & 1;   // output row / column phase
   constexpr int BNC = DUAL ? BN / 2 : BN;                                              // channels per N tile
   const int nw0 = DUAL ? (wn % (WNW / 2)) * (16 * NT) : wn * (16 * NT);               // this wave's first channel in the N tile
@@ -607,7 +550,6 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : (WNW * WMW ==
   float* tw = (float*)smem + wave * EPI_TILE;
   float* red = (float*)smem + NWV * EPI_TILE;          // [2 (wm)][BN][2]
   const int f8 = lane & 7, prow = lane >> 3;
-  // output addressing as in conv_mfma.hip: 32-bit element offsets inside image b, row / column-half strides wave-uniform
   const int egy = a.n_groups > 1 ? gy : 0, egx = a.n_groups > 1 ? gx : 0;   // (DUAL: n_groups = 2)
   const int tyb = ty0 + wm * MT, oyb = tyb * a.out_sy + egy;
   const int txl = tx0 + prow, oxl = txl * a.out_sx + egx;
@@ -617,34 +559,24 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : (WNW * WMW ==
   unsigned char* const yb = (unsigned char*)a.y + img * a.out_ld * ES;
   const float* const nzb = a.noise ? a.noise + img : nullptr;
   const unsigned char* const rb = a.residual ? (const unsigned char*)a.residual + img * a.res_ld * ES : nullptr;
-  // bias and noise of the whole wave tile fetched before the first store (vmcnt counts stores and retires in order: conv_mfma.hip)
-  // (buffer loads, every request unconditional -- a pixel outside the tile / image and a launch without noise read out of range and
-  //  get zero: as conditional global loads hipcc issued them one by one, each with its own wait; conv_mfma2.hip's UP9 epilogue)
   float nzv[2 * MT];
   float4 bva[NT / 2];
-  const __amdgpu_buffer_rsrc_t nrs = __builtin_amdgcn_make_buffer_rsrc((void*)(nzb ? (const void*)nzb : (const void*)yb), 0,
-                                                                       nzb ? a.out_h * a.out_w * 4 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t nrs = conv_epi_noise_rsrc(nzb, yb, a.out_h * a.out_w);
 #pragma unroll
   for (int i = 0; i < 2 * MT; ++i) {
     const int r = i >> 1, c8 = i & 1;
     const bool ok = tyb + r < a.tile_h && oyb + r * a.out_sy < a.out_h && (c8 ? okx1 : okx0);
-    nzv[i] = a.noise_weight * __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                  nrs, ok ? (pix0 + r * rs_pix + c8 * 8 * a.out_sx) * 4 : (int)0x80000000, 0, 0));
+    nzv[i] = a.noise_weight * conv_epi_noise(nrs, ok, pix0 + r * rs_pix + c8 * 8 * a.out_sx);
   }
 #pragma unroll
   for (int pass = 0; pass < NT / 2; ++pass) {
     const int n0 = ntile * BNC + nw0 + pass * 32 + f8 * 4;
-    bva[pass] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(__builtin_amdgcn_make_buffer_rsrc((void*)(a.bias ? (const void*)a.bias : (const void*)a.y), 0, a.bias ? a.cout * 4 : 0, 0x00020000), n0 * 4, 0, 0));   // (out of range -> zeros)
+    bva[pass] = conv_epi_bias4(a.bias, a.y, a.cout, n0);
   }
   float4 s1a[NT / 2], s2a[NT / 2];
 #pragma unroll
   for (int i = 0; i < NT / 2; ++i) { s1a[i] = make_float4(0.f, 0.f, 0.f, 0.f); s2a[i] = s1a[i]; }
-  // The pass loops are instantiated per (activation, residual mode): with both as run-time values hipcc evaluated the
-  // leaky-ReLU AND the PReLU branch of every element and selected (~30 VALU instructions per element, 27.7 k cycles per tile
-  // = 9 % of a 72-step tile, profiles/r02_conv_trace_v2.txt); a specialised pass needs ~10.
   auto epi_passes = [&](auto act_c, auto res_c) {
-#pragma clang fp contract(off)   // no fused multiply-add here: every kernel family's epilogue must round like the others'
-    const int ACT = act_c.value, RES = res_c.value;   // RES: 0 none, 1 joins before the activation, 2 after
 #pragma unroll
   for (int mh = 0; mh < (MT + 3) / 4; ++mh) {
     const int MG = MT - mh * 4 < 4 ? MT - mh * 4 : 4;     // m-tiles of this group (MT = 6: 4 + 2)
@@ -673,24 +605,13 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : (WNW * WMW ==
         const bool rowok = tyb + r < a.tile_h && oyb + r * a.out_sy < a.out_h;
         if (nok && rowok && (c8 ? okx1 : okx0)) {
           const int d = r * rs_pix + c8 * 8 * a.out_sx;
-          const float nz = nzv[mh * 8 + it];
           float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (RES) rv = st_ld4<IOS>(rb, ro0 + d * a.res_ld);
-          float o[4] = {v.x + bv.x + nz, v.y + bv.y + nz, v.z + bv.z + nz, v.w + bv.w + nz};
-          const float r4[4] = {rv.x, rv.y, rv.z, rv.w};
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            float t = o[c];
-            if (RES == 1) t += r4[c];
-            if (ACT == PPST_ACT_LRELU) t = (t > 0.f ? t : t * 0.2f) * 1.41421356237309515f;
-            else if (ACT == PPST_ACT_PRELU) t = t >= 0.f ? t : t * slope;
-            if (RES == 2) t += r4[c];
-            o[c] = t * a.out_scale;
-          }
+          if (res_c.value) rv = st_ld4<IOS>(rb, ro0 + d * a.res_ld);
+          float o[4];
+          conv_epi_value4(o, v, bv, nzv[mh * 8 + it], rv, slope, a.out_scale, act_c, res_c);
           if (IOS == PPST_ST_F32) PPST_EPI_STORE((float*)yb + (yo0 + d * a.out_ld), o);
           else st_st4<IOS>(yb, yo0 + d * a.out_ld, make_float4(o[0], o[1], o[2], o[3]));
-          s1a[pass].x += o[0]; s1a[pass].y += o[1]; s1a[pass].z += o[2]; s1a[pass].w += o[3];
-          s2a[pass].x += o[0] * o[0]; s2a[pass].y += o[1] * o[1]; s2a[pass].z += o[2] * o[2]; s2a[pass].w += o[3] * o[3];
+          conv_epi_accum(s1a[pass], s2a[pass], o);
         }
       }
       __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -698,34 +619,14 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : (WNW * WMW ==
     }
   }
   };
-  {
-    const int resm = a.residual ? (res_after ? 2 : 1) : 0;
-#define EPI_GO(A_)                                                                                    \
-  do {                                                                                                \
-    if (resm == 0) epi_passes(EpiC<A_>{}, EpiC<0>{});                                                 \
-    else if (resm == 1) epi_passes(EpiC<A_>{}, EpiC<1>{});                                            \
-    else epi_passes(EpiC<A_>{}, EpiC<2>{});                                                           \
-  } while (0)
-    if (!X3) epi_passes(EpiR{act}, EpiR{resm});        // reduced-precision kernels: one generic instance
-    else if (act == PPST_ACT_LRELU) EPI_GO(PPST_ACT_LRELU);
-    else if (act == PPST_ACT_PRELU) EPI_GO(PPST_ACT_PRELU);
-    else EPI_GO(PPST_ACT_NONE);
-#undef EPI_GO
-  }
+  CONV_EPI_DISPATCH(X3, epi_passes, act, a.residual ? (res_after ? 2 : 1) : 0);
   if (a.stats) {
     __syncthreads();     // the transposition tiles are done: `red` lies behind them, but other waves may still be in their last pass
 #pragma unroll
     for (int pass = 0; pass < NT / 2; ++pass) {
       float4 s1 = s1a[pass], s2 = s2a[pass];
-#pragma unroll
-      for (int o = 8; o < 64; o <<= 1) {
-        s1.x += __shfl_xor(s1.x, o, 64); s1.y += __shfl_xor(s1.y, o, 64); s1.z += __shfl_xor(s1.z, o, 64); s1.w += __shfl_xor(s1.w, o, 64);
-        s2.x += __shfl_xor(s2.x, o, 64); s2.y += __shfl_xor(s2.y, o, 64); s2.z += __shfl_xor(s2.z, o, 64); s2.w += __shfl_xor(s2.w, o, 64);
-      }
-      if (prow == 0) {
-        float* r = red + (wm * BN + wn * (16 * NT) + pass * 32 + f8 * 4) * 2;
-        r[0] = s1.x; r[1] = s2.x; r[2] = s1.y; r[3] = s2.y; r[4] = s1.z; r[5] = s2.z; r[6] = s1.w; r[7] = s2.w;
-      }
+      conv_epi_xor_sum<8>(s1, s2);
+      if (prow == 0) conv_epi_put_sums(red + (wm * BN + wn * (16 * NT) + pass * 32 + f8 * 4) * 2, s1, s2);
     }
     __syncthreads();
     const int tiles = a.tiles_y * a.tiles_x;
@@ -755,26 +656,8 @@ __global__ __launch_bounds__(64 * WNW * WMW, WNW * WMW == 12 ? 3 : (WNW * WMW ==
 
 // Entry used by ppst_conv2d_mfma (conv_mfma.hip) for the variants 2, 7, 9 and 11.
 int ppst_conv2d_mfma2_launch(const ppst_conv_args* a, int n_tiles, int tiles_y, int tiles_x, hipStream_t st) {
-  Conv2KArgs k;
-  k.x = (const float*)a->x; k.wpack = (const unsigned short*)a->wpack; k.steps = (const int4*)a->steps; k.y = (float*)a->y;
-  k.bias = (const float*)a->bias; k.noise = (const float*)a->noise; k.prelu = (const float*)a->prelu;
-  k.stats = (float*)a->stats; k.residual = (const float*)a->residual;
-  k.noise_weight = a->noise_weight; k.out_scale = a->out_scale;
-  k.B = a->B; k.in_h = a->in_h; k.in_w = a->in_w; k.in_ld = a->in_ld; k.out_h = a->out_h; k.out_w = a->out_w;
-  k.out_ld = a->out_ld; k.cout = a->cout; k.nsteps = a->nsteps; k.n_groups = a->n_groups; k.pad_mode = a->pad_mode;
-  k.in_off_y = a->in_off_y; k.in_off_x = a->in_off_x; k.out_sy = a->out_sy; k.out_sx = a->out_sx; k.act = a->act;
-  k.res_ld = a->res_ld; k.tile_h = a->tile_h; k.tile_w = a->tile_w;
-  k.tiles_y = tiles_y; k.tiles_x = tiles_x; k.n_tiles = n_tiles;
-  k.in_ss = (const float*)a->in_scale_shift; k.in_prelu = (const float*)a->in_prelu;
-  k.in_c = a->in_c; k.in_act = a->in_act;
-  k.early_a = a->early_a ? 1 : 0;
-  k.dbg = nullptr;
-#ifdef PPST_CONV_TRACE
-  k.dbg = (unsigned long long*)a->prelu;   // diagnostic builds: the (unused) prelu slot carries the debug buffer
-  k.prelu = nullptr;
-#endif
+  ConvKArgs k = conv_kargs_fill(a, n_tiles, tiles_y, tiles_x);
   const int blocks = a->n_groups * n_tiles * a->B * tiles_y * tiles_x;
-  k.ks.scratch = nullptr; k.ks.flags = nullptr; k.ks.epoch = 0; k.ks.S = 1;
   if (a->ksplit > 1) {
     // across-block K split: the N-256 kernel in its plain forms (8 m-tiles x 4 n-tiles per wave, 8 waves) -- fp32-class mode on fp32
     // tensors, single-pass modes on half-stored ones (what the train step launches); 128 accumulator registers per thread

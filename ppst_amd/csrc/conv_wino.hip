@@ -29,7 +29,7 @@
 //     next K-step while the other half's 48 MFMAs run, so the L2 latency hides under the wave's own MFMAs and the partner wave's;
 //   * the four m_i of a pixel pair sit in four waves: the output transform runs through LDS (which the epilogue's transposition
 //     needs anyway), 32 channels per pass, double-buffered, one barrier per pass.
-#include "common.h"
+#include "conv_common.h"
 
 struct WinoKArgs {
   const float* x;
@@ -50,18 +50,9 @@ struct WinoKArgs {
   KSplitDev ks;          // across-block K split (common.h): grid row y runs chunks [y * nchunk / S, (y + 1) * nchunk / S)
 };
 
-__device__ __forceinline__ int wino_pad_index(int i, int n, int mode) {
-  if (mode == PPST_PAD_REFLECT) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * (n - 1) - i;
-  }
-  return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
-
 #define WINO_LDA(dst, off) dst = *(const bf16x8*)(smem + (off))
 #define WINO_MFMA(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_, b_, c_, 0, 0, 0)
 #define WINO_STEP_BYTES 8192   // one wave's weight fragments of one K-step: 4 n-tiles x (hi | lo) x 64 lanes x 16 B
-#define WINO_OOB ((int)0x80000000)   // buffer-load offset of a padding item: out of range of every image (< 2^31 bytes) -> zeros
 
 // split_bf16x4 (common.h) with the residual formed by scalar subtractions: packed fp32 arithmetic beside MFMAs costs more than two
 // plain instructions (microarch guide), and this kernel's staging runs in the MFMA stream.  Same conversions, same subtraction:
@@ -107,13 +98,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(WinoKArgs a) {
   __shared__ __attribute__((aligned(256))) unsigned char smem[2 * ABUF + 1024 * 2 * 4];
   float* const ss_lds = (float*)(smem + 2 * ABUF);
 
-  // XCD-aware block -> (n tile, image tile) map: as conv_mfma.hip (bijective remap, N-major order)
-  const int nwg = gridDim.x;
-  int wid;
-  {
-    int id = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = id & 7;
-    wid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-  }
+  // XCD-aware block -> (n tile, image tile) map, N-major order (conv_common.h)
+  const int wid = xcd_block_id(blockIdx.x, gridDim.x);
   const int m_count = a.B * a.tiles_y * a.tiles_x;
   const int ntile = wid / m_count;
   int midx = wid - ntile * m_count;
@@ -161,8 +147,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(WinoKArgs a) {
     auto col = [&](int k, bool& ok) __attribute__((always_inline)) {
       int ix = tx0 + 2 * sp - 1 + k;
       ok = (ix >= 0 && ix < a.in_w) || a.pad_mode != PPST_PAD_ZERO;
-      ix = wino_pad_index(ix, a.in_w, a.pad_mode);
-      return ok ? (ix * a.in_ld + sg * 8) * 4 : WINO_OOB;
+      ix = conv_pad_index(ix, a.in_w, a.pad_mode);
+      return ok ? (ix * a.in_ld + sg * 8) * 4 : CONV_OOB;
     };
     colA = col(se ? 3 : 0, okA);
     colB = col(se ? 1 : 2, okB);
@@ -178,7 +164,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(WinoKArgs a) {
     const bool inb = iy >= 0 && iy < a.in_h;
     int o = -1;
     if (hrow < HH && (inb || a.pad_mode != PPST_PAD_ZERO)) {
-      iy = wino_pad_index(iy, a.in_h, a.pad_mode);
+      iy = conv_pad_index(iy, a.in_h, a.pad_mode);
       o = iy * a.in_w * a.in_ld * 4;          // bytes, < 2^31: the entry point rejects larger images
     }
     rowoff[r] = __builtin_amdgcn_readfirstlane(o);
@@ -186,7 +172,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(WinoKArgs a) {
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, a.in_h * a.in_w * a.in_ld * 4, 0x00020000);
   const float in_slope = (INSS && a.in_act == PPST_ACT_PRELU && a.in_prelu) ? a.in_prelu[0] : 0.f;
   // normalise-on-load activation, branch-free: act(t) = (t > 0 ? t : t * in_neg) * in_pos with (in_neg, in_pos) = (1, 1) none,
-  // (0.2, sqrt 2) leaky ReLU, (slope, 1) PReLU -- the same operations as conv_mfma.hip's three-way form, element for element
+  // (0.2, sqrt 2) leaky ReLU, (slope, 1) PReLU -- the same operations as conv_in_act (conv_common.h), element for element
   const float in_neg = !INSS ? 1.f : a.in_act == PPST_ACT_LRELU ? 0.2f : a.in_act == PPST_ACT_PRELU ? in_slope : 1.f;
   const float in_pos = (INSS && a.in_act == PPST_ACT_LRELU) ? 1.41421356237309515f : 1.f;
   auto in_act = [&](float t) __attribute__((always_inline)) -> float { return (t > 0.f ? t : t * in_neg) * in_pos; };
@@ -197,7 +183,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(WinoKArgs a) {
     const int so = (rowoff[r] >= 0 ? rowoff[r] : 0) + chan * 4;
     // (without normalise-on-load the kernel has the two registers per row to spare: the row's requests go out of range and come back
     //  as zeros; with it they are requested at row 0 and zeroed by the prep's mask)
-    const int va = (INMODE == 0 && rowoff[r] < 0) ? WINO_OOB : colA, vb = (INMODE == 0 && rowoff[r] < 0) ? WINO_OOB : colB;
+    const int va = (INMODE == 0 && rowoff[r] < 0) ? CONV_OOB : colA, vb = (INMODE == 0 && rowoff[r] < 0) ? CONV_OOB : colB;
     // (channels 4-7: +16 bytes on the SCALAR offset -- two address registers per lane instead of four; the four spilled in
     //  the normalise-on-load build, and every scratch reload is a vector-memory operation the in-order vmcnt has to drain)
     q[0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrs, va, so, 0));
@@ -429,29 +415,23 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(WinoKArgs a) {
   const float* const nzb = a.noise ? a.noise + img : nullptr;
   const float* const rb = a.residual ? a.residual + img * a.res_ld : nullptr;
   // pass ph, item it: pair row m = 32 ph + 16 it + mloc -> tile row m >> 3, pair m & 7
-  // bias and noise fetched before the first store (vmcnt counts stores and retires in order: conv_mfma.hip)
-  const float4 bv = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(__builtin_amdgcn_make_buffer_rsrc((void*)(a.bias ? (const void*)a.bias : (const void*)a.y), 0, a.bias ? a.cout * 4 : 0, 0x00020000), n0 * 4, 0, 0));     // (out of range -> zeros)
-  // (buffer loads, every request unconditional: a pixel outside the image -- and a launch without noise -- reads out of range and gets
-  //  zero.  As conditional global loads hipcc issued them one by one, each with its own wait: found in the nine-product upscale's
-  //  epilogue, conv_mfma2.hip, where 32 of them cost 0.3 ms of a 2.6-ms launch)
+  // bias and noise fetched before the first store (conv_common.h)
+  const float4 bv = conv_epi_bias4(a.bias, a.y, a.cout, n0);
   float nzv[8 * NIT];
   {
-    const __amdgpu_buffer_rsrc_t nrs = __builtin_amdgcn_make_buffer_rsrc((void*)(nzb ? nzb : (const float*)yb), 0,
-                                                                         nzb ? a.in_h * a.in_w * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t nrs = conv_epi_noise_rsrc(nzb, yb, a.in_h * a.in_w);
 #pragma unroll
     for (int i = 0; i < 8 * NIT; ++i) {
       const int m = 32 * (i / (2 * NIT)) + NML * ((i >> 1) % NIT) + mloc;
       const int oy = ty0 + (m >> 3), ox = tx0 + 2 * (m & 7) + (i & 1);
-      nzv[i] = a.noise_weight * __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                    nrs, (oy < a.in_h && ox < a.in_w) ? (oy * a.in_w + ox) * 4 : WINO_OOB, 0, 0));
+      nzv[i] = a.noise_weight * conv_epi_noise(nrs, oy < a.in_h && ox < a.in_w, oy * a.in_w + ox);
     }
   }
   float4 s1a = make_float4(0.f, 0.f, 0.f, 0.f), s2a = s1a;
   const int resm = a.residual ? (res_after ? 2 : 1) : 0;
   constexpr int TROW2 = 132, TXI2 = 32 * TROW2, TBUF2 = 4 * TXI2;     // floats: 67584 B per buffer
+  // (the activation is a compile-time tag, the residual mode stays a run-time value: this kernel sits at 256 registers)
   auto epi_passes = [&](auto act_c) __attribute__((always_inline)) {
-#pragma clang fp contract(off)   // no fused multiply-add here: every kernel family's epilogue rounds alike
-    const int ACT = act_c.value;
 #pragma unroll
     for (int ph = 0; ph < 4; ++ph) {
       float* tw = T + (ph & 1) * TBUF2 + xi * TXI2 + nh * 64 + r16;
@@ -473,27 +453,16 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(WinoKArgs a) {
 #pragma unroll
         for (int px = 0; px < 2; ++px) {
           if (nok && oy < a.in_h && ox0 + px < a.in_w) {
-            float o[4];
-            if (px == 0) { o[0] = (v0.x + v1.x) + v2.x; o[1] = (v0.y + v1.y) + v2.y; o[2] = (v0.z + v1.z) + v2.z; o[3] = (v0.w + v1.w) + v2.w; }
-            else         { o[0] = (v1.x - v2.x) + v3.x; o[1] = (v1.y - v2.y) + v3.y; o[2] = (v1.z - v2.z) + v3.z; o[3] = (v1.w - v2.w) + v3.w; }
+            float4 o4;
+            if (px == 0) o4 = make_float4((v0.x + v1.x) + v2.x, (v0.y + v1.y) + v2.y, (v0.z + v1.z) + v2.z, (v0.w + v1.w) + v2.w);
+            else         o4 = make_float4((v1.x - v2.x) + v3.x, (v1.y - v2.y) + v3.y, (v1.z - v2.z) + v3.z, (v1.w - v2.w) + v3.w);
             const int pix = oy * a.in_w + ox0 + px;
-            const float nz = nzv[ph * 2 * NIT + it * 2 + px];
             float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
             if (resm) rv = *(const float4*)(rb + (pix * a.res_ld + n0));
-            const float r4[4] = {rv.x, rv.y, rv.z, rv.w};
-            const float b4[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-            for (int cc = 0; cc < 4; ++cc) {
-              float t = o[cc] + b4[cc] + nz;
-              if (resm == 1) t += r4[cc];
-              if (ACT == PPST_ACT_LRELU) t = (t > 0.f ? t : t * 0.2f) * 1.41421356237309515f;
-              else if (ACT == PPST_ACT_PRELU) t = t >= 0.f ? t : t * slope;
-              if (resm == 2) t += r4[cc];
-              o[cc] = t * a.out_scale;
-            }
+            float o[4];
+            conv_epi_value4(o, o4, bv, nzv[ph * 2 * NIT + it * 2 + px], rv, slope, a.out_scale, act_c, EpiR{resm});
             PPST_EPI_STORE(yb + (pix * a.out_ld + n0), o);
-            s1a.x += o[0]; s1a.y += o[1]; s1a.z += o[2]; s1a.w += o[3];
-            s2a.x += o[0] * o[0]; s2a.y += o[1] * o[1]; s2a.z += o[2] * o[2]; s2a.w += o[3] * o[3];
+            conv_epi_accum(s1a, s2a, o);
           }
         }
       }
@@ -506,13 +475,9 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(WinoKArgs a) {
   if (a.stats) {
     // a thread's sums cover its 4 channels over 16 pixels; the other lane of the wave with the same channels is lane ^ 32
     float4 s1 = s1a, s2 = s2a;
-    s1.x += __shfl_xor(s1.x, 32, 64); s1.y += __shfl_xor(s1.y, 32, 64); s1.z += __shfl_xor(s1.z, 32, 64); s1.w += __shfl_xor(s1.w, 32, 64);
-    s2.x += __shfl_xor(s2.x, 32, 64); s2.y += __shfl_xor(s2.y, 32, 64); s2.z += __shfl_xor(s2.z, 32, 64); s2.w += __shfl_xor(s2.w, 32, 64);
+    conv_epi_xor_sum<32>(s1, s2);
     __syncthreads();     // every wave has left its last pass (which read buffer 1; `red` lies in buffer 0)
-    if (lane < 32) {
-      float* r = red + (wave * 128 + f32_ * 4) * 2;
-      r[0] = s1.x; r[1] = s2.x; r[2] = s1.y; r[3] = s2.y; r[4] = s1.z; r[5] = s2.z; r[6] = s1.w; r[7] = s2.w;
-    }
+    if (lane < 32) conv_epi_put_sums(red + (wave * 128 + f32_ * 4) * 2, s1, s2);
     __syncthreads();
     if (tid < 128) {
       const int n = ntile * 128 + tid;

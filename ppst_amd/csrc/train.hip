@@ -12,7 +12,7 @@
 //  * small glue: scatter of the per-step gradients into the (Cout,Cin,k,k) parameter layout,
 //    FromRGB weight gradient, column sums (bias gradients), linear layer gradients, LSGAN
 //    loss/gradient, Adam.
-#include "common.h"
+#include "conv_common.h"   // the XCD block map
 
 // ------------------------------------------------------------ conv wgrad ----
 // partial[split][step][n][32] = sum over this split's pixels of dY[p][n] * X[p + tap(step)][chan(step) + k]
@@ -250,12 +250,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2_kernel(const float* __r
   unsigned char* const imx = smem + IMG_DY;                   // NCH x [136 px][8 quads][16 B]
   const int tid = threadIdx.x, lane = tid & 63, nw = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, kb = lane >> 5;
-  int bx, by, bz;                                             // XCD-aware block map (the comment in front of conv_wgrad_tr2_kernel)
+  int bx, by, bz;                                             // XCD-aware block map (conv_common.h; the comment in front of conv_wgrad_tr2_kernel)
   {
     const int nb = gridDim.x * gridDim.y * gridDim.z;
     const int id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const int q8 = nb >> 3, r8 = nb & 7, xcd = id & 7;
-    int v = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
+    int v = xcd_block_id(id, nb);
     bx = v % (int)gridDim.x; v /= (int)gridDim.x;
     by = v % (int)gridDim.y; bz = v / (int)gridDim.y;
   }
@@ -476,12 +475,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2b_kernel(const unsigned 
   __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63, nw = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, kb = lane >> 5;
-  int bx, by, bz;                                             // XCD-aware block map (the comment in front of conv_wgrad_tr2_kernel)
+  int bx, by, bz;                                             // XCD-aware block map (conv_common.h; the comment in front of conv_wgrad_tr2_kernel)
   {
     const int nb = gridDim.x * gridDim.y * gridDim.z;
     const int id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const int q8 = nb >> 3, r8 = nb & 7, xcd = id & 7;
-    int v = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
+    int v = xcd_block_id(id, nb);
     bx = v % (int)gridDim.x; v /= (int)gridDim.x;
     by = v % (int)gridDim.y; bz = v / (int)gridDim.y;
   }

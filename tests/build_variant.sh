@@ -4,6 +4,7 @@
 set -e
 name=$1; shift
 cd "$(dirname "$0")/.."
+python -m ppst_amd.build   # the other objects, current with every header of build.HEADERS (common.h, conv_common.h, ..)
 obj=ppst_amd/csrc/_obj/conv_mfma_$name.o
 obj2=ppst_amd/csrc/_obj/conv_mfma_2$name.o
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result "$@" -c ppst_amd/csrc/conv_mfma.hip -o $obj
