@@ -708,6 +708,94 @@ int64_t ppst_jpeg_decode_ws(const ppst_jpeg_dec_image* imgs, int B, int subseq_w
 int ppst_jpeg_decode(const void* bytes, int64_t nbytes, const ppst_jpeg_dec_image* imgs_host, const void* imgs_dev, void* out_u8,
                      int64_t out_bytes, void* status, int B, int subseq_words, void* work, void* stream);
 
+/* PNG decode on the device (ppst_amd/csrc/png_parse.hip: host parser; ppst_amd/csrc/png_decode.hip: kernels): B PNG files of
+ * DIFFERENT sizes and colour types, packed into one byte buffer, -> uint8 HWC images, equal byte for byte to what Pillow reads
+ * (numpy.asarray(Image.open(f)); with expand_grey / drop_alpha: Image.open(f).convert("RGB")).  Integer code only.
+ *   accepted     8 bits per sample; colour type 0 (grey), 2 (RGB) or 6 (RGBA); no interlace; compression and filter method 0; at
+ *                least one IDAT, all IDAT chunks consecutive; IEND.  Ancillary chunks (tRNS included) and PLTE in a colour file
+ *                are skipped.
+ *   refused      by ppst_png_parse with one PPST_PNG_E_* each (below); the parser bounds every read by n, trusts no chunk length,
+ *                computes no CRC and inflates nothing
+ *   descriptor   ppst_png_dec_image, plain data: the parser fills everything but the caller's fields (file_off: where the file
+ *                starts in the packed buffer; out_off: where image i starts in out_u8; span_off: index of the file's first span
+ *                in the device span array; mirror: columns reversed; expand_grey: a grey file is written as three equal
+ *                channels; drop_alpha: an RGBA file is written as RGB).  The span table, one ppst_png_span per chunk in file
+ *                order, is the caller's array: type (the four bytes, big-endian), off (of the chunk's DATA within the file), len,
+ *                crc (as stored), idat.  When span_cap is too small the parser returns PPST_PNG_E_SPANS and nspans holds the
+ *                count a second call needs.
+ *   stages       (a) per chunk: CRC-32 over type + data against the stored one; IDAT payloads concatenated to one zlib stream;
+ *                the zlib header (CM 8, CINFO <= 7, no FDICT, a multiple of 31);
+ *                (b) inflate, one workgroup per image, deflate blocks in order: stored blocks copied; for a fixed or dynamic
+ *                block the code tables are built in LDS and the block's bits are cut into subsequences of 32 * subseq_words
+ *                bits (0: the default, 4 words; 2 .. 128).  The state at a boundary is the bit position of the first token at or
+ *                behind it; subsequence 0 enters exactly, every other one is guessed to enter at its boundary; a round decodes
+ *                every subsequence whose entry changed and hands its exit to its successor; rounds repeat until no entry
+ *                changes (at most #subsequences rounds per window of one subsequence per lane).  A second decode writes, for
+ *                the n = H (1 + W C) bytes of the stream, raw[pos] (literals) and src[pos]: pos for a literal,
+ *                pos + (i mod d) - d for byte i of a match at distance d;
+ *                (c) pointer jumping src[i] <- src[src[i]] in place, ceil(log2 n) + 1 launches; stream[i] = raw[src[i]];
+ *                Adler-32 of the stream against the trailer;
+ *                (d) the five row filters undone (one workgroup per image, a row per lane, skewed by one pixel per row), HWC
+ *                store with mirror / expand_grey / drop_alpha.
+ *   status       int32 [B], 0 = decoded; else a sum of PPST_PNG_S_* (below): the image's pixels are then undefined (but written
+ *                within its own bytes only) and every other image of the batch is unaffected
+ *   ppst_png_parse      host code, no GPU
+ *   ppst_png_decode_ws  host code: bytes of the caller-owned workspace for these B descriptors (> 0); PPST_EINVAL for B < 0,
+ *                       subseq_words of 1 or above 128, or a descriptor the parser would not have made
+ *   ppst_png_decode     files: the packed files on the device (files_bytes of them); descs_host: the descriptors (launch
+ *                       geometry); descs_dev: a copy of the same B descriptors on the device; spans_dev: the span tables on the
+ *                       device, file i's nspans entries from span_off; out_u8: out_bytes bytes, image i is HWC at out_off with
+ *                       C = 1, 3 or 4; every file and image must lie inside its buffer: PPST_EINVAL.  work, out_u8, descs_dev,
+ *                       spans_dev: 16-byte aligned.  After the call the first B int32 of work hold, per image, the largest
+ *                       number of rounds one window of the subsequence iteration took.  B = 0: PPST_OK, nothing touched.
+ *                       spans_dev and work carry no length in this interface: the entry point trusts that spans_dev holds
+ *                       span_off + nspans entries for every file and that work has ppst_png_decode_ws bytes (the kernels still
+ *                       clamp every span to its file before reading through it). */
+#define PPST_PNG_E_SIGNATURE (-201)  /* not the eight signature bytes */
+#define PPST_PNG_E_TRUNCATED (-202)  /* the file ends inside a chunk */
+#define PPST_PNG_E_IHDR (-203)       /* the first chunk is not IHDR, or not of 13 bytes; a second IHDR */
+#define PPST_PNG_E_DEPTH (-204)      /* bit depth other than 8 */
+#define PPST_PNG_E_COLOUR (-205)     /* palette (3), grey + alpha (4), or no colour type at all */
+#define PPST_PNG_E_INTERLACE (-206)  /* Adam7 (or an unknown interlace method) */
+#define PPST_PNG_E_SIZE (-207)       /* H or W 0 (or beyond 2^31 - 1) */
+#define PPST_PNG_E_TOO_LARGE (-208)  /* H (1 + W C) >= 2^31, or a file of 2^28 bytes or more */
+#define PPST_PNG_E_IDAT (-209)       /* no IDAT, or IDAT chunks that are not consecutive */
+#define PPST_PNG_E_IEND (-210)       /* no IEND */
+#define PPST_PNG_E_APNG (-211)       /* acTL: an animation */
+#define PPST_PNG_E_METHOD (-212)     /* compression or filter method other than 0 */
+#define PPST_PNG_E_SPANS (-213)      /* span_cap too small: nspans holds the count needed */
+#define PPST_PNG_S_CRC 1             /* status bits: a chunk's CRC-32 */
+#define PPST_PNG_S_ZLIB 2            /*   zlib header */
+#define PPST_PNG_S_BTYPE 4           /*   block type 3 */
+#define PPST_PNG_S_STORED 8          /*   LEN / NLEN of a stored block, or a stored block beyond the stream */
+#define PPST_PNG_S_LENGTHS 16        /*   code lengths: over-subscribed, incomplete, bad repeat, too many symbols, no end-of-block */
+#define PPST_PNG_S_CODE 32           /*   a code no table defines */
+#define PPST_PNG_S_DISTANCE 64       /*   a distance beyond the bytes produced so far */
+#define PPST_PNG_S_STREAM 128        /*   more or fewer than H (1 + W C) bytes, or the bits end before the final block does */
+#define PPST_PNG_S_ADLER 256         /*   Adler-32 */
+#define PPST_PNG_S_FILTER 512        /*   a filter byte above 4 */
+typedef struct ppst_png_span {
+  uint32_t type;              /* 'I' << 24 | 'D' << 16 | 'A' << 8 | 'T' */
+  int32_t off, len;           /* the chunk's data within the file */
+  uint32_t crc;               /* as the file states it */
+  int32_t idat;               /* 1: an IDAT chunk */
+} ppst_png_span;
+typedef struct ppst_png_dec_image {
+  int32_t H, W, colour, channels;
+  int32_t nspans;             /* chunks of the file */
+  int32_t first_idat, nidat;  /* span indices: the IDAT chunks are first_idat .. first_idat + nidat - 1 */
+  int32_t idat_bytes;         /* the sum of their lengths: the zlib stream */
+  int64_t file_len;
+  int64_t file_off, out_off, span_off;       /* the caller's */
+  int32_t mirror, expand_grey, drop_alpha;
+  int32_t pad_;
+} ppst_png_dec_image;
+int ppst_png_parse(const void* file, int64_t n, ppst_png_dec_image* out, ppst_png_span* spans, int span_cap);
+int64_t ppst_png_decode_ws(const ppst_png_dec_image* descs, int B, int subseq_words);
+int ppst_png_decode(const void* files, int64_t files_bytes, const ppst_png_dec_image* descs_host, const void* descs_dev,
+                    const void* spans_dev, void* out_u8, int64_t out_bytes, void* status, int B, int subseq_words, void* work,
+                    void* stream);
+
 /* ------------------------------------------------ LPIPS-AlexNet metric ---- */
 /* LPIPS v0.1, net = 'alex', lpips = True, spatial = False, normalize = False, eval mode (csrc/lpips.hip): for two fp32 image
  * batches a, b (B, 3, H, W)

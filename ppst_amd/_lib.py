@@ -69,6 +69,19 @@ class JpegDecImage(ctypes.Structure):
                 ("bits", _u8 * 16 * 4), ("vals", _u8 * 256 * 4), ("file_off", i64), ("out_off", i64), ("mirror", i32), ("expand_grey", i32)]
 
 
+class PngSpan(ctypes.Structure):
+    """ppst_png_span (include/ppst_hip.h): one chunk of a PNG file."""
+    _fields_ = [("type", ctypes.c_uint32), ("off", i32), ("len", i32), ("crc", ctypes.c_uint32), ("idat", i32)]
+
+
+class PngDecImage(ctypes.Structure):
+    """ppst_png_dec_image (include/ppst_hip.h): one file's descriptor, filled by ppst_png_parse but for the caller's fields
+    (file_off, out_off, span_off, mirror, expand_grey, drop_alpha)."""
+    _fields_ = [("H", i32), ("W", i32), ("colour", i32), ("channels", i32), ("nspans", i32), ("first_idat", i32), ("nidat", i32),
+                ("idat_bytes", i32), ("file_len", i64), ("file_off", i64), ("out_off", i64), ("span_off", i64),
+                ("mirror", i32), ("expand_grey", i32), ("drop_alpha", i32), ("pad_", i32)]
+
+
 GROUP_MAX = 32           # PPST_GROUP_MAX
 
 
@@ -169,6 +182,9 @@ _SIGS = {
     "ppst_jpeg_parse": (i32, [vp, i64, ctypes.POINTER(JpegDecImage)]),
     "ppst_jpeg_decode_ws": (i64, [ctypes.POINTER(JpegDecImage), i32, i32]),
     "ppst_jpeg_decode": (i32, [vp, i64, ctypes.POINTER(JpegDecImage), vp, vp, i64, vp, i32, i32, vp, vp]),
+    "ppst_png_parse": (i32, [vp, i64, ctypes.POINTER(PngDecImage), ctypes.POINTER(PngSpan), i32]),
+    "ppst_png_decode_ws": (i64, [ctypes.POINTER(PngDecImage), i32, i32]),
+    "ppst_png_decode": (i32, [vp, i64, ctypes.POINTER(PngDecImage), vp, vp, vp, i64, vp, i32, i32, vp, vp]),
     "ppst_lpips_pack_floats": (i64, []),
     "ppst_lpips_pack": (i32, [vp, vp, vp, vp, vp, vp, vp]),
     "ppst_lpips_dims": (i32, [i32, i32, ctypes.POINTER(i32)]),
@@ -264,6 +280,15 @@ JPEG_REFUSALS = {-101: "truncated file", -102: "not a JPEG file (no SOI)", -103:
                  -114: "spectral selection or approximation other than 0, 63, 0"}
 # the bits of ppst_jpeg_decode's status words (PPST_JPEG_S_*)
 JPEG_STATUS_BITS = {1: "marker inside the scan", 2: "restart marker count", 4: "restart marker order", 8: "undefined code", 16: "block count"}
+# ppst_png_parse's refusals (PPST_PNG_E_* of include/ppst_hip.h; -213, the span array too small, is handled by ops.png_parse)
+PNG_REFUSALS = {-201: "not a PNG file (bad signature)", -202: "truncated file", -203: "IHDR not first, or of the wrong size",
+                -204: "bit depth other than 8", -205: "palette or grey + alpha colour type", -206: "Adam7 interlace",
+                -207: "height or width 0", -208: "image or file too large", -209: "IDAT missing or not consecutive",
+                -210: "IEND missing", -211: "APNG animation (acTL)", -212: "compression or filter method other than 0"}
+PNG_E_SPANS = -213
+# the bits of ppst_png_decode's status words (PPST_PNG_S_*)
+PNG_STATUS_BITS = {1: "chunk CRC", 2: "zlib header", 4: "block type 3", 8: "stored-length mismatch", 16: "bad code lengths",
+                   32: "undefined code", 64: "distance too far", 128: "stream length", 256: "Adler-32", 512: "filter byte"}
 
 
 def check(rc, what):

@@ -246,7 +246,7 @@ def _check_decoder(decode):
 @contextlib.contextmanager
 def decoder(name):
     """``with decoder("device"):`` -- load_images, evaluate_swap_files and evaluate_grid_folder called from THIS thread inside the
-    block decode JPEG files with the HIP decoder (load_images' ``decode=`` argument still wins).  ValueError for an unknown name,
+    block decode JPEG and PNG files with the HIP decoders (load_images' ``decode=`` argument still wins).  ValueError for an unknown name,
     before anything runs."""
     _check_decoder(name)
     prev = current_decoder()
@@ -264,8 +264,9 @@ def _read_file(path):
 
 def decode_files_device(blobs, names, device="cuda", mirror=None):
     """The device half of ``decode="device"``: blobs[i] = the bytes of file names[i].  -> list with a (H,W,3) uint8 device tensor
-    where the HIP decoder took the file and decoded it with status 0 (one batched call over all of them, imageio / ops.jpeg_decode),
-    None where the host has to: another extension, a file the parser refuses, a non-zero status."""
+    where a HIP decoder took the file and decoded it with status 0 (one batched call over all .jpg / .jpeg files, ops.jpeg_decode,
+    and one over all .png files, ops.png_decode), None where the host has to: another extension, a file the parser refuses, a
+    non-zero status."""
     out = [None] * len(blobs)
     parsed = {i: ops.jpeg_parse(b) for i, (b, n) in enumerate(zip(blobs, names)) if n.lower().endswith((".jpg", ".jpeg"))}
     take = [i for i in sorted(parsed) if parsed[i][0] == 0]
@@ -275,14 +276,22 @@ def decode_files_device(blobs, names, device="cuda", mirror=None):
                                         parsed=[parsed[i][1] for i in take])
         for i, v, st in zip(take, views, status.cpu().tolist()):
             out[i] = v if st == 0 else None
+    parsed = {i: ops.png_parse(b) for i, (b, n) in enumerate(zip(blobs, names)) if n.lower().endswith(".png")}
+    take = [i for i in sorted(parsed) if parsed[i][0] == 0]
+    if take:                                                     # grey -> three channels, alpha dropped: Pillow's convert("RGB")
+        views, status = ops.png_decode([blobs[i] for i in take], expand_grey=True, drop_alpha=True, device=device,
+                                       mirror=None if mirror is None else [mirror[i] for i in take],
+                                       parsed=[parsed[i][1:] for i in take])
+        for i, v, st in zip(take, views, status.cpu().tolist()):
+            out[i] = v if st == 0 else None
     return out
 
 
 def load_images(paths, load_size=512, device="cuda", pool=None, decode=None):
     """data/base_dataset.py:85-171 (scale_shortside + make_power_2 + ToTensor + Normalize) for a list of files: decode on
     host threads, everything else on the device.  Returns a list of (1,3,H,W) tensors (sizes may differ per file).
-    ``decode="device"``: the threads only read the files' bytes; the .jpg / .jpeg files the HIP decoder takes are decoded in ONE
-    batched call on the device (bit-identical to Pillow), every other file -- and any the device reports damaged -- goes through
+    ``decode="device"``: the threads only read the files' bytes; the .jpg / .jpeg and the .png files the HIP decoders take are
+    decoded in ONE batched call each on the device (bit-identical to Pillow), every other file -- and any the device reports damaged -- goes through
     Pillow as before, so a file fails here exactly when it fails with ``"host"``.  ``decode=None``: the module's setting (``decoder``)."""
     from . import imageio
     decode = current_decoder() if decode is None else decode
@@ -402,7 +411,7 @@ def evaluate_grid_folder(model, dataroot, out_dir, rank=0, world=1, smooth=True,
     Multi-GPU: every rank reads all inputs (they are small), computes its share (swapping_grid) and writes its own files.
     ``png``: "host" = Pillow on the worker threads, "device" = the HIP encoder (the threads only write the bytes).
     ``format="jpeg"``: JPEG files of that quality and subsampling under the same names with .jpg, by the same switch.
-    Inside ``with evaluation.decoder("device"):`` the threads read bytes and the HIP decoder takes the JPEG files it can in one
+    Inside ``with evaluation.decoder("device"):`` the threads read bytes and the HIP decoders take the JPEG and PNG files they can in one
     batched call (load_images); otherwise Pillow decodes on the worker threads."""
     import os
     _check_encoder(png)

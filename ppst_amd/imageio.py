@@ -15,6 +15,8 @@ row filters, deflate and checksums as HIP kernels) and brings only the file byte
 for baseline JPEG files (csrc/jpeg.hip: colour conversion, integer DCT, Huffman coding and restart intervals as HIP kernels).
 ``decode_jpeg`` is the way in: baseline JPEG files of any origin -> uint8 tensors on the device, equal to Pillow's decode byte for
 byte (csrc/jpeg_decode.hip: a parallel Huffman decoder for one sequential stream, integer IDCT, upsampling and colour).
+``decode_png`` is the same for 8-bit grey / RGB / RGBA PNG files (csrc/png_decode.hip: chunk CRCs, a parallel inflate, LZ77
+back-references by pointer jumping, the row filters undone).
 """
 import math
 
@@ -205,6 +207,37 @@ def decode_jpeg(blobs, mode=None, device="cuda"):
         if st:
             why = ", ".join(v for k, v in sorted(_lib.JPEG_STATUS_BITS.items()) if st & k)
             raise OSError("decode_jpeg: file %d is damaged (%s)" % (i, why))
+    return views
+
+
+def png_info(blob):
+    """What the device decoder would do with this file, without a GPU (ppst_png_parse): {"supported": True, "height", "width",
+    "colour_type" (0, 2 or 6), "channels", "chunks" [(type, data offset, length) per chunk], "idat_chunks", "idat_bytes"} or
+    {"supported": False, "code", "reason"}."""
+    from . import _lib
+    rc, d, spans = ops.png_parse(blob)
+    if rc != 0:
+        return {"supported": False, "code": rc, "reason": _lib.PNG_REFUSALS.get(rc, "error %d" % rc)}
+    return {"supported": True, "height": d.H, "width": d.W, "colour_type": d.colour, "channels": d.channels,
+            "chunks": [(int(s.type).to_bytes(4, "big").decode("latin-1"), s.off, s.len) for s in spans[:d.nspans]],
+            "idat_chunks": d.nidat, "idat_bytes": d.idat_bytes}
+
+
+def decode_png(blobs, mode=None, device="cuda"):
+    """blobs: list of PNG files (bytes; 8 bits per sample, grey / RGB / RGBA, not interlaced; sizes and types may differ) -> list
+    of (H,W,C) uint8 tensors on the device, each equal to ``numpy.asarray(PIL.Image.open(file))``: C = 1, 3 or 4.
+    ``mode="RGB"``: every image comes out with three channels, as Pillow's ``convert("RGB")`` gives them (grey three times, alpha
+    dropped).  One batched call (ops.png_decode).  ValueError with the parser's reason for a file the decoder does not take
+    (palette, 16-bit, interlaced, ...: ``png_info`` tells without a GPU); OSError naming the status bits for a file the device
+    found damaged."""
+    from . import _lib
+    if mode not in (None, "RGB"):
+        raise ValueError("mode must be None or 'RGB', not %r" % (mode,))
+    views, status = ops.png_decode(blobs, expand_grey=(mode == "RGB"), drop_alpha=(mode == "RGB"), device=device)
+    for i, st in enumerate(status.cpu().tolist()):
+        if st:
+            why = ", ".join(v for k, v in sorted(_lib.PNG_STATUS_BITS.items()) if st & k)
+            raise OSError("decode_png: file %d is damaged (%s)" % (i, why))
     return views
 
 

@@ -1894,6 +1894,128 @@ def jpeg_decode(blobs, expand_grey=False, mirror=None, subseq_words=0, device="c
     return (call.views(), call.status, call.rounds()) if rounds else (call.views(), call.status)
 
 
+def png_parse(blob):
+    """bytes of a PNG file -> (ppst_png_parse's return code, the descriptor it filled, its span table: a ctypes array of
+    ``nspans`` PngSpan).  Host code: no GPU.  The span array is sized by a first call and, when the file has more chunks than
+    that, by the count the parser leaves."""
+    blob = blob if isinstance(blob, bytes) else bytes(blob)
+    d = _lib.PngDecImage()
+    cap = 16
+    while True:
+        spans = (_lib.PngSpan * cap)()
+        rc = lib.ppst_png_parse(blob, len(blob), ctypes.byref(d), spans, cap)
+        if rc != _lib.PNG_E_SPANS:
+            return rc, d, spans
+        cap = d.nspans
+
+
+class _PngDecodeCall:
+    """One batched PNG decode, prepared: the files parsed and packed into one pinned buffer with their descriptors and span tables
+    behind them (one host-to-device copy), output / status / workspace from torch's allocator.  ``launch()`` runs the kernels
+    (again and again: tests/png_decode_time.py times them alone)."""
+
+    def __init__(self, blobs, expand_grey, drop_alpha, mirror, subseq_words, dev, parsed=None):
+        blobs = [b if isinstance(b, bytes) else bytes(b) for b in blobs]
+        B = self.B = len(blobs)
+        if mirror is not None and len(mirror) != B:
+            raise ValueError("mirror must be None or one flag per file")
+        if parsed is not None and len(parsed) != B:
+            raise ValueError("parsed must be None or one (descriptor, spans) pair per file")
+        for flag in (expand_grey, drop_alpha):
+            if isinstance(flag, (list, tuple)) and len(flag) != B:
+                raise ValueError("expand_grey and drop_alpha must be one flag, or one flag per file")
+        if isinstance(subseq_words, bool) or not isinstance(subseq_words, int) or not (subseq_words == 0 or 2 <= subseq_words <= 128):
+            raise ValueError("png_decode: subseq_words must be 0 (the default) or 2 .. 128, got %r" % (subseq_words,))
+        self.subseq_words, self.dev = subseq_words, dev
+        descs = self.descs = (_lib.PngDecImage * max(B, 1))()
+        tables = []
+        file_off, out_off, span_off = 0, 0, 0
+        for i, blob in enumerate(blobs):
+            if parsed is not None:
+                d0, spans = parsed[i]
+            else:
+                rc, d0, spans = png_parse(blob)
+                if rc != 0:
+                    raise ValueError("png_decode: file %d: %s" % (i, _lib.PNG_REFUSALS.get(rc, "error %d" % rc)))
+            descs[i] = d0                                        # (a copy: the caller's descriptor keeps its own fields)
+            d = descs[i]
+            if d.file_len != len(blob) or d.nspans < 1 or len(spans) < d.nspans:
+                raise ValueError("png_decode: file %d: the descriptor is not this file's" % i)
+            tables.append(spans)
+            d.file_off, d.out_off, d.span_off = file_off, out_off, span_off
+            d.mirror = int(bool(mirror[i])) if mirror is not None else 0
+            d.expand_grey, d.drop_alpha = int(self._flag(expand_grey, i)), int(self._flag(drop_alpha, i))
+            file_off += (len(blob) + 15) & ~15
+            out_off += (d.H * d.W * self._channels(d) + 15) & ~15
+            span_off += d.nspans
+        self.nbytes, self.out_bytes = file_off, out_off
+        self.status = torch.zeros((B,), device=dev, dtype=torch.int32)
+        if B == 0:
+            return
+        ws = lib.ppst_png_decode_ws(descs, B, subseq_words)
+        if ws < 0:
+            raise ValueError("png_decode: the library refused the descriptors (%d)" % ws)
+        nd, span_size = ctypes.sizeof(_lib.PngDecImage) * B, ctypes.sizeof(_lib.PngSpan)
+        ns = (span_off * span_size + 15) & ~15
+        host = torch.empty((file_off + nd + ns,), dtype=torch.uint8).pin_memory()
+        hv = host.numpy()
+        for i, blob in enumerate(blobs):
+            hv[descs[i].file_off:descs[i].file_off + len(blob)] = memoryview(blob)
+        ctypes.memmove(host.data_ptr() + file_off, ctypes.addressof(descs), nd)       # descriptors and spans ride behind the files
+        for i in range(B):
+            ctypes.memmove(host.data_ptr() + file_off + nd + descs[i].span_off * span_size, ctypes.addressof(tables[i]),
+                           descs[i].nspans * span_size)
+        # (torch's caching host allocator keeps a pinned block from reuse until the copies recorded on it are done)
+        onchip = host.to(dev, non_blocking=True)
+        self.packed, self.ddesc, self.dspans = onchip[:file_off], onchip[file_off:file_off + nd], onchip[file_off + nd:]
+        self.out = torch.empty((out_off,), device=dev, dtype=torch.uint8)
+        self.work = torch.empty((ws,), device=dev, dtype=torch.uint8)
+
+    @staticmethod
+    def _flag(flag, i):
+        """one flag for the batch, or a list of one per file"""
+        return bool(flag[i]) if isinstance(flag, (list, tuple)) else bool(flag)
+
+    @staticmethod
+    def _channels(d):
+        return (3 if d.expand_grey else 1) if d.channels == 1 else (3 if d.channels == 3 or d.drop_alpha else 4)
+
+    def launch(self):
+        if self.B:
+            with torch.cuda.device(self.dev):
+                check(lib.ppst_png_decode(_p(self.packed), self.nbytes, self.descs, _p(self.ddesc), _p(self.dspans), _p(self.out),
+                                          self.out_bytes, _p(self.status), self.B, self.subseq_words, _p(self.work), _stream()),
+                      "ppst_png_decode")
+        return self
+
+    def views(self):
+        out = []
+        for i in range(self.B):
+            d = self.descs[i]
+            C = self._channels(d)
+            out.append(self.out[d.out_off:d.out_off + d.H * d.W * C].view(d.H, d.W, C))
+        return out
+
+    def rounds(self):
+        return self.work[:4 * self.B].view(torch.int32).clone() if self.B else self.status.clone()
+
+
+def png_decode(blobs, expand_grey=False, drop_alpha=False, mirror=None, device="cuda", parsed=None, subseq_words=0, rounds=False):
+    """blobs: B PNG files (bytes) of any sizes, 8-bit grey / RGB / RGBA -> (list of B (H,W,C) uint8 views of one device buffer,
+    status (B,) int32 on the device; 0 = decoded: include/ppst_hip.h, csrc/png_decode.hip).  C = 1, 3 or 4 as the file has it;
+    ``expand_grey``: a grey file comes out with three equal channels; ``drop_alpha``: an RGBA file comes out as RGB (each one
+    flag, or a list of B flags); ``mirror``: None or B flags, image i comes out with its columns reversed.  The files, descriptors and span tables are packed into one
+    pinned buffer: one host-to-device copy.  A file the parser refuses raises ValueError with its reason.  ``parsed``: the
+    files' (descriptor, spans) pairs where the caller has them already (``png_parse`` returned 0 for each).  ``subseq_words``:
+    32-bit words per subsequence of the parallel inflate, 0 = the default.  ``rounds``: also return the (B,) int32 tensor of
+    rounds the subsequence iteration took."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("png_decode needs a CUDA (HIP) device (no CPU fallback)")
+    call = _PngDecodeCall(blobs, expand_grey, drop_alpha, mirror, subseq_words, dev, parsed).launch()
+    return (call.views(), call.status, call.rounds()) if rounds else (call.views(), call.status)
+
+
 def resample_f32(x, out_h, out_w, clamp=None):
     """x (..., H, W) float32 on the device -> (..., out_h, out_w): Pillow's antialiased bicubic on every plane, both axes in one
     launch (ppst_resample_f32; the fp32 weight tables are imageio.resample_tables_f32).  ``clamp`` = (lo, hi) or None."""

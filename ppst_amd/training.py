@@ -111,10 +111,12 @@ class CelebAMaskDataset:
     (base_dataset.py:130-132, CelebAMask_dataset.py:17-18); here ONE draw flips both.  (2) the reference resizes the 'L' label
     image with its BICUBIC transform and then compares ``mask_np == i``; at the dataset's native 512 that is the identity, off
     size it invents label values -- here labels are resized NEAREST.  The next batch is decoded on a worker thread while the
-    current step runs (the reference: DataLoader workers).  ``decode="device"``: the worker thread only reads the image files and
-    parses their headers; ``next()`` decodes the batch's JPEG files in one call of the HIP decoder (imageio / ops.jpeg_decode), the
-    flip as its ``mirror`` -- the same batches, bit for bit.  Files the decoder does not take go through Pillow as before; labels
-    stay PNG on the host."""
+    current step runs (the reference: DataLoader workers).  ``decode="device"``: the worker thread only reads the files and
+    parses their headers; ``next()`` decodes the batch's JPEG files in one call of the HIP JPEG decoder and its PNG files -- images
+    and labels together -- in one call of the HIP PNG decoder (ops.jpeg_decode, ops.png_decode), the flip as their ``mirror`` -- the
+    same batches, bit for bit.  A label file takes that path when it is a grey (colour type 0) PNG whose size already equals the
+    preprocessed image's: it is mirrored with the image's draw and cast to int64 on the device.  Every other label file keeps the
+    Pillow ``convert("L")`` + NEAREST path, and image files the decoders do not take go through Pillow as before."""
 
     def __init__(self, dataroot, size=512, batch_size=2, rank=0, world=1, device="cuda", seed=0, preprocess="resize",
                  flip=True, prefetch=True, decode="host"):
@@ -143,29 +145,48 @@ class CelebAMaskDataset:
         g.shuffle(order)
         return order[self.rank::self.world] or order[:1]
 
+    def _out_size(self, W, H):
+        """(W, H) of the preprocessed image of a W x H file"""
+        from . import imageio
+        if self.preprocess == "resize":
+            return imageio.make_power_2_size(self.size, self.size)
+        return imageio.make_power_2_size(*imageio.scale_shortside_size(W, H, self.size))
+
     def _decode(self, idx):
-        """host side: file -> (uint8 HWC image, PIL 'L' label), optionally mirrored together.  With the device decoder a JPEG file
-        it takes stays bytes here: the image is then (bytes, mirror flag, path, parsed descriptor)."""
+        """host side: file -> (uint8 HWC image, PIL 'L' label), optionally mirrored together.  With the device decoder a JPEG or PNG
+        file it takes stays bytes here: the image is then (bytes, mirror flag, path, parsed descriptor) -- the descriptor of a PNG
+        file is the pair (descriptor, spans) --, and so is the label where it is a grey PNG of the preprocessed image's size."""
         from PIL import Image
         ip, lp = self.pairs[idx]
         try:
-            blob = None
-            if self.decode == "device" and ip.lower().endswith((".jpg", ".jpeg")):
+            blob, lblob = None, None
+            if self.decode == "device" and ip.lower().endswith((".jpg", ".jpeg", ".png")):
                 with open(ip, "rb") as f:
                     blob = f.read()
-                rc, desc = ops.jpeg_parse(blob)
+                if ip.lower().endswith(".png"):
+                    rc, d, spans = ops.png_parse(blob)
+                    desc, wh = (d, spans), (d.W, d.H)
+                else:
+                    rc, desc = ops.jpeg_parse(blob)
+                    wh = (desc.W, desc.H)
                 if rc != 0:
                     blob = None
             img = np.asarray(Image.open(ip).convert("RGB")) if blob is None else None
-            lab = Image.open(lp).convert("L")
+            if self.decode == "device":
+                with open(lp, "rb") as f:
+                    lblob = f.read()
+                rc, d, spans = ops.png_parse(lblob)
+                if rc != 0 or d.colour != 0 or (d.W, d.H) != self._out_size(*(wh if blob is not None else (img.shape[1], img.shape[0]))):
+                    lblob = None
+            lab = Image.open(lp).convert("L") if lblob is None else None
         except OSError as err:                                   # CelebAMask_dataset.py:33-38: retry a random index
             print(err)
             return self._decode(self.rng.randrange(len(self.pairs)))
         flip = bool(self.flip and self.rng.random() < 0.5)
         if flip:
             img = np.ascontiguousarray(img[:, ::-1]) if img is not None else None
-            lab = lab.transpose(Image.FLIP_LEFT_RIGHT)
-        return (img if blob is None else (blob, flip, ip, desc)), lab
+            lab = lab.transpose(Image.FLIP_LEFT_RIGHT) if lab is not None else None
+        return (img if blob is None else (blob, flip, ip, desc)), (lab if lblob is None else (lblob, flip, lp, (d, spans)))
 
     def _decode_on_device(self, batch):
         """[(image | (bytes, flip, path, descriptor), label)] -> the same with every image a uint8 HWC array or device tensor: one
@@ -173,24 +194,39 @@ class CelebAMaskDataset:
         a random index as in ``_decode`` (that draw is then made on the consumer's thread: the order of draws, and so the batches
         that follow, differ from ``decode="host"`` from such a file on -- with sound files the two give the same batches)."""
         from PIL import Image
-        todo = [n for n, (img, _) in enumerate(batch) if isinstance(img, tuple)]
-        if not todo:
+        is_png = lambda item: isinstance(item[3], tuple)
+        jpegs = [(n, 0) for n, (img, _) in enumerate(batch) if isinstance(img, tuple) and not is_png(img)]
+        pngs = [(n, k) for n, pair in enumerate(batch) for k in (0, 1) if isinstance(pair[k], tuple) and (k == 1 or is_png(pair[k]))]
+        if not jpegs and not pngs:
             return batch
-        views, status = ops.jpeg_decode([batch[n][0][0] for n in todo], expand_grey=True, mirror=[batch[n][0][1] for n in todo],
-                                        device=self.device, parsed=[batch[n][0][3] for n in todo])
-        batch = list(batch)
-        for n, v, st in zip(todo, views, status.cpu().tolist()):
-            (_, flip, path, _), lab = batch[n]
-            if st != 0:                                          # damaged scan: what the host decoder makes of it
+        done = {}                                                # (sample, 0: image / 1: label) -> (view, status)
+        if jpegs:
+            items = [batch[n][0] for n, _ in jpegs]
+            views, status = ops.jpeg_decode([it[0] for it in items], expand_grey=True, mirror=[it[1] for it in items],
+                                            device=self.device, parsed=[it[3] for it in items])
+            done.update(zip(jpegs, zip(views, status.cpu().tolist())))
+        if pngs:                                                 # images come out RGB, labels as the one channel they are
+            items = [batch[n][k] for n, k in pngs]
+            views, status = ops.png_decode([it[0] for it in items], expand_grey=[k == 0 for _, k in pngs], drop_alpha=True,
+                                           mirror=[it[1] for it in items], device=self.device, parsed=[it[3] for it in items])
+            done.update(zip(pngs, zip(views, status.cpu().tolist())))
+        batch = [list(pair) for pair in batch]
+        for (n, k), (v, st) in sorted(done.items()):
+            if batch[n] is None:
+                continue
+            _, flip, path, _ = batch[n][k]
+            if st != 0:                                          # damaged data: what the host decoder makes of it
                 try:
-                    v = np.asarray(Image.open(path).convert("RGB"))
+                    v = Image.open(path).convert("L" if k else "RGB")
+                    v = (v.transpose(Image.FLIP_LEFT_RIGHT) if flip else v) if k else np.asarray(v)
                 except OSError as err:                           # CelebAMask_dataset.py:33-38: retry a random index
                     print(err)
-                    batch[n] = self._decode_on_device([self._decode(self.rng.randrange(len(self.pairs)))])[0]
+                    batch[n] = None
                     continue
-                v = np.ascontiguousarray(v[:, ::-1]) if flip else v
-            batch[n] = (v, lab)
-        return batch
+                v = np.ascontiguousarray(v[:, ::-1]) if (flip and not k) else v
+            batch[n][k] = v[:, :, 0] if (k and isinstance(v, torch.Tensor)) else v
+        return [tuple(pair) if pair is not None else self._decode_on_device([self._decode(self.rng.randrange(len(self.pairs)))])[0]
+                for pair in batch]
 
     def _to_device(self, img, lab):
         from PIL import Image
@@ -199,7 +235,11 @@ class CelebAMaskDataset:
         img = img if isinstance(img, torch.Tensor) else torch.from_numpy(img).to(self.device)
         x = fn(img[None], self.size)[0]
         H, W = x.shape[1], x.shape[2]
-        lab = torch.from_numpy(np.asarray(lab.resize((W, H), Image.NEAREST)).astype(np.int64))
+        if isinstance(lab, torch.Tensor):                        # decoded on the device: already (H, W), already mirrored
+            assert tuple(lab.shape) == (H, W), (tuple(lab.shape), H, W)
+            lab = lab.to(torch.int64)
+        else:
+            lab = torch.from_numpy(np.asarray(lab.resize((W, H), Image.NEAREST)).astype(np.int64))
         return x, lab
 
     def _load(self, idx):
@@ -242,7 +282,7 @@ class CelebAMaskDataset:
         else:
             cur = self._decode_batch()
         xs, labs = zip(*(self._to_device(img, lab) for img, lab in self._decode_on_device(cur)))
-        labels = torch.stack(labs).to(self.device)
+        labels = torch.stack([lab.to(self.device) for lab in labs])
         return {"real_A": torch.stack(xs).contiguous(), "mask_A": glue.one_hot_mask(labels)}
 
 
