@@ -14,7 +14,10 @@
 //   2. jpeg_layout_kernel  one workgroup per image: interval offsets (exclusive sum), the header, EOI, the file length;
 //      jpeg_gather_kernel  one workgroup per interval: slot -> its offset at any byte alignment, RSTm behind it.
 // All of it is integer code: the bytes are a pure function of the pixels, whatever the batch.  No workgroup waits for another.
+// Shared with the other coders: the workgroup scan and the slot-to-file copy (codec_common.h), the zigzag order (jpeg_common.h).
 #include "common.h"
+#include "codec_common.h"
+#include "jpeg_common.h"
 #include <string.h>
 
 #define JPEG_NT 256                            // threads of the scan workgroup
@@ -31,15 +34,13 @@ static_assert(JPEG_SLOT == JPEG_IVL_BYTES(JPEG_NBLK) && JPEG_SLOT % 16 == 0, "sl
 static_assert(JPEG_NBLK <= 128 && JPEG_NBLK % 6 == 0, "two scan rounds of one wave; whole MCUs");
 
 // ------------------------------------------------------------------------------------------------------------- the tables
-// T.81 Annex K: K.1 / K.2 (quantisation, natural order), Figure 5 (zigzag), K.3 - K.6 (the "typical" Huffman tables).  One
-// initialiser each, read by the host (header) and the device (codes): both write from the same constants.
+// T.81 Annex K: K.1 / K.2 (quantisation, natural order), K.3 - K.6 (the "typical" Huffman tables).  One initialiser each, read by
+// the host (header) and the device (codes): both write from the same constants.  The zigzag order (H_ZIGZAG, D_ZIGZAG): jpeg_common.h.
 #define JPEG_QBASE { \
   {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62, \
    18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99}, \
   {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99, \
    99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}}
-#define JPEG_ZIGZAG {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, \
-                     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63}
 #define JPEG_DC_BITS {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}}
 #define JPEG_DC_VALS {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}
 #define JPEG_AC_BITS {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}}
@@ -62,12 +63,10 @@ static_assert(JPEG_NBLK <= 128 && JPEG_NBLK % 6 == 0, "two scan rounds of one wa
 #define JPEG_NAC 162
 
 static const unsigned char H_QBASE[2][64] = JPEG_QBASE;
-static const unsigned char H_ZIGZAG[64] = JPEG_ZIGZAG;
 static const unsigned char H_DC_BITS[2][16] = JPEG_DC_BITS;
 static const unsigned char H_DC_VALS[JPEG_NDC] = JPEG_DC_VALS;
 static const unsigned char H_AC_BITS[2][16] = JPEG_AC_BITS;
 static const unsigned char H_AC_VALS[2][JPEG_NAC] = JPEG_AC_VALS;
-__constant__ unsigned char D_ZIGZAG[64] = JPEG_ZIGZAG;
 __constant__ unsigned char D_DC_BITS[2][16] = JPEG_DC_BITS;
 __constant__ unsigned char D_DC_VALS[JPEG_NDC] = JPEG_DC_VALS;
 __constant__ unsigned char D_AC_BITS[2][16] = JPEG_AC_BITS;
@@ -111,7 +110,7 @@ struct JpegLds {
   unsigned char izz[64];               // natural index -> zigzag position
   unsigned blkbits[JPEG_NBLK];
   unsigned blkoff[JPEG_NBLK];
-  unsigned wave_tot[2][JPEG_NT / 64];
+  int wave_tot[2][JPEG_NT / 64];
   unsigned total;
 };
 
@@ -125,30 +124,6 @@ __device__ __forceinline__ void jpeg_put_bits(unsigned* img, unsigned pos, unsig
   if ((unsigned)(a >> 32)) atomicOr(&img[w], (unsigned)(a >> 32));
   if ((unsigned)a) atomicOr(&img[w + 1], (unsigned)a);
   if (lo) atomicOr(&img[w + 2], lo);
-}
-
-// exclusive prefix of v over the workgroup, added to `base` (every thread's copy, advanced by the total); one barrier; `slot`
-// alternates 0 / 1 between consecutive calls
-__device__ __forceinline__ unsigned jpeg_block_scan(unsigned v, unsigned& base, unsigned (*wave_tot)[JPEG_NT / 64], int slot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wave_tot[slot][wave] = inc;
-  __syncthreads();
-  unsigned before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < JPEG_NT / 64; ++w) {
-    const unsigned t = wave_tot[slot][w];
-    before += w < wave ? t : 0u;
-    all += t;
-  }
-  const unsigned pos = base + before + inc - v;
-  base += all;
-  return pos;
 }
 
 // The code of lane `lane`'s coefficient v (lane 0: the DC difference) of a block whose non-zero AC lanes are `acmask`:
@@ -351,7 +326,9 @@ __global__ __launch_bounds__(JPEG_NT) void jpeg_scan_kernel(const unsigned char*
     const unsigned word = nv ? s.u.img[w] : 0u;
     unsigned nff = 0;
     for (int i = 0; i < nv; ++i) nff += ((word >> (24 - 8 * i)) & 255u) == 255u;
-    unsigned at = jpeg_block_scan((unsigned)nv + nff, base, s.wave_tot, slot);
+    int round_bytes;                                                // (wg_scan: codec_common.h; <= 8 bytes per thread)
+    unsigned at = base + (unsigned)wg_scan<JPEG_NT, false>(nv + (int)nff, round_bytes, s.wave_tot, slot);
+    base += (unsigned)round_bytes;
     for (int i = 0; i < nv; ++i) {
       const unsigned c = (word >> (24 - 8 * i)) & 255u;
       out[at++] = (unsigned char)c;
@@ -366,15 +343,18 @@ __global__ __launch_bounds__(JPEG_NT) void jpeg_scan_kernel(const unsigned char*
 __global__ __launch_bounds__(JPEG_NT) void jpeg_layout_kernel(const unsigned* __restrict__ meta, int64_t* __restrict__ offs,
                                                               unsigned char* __restrict__ files, int64_t* __restrict__ sizes, JpegGeom g,
                                                               JpegHead head) {
-  __shared__ unsigned wave_tot[2][JPEG_NT / 64];
+  __shared__ int wave_tot[2][JPEG_NT / 64];
   const int b = blockIdx.x, tid = threadIdx.x;
   unsigned char* file = files + (int64_t)b * g.bound;
-  unsigned base = (unsigned)g.head;                                 // (the bound is below 2^32: jpeg_geom)
+  // (the bound is below 2^32: jpeg_geom.  The base passes 2^31 in a large file; a round's prefix, <= 256 slots, fits an int)
+  unsigned base = (unsigned)g.head;
   int slot = 0;
   for (int i0 = 0; i0 < g.NI; i0 += JPEG_NT, slot ^= 1) {
     const int i = i0 + tid;
     const unsigned v = i < g.NI ? meta[(int64_t)b * g.NI + i] + (i < g.NI - 1 ? 2u : 0u) : 0u;
-    const unsigned at = jpeg_block_scan(v, base, wave_tot, slot);
+    int round_bytes;
+    const unsigned at = base + (unsigned)wg_scan<JPEG_NT, false>((int)v, round_bytes, wave_tot, slot);
+    base += (unsigned)round_bytes;
     if (i < g.NI) offs[(int64_t)b * g.NI + i] = at;
   }
   for (int i = tid; i < g.head; i += JPEG_NT) file[i] = (unsigned char)(head.w[i >> 2] >> (8 * (i & 3)));
@@ -394,16 +374,7 @@ __global__ __launch_bounds__(256) void jpeg_gather_kernel(const unsigned char* _
   const unsigned char* src = slots + blk * JPEG_SLOT;
   unsigned char* dst = files + b * g.bound + offs[blk];
   if (threadIdx.x == 0 && it < g.NI - 1) { dst[n] = 0xFF; dst[n + 1] = (unsigned char)(0xD0 + (it & 7)); }
-  const unsigned lead = (unsigned)((4 - ((uintptr_t)dst & 3)) & 3);      // bytes up to the first aligned word of the file
-  if (threadIdx.x < lead && threadIdx.x < n) dst[threadIdx.x] = src[threadIdx.x];
-  if (n <= lead) return;
-  const unsigned words = (n - lead) >> 2;
-  for (unsigned i = threadIdx.x; i < words; i += 256) {
-    const unsigned char* q = src + lead + 4 * i;
-    *reinterpret_cast<unsigned*>(dst + lead + 4 * i) = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16) | ((unsigned)q[3] << 24);
-  }
-  const unsigned done = lead + 4 * words;
-  if (threadIdx.x < n - done) dst[done + threadIdx.x] = src[done + threadIdx.x];
+  slot_to_file<256>(src, dst, n);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- host

@@ -1,8 +1,9 @@
 // JPEG decode on the device: baseline sequential DCT files of any origin -> uint8 HWC, equal to libjpeg-turbo's default decoder
 // (DESIGN.md "JPEG decode on the device"; the format and arithmetic: include/ppst_hip.h).  A batch holds files of different sizes
 // and samplings: every kernel runs on a grid (largest per-image count, B) and a workgroup beyond its image's count leaves.
-//   0. jd_plan_kernel     one workgroup: every image's geometry, layout and place in the workspace (a serial prefix over the B
-//                         images), stored for the other kernels; status and round counts to zero;  jd_zero_kernel: the coefficient arrays to zero
+//   0. plan_kernel<JdImg> one workgroup: every image's geometry, layout and place in the workspace (a serial prefix over the B
+//                         images), stored for the other kernels; status and round counts to zero (codec_common.h, with the head
+//                         of the workspace and the workgroup scan; the format's part: codec_fill);  jd_zero_kernel: the coefficient arrays to zero
 //   1. jd_count_kernel    one workgroup per 4096-byte chunk of the entropy-coded segment: bytes that stay, restart markers
 //      jd_offsets_kernel  one workgroup per image: exclusive prefix over the chunks' counts, the marker total against the header's
 //      jd_compact_kernel  per chunk again: the clean stream (no stuffed 00, no RSTm), the clean offset behind every RSTm
@@ -11,18 +12,18 @@
 //   3. jd_idct_kernel     32 blocks per workgroup: dequantise, jidctint columns then rows, planar Y / Cb / Cr padded to whole MCUs
 //   4. jd_colour_kernel   one thread per pixel: fancy h2v2 chroma, YCbCr -> RGB, crop, mirror
 // Integer code throughout.  No workgroup waits for another: the stages meet at launch boundaries only.
+// Shared with the encoder (jpeg_common.h): the zigzag order.
 #include "common.h"
+#include "codec_common.h"
+#include "jpeg_common.h"
 
-#define JD_CHUNK_T 256                          // threads of the stream kernels
+#define JD_CHUNK_T 256                         // threads of the stream kernels
 #define JD_CHUNK 4096                           // bytes of the segment per workgroup: 16 per thread
 #define JD_ENT_T 1024                           // threads of the entropy workgroup
 #define JD_IDCT_BLOCKS 32                       // 8 x 8 blocks per IDCT workgroup of 256 threads
 #define JD_SUBSEQ_DEFAULT 32                    // words: 1024 bits
 #define JD_SUBSEQ_MAX 65536
 #define JD_SCAN_MAX (1 << 28)                   // bytes of one file's segment: its bit positions stay below 2^31
-
-__constant__ unsigned char JD_ZIGZAG[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-                                            35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // ---------------------------------------------------------------------------------------------------------------- geometry
 struct JdGeom {
@@ -37,8 +38,6 @@ struct JdGeom {
 };
 // byte offsets of one image's arrays from its base (each a multiple of 16)
 struct JdLayout { int64_t chunk, ivl, clean, sub, coef, plane, total; };
-
-__host__ __device__ inline int64_t jd_a16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 __host__ __device__ inline void jd_geom(const ppst_jpeg_dec_image& d, int sw, JdGeom* g) {
   g->ss = d.ss;
@@ -62,73 +61,27 @@ __host__ __device__ inline void jd_geom(const ppst_jpeg_dec_image& d, int sw, Jd
 
 __host__ __device__ inline void jd_layout(const ppst_jpeg_dec_image& d, const JdGeom& g, JdLayout* l) {
   int64_t at = 0;
-  l->chunk = at; at = jd_a16(at + (int64_t)g.nchunk * 8);
-  l->ivl = at;   at = jd_a16(at + ((int64_t)g.NI + 1) * 4);
-  l->clean = at; at = jd_a16(at + (int64_t)g.L + 8);
-  l->sub = at;   at = jd_a16(at + (int64_t)g.nsub * 6 * 4);
-  l->coef = at;  at = jd_a16(at + (int64_t)g.nblk * 128);
-  l->plane = at; at = jd_a16(at + (int64_t)g.pwy * g.phy + (d.ncomp == 3 ? 2 * (int64_t)g.pwc * g.phc : 0));
+  l->chunk = at; at = a16(at + (int64_t)g.nchunk * 8);
+  l->ivl = at;   at = a16(at + ((int64_t)g.NI + 1) * 4);
+  l->clean = at; at = a16(at + (int64_t)g.L + 8);
+  l->sub = at;   at = a16(at + (int64_t)g.nsub * 6 * 4);
+  l->coef = at;  at = a16(at + (int64_t)g.nblk * 128);
+  l->plane = at; at = a16(at + (int64_t)g.pwy * g.phy + (d.ncomp == 3 ? 2 * (int64_t)g.pwc * g.phc : 0));
   l->total = at;
 }
 
-struct JdImg {                                  // what a workgroup needs of its image: written once by jd_plan_kernel
+struct JdImg {                                  // what a workgroup needs of its image: written once by plan_kernel (codec_common.h)
   JdGeom g;
   JdLayout l;
   int64_t base_off;                             // the image's arrays start here in the workspace
 };
-// the head of the workspace: int32 rounds[B], then JdImg plan[B]
-__host__ __device__ inline int64_t jd_head_bytes(int B) { return jd_a16((int64_t)B * 4) + jd_a16((int64_t)B * (int64_t)sizeof(JdImg)); }
-
-// the plan of image i (uniform loads of the fields a kernel uses: geometry and layout are worked out once per call, not per thread)
-__device__ __forceinline__ const JdImg& jd_open(int B, void* work, int i) {
-  return ((const JdImg*)((unsigned char*)work + jd_a16((int64_t)B * 4)))[i];
-}
-
-// exclusive prefix of v over the NT threads of the workgroup and the total; one barrier; `slot` alternates between calls
-template <int NT>
-__device__ __forceinline__ int jd_block_scan(int v, int& total, int (*wave_tot)[NT / 64], int slot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wave_tot[slot][wave] = inc;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < NT / 64; ++w) {
-    const int t = wave_tot[slot][w];
-    before += w < wave ? t : 0;
-    all += t;
-  }
-  total = all;
-  return before + inc - v;
-}
-
-// --------------------------------------------------------------------------------------------------------------------- plan
-__global__ __launch_bounds__(256) void jd_plan_kernel(const ppst_jpeg_dec_image* __restrict__ imgs, int B, int sw, void* work,
-                                                      int* __restrict__ status) {
-  int* rounds = (int*)work;
-  JdImg* plans = (JdImg*)((unsigned char*)work + jd_a16((int64_t)B * 4));
-  for (int i = threadIdx.x; i < B; i += 256) { rounds[i] = 0; status[i] = 0; }
-  for (int i = threadIdx.x; i < B; i += 256) {
-    jd_geom(imgs[i], sw, &plans[i].g);
-    jd_layout(imgs[i], plans[i].g, &plans[i].l);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int64_t at = jd_head_bytes(B);
-    for (int i = 0; i < B; ++i) {
-      plans[i].base_off = at;
-      at += plans[i].l.total;
-    }
-  }
+__host__ __device__ inline void codec_fill(const ppst_jpeg_dec_image& d, int sw, JdImg* im) {
+  jd_geom(d, sw, &im->g);
+  jd_layout(d, im->g, &im->l);
 }
 
 __global__ __launch_bounds__(256) void jd_zero_kernel(const ppst_jpeg_dec_image* __restrict__ imgs, int B, int sw, void* work) {
-  const JdImg& im = jd_open(B, work, blockIdx.y);
+  const JdImg& im = open_plan<JdImg>(B, work, blockIdx.y);
   unsigned char* const base = (unsigned char*)work + im.base_off;
   const int64_t n16 = (int64_t)im.g.nblk * 8;                        // 16-byte pieces of the coefficient array
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -156,7 +109,7 @@ __global__ __launch_bounds__(JD_CHUNK_T) void jd_count_kernel(const unsigned cha
                                                               int B, int sw, void* work, int* __restrict__ status) {
   __shared__ int wt[2][JD_CHUNK_T / 64];
   const int i = blockIdx.y;
-  const JdImg& im = jd_open(B, work, i);
+  const JdImg& im = open_plan<JdImg>(B, work, i);
   unsigned char* const base = (unsigned char*)work + im.base_off;
   if ((int)blockIdx.x >= im.g.nchunk) return;
   const unsigned char* s = bytes + imgs[i].file_off + imgs[i].scan_off;
@@ -171,8 +124,8 @@ __global__ __launch_bounds__(JD_CHUNK_T) void jd_count_kernel(const unsigned cha
     bad |= c == 3;
   }
   int tk, tr;
-  jd_block_scan<JD_CHUNK_T>(kept, tk, wt, 0);
-  jd_block_scan<JD_CHUNK_T>(rst, tr, wt, 1);
+  wg_scan<JD_CHUNK_T, false>(kept, tk, wt, 0);
+  wg_scan<JD_CHUNK_T, false>(rst, tr, wt, 1);
   if (threadIdx.x == 0) {
     unsigned* ci = (unsigned*)(base + im.l.chunk);
     ci[2 * blockIdx.x] = (unsigned)tk;
@@ -185,7 +138,7 @@ __global__ __launch_bounds__(JD_CHUNK_T) void jd_offsets_kernel(const ppst_jpeg_
                                                                 int* __restrict__ status) {
   __shared__ int wt[2][JD_CHUNK_T / 64];
   const int i = blockIdx.x;
-  const JdImg& im = jd_open(B, work, i);
+  const JdImg& im = open_plan<JdImg>(B, work, i);
   unsigned char* const base = (unsigned char*)work + im.base_off;
   unsigned* ci = (unsigned*)(base + im.l.chunk);
   int base_k = 0, base_r = 0;
@@ -193,8 +146,8 @@ __global__ __launch_bounds__(JD_CHUNK_T) void jd_offsets_kernel(const ppst_jpeg_
     const int c = c0 + threadIdx.x;
     const int k = c < im.g.nchunk ? (int)ci[2 * c] : 0, r = c < im.g.nchunk ? (int)ci[2 * c + 1] : 0;
     int tk, tr;
-    const int pk = jd_block_scan<JD_CHUNK_T>(k, tk, wt, 0);
-    const int pr = jd_block_scan<JD_CHUNK_T>(r, tr, wt, 1);
+    const int pk = wg_scan<JD_CHUNK_T, false>(k, tk, wt, 0);
+    const int pr = wg_scan<JD_CHUNK_T, false>(r, tr, wt, 1);
     if (c < im.g.nchunk) { ci[2 * c] = (unsigned)(base_k + pk); ci[2 * c + 1] = (unsigned)(base_r + pr); }
     base_k += tk; base_r += tr;
     __syncthreads();                                               // wt is reused by the next round
@@ -211,7 +164,7 @@ __global__ __launch_bounds__(JD_CHUNK_T) void jd_compact_kernel(const unsigned c
                                                                 int B, int sw, void* work, int* __restrict__ status) {
   __shared__ int wt[2][JD_CHUNK_T / 64];
   const int i = blockIdx.y;
-  const JdImg& im = jd_open(B, work, i);
+  const JdImg& im = open_plan<JdImg>(B, work, i);
   unsigned char* const base = (unsigned char*)work + im.base_off;
   if ((int)blockIdx.x >= im.g.nchunk) return;
   const unsigned char* s = bytes + imgs[i].file_off + imgs[i].scan_off;
@@ -226,7 +179,7 @@ __global__ __launch_bounds__(JD_CHUNK_T) void jd_compact_kernel(const unsigned c
     rst += cls[j] == 2;
   }
   int tot;
-  const int pos = jd_block_scan<JD_CHUNK_T>(kept | (rst << 16), tot, wt, 0);      // kept <= 4096, markers <= 2048 per chunk
+  const int pos = wg_scan<JD_CHUNK_T, false>(kept | (rst << 16), tot, wt, 0);      // kept <= 4096, markers <= 2048 per chunk
   const unsigned* ci = (const unsigned*)(base + im.l.chunk);
   unsigned at = ci[2 * blockIdx.x] + (unsigned)(pos & 0xFFFF);                      // < L: every kept byte is a byte of the segment
   int ord = (int)ci[2 * blockIdx.x + 1] + (pos >> 16);
@@ -338,7 +291,7 @@ __global__ __launch_bounds__(JD_ENT_T) void jd_entropy_kernel(const ppst_jpeg_de
                                                               int* __restrict__ status) {
   __shared__ JdTabs T;
   const int i = blockIdx.y, it = blockIdx.x, tid = threadIdx.x;
-  const JdImg& im = jd_open(B, work, i);
+  const JdImg& im = open_plan<JdImg>(B, work, i);
   unsigned char* const base = (unsigned char*)work + im.base_off;
   if (it >= im.g.NI) return;
   // the stream stage refused the file: its interval table may be incomplete.  Only the bits earlier launches set are looked at:
@@ -415,7 +368,7 @@ __global__ __launch_bounds__(JD_ENT_T) void jd_entropy_kernel(const ppst_jpeg_de
   int mine = 0;
   for (unsigned q = i0; q < i1; ++q) mine += (int)N[q];
   int total;
-  int blk = jd_block_scan<JD_ENT_T>(mine, total, T.wt, 0);
+  int blk = wg_scan<JD_ENT_T, false>(mine, total, T.wt, 0);
   int bad = 0;
   for (unsigned q = i0; q < i1; ++q) {
     bad |= jd_run<true>(T, cw, origin, nbits, min(nbits, (q + 1) * SB), bpm, Ep[q], Es[q], coef, blk, nb).bad;
@@ -436,9 +389,9 @@ __global__ __launch_bounds__(JD_ENT_T) void jd_entropy_kernel(const ppst_jpeg_de
       sum0 += c == 0 ? v : 0; sum1 += c == 1 ? v : 0; sum2 += c == 2 ? v : 0;
     }
   int t;
-  int pre0 = jd_block_scan<JD_ENT_T>(sum0, t, T.wt, 1);
-  int pre1 = jd_block_scan<JD_ENT_T>(sum1, t, T.wt, 0);
-  int pre2 = jd_block_scan<JD_ENT_T>(sum2, t, T.wt, 1);
+  int pre0 = wg_scan<JD_ENT_T, false>(sum0, t, T.wt, 1);
+  int pre1 = wg_scan<JD_ENT_T, false>(sum1, t, T.wt, 0);
+  int pre2 = wg_scan<JD_ENT_T, false>(sum2, t, T.wt, 1);
   for (int m = m0; m < m1; ++m)
     for (int j = 0; j < bpm; ++j) {
       const int c = bpm == 6 ? (j < 4 ? 0 : j - 3) : j;
@@ -476,7 +429,7 @@ __device__ __forceinline__ void jd_idct8(const int* in, int* out) {
 __global__ __launch_bounds__(256) void jd_idct_kernel(const ppst_jpeg_dec_image* __restrict__ imgs, int B, int sw, void* work) {
   __shared__ int ws[JD_IDCT_BLOCKS][64];
   const int i = blockIdx.y, tid = threadIdx.x;
-  const JdImg& im = jd_open(B, work, i);
+  const JdImg& im = open_plan<JdImg>(B, work, i);
   unsigned char* const base = (unsigned char*)work + im.base_off;
   const int64_t blk0 = (int64_t)blockIdx.x * JD_IDCT_BLOCKS;
   if (blk0 >= im.g.nblk) return;
@@ -492,7 +445,7 @@ __global__ __launch_bounds__(256) void jd_idct_kernel(const ppst_jpeg_dec_image*
       const int c = bpm == 6 ? (slot < 4 ? 0 : slot - 3) : slot;
       v = (int)coef[blk * 64 + k] * (int)d.qt[c][k];
     }
-    ws[j][JD_ZIGZAG[k]] = v;
+    ws[j][D_ZIGZAG[k]] = v;
   }
   __syncthreads();
   const int j = tid >> 3, c8 = tid & 7;
@@ -541,7 +494,7 @@ __device__ __forceinline__ int jd_fancy(const unsigned char* __restrict__ c, int
 __global__ __launch_bounds__(256) void jd_colour_kernel(const ppst_jpeg_dec_image* __restrict__ imgs, int B, int sw, void* work,
                                                         unsigned char* __restrict__ out_u8) {
   const int i = blockIdx.y;
-  const JdImg& im = jd_open(B, work, i);
+  const JdImg& im = open_plan<JdImg>(B, work, i);
   unsigned char* const base = (unsigned char*)work + im.base_off;
   const ppst_jpeg_dec_image& d = imgs[i];
   const int64_t px = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -606,14 +559,12 @@ static bool jd_sw_ok(int sw) { return sw == 0 || (sw >= 2 && sw <= JD_SUBSEQ_MAX
 extern "C" int64_t ppst_jpeg_decode_ws(const ppst_jpeg_dec_image* imgs, int B, int subseq_words) {
   if (B < 0 || B > 65535 || !jd_sw_ok(subseq_words)) return PPST_EINVAL;
   if (B > 0 && !imgs) return PPST_ENULL;
-  int64_t total = jd_head_bytes(B > 0 ? B : 1);
+  int64_t total = head_bytes<JdImg>(B > 0 ? B : 1);
   for (int i = 0; i < B; ++i) {
     if (!jd_valid(imgs[i])) return PPST_EINVAL;
-    JdGeom g;
-    JdLayout l;
-    jd_geom(imgs[i], subseq_words, &g);
-    jd_layout(imgs[i], g, &l);
-    total += l.total;
+    JdImg im;
+    codec_fill(imgs[i], subseq_words, &im);
+    total += im.l.total;
   }
   return total;
 }
@@ -645,7 +596,7 @@ extern "C" int ppst_jpeg_decode(const void* bytes, int64_t nbytes, const ppst_jp
   int* stt = (int*)status;
   const int sw = subseq_words;
   static_assert(sizeof(JdTabs) <= 16 * 1024, "the entropy workgroup's tables");
-  PPST_LAUNCH(jd_plan_kernel, dim3(1), dim3(256), 0, st, dd, B, sw, work, stt);
+  PPST_LAUNCH(plan_kernel<JdImg>, dim3(1), dim3(256), 0, st, dd, B, sw, work, stt);
   PPST_LAUNCH(jd_zero_kernel, dim3((unsigned)cdiv64(max_blk * 8, 256), (unsigned)B), dim3(256), 0, st, dd, B, sw, work);
   PPST_LAUNCH(jd_count_kernel, dim3((unsigned)max_chunk, (unsigned)B), dim3(JD_CHUNK_T), 0, st, by, dd, B, sw, work, stt);
   PPST_LAUNCH(jd_offsets_kernel, dim3((unsigned)B), dim3(JD_CHUNK_T), 0, st, dd, B, sw, work, stt);

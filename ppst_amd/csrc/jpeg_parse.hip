@@ -1,19 +1,10 @@
 // JPEG decode on the device, the host half: ppst_jpeg_parse walks a file's markers and fills the descriptor the kernels of
 // jpeg_decode.hip read (include/ppst_hip.h "JPEG decode on the device").  Plain C++ with no GPU call and no dependency but the
 // header: tests/jpeg_parse_san.cpp compiles this file as host code under the address and undefined-behaviour sanitizers.
-// Every read goes through Rd, which knows n: no segment length is trusted.
+// Every read goes through Rd (parse_reader.h, shared with png_parse.hip), which knows n: no segment length is trusted.
 #include <string.h>
 #include "../../include/ppst_hip.h"
-
-namespace {
-struct Rd {
-  const unsigned char* p;
-  int64_t n;
-  bool has(int64_t at, int64_t len) const { return at >= 0 && len >= 0 && at <= n && len <= n - at; }
-  int u8(int64_t at) const { return p[at]; }                                  // callers check has() first
-  int u16(int64_t at) const { return (p[at] << 8) | p[at + 1]; }
-};
-}  // namespace
+#include "parse_reader.h"
 
 extern "C" int ppst_jpeg_parse(const void* file, int64_t n, ppst_jpeg_dec_image* out) {
   if (!out) return PPST_ENULL;

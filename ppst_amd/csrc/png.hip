@@ -10,7 +10,10 @@
 //   3. png_layout_kernel   one workgroup per image: piece offsets, signature + IHDR, the combined Adler-32 (an IDAT chunk of
 //                          four bytes), IEND, the file size;  png_gather_kernel copies the chunks to their offsets.
 // All of it is integer code on bytes, bits and LDS words: deterministic, the same file for the same pixels whatever the batch.
+// Shared with the other coders: the workgroup scan and the slot-to-file copy (codec_common.h); the CRC-32, the Paeth predictor, the
+// code-length order and the joining of Adler-32 partial sums (png_common.h).
 #include "common.h"
+#include "codec_common.h"
 #include "png_common.h"
 
 #define PNG_PIECE 32768                       // bytes of the filtered stream per deflate block / workgroup / IDAT chunk
@@ -36,10 +39,6 @@ struct PngGeom {
 struct PngHead { unsigned w[9]; };            // the 33 bytes in front of the first IDAT (built on the host), little-endian words
 
 __device__ __forceinline__ int png_abs8(int v) { v &= 255; return v < 128 ? v : 256 - v; }
-__device__ __forceinline__ int png_paeth(int a, int b, int c) {
-  const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
-  return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-}
 
 // ---------------------------------------------------------------------------------------------------------------- filter
 // One wave per row (4 rows per block).  A row's candidates read the raw row above only: rows are independent.
@@ -198,7 +197,7 @@ struct DeflateLds {
   unsigned clcode[19];
   unsigned num_ll[16];
   HuffScratch hs;
-  unsigned wave_tot[2][PNG_NT / 64];
+  int wave_tot[2][PNG_NT / 64];
   unsigned bits, adler_a, adler_b, crc;
   int ok;
 };
@@ -213,30 +212,6 @@ __device__ __forceinline__ void put_bits(unsigned* out, unsigned pos, unsigned l
   if ((unsigned)(lo >> 32)) atomicOr(&out[w + 1], (unsigned)(lo >> 32));
   if (hi) atomicOr(&out[w + 2], hi);
 }
-// exclusive prefix of `nbits` over the workgroup, added to *base (every thread's copy); one barrier; `slot` alternates 0 / 1
-__device__ __forceinline__ unsigned block_scan_bits(unsigned nbits, unsigned& base, DeflateLds& s, int slot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned inc = nbits;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) s.wave_tot[slot][wave] = inc;
-  __syncthreads();
-  unsigned before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < PNG_NT / 64; ++w) {
-    const unsigned t = s.wave_tot[slot][w];
-    before += w < wave ? t : 0u;
-    all += t;
-  }
-  const unsigned pos = base + before + inc - nbits;
-  base += all;
-  return pos;
-}
-
-__constant__ unsigned char PNG_CL_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
 __global__ __launch_bounds__(PNG_NT) void png_deflate_kernel(const unsigned char* __restrict__ filt, unsigned char* __restrict__ slots,
                                                               unsigned* __restrict__ meta, PngGeom g) {
@@ -331,7 +306,10 @@ __global__ __launch_bounds__(PNG_NT) void png_deflate_kernel(const unsigned char
     const unsigned char* inb = reinterpret_cast<const unsigned char*>(inw);
     for (int i = tid; i < np; i += PNG_NT) outb[data0 + 5 + i] = inb[i];
   } else {
+    // every round places its bits behind `base`: the exclusive prefix over the workgroup (wg_scan, codec_common.h), then base
+    // advances by the round's total in every thread's copy
     unsigned base = (unsigned)data0 * 8;
+    int round_bits;
     // header round: thread 0 = BFINAL, BTYPE = 2, HLIT = 0 (257), HDIST = 1 (2), HCLEN = 15 (19); threads 1..19 = the code-length
     // code's lengths in the format's order; threads 20..278 = the 259 lengths, coded (no repeat codes 16 / 17 / 18)
     {
@@ -340,7 +318,8 @@ __global__ __launch_bounds__(PNG_NT) void png_deflate_kernel(const unsigned char
       if (tid == 0) { v = (final_piece ? 1u : 0u) | (2u << 1) | (0u << 3) | (1u << 8) | (15u << 13); nb = 17; }
       else if (tid < 20) { v = s.cllen[PNG_CL_ORDER[tid - 1]]; nb = 3; }
       else if (tid < 20 + PNG_NLIT + 2) { const unsigned c = s.clcode[s.len[tid - 20]]; v = c & 0xffffu; nb = (int)(c >> 16); }
-      const unsigned pos = block_scan_bits((unsigned)nb, base, s, 0);
+      const unsigned pos = base + (unsigned)wg_scan<PNG_NT, false>(nb, round_bits, s.wave_tot, 0);
+      base += (unsigned)round_bits;
       put_bits(s.out, pos, v, nb);
     }
     // symbol rounds: one word (4 bytes, <= 60 bits) per thread
@@ -358,7 +337,8 @@ __global__ __launch_bounds__(PNG_NT) void png_deflate_kernel(const unsigned char
           nb += (int)(c >> 16);
         }
       }
-      const unsigned pos = block_scan_bits((unsigned)nb, base, s, slot);
+      const unsigned pos = base + (unsigned)wg_scan<PNG_NT, false>(nb, round_bits, s.wave_tot, slot);
+      base += (unsigned)round_bits;
       put_bits(s.out, pos, v, nb);
     }
     // end of block, then the aligning empty stored block
@@ -432,8 +412,7 @@ __global__ __launch_bounds__(256) void png_layout_kernel(const unsigned* __restr
       for (int i = 0; i < cnt; ++i) {
         offs[(int64_t)b * g.P + p0 + i] = off;
         off += rec[i][0];
-        bb = (unsigned)((bb + (unsigned long long)(rec[i][3] % 65521u) * a + rec[i][2]) % 65521u);
-        a = (a + rec[i][1]) % 65521u;
+        adler_join(a, bb, rec[i][3], rec[i][1], rec[i][2]);
       }
     }
   }
@@ -457,19 +436,7 @@ __global__ __launch_bounds__(256) void png_gather_kernel(const unsigned char* __
                                                          const int64_t* __restrict__ offs, unsigned char* __restrict__ files, PngGeom g) {
   const int64_t blk = blockIdx.x;
   const int64_t b = blk / g.P;
-  const unsigned n = meta[blk * 4];
-  const unsigned char* src = slots + blk * PNG_SLOT;
-  unsigned char* dst = files + b * g.bound + offs[blk];
-  const unsigned lead = (unsigned)((4 - ((uintptr_t)dst & 3)) & 3);      // bytes up to the first aligned word of the file
-  if (threadIdx.x < lead && threadIdx.x < n) dst[threadIdx.x] = src[threadIdx.x];
-  if (n <= lead) return;
-  const unsigned words = (n - lead) >> 2;
-  for (unsigned i = threadIdx.x; i < words; i += 256) {
-    const unsigned char* q = src + lead + 4 * i;
-    *reinterpret_cast<unsigned*>(dst + lead + 4 * i) = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16) | ((unsigned)q[3] << 24);
-  }
-  const unsigned done = lead + 4 * words;
-  if (threadIdx.x < n - done) dst[done + threadIdx.x] = src[done + threadIdx.x];
+  slot_to_file<256>(slots + blk * PNG_SLOT, files + b * g.bound + offs[blk], meta[blk * 4]);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- host

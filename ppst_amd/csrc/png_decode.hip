@@ -1,7 +1,8 @@
 // PNG decode on the device: 8-bit grey / RGB / RGBA files of any origin -> uint8 HWC, equal to what Pillow reads (DESIGN.md "PNG
 // decode on the device"; the format and the scheme: include/ppst_hip.h).  A batch holds files of different sizes and colour
 // types: every kernel runs on a grid (largest per-image count, B) and a workgroup beyond its image's count leaves.
-//   0. pd_plan_kernel      one workgroup: every image's layout and place in the workspace, stored for the other kernels
+//   0. plan_kernel<PdImg>  one workgroup: every image's layout and place in the workspace, stored for the other kernels
+//                          (codec_common.h, with the head of the workspace and the workgroup scan; the format's part: codec_fill)
 //   1. pd_offsets_kernel   one workgroup per image: where every IDAT payload goes in the zlib stream (exclusive prefix over the
 //                          chunk lengths), the zlib header, the image's counters to zero
 //      pd_chunk_kernel     one workgroup per chunk: CRC-32 over type + data against the stored one; an IDAT payload is copied
@@ -14,7 +15,9 @@
 //                          lane one pixel behind the lane above it; HWC store
 // Integer code throughout.  No workgroup waits for another: the stages meet at launch boundaries only, and inside a workgroup
 // at barriers only.  Every loop over file data has a bound that does not depend on the data.
+// Shared with the encoder (png_common.h): the CRC-32, the Paeth predictor, the code-length order, the joining of Adler-32 sums.
 #include "common.h"
+#include "codec_common.h"
 #include "png_common.h"
 
 #define PD_T 256                                // threads of the stream kernels
@@ -24,13 +27,11 @@
 #define PD_SUBSEQ_MAX 128                       // 4096 bits: a lane's byte count stays below 2^20 (258 bytes from 2 bits), a window's below 2^31
 #define PD_ROUNDS_MAX 33                        // pointer-jumping launches: ceil(log2 n) + 1 <= 32
 #define PD_DEAD 0xFFFFFFFFu                     // the exit of a subsequence that met the end of the block
-#define PD_ADLER 65521u
 
 __constant__ unsigned short PD_LBASE[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
 __constant__ unsigned char PD_LEXT[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
 __constant__ unsigned short PD_DBASE[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
 __constant__ unsigned char PD_DEXT[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
-__constant__ unsigned char PD_CLORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
 // ------------------------------------------------------------------------------------------------------------------ layout
 struct PdGeom {
@@ -45,8 +46,6 @@ struct PdGeom {
 // byte offsets of one image's arrays from its base (each a multiple of 16)
 struct PdLayout { int64_t soff, zs, raw, src, stream, part, cnt, total; };
 // cnt: int32 [PD_ROUNDS_MAX] change counters, then [PD_ROUNDS_MAX] = the bit behind the final block
-
-__host__ __device__ inline int64_t pd_a16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 __host__ __device__ inline void pd_geom(const ppst_png_dec_image& d, int sw, PdGeom* g) {
   g->H = d.H; g->W = d.W; g->C = d.channels;
@@ -63,56 +62,24 @@ __host__ __device__ inline void pd_geom(const ppst_png_dec_image& d, int sw, PdG
 
 __host__ __device__ inline void pd_layout(const ppst_png_dec_image& d, const PdGeom& g, PdLayout* l) {
   int64_t at = 0;
-  l->soff = at;   at = pd_a16(at + ((int64_t)d.nidat + 1) * 4);
-  l->zs = at;     at = pd_a16(at + (int64_t)g.L + 16);
-  l->raw = at;    at = pd_a16(at + (int64_t)g.n);
-  l->src = at;    at = pd_a16(at + (int64_t)g.n * 4);
-  l->stream = at; at = pd_a16(at + (int64_t)g.n);
-  l->part = at;   at = pd_a16(at + (int64_t)g.nchunk * 8);
-  l->cnt = at;    at = pd_a16(at + (PD_ROUNDS_MAX + 1) * 4);
+  l->soff = at;   at = a16(at + ((int64_t)d.nidat + 1) * 4);
+  l->zs = at;     at = a16(at + (int64_t)g.L + 16);
+  l->raw = at;    at = a16(at + (int64_t)g.n);
+  l->src = at;    at = a16(at + (int64_t)g.n * 4);
+  l->stream = at; at = a16(at + (int64_t)g.n);
+  l->part = at;   at = a16(at + (int64_t)g.nchunk * 8);
+  l->cnt = at;    at = a16(at + (PD_ROUNDS_MAX + 1) * 4);
   l->total = at;
 }
 
-struct PdImg {                                  // what a workgroup needs of its image: written once by pd_plan_kernel
+struct PdImg {                                  // what a workgroup needs of its image: written once by plan_kernel (codec_common.h)
   PdGeom g;
   PdLayout l;
   int64_t base_off;
 };
-// the head of the workspace: int32 rounds[B], then PdImg plan[B]
-__host__ __device__ inline int64_t pd_head_bytes(int B) { return pd_a16((int64_t)B * 4) + pd_a16((int64_t)B * (int64_t)sizeof(PdImg)); }
-__device__ __forceinline__ const PdImg& pd_open(int B, void* work, int i) {
-  return ((const PdImg*)((unsigned char*)work + pd_a16((int64_t)B * 4)))[i];
-}
-
-// exclusive prefix of v over the NT threads of the workgroup and the total; one barrier; `slot` alternates between calls
-template <int NT>
-__device__ __forceinline__ int pd_block_scan(int v, int& total, int (*wave_tot)[NT / 64], int slot) {
-  int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  // (opaque to the optimiser: the lane compares below are then made here, not once per kernel and kept in scalar register
-  // pairs across the caller's loops, where they were spilled)
-  asm volatile("" : "+v"(lane));
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wave_tot[slot][wave] = inc;
-  __syncthreads();
-  // the wave totals, scanned again by every wave in its first NT / 64 lanes (sixteen compares of the wave number against
-  // constants would each be kept in a scalar register pair across the caller's loops)
-  static_assert(NT / 64 <= 64, "one lane per wave total");
-  const int mine = wave_tot[slot][lane < NT / 64 ? lane : 0];
-  int winc = lane < NT / 64 ? mine : 0;
-#pragma unroll
-  for (int o = 1; o < NT / 64; o <<= 1) {
-    const int t = __shfl_up(winc, o, 64);
-    if (lane >= o) winc += t;
-  }
-  total = __shfl(winc, NT / 64 - 1, 64);
-  const int before = __shfl(winc - mine, wave, 64);
-  return before + inc - v;
+__host__ __device__ inline void codec_fill(const ppst_png_dec_image& d, int sw, PdImg* im) {
+  pd_geom(d, sw, &im->g);
+  pd_layout(d, im->g, &im->l);
 }
 
 // a span as the kernels use it: clamped to the file, so that no field of the table can take a read outside the file's bytes
@@ -123,32 +90,12 @@ __device__ __forceinline__ bool pd_span(const ppst_png_dec_image& d, const ppst_
   return ok;
 }
 
-// --------------------------------------------------------------------------------------------------------------------- plan
-__global__ __launch_bounds__(256) void pd_plan_kernel(const ppst_png_dec_image* __restrict__ descs, int B, int sw, void* work,
-                                                      int* __restrict__ status) {
-  int* rounds = (int*)work;
-  PdImg* plans = (PdImg*)((unsigned char*)work + pd_a16((int64_t)B * 4));
-  for (int i = threadIdx.x; i < B; i += 256) {
-    rounds[i] = 0; status[i] = 0;
-    pd_geom(descs[i], sw, &plans[i].g);
-    pd_layout(descs[i], plans[i].g, &plans[i].l);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int64_t at = pd_head_bytes(B);
-    for (int i = 0; i < B; ++i) {
-      plans[i].base_off = at;
-      at += plans[i].l.total;
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------------------------- gather
 __global__ __launch_bounds__(PD_T) void pd_offsets_kernel(const unsigned char* __restrict__ files, const ppst_png_dec_image* __restrict__ descs,
                                                           const ppst_png_span* __restrict__ spans, int B, void* work, int* __restrict__ status) {
   __shared__ int wt[2][PD_T / 64];
   const int i = blockIdx.x, tid = threadIdx.x;
-  const PdImg& im = pd_open(B, work, i);
+  const PdImg& im = open_plan<PdImg>(B, work, i);
   unsigned char* const base = (unsigned char*)work + im.base_off;
   const ppst_png_dec_image& d = descs[i];
   const ppst_png_span* sp = spans + d.span_off + d.first_idat;
@@ -156,7 +103,7 @@ __global__ __launch_bounds__(PD_T) void pd_offsets_kernel(const unsigned char* _
   int* cnt = (int*)(base + im.l.cnt);
   for (int k = tid; k < PD_ROUNDS_MAX + 1; k += PD_T) cnt[k] = 0;
   unsigned char* zs = base + im.l.zs;
-  const int64_t zcap = pd_a16((int64_t)im.g.L + 16);
+  const int64_t zcap = a16((int64_t)im.g.L + 16);
   for (int64_t k = (int64_t)im.g.L + tid; k < zcap; k += PD_T) zs[k] = 0;        // the words behind the stream read as zero
   int run = 0, bad = 0;
   for (int c0 = 0; c0 < d.nidat; c0 += PD_T) {
@@ -164,7 +111,7 @@ __global__ __launch_bounds__(PD_T) void pd_offsets_kernel(const unsigned char* _
     unsigned off = 0, len = 0;
     if (c < d.nidat) bad |= !pd_span(d, sp[c], &off, &len);
     int tot;
-    const int pre = pd_block_scan<PD_T>((int)len, tot, wt, 0);
+    const int pre = wg_scan<PD_T, true>((int)len, tot, wt, 0);
     if (c < d.nidat) soff[c] = (unsigned)(run + pre);
     run += tot;
     __syncthreads();                                               // wt is reused by the next round
@@ -190,7 +137,7 @@ __global__ __launch_bounds__(PD_T) void pd_chunk_kernel(const unsigned char* __r
   const int i = blockIdx.y, j = blockIdx.x, tid = threadIdx.x;
   const ppst_png_dec_image& d = descs[i];
   if (j >= d.nspans) return;
-  const PdImg& im = pd_open(B, work, i);
+  const PdImg& im = open_plan<PdImg>(B, work, i);
   unsigned char* const base = (unsigned char*)work + im.base_off;
   const ppst_png_span& s = spans[d.span_off + j];
   unsigned off, len;
@@ -366,7 +313,7 @@ __device__ void pd_block_header(PdTabs& T, const unsigned* __restrict__ zw, cons
   // the code-length code: its 19 lengths live in lens[300 .. 318] while its table is built
   unsigned char* cl = T.lens + 300;
   for (int k = 0; k < 19; ++k) cl[k] = 0;
-  for (int k = 0; k < hclen; ++k) { cl[PD_CLORDER[k]] = (unsigned char)(pd_peek(zw, p) & 7u); p += 3; }
+  for (int k = 0; k < hclen; ++k) { cl[PNG_CL_ORDER[k]] = (unsigned char)(pd_peek(zw, p) & 7u); p += 3; }
   int* count = T.lit.count;                                         // (scratch: the block's own codes are built later)
   unsigned* next = T.lit.first;
   int left = 1;
@@ -454,7 +401,7 @@ __device__ __forceinline__ PdRun pd_run(const PdTabs& T, const unsigned* __restr
 __global__ __launch_bounds__(PD_INF_T) void pd_inflate_kernel(const ppst_png_dec_image* __restrict__ descs, int B, void* work, int* __restrict__ status) {
   __shared__ PdTabs T;
   const int i = blockIdx.x, tid = threadIdx.x;
-  const PdImg& im = pd_open(B, work, i);
+  const PdImg& im = open_plan<PdImg>(B, work, i);
   unsigned char* const base = (unsigned char*)work + im.base_off;
   const unsigned char* zs = base + im.l.zs;
   const unsigned* zw = (const unsigned*)zs;
@@ -475,7 +422,7 @@ __global__ __launch_bounds__(PD_INF_T) void pd_inflate_kernel(const ppst_png_dec
   const unsigned max_blocks = nbits / 3u + 1u;
   for (unsigned blk = 0; blk < max_blocks; ++blk) {
     int tb = tid;                                                    // the thread number for the per-block steps, opaque for the
-    asm volatile("" : "+v"(tb));                                     // same reason as in pd_block_scan
+    asm volatile("" : "+v"(tb));                                     // same reason as in wg_scan
     if (tb == 0) pd_block_header(T, zw, zs, L);
     __syncthreads();
     if (T.stop) break;
@@ -540,7 +487,7 @@ __global__ __launch_bounds__(PD_INF_T) void pd_inflate_kernel(const ppst_png_dec
         __syncthreads();
         const bool live = active && tid <= T.eob_lane;
         int total;
-        const int pre = pd_block_scan<PD_INF_T>(live ? mine : 0, total, T.wt, 0);
+        const int pre = wg_scan<PD_INF_T, true>(live ? mine : 0, total, T.wt, 0);
         if (tid == T.eob_lane) T.eob_p = eob_p;
         if (total > n - outpos) { if (tid == 0) T.bits |= PPST_PNG_S_STREAM; fault = true; }
         if (live && !fault) {
@@ -581,7 +528,7 @@ __global__ __launch_bounds__(PD_INF_T) void pd_inflate_kernel(const ppst_png_dec
 __global__ __launch_bounds__(PD_T) void pd_jump_kernel(int B, void* work, const int* __restrict__ status, int round) {
   __shared__ int any;
   const int i = blockIdx.y;
-  const PdImg& im = pd_open(B, work, i);
+  const PdImg& im = open_plan<PdImg>(B, work, i);
   unsigned char* const base = (unsigned char*)work + im.base_off;
   int* cnt = (int*)(base + im.l.cnt);
   if (round >= im.g.jumps || status[i] != 0) return;                  // (a damaged stream may leave src undefined: not followed)
@@ -612,7 +559,7 @@ __global__ __launch_bounds__(PD_T) void pd_jump_kernel(int B, void* work, const 
 __global__ __launch_bounds__(PD_T) void pd_resolve_kernel(int B, void* work, const int* __restrict__ status) {
   __shared__ unsigned sa, sb;
   const int i = blockIdx.y, tid = threadIdx.x;
-  const PdImg& im = pd_open(B, work, i);
+  const PdImg& im = open_plan<PdImg>(B, work, i);
   unsigned char* const base = (unsigned char*)work + im.base_off;
   if ((int)blockIdx.x >= im.g.nchunk || status[i] != 0) return;
   if (tid == 0) { sa = 0; sb = 0; }
@@ -632,12 +579,12 @@ __global__ __launch_bounds__(PD_T) void pd_resolve_kernel(int B, void* work, con
     a += v;
     b += (unsigned)(m - j) * v;                                        // <= 16 * 4096 * 255
   }
-  if (a) { atomicAdd(&sa, a); atomicAdd(&sb, b % PD_ADLER); }           // <= 256 * 65520
+  if (a) { atomicAdd(&sa, a); atomicAdd(&sb, b % PNG_ADLER); }           // <= 256 * 65520
   __syncthreads();
   if (tid == 0) {
     unsigned* part = (unsigned*)(base + im.l.part);
-    part[2 * blockIdx.x] = sa % PD_ADLER;
-    part[2 * blockIdx.x + 1] = sb % PD_ADLER;
+    part[2 * blockIdx.x] = sa % PNG_ADLER;
+    part[2 * blockIdx.x + 1] = sb % PNG_ADLER;
   }
 }
 
@@ -647,10 +594,6 @@ __device__ __forceinline__ unsigned pd_load_px(const unsigned char* __restrict__
   if (C >= 3) v |= ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
   if (C == 4) v |= (unsigned)p[3] << 24;
   return v;
-}
-__device__ __forceinline__ int pd_paeth(int a, int b, int c) {
-  const int pa = abs(b - c), pb = abs(a - c), pc = abs(a + b - 2 * c);
-  return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
 }
 
 // Rows in bands of 64: lane l of a wave owns row 64 band + l and is one pixel behind lane l - 1, whose last pixel -- the one above
@@ -662,7 +605,7 @@ __global__ __launch_bounds__(PD_INF_T) void pd_unfilter_kernel(const ppst_png_de
                                                                unsigned char* __restrict__ out_u8, int* __restrict__ status) {
   __shared__ int skip;
   const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const PdImg& im = pd_open(B, work, i);
+  const PdImg& im = open_plan<PdImg>(B, work, i);
   unsigned char* const base = (unsigned char*)work + im.base_off;
   const ppst_png_dec_image& d = descs[i];
   if (tid == 0) skip = status[i] != 0;
@@ -674,11 +617,8 @@ __global__ __launch_bounds__(PD_INF_T) void pd_unfilter_kernel(const ppst_png_de
     const unsigned* part = (const unsigned*)(base + im.l.part);
     const int* cnt = (const int*)(base + im.l.cnt);
     unsigned a = 1, b = 0;
-    for (int c = 0; c < im.g.nchunk; ++c) {
-      const unsigned m = (unsigned)min(PD_CHUNK, im.g.n - c * PD_CHUNK);
-      b = (b + (unsigned)(((uint64_t)m * a) % PD_ADLER) + part[2 * c + 1]) % PD_ADLER;
-      a = (a + part[2 * c]) % PD_ADLER;
-    }
+    for (int c = 0; c < im.g.nchunk; ++c)
+      adler_join(a, b, (unsigned)min(PD_CHUNK, im.g.n - c * PD_CHUNK), part[2 * c], part[2 * c + 1]);
     const unsigned at = ((unsigned)cnt[PD_ROUNDS_MAX] + 7u) >> 3;
     const unsigned char* zs = base + im.l.zs;
     bool bad = at + 4 > im.g.L;
@@ -716,7 +656,7 @@ __global__ __launch_bounds__(PD_INF_T) void pd_unfilter_kernel(const ppst_png_de
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             const int fa = (int)((left >> (8 * c)) & 255u), fb = (int)((up >> (8 * c)) & 255u), fc = (int)((ul >> (8 * c)) & 255u);
-            const int add = ft == 1 ? fa : (ft == 2 ? fb : (ft == 3 ? (fa + fb) >> 1 : (ft == 4 ? pd_paeth(fa, fb, fc) : 0)));
+            const int add = ft == 1 ? fa : (ft == 2 ? fb : (ft == 3 ? (fa + fb) >> 1 : (ft == 4 ? png_paeth(fa, fb, fc) : 0)));
             r |= ((((f >> (8 * c)) & 255u) + (unsigned)add) & 255u) << (8 * c);
           }
           unsigned char* q = cur + (int64_t)x * C;
@@ -759,14 +699,12 @@ static bool pd_sw_ok(int sw) { return sw == 0 || (sw >= 2 && sw <= PD_SUBSEQ_MAX
 extern "C" int64_t ppst_png_decode_ws(const ppst_png_dec_image* descs, int B, int subseq_words) {
   if (B < 0 || B > 65535 || !pd_sw_ok(subseq_words)) return PPST_EINVAL;
   if (B > 0 && !descs) return PPST_ENULL;
-  int64_t total = pd_head_bytes(B > 0 ? B : 1);
+  int64_t total = head_bytes<PdImg>(B > 0 ? B : 1);
   for (int i = 0; i < B; ++i) {
     if (!pd_valid(descs[i])) return PPST_EINVAL;
-    PdGeom g;
-    PdLayout l;
-    pd_geom(descs[i], subseq_words, &g);
-    pd_layout(descs[i], g, &l);
-    total += l.total;
+    PdImg im;
+    codec_fill(descs[i], subseq_words, &im);
+    total += im.l.total;
   }
   return total;
 }
@@ -799,7 +737,7 @@ extern "C" int ppst_png_decode(const void* files, int64_t files_bytes, const pps
   int* stt = (int*)status;
   static_assert(sizeof(PdTabs) <= 16 * 1024, "the inflate workgroup's tables");
   static_assert(PD_ROUNDS_MAX >= 33, "one counter per pointer-jumping round");
-  PPST_LAUNCH(pd_plan_kernel, dim3(1), dim3(256), 0, st, dd, B, subseq_words, work, stt);
+  PPST_LAUNCH(plan_kernel<PdImg>, dim3(1), dim3(256), 0, st, dd, B, subseq_words, work, stt);
   PPST_LAUNCH(pd_offsets_kernel, dim3((unsigned)B), dim3(PD_T), 0, st, by, dd, sp, B, work, stt);
   PPST_LAUNCH(pd_chunk_kernel, dim3((unsigned)max_spans, (unsigned)B), dim3(PD_T), 0, st, by, dd, sp, B, work, stt);
   PPST_LAUNCH(pd_inflate_kernel, dim3((unsigned)B), dim3(PD_INF_T), 0, st, dd, B, work, stt);

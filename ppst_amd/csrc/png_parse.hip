@@ -1,20 +1,12 @@
 // PNG decode on the device, the host half: ppst_png_parse walks a file's chunks and fills the descriptor and the span table the
 // kernels of png_decode.hip read (include/ppst_hip.h "PNG decode on the device").  Plain C++ with no GPU call and no dependency
 // but the header: tests/png_parse_san.cpp compiles this file as host code under the address and undefined-behaviour sanitizers.
-// Every read goes through Rd, which knows n: no chunk length is trusted.  No CRC is computed and nothing is inflated here.
+// Every read goes through Rd (parse_reader.h, shared with jpeg_parse.hip), which knows n: no chunk length is trusted.  No CRC is computed and nothing is inflated here.
 #include <string.h>
 #include "../../include/ppst_hip.h"
+#include "parse_reader.h"
 
 namespace {
-struct Rd {
-  const unsigned char* p;
-  int64_t n;
-  bool has(int64_t at, int64_t len) const { return at >= 0 && len >= 0 && at <= n && len <= n - at; }
-  int u8(int64_t at) const { return p[at]; }                                  // callers check has() first
-  uint32_t u32(int64_t at) const {
-    return ((uint32_t)p[at] << 24) | ((uint32_t)p[at + 1] << 16) | ((uint32_t)p[at + 2] << 8) | (uint32_t)p[at + 3];
-  }
-};
 constexpr uint32_t tag(char a, char b, char c, char d) {
   return ((uint32_t)(unsigned char)a << 24) | ((uint32_t)(unsigned char)b << 16) | ((uint32_t)(unsigned char)c << 8) | (uint32_t)(unsigned char)d;
 }

@@ -268,22 +268,14 @@ def decode_files_device(blobs, names, device="cuda", mirror=None):
     and one over all .png files, ops.png_decode), None where the host has to: another extension, a file the parser refuses, a
     non-zero status."""
     out = [None] * len(blobs)
-    parsed = {i: ops.jpeg_parse(b) for i, (b, n) in enumerate(zip(blobs, names)) if n.lower().endswith((".jpg", ".jpeg"))}
-    take = [i for i in sorted(parsed) if parsed[i][0] == 0]
-    if take:
-        views, status = ops.jpeg_decode([blobs[i] for i in take], expand_grey=True, device=device,
-                                        mirror=None if mirror is None else [mirror[i] for i in take],
-                                        parsed=[parsed[i][1] for i in take])
-        for i, v, st in zip(take, views, status.cpu().tolist()):
-            out[i] = v if st == 0 else None
-    parsed = {i: ops.png_parse(b) for i, (b, n) in enumerate(zip(blobs, names)) if n.lower().endswith(".png")}
-    take = [i for i in sorted(parsed) if parsed[i][0] == 0]
-    if take:                                                     # grey -> three channels, alpha dropped: Pillow's convert("RGB")
-        views, status = ops.png_decode([blobs[i] for i in take], expand_grey=True, drop_alpha=True, device=device,
-                                       mirror=None if mirror is None else [mirror[i] for i in take],
-                                       parsed=[parsed[i][1:] for i in take])
-        for i, v, st in zip(take, views, status.cpu().tolist()):
-            out[i] = v if st == 0 else None
+    for codec in ops.CODECS:                                     # (the table that decides which coder takes a file)
+        parsed = {i: codec.parse(b) for i, (b, n) in enumerate(zip(blobs, names)) if ops.codec_for(n) is codec}
+        take = [i for i in sorted(parsed) if parsed[i][0] == 0]
+        if take:                                                 # codec.rgb: what Pillow's convert("RGB") gives
+            views, status = codec.decode([blobs[i] for i in take], device=device, parsed=[parsed[i][1] for i in take],
+                                         mirror=None if mirror is None else [mirror[i] for i in take], **codec.rgb)
+            for i, v, st in zip(take, views, status.cpu().tolist()):
+                out[i] = v if st == 0 else None
     return out
 
 

@@ -203,10 +203,7 @@ def decode_jpeg(blobs, mode=None, device="cuda"):
     if mode not in (None, "RGB"):
         raise ValueError("mode must be None or 'RGB', not %r" % (mode,))
     views, status = ops.jpeg_decode(blobs, expand_grey=(mode == "RGB"), device=device)
-    for i, st in enumerate(status.cpu().tolist()):
-        if st:
-            why = ", ".join(v for k, v in sorted(_lib.JPEG_STATUS_BITS.items()) if st & k)
-            raise OSError("decode_jpeg: file %d is damaged (%s)" % (i, why))
+    _raise_damaged("decode_jpeg", status, _lib.JPEG_STATUS_BITS)
     return views
 
 
@@ -234,11 +231,15 @@ def decode_png(blobs, mode=None, device="cuda"):
     if mode not in (None, "RGB"):
         raise ValueError("mode must be None or 'RGB', not %r" % (mode,))
     views, status = ops.png_decode(blobs, expand_grey=(mode == "RGB"), drop_alpha=(mode == "RGB"), device=device)
+    _raise_damaged("decode_png", status, _lib.PNG_STATUS_BITS)
+    return views
+
+
+def _raise_damaged(who, status, bits):
+    """OSError naming the status bits of the first file the device found damaged"""
     for i, st in enumerate(status.cpu().tolist()):
         if st:
-            why = ", ".join(v for k, v in sorted(_lib.PNG_STATUS_BITS.items()) if st & k)
-            raise OSError("decode_png: file %d is damaged (%s)" % (i, why))
-    return views
+            raise OSError("%s: file %d is damaged (%s)" % (who, i, ", ".join(v for k, v in sorted(bits.items()) if st & k)))
 
 
 def _files_to_bytes(files, sizes):

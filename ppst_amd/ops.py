@@ -1760,21 +1760,28 @@ def guided_filter(guide_u8, src_u8, r=30, eps=(0.02 * 255) ** 2, want_u8=False):
     return (out, out_u8) if want_u8 else out
 
 
+def _encode(name, u8, limits, geom=(), settings=()):
+    """What png_encode and jpeg_encode do: the slots from the library's bound, the workspace from torch's allocator, one call.
+    ``geom``: the codec's arguments behind (H, W, C) of its bound and workspace; ``settings``: those of its encode call."""
+    if not isinstance(u8, torch.Tensor) or not u8.is_cuda or u8.dtype != torch.uint8 or u8.dim() != 4:
+        raise RuntimeError("%s_encode needs a CUDA uint8 (B,H,W,C) tensor (no CPU fallback)" % name)
+    u8 = u8.contiguous()
+    B, H, W, C = u8.shape
+    bound = getattr(lib, "ppst_%s_bound" % name)(H, W, C, *geom)
+    if bound < 0:
+        raise RuntimeError("%s_encode: unsupported image shape %s (%s)" % (name, tuple(u8.shape), limits))
+    files = torch.empty((B, bound), device=u8.device, dtype=torch.uint8)
+    sizes = torch.empty((B,), device=u8.device, dtype=torch.int64)
+    work = torch.empty(getattr(lib, "ppst_%s_ws" % name)(B, H, W, C, *geom), device=u8.device, dtype=torch.uint8)
+    fn = "ppst_%s_encode" % name
+    check(getattr(lib, fn)(_p(u8), _p(files), _p(sizes), B, H, W, C, *settings, _p(work), _stream()), fn)
+    return files, sizes
+
+
 def png_encode(u8):
     """(B,H,W,C) uint8 on the device, C = 1 or 3 -> (files (B, bound) uint8, sizes (B,) int64), both on the device: file i is
     files[i, :sizes[i]] (csrc/png.hip).  The workspace comes from torch's allocator; nothing synchronises the host."""
-    if not isinstance(u8, torch.Tensor) or not u8.is_cuda or u8.dtype != torch.uint8 or u8.dim() != 4:
-        raise RuntimeError("png_encode needs a CUDA uint8 (B,H,W,C) tensor (no CPU fallback)")
-    u8 = u8.contiguous()
-    B, H, W, C = u8.shape
-    bound = lib.ppst_png_bound(H, W, C)
-    if bound < 0:
-        raise RuntimeError("png_encode: unsupported image shape %s (C must be 1 or 3)" % (tuple(u8.shape),))
-    files = torch.empty((B, bound), device=u8.device, dtype=torch.uint8)
-    sizes = torch.empty((B,), device=u8.device, dtype=torch.int64)
-    work = torch.empty(lib.ppst_png_ws(B, H, W, C), device=u8.device, dtype=torch.uint8)
-    check(lib.ppst_png_encode(_p(u8), _p(files), _p(sizes), B, H, W, C, _p(work), _stream()), "ppst_png_encode")
-    return files, sizes
+    return _encode("png", u8, "C must be 1 or 3")
 
 
 JPEG_SUBSAMPLING = {"4:4:4": 0, "4:2:0": 2}        # PPST_JPEG_444 / PPST_JPEG_420 (Pillow's numbers)
@@ -1794,18 +1801,7 @@ def jpeg_encode(u8, quality=90, subsampling="4:2:0"):
     file i is files[i, :sizes[i]], a baseline JPEG (csrc/jpeg.hip; the format: include/ppst_hip.h).  The workspace comes from
     torch's allocator; nothing synchronises the host."""
     ss = check_jpeg_settings(quality, subsampling)
-    if not isinstance(u8, torch.Tensor) or not u8.is_cuda or u8.dtype != torch.uint8 or u8.dim() != 4:
-        raise RuntimeError("jpeg_encode needs a CUDA uint8 (B,H,W,C) tensor (no CPU fallback)")
-    u8 = u8.contiguous()
-    B, H, W, C = u8.shape
-    bound = lib.ppst_jpeg_bound(H, W, C, ss)
-    if bound < 0:
-        raise RuntimeError("jpeg_encode: unsupported image shape %s (C must be 1 or 3, H and W at most 65535)" % (tuple(u8.shape),))
-    files = torch.empty((B, bound), device=u8.device, dtype=torch.uint8)
-    sizes = torch.empty((B,), device=u8.device, dtype=torch.int64)
-    work = torch.empty(lib.ppst_jpeg_ws(B, H, W, C, ss), device=u8.device, dtype=torch.uint8)
-    check(lib.ppst_jpeg_encode(_p(u8), _p(files), _p(sizes), B, H, W, C, quality, ss, _p(work), _stream()), "ppst_jpeg_encode")
-    return files, sizes
+    return _encode("jpeg", u8, "C must be 1 or 3, H and W at most 65535", (ss,), (quality, ss))
 
 
 def jpeg_parse(blob):
@@ -1813,85 +1809,6 @@ def jpeg_parse(blob):
     d = _lib.JpegDecImage()
     blob = blob if isinstance(blob, bytes) else bytes(blob)
     return lib.ppst_jpeg_parse(blob, len(blob), ctypes.byref(d)), d
-
-
-class _JpegDecodeCall:
-    """One batched decode, prepared: the files parsed and packed into one pinned buffer, one host-to-device copy of bytes and one of
-    descriptors, output / status / workspace from torch's allocator.  ``launch()`` runs the kernels (again and again:
-    tests/jpeg_decode_time.py times them alone)."""
-
-    def __init__(self, blobs, expand_grey, mirror, subseq_words, dev, parsed=None):
-        blobs = [b if isinstance(b, bytes) else bytes(b) for b in blobs]
-        B = self.B = len(blobs)
-        if mirror is not None and len(mirror) != B:
-            raise ValueError("mirror must be None or one flag per file")
-        if parsed is not None and len(parsed) != B:
-            raise ValueError("parsed must be None or one descriptor per file")
-        self.subseq_words, self.dev = subseq_words, dev
-        descs = self.descs = (_lib.JpegDecImage * max(B, 1))()
-        file_off, out_off = 0, 0
-        for i, blob in enumerate(blobs):
-            if parsed is not None:
-                descs[i] = parsed[i]                             # (a copy: the caller's descriptor keeps its own four fields)
-            else:
-                rc = lib.ppst_jpeg_parse(blob, len(blob), ctypes.byref(descs[i]))
-                if rc != 0:
-                    raise ValueError("jpeg_decode: file %d: %s" % (i, _lib.JPEG_REFUSALS.get(rc, "error %d" % rc)))
-            d = descs[i]
-            d.file_off, d.out_off = file_off, out_off
-            d.mirror, d.expand_grey = int(bool(mirror[i])) if mirror is not None else 0, int(bool(expand_grey))
-            file_off += (len(blob) + 15) & ~15
-            out_off += (d.H * d.W * (3 if d.ncomp == 3 or expand_grey else 1) + 15) & ~15
-        self.nbytes, self.out_bytes = file_off, out_off
-        self.status = torch.zeros((B,), device=dev, dtype=torch.int32)
-        if B == 0:
-            return
-        ws = lib.ppst_jpeg_decode_ws(descs, B, subseq_words)
-        if ws < 0:
-            raise ValueError("jpeg_decode: subseq_words must be 0 (the default) or 2 .. 65536, got %r" % (subseq_words,))
-        nd = ctypes.sizeof(_lib.JpegDecImage) * B
-        host = torch.empty((file_off + nd,), dtype=torch.uint8).pin_memory()
-        hv = host.numpy()
-        for i, blob in enumerate(blobs):
-            hv[descs[i].file_off:descs[i].file_off + len(blob)] = memoryview(blob)
-        ctypes.memmove(host.data_ptr() + file_off, ctypes.addressof(descs), nd)       # the descriptors ride behind the files
-        # (torch's caching host allocator keeps a pinned block from reuse until the copies recorded on it are done)
-        self.packed = host[:file_off].to(dev, non_blocking=True)
-        self.ddesc = host[file_off:].to(dev, non_blocking=True)
-        self.out = torch.empty((out_off,), device=dev, dtype=torch.uint8)
-        self.work = torch.empty((ws,), device=dev, dtype=torch.uint8)
-
-    def launch(self):
-        if self.B:
-            with torch.cuda.device(self.dev):
-                check(lib.ppst_jpeg_decode(_p(self.packed), self.nbytes, self.descs, _p(self.ddesc), _p(self.out), self.out_bytes,
-                                           _p(self.status), self.B, self.subseq_words, _p(self.work), _stream()), "ppst_jpeg_decode")
-        return self
-
-    def views(self):
-        out = []
-        for i in range(self.B):
-            d = self.descs[i]
-            C = 3 if d.ncomp == 3 or d.expand_grey else 1
-            out.append(self.out[d.out_off:d.out_off + d.H * d.W * C].view(d.H, d.W, C))
-        return out
-
-    def rounds(self):
-        return self.work[:4 * self.B].view(torch.int32).clone() if self.B else self.status.clone()
-
-
-def jpeg_decode(blobs, expand_grey=False, mirror=None, subseq_words=0, device="cuda", rounds=False, parsed=None):
-    """blobs: B baseline JPEG files (bytes) of any sizes and samplings -> (list of B (H,W,C) uint8 views of one device buffer,
-    status (B,) int32 on the device; 0 = decoded: include/ppst_hip.h, csrc/jpeg_decode.hip).  C = 1 for a grey file, 3 for a colour
-    one and for a grey one with ``expand_grey``; ``mirror``: None or B flags, image i comes out with its columns reversed.  The files
-    are packed into one pinned buffer: one host-to-device copy of bytes, one of descriptors.  A file the parser refuses raises
-    ValueError with its reason.  ``rounds``: also return the (B,) int32 tensor of rounds the subsequence iteration took.
-    ``parsed``: the files' descriptors where the caller has them already (``jpeg_parse`` returned 0 for each): nothing is parsed twice."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("jpeg_decode needs a CUDA (HIP) device (no CPU fallback)")
-    call = _JpegDecodeCall(blobs, expand_grey, mirror, subseq_words, dev, parsed).launch()
-    return (call.views(), call.status, call.rounds()) if rounds else (call.views(), call.status)
 
 
 def png_parse(blob):
@@ -1909,95 +1826,154 @@ def png_parse(blob):
         cap = d.nspans
 
 
-class _PngDecodeCall:
-    """One batched PNG decode, prepared: the files parsed and packed into one pinned buffer with their descriptors and span tables
-    behind them (one host-to-device copy), output / status / workspace from torch's allocator.  ``launch()`` runs the kernels
-    (again and again: tests/png_decode_time.py times them alone)."""
+class _DecodeCall:
+    """One batched decode, prepared: the files parsed and packed into one pinned buffer with their descriptors (and, where the
+    format has them, span tables) behind them, one host-to-device copy, output / status / workspace from torch's allocator.
+    ``launch()`` runs the kernels (again and again: tests/jpeg_decode_time.py and tests/png_decode_time.py time them alone).
+    A format supplies its descriptor type ``Desc`` (and ``Span``; None: no span tables), the two library functions ``lib_ws`` and
+    ``lib_decode``, its texts (``name``, ``refusals``, ``parsed_what``, ``ws_refused``) and the methods ``parse`` (blob -> (rc,
+    descriptor, spans)), ``channels`` and ``set_flags``; ``flags`` are its keyword flags."""
+    Span = None
 
-    def __init__(self, blobs, expand_grey, drop_alpha, mirror, subseq_words, dev, parsed=None):
+    def __init__(self, blobs, mirror, subseq_words, dev, parsed=None, **flags):
         blobs = [b if isinstance(b, bytes) else bytes(b) for b in blobs]
         B = self.B = len(blobs)
         if mirror is not None and len(mirror) != B:
             raise ValueError("mirror must be None or one flag per file")
         if parsed is not None and len(parsed) != B:
-            raise ValueError("parsed must be None or one (descriptor, spans) pair per file")
-        for flag in (expand_grey, drop_alpha):
-            if isinstance(flag, (list, tuple)) and len(flag) != B:
-                raise ValueError("expand_grey and drop_alpha must be one flag, or one flag per file")
-        if isinstance(subseq_words, bool) or not isinstance(subseq_words, int) or not (subseq_words == 0 or 2 <= subseq_words <= 128):
-            raise ValueError("png_decode: subseq_words must be 0 (the default) or 2 .. 128, got %r" % (subseq_words,))
-        self.subseq_words, self.dev = subseq_words, dev
-        descs = self.descs = (_lib.PngDecImage * max(B, 1))()
+            raise ValueError("parsed must be None or one %s per file" % self.parsed_what)
+        self.subseq_words, self.dev, self.flags = subseq_words, dev, flags
+        self.check_flags()
+        descs = self.descs = (self.Desc * max(B, 1))()
         tables = []
         file_off, out_off, span_off = 0, 0, 0
         for i, blob in enumerate(blobs):
             if parsed is not None:
-                d0, spans = parsed[i]
+                d0, spans = parsed[i] if self.Span else (parsed[i], None)
             else:
-                rc, d0, spans = png_parse(blob)
+                rc, d0, spans = self.parse(blob)
                 if rc != 0:
-                    raise ValueError("png_decode: file %d: %s" % (i, _lib.PNG_REFUSALS.get(rc, "error %d" % rc)))
+                    raise ValueError("%s_decode: file %d: %s" % (self.name, i, self.refusals.get(rc, "error %d" % rc)))
             descs[i] = d0                                        # (a copy: the caller's descriptor keeps its own fields)
             d = descs[i]
-            if d.file_len != len(blob) or d.nspans < 1 or len(spans) < d.nspans:
-                raise ValueError("png_decode: file %d: the descriptor is not this file's" % i)
-            tables.append(spans)
-            d.file_off, d.out_off, d.span_off = file_off, out_off, span_off
+            if self.Span:
+                if d.file_len != len(blob) or d.nspans < 1 or len(spans) < d.nspans:
+                    raise ValueError("%s_decode: file %d: the descriptor is not this file's" % (self.name, i))
+                tables.append(spans)
+                d.span_off = span_off
+                span_off += d.nspans
+            d.file_off, d.out_off = file_off, out_off
             d.mirror = int(bool(mirror[i])) if mirror is not None else 0
-            d.expand_grey, d.drop_alpha = int(self._flag(expand_grey, i)), int(self._flag(drop_alpha, i))
+            self.set_flags(d, i)
             file_off += (len(blob) + 15) & ~15
-            out_off += (d.H * d.W * self._channels(d) + 15) & ~15
-            span_off += d.nspans
+            out_off += (d.H * d.W * self.channels(d) + 15) & ~15
         self.nbytes, self.out_bytes = file_off, out_off
         self.status = torch.zeros((B,), device=dev, dtype=torch.int32)
         if B == 0:
             return
-        ws = lib.ppst_png_decode_ws(descs, B, subseq_words)
+        ws = self.lib_ws(descs, B, subseq_words)
         if ws < 0:
-            raise ValueError("png_decode: the library refused the descriptors (%d)" % ws)
-        nd, span_size = ctypes.sizeof(_lib.PngDecImage) * B, ctypes.sizeof(_lib.PngSpan)
+            raise ValueError(self.ws_refused(ws))
+        nd, span_size = ctypes.sizeof(self.Desc) * B, ctypes.sizeof(self.Span) if self.Span else 0
         ns = (span_off * span_size + 15) & ~15
         host = torch.empty((file_off + nd + ns,), dtype=torch.uint8).pin_memory()
         hv = host.numpy()
         for i, blob in enumerate(blobs):
             hv[descs[i].file_off:descs[i].file_off + len(blob)] = memoryview(blob)
         ctypes.memmove(host.data_ptr() + file_off, ctypes.addressof(descs), nd)       # descriptors and spans ride behind the files
-        for i in range(B):
-            ctypes.memmove(host.data_ptr() + file_off + nd + descs[i].span_off * span_size, ctypes.addressof(tables[i]),
-                           descs[i].nspans * span_size)
+        for d, spans in zip(descs, tables):
+            ctypes.memmove(host.data_ptr() + file_off + nd + d.span_off * span_size, ctypes.addressof(spans), d.nspans * span_size)
         # (torch's caching host allocator keeps a pinned block from reuse until the copies recorded on it are done)
         onchip = host.to(dev, non_blocking=True)
         self.packed, self.ddesc, self.dspans = onchip[:file_off], onchip[file_off:file_off + nd], onchip[file_off + nd:]
         self.out = torch.empty((out_off,), device=dev, dtype=torch.uint8)
         self.work = torch.empty((ws,), device=dev, dtype=torch.uint8)
 
-    @staticmethod
-    def _flag(flag, i):
-        """one flag for the batch, or a list of one per file"""
-        return bool(flag[i]) if isinstance(flag, (list, tuple)) else bool(flag)
-
-    @staticmethod
-    def _channels(d):
-        return (3 if d.expand_grey else 1) if d.channels == 1 else (3 if d.channels == 3 or d.drop_alpha else 4)
+    def check_flags(self):
+        pass
 
     def launch(self):
         if self.B:
+            tabs = (_p(self.dspans),) if self.Span else ()
             with torch.cuda.device(self.dev):
-                check(lib.ppst_png_decode(_p(self.packed), self.nbytes, self.descs, _p(self.ddesc), _p(self.dspans), _p(self.out),
-                                          self.out_bytes, _p(self.status), self.B, self.subseq_words, _p(self.work), _stream()),
-                      "ppst_png_decode")
+                check(self.lib_decode(_p(self.packed), self.nbytes, self.descs, _p(self.ddesc), *tabs, _p(self.out), self.out_bytes,
+                                      _p(self.status), self.B, self.subseq_words, _p(self.work), _stream()), "ppst_%s_decode" % self.name)
         return self
 
     def views(self):
         out = []
         for i in range(self.B):
             d = self.descs[i]
-            C = self._channels(d)
+            C = self.channels(d)
             out.append(self.out[d.out_off:d.out_off + d.H * d.W * C].view(d.H, d.W, C))
         return out
 
     def rounds(self):
         return self.work[:4 * self.B].view(torch.int32).clone() if self.B else self.status.clone()
+
+    @classmethod
+    def run(cls, blobs, mirror, subseq_words, device, parsed, rounds, **flags):
+        """the body of jpeg_decode / png_decode"""
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("%s_decode needs a CUDA (HIP) device (no CPU fallback)" % cls.name)
+        call = cls(blobs, mirror, subseq_words, dev, parsed, **flags).launch()
+        return (call.views(), call.status, call.rounds()) if rounds else (call.views(), call.status)
+
+
+class _JpegDecodeCall(_DecodeCall):
+    name, Desc, refusals, parsed_what = "jpeg", _lib.JpegDecImage, _lib.JPEG_REFUSALS, "descriptor"
+    lib_ws, lib_decode = lib.ppst_jpeg_decode_ws, lib.ppst_jpeg_decode
+
+    def ws_refused(self, ws):
+        return "jpeg_decode: subseq_words must be 0 (the default) or 2 .. 65536, got %r" % (self.subseq_words,)
+
+    @staticmethod
+    def parse(blob):
+        return jpeg_parse(blob) + (None,)
+
+    def set_flags(self, d, i):
+        d.expand_grey = int(bool(self.flags["expand_grey"]))
+
+    @staticmethod
+    def channels(d):
+        return 3 if d.ncomp == 3 or d.expand_grey else 1
+
+
+def jpeg_decode(blobs, expand_grey=False, mirror=None, subseq_words=0, device="cuda", rounds=False, parsed=None):
+    """blobs: B baseline JPEG files (bytes) of any sizes and samplings -> (list of B (H,W,C) uint8 views of one device buffer,
+    status (B,) int32 on the device; 0 = decoded: include/ppst_hip.h, csrc/jpeg_decode.hip).  C = 1 for a grey file, 3 for a colour
+    one and for a grey one with ``expand_grey``; ``mirror``: None or B flags, image i comes out with its columns reversed.  The files
+    and their descriptors are packed into one pinned buffer: one host-to-device copy.  A file the parser refuses raises
+    ValueError with its reason.  ``rounds``: also return the (B,) int32 tensor of rounds the subsequence iteration took.
+    ``parsed``: the files' descriptors where the caller has them already (``jpeg_parse`` returned 0 for each): nothing is parsed twice."""
+    return _JpegDecodeCall.run(blobs, mirror, subseq_words, device, parsed, rounds, expand_grey=expand_grey)
+
+
+class _PngDecodeCall(_DecodeCall):
+    name, Desc, Span, refusals, parsed_what = "png", _lib.PngDecImage, _lib.PngSpan, _lib.PNG_REFUSALS, "(descriptor, spans) pair"
+    lib_ws, lib_decode = lib.ppst_png_decode_ws, lib.ppst_png_decode
+    parse = staticmethod(png_parse)
+
+    def ws_refused(self, ws):
+        return "png_decode: the library refused the descriptors (%d)" % ws
+
+    def check_flags(self):
+        for flag in self.flags.values():
+            if isinstance(flag, (list, tuple)) and len(flag) != self.B:
+                raise ValueError("expand_grey and drop_alpha must be one flag, or one flag per file")
+        sw = self.subseq_words
+        if isinstance(sw, bool) or not isinstance(sw, int) or not (sw == 0 or 2 <= sw <= 128):
+            raise ValueError("png_decode: subseq_words must be 0 (the default) or 2 .. 128, got %r" % (sw,))
+
+    def set_flags(self, d, i):
+        """each one flag for the batch, or a list of one per file"""
+        for name, flag in self.flags.items():
+            setattr(d, name, int(bool(flag[i] if isinstance(flag, (list, tuple)) else flag)))
+
+    @staticmethod
+    def channels(d):
+        return (3 if d.expand_grey else 1) if d.channels == 1 else (3 if d.channels == 3 or d.drop_alpha else 4)
 
 
 def png_decode(blobs, expand_grey=False, drop_alpha=False, mirror=None, device="cuda", parsed=None, subseq_words=0, rounds=False):
@@ -2009,11 +1985,33 @@ def png_decode(blobs, expand_grey=False, drop_alpha=False, mirror=None, device="
     files' (descriptor, spans) pairs where the caller has them already (``png_parse`` returned 0 for each).  ``subseq_words``:
     32-bit words per subsequence of the parallel inflate, 0 = the default.  ``rounds``: also return the (B,) int32 tensor of
     rounds the subsequence iteration took."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("png_decode needs a CUDA (HIP) device (no CPU fallback)")
-    call = _PngDecodeCall(blobs, expand_grey, drop_alpha, mirror, subseq_words, dev, parsed).launch()
-    return (call.views(), call.status, call.rounds()) if rounds else (call.views(), call.status)
+    return _PngDecodeCall.run(blobs, mirror, subseq_words, device, parsed, rounds, expand_grey=expand_grey, drop_alpha=drop_alpha)
+
+
+# The table from file extension to codec: the one place that decides which coder takes a file.  ``parse``: blob -> (return
+# code, what the codec's ``decode`` takes as an entry of ``parsed``, the descriptor with the file's H and W); ``rgb``: the
+# decode flags that give what Pillow's convert("RGB") gives.
+Codec = collections.namedtuple("Codec", "name extensions parse decode rgb")
+
+
+def _jpeg_entry(blob):
+    rc, d = jpeg_parse(blob)
+    return rc, d, d
+
+
+def _png_entry(blob):
+    rc, d, spans = png_parse(blob)
+    return rc, (d, spans), d
+
+
+JPEG = Codec("jpeg", (".jpg", ".jpeg"), _jpeg_entry, jpeg_decode, {"expand_grey": True})
+PNG = Codec("png", (".png",), _png_entry, png_decode, {"expand_grey": True, "drop_alpha": True})
+CODECS = (JPEG, PNG)                                # (batched calls are made in this order)
+
+
+def codec_for(path):
+    """the codec whose device decoder takes a file of this name, None: the host's business"""
+    return next((c for c in CODECS if path.lower().endswith(c.extensions)), None)
 
 
 def resample_f32(x, out_h, out_w, clamp=None):

@@ -154,28 +154,25 @@ class CelebAMaskDataset:
 
     def _decode(self, idx):
         """host side: file -> (uint8 HWC image, PIL 'L' label), optionally mirrored together.  With the device decoder a JPEG or PNG
-        file it takes stays bytes here: the image is then (bytes, mirror flag, path, parsed descriptor) -- the descriptor of a PNG
-        file is the pair (descriptor, spans) --, and so is the label where it is a grey PNG of the preprocessed image's size."""
+        file it takes stays bytes here: the image is then (bytes, mirror flag, path, what its codec parsed: an entry of the decode
+        call's ``parsed``), and so is the label where it is a grey PNG of the preprocessed image's size.  Which codec takes a
+        file: ops.codec_for."""
         from PIL import Image
         ip, lp = self.pairs[idx]
         try:
             blob, lblob = None, None
-            if self.decode == "device" and ip.lower().endswith((".jpg", ".jpeg", ".png")):
+            if self.decode == "device" and ops.codec_for(ip) is not None:
                 with open(ip, "rb") as f:
                     blob = f.read()
-                if ip.lower().endswith(".png"):
-                    rc, d, spans = ops.png_parse(blob)
-                    desc, wh = (d, spans), (d.W, d.H)
-                else:
-                    rc, desc = ops.jpeg_parse(blob)
-                    wh = (desc.W, desc.H)
+                rc, desc, head = ops.codec_for(ip).parse(blob)
+                wh = (head.W, head.H)
                 if rc != 0:
                     blob = None
             img = np.asarray(Image.open(ip).convert("RGB")) if blob is None else None
             if self.decode == "device":
                 with open(lp, "rb") as f:
                     lblob = f.read()
-                rc, d, spans = ops.png_parse(lblob)
+                rc, ldesc, d = ops.PNG.parse(lblob)
                 if rc != 0 or d.colour != 0 or (d.W, d.H) != self._out_size(*(wh if blob is not None else (img.shape[1], img.shape[0]))):
                     lblob = None
             lab = Image.open(lp).convert("L") if lblob is None else None
@@ -186,7 +183,7 @@ class CelebAMaskDataset:
         if flip:
             img = np.ascontiguousarray(img[:, ::-1]) if img is not None else None
             lab = lab.transpose(Image.FLIP_LEFT_RIGHT) if lab is not None else None
-        return (img if blob is None else (blob, flip, ip, desc)), (lab if lblob is None else (lblob, flip, lp, (d, spans)))
+        return (img if blob is None else (blob, flip, ip, desc)), (lab if lblob is None else (lblob, flip, lp, ldesc))
 
     def _decode_on_device(self, batch):
         """[(image | (bytes, flip, path, descriptor), label)] -> the same with every image a uint8 HWC array or device tensor: one
@@ -194,22 +191,25 @@ class CelebAMaskDataset:
         a random index as in ``_decode`` (that draw is then made on the consumer's thread: the order of draws, and so the batches
         that follow, differ from ``decode="host"`` from such a file on -- with sound files the two give the same batches)."""
         from PIL import Image
-        is_png = lambda item: isinstance(item[3], tuple)
-        jpegs = [(n, 0) for n, (img, _) in enumerate(batch) if isinstance(img, tuple) and not is_png(img)]
-        pngs = [(n, k) for n, pair in enumerate(batch) for k in (0, 1) if isinstance(pair[k], tuple) and (k == 1 or is_png(pair[k]))]
-        if not jpegs and not pngs:
+        todo = {}                                                # codec's name -> [(sample, 0: image / 1: label)]; labels are PNG files
+        for n, pair in enumerate(batch):
+            for k in (0, 1):
+                if isinstance(pair[k], tuple):
+                    todo.setdefault((ops.PNG if k else ops.codec_for(pair[k][2])).name, []).append((n, k))
+        if not todo:
             return batch
         done = {}                                                # (sample, 0: image / 1: label) -> (view, status)
-        if jpegs:
-            items = [batch[n][0] for n, _ in jpegs]
-            views, status = ops.jpeg_decode([it[0] for it in items], expand_grey=True, mirror=[it[1] for it in items],
-                                            device=self.device, parsed=[it[3] for it in items])
-            done.update(zip(jpegs, zip(views, status.cpu().tolist())))
-        if pngs:                                                 # images come out RGB, labels as the one channel they are
-            items = [batch[n][k] for n, k in pngs]
-            views, status = ops.png_decode([it[0] for it in items], expand_grey=[k == 0 for _, k in pngs], drop_alpha=True,
-                                           mirror=[it[1] for it in items], device=self.device, parsed=[it[3] for it in items])
-            done.update(zip(pngs, zip(views, status.cpu().tolist())))
+        for codec in ops.CODECS:
+            keys = todo.get(codec.name)
+            if not keys:
+                continue
+            items = [batch[n][k] for n, k in keys]
+            flags = dict(codec.rgb)                              # images come out RGB, labels as the one channel they are
+            if any(k for _, k in keys):
+                flags["expand_grey"] = [k == 0 for _, k in keys]
+            views, status = codec.decode([it[0] for it in items], mirror=[it[1] for it in items], device=self.device,
+                                         parsed=[it[3] for it in items], **flags)
+            done.update(zip(keys, zip(views, status.cpu().tolist())))
         batch = [list(pair) for pair in batch]
         for (n, k), (v, st) in sorted(done.items()):
             if batch[n] is None:

@@ -4,7 +4,7 @@
 
 B = 8 photo-like images of 512^2 and 1024^2 at q 90, 4:2:0, written by Pillow (no restart markers: one Huffman stream per file) and
 by our encoder (DRI 16 MCUs).  HIP events around 20 calls after 3 warm-up calls: the kernels alone (ppst_jpeg_decode on files that
-are already on the device) and the whole ops.jpeg_decode (parse, pack, two copies, kernels).  Rounds to convergence per file.
+are already on the device) and the whole ops.jpeg_decode (parse, pack, the copy, kernels).  Rounds to convergence per file.
 Yardstick, same process: Pillow's decode of the same files on 8 threads (what evaluation.load_images does with decode="host")
 and on one thread."""
 import io
@@ -58,7 +58,7 @@ def main():
             files["pillow (no DRI)"].append(buf.getvalue())
         for who, blobs in files.items():
             for sw in (0, 8, 128):
-                call = ops._JpegDecodeCall(blobs, False, None, sw, dev)
+                call = ops._JpegDecodeCall(blobs, None, sw, dev, expand_grey=False)
                 ms_k = device_ms(call.launch)
                 torch.cuda.synchronize()
                 assert call.status.cpu().tolist() == [0] * B

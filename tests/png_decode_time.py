@@ -73,7 +73,7 @@ def main():
     sets.append(("512^2 labels pillow", [pillow_file(a) for a in labels]))
     for who, blobs in sets:
         for sw in WORDS:
-            call = ops._PngDecodeCall(blobs, False, False, None, sw, dev)
+            call = ops._PngDecodeCall(blobs, None, sw, dev, expand_grey=False, drop_alpha=False)
             ms_k = device_ms(call.launch)
             torch.cuda.synchronize()
             assert call.status.cpu().tolist() == [0] * B

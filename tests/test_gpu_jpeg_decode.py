@@ -87,6 +87,17 @@ def test_more_subsequences_than_threads():
     _check_batch([blob], "random256 sw 2", subseq_words=2)
 
 
+def test_segment_of_more_chunks_than_the_offsets_workgroup_has_threads():
+    """520^2 random pixels at q 100, 4:4:4: an entropy-coded segment above 1 MiB, more than 256 chunks of 4096 bytes -- the second
+    round of jd_offsets_kernel's loop over the workgroup scan (csrc/codec_common.h), whose base carries over from the first."""
+    from ppst_amd import ops
+    arr = np.random.default_rng(6).integers(0, 256, (520, 520, 3), dtype=np.uint8)
+    blob = D.pillow_file(arr, 100, "4:4:4")
+    rc, d = ops.jpeg_parse(blob)
+    assert rc == 0 and d.scan_len > 256 * 4096, d.scan_len
+    _check_batch([blob], "random520")
+
+
 def test_mirror_expand_grey_and_batch_independence():
     from ppst_amd import ops
     blobs = list(_pillow_files(90, "4:2:0", False))
