@@ -15,6 +15,9 @@ Tolerances (rel = max|a-b| / max|b|):
   activation path ....................... every launch form and edge of the elementwise, statistics, pooling, resize and NHWC
                                           blur kernels against float64 at the bars above, half storage bit-equal to the fp32
                                           launch rounded once: tests/test_gpu_act.py
+  forward conv staging .................. every kernel family at edge extents, the three paddings, in_ss and channel slices against
+                                          float64 at the fused-conv bars (2e-2 / 3e-3 single-pass bf16 / fp16, 5e-6 exact fp32):
+                                          tests/test_gpu_conv_geometry.py
 """
 import os
 import sys
