@@ -836,6 +836,48 @@ int64_t ppst_lpips_bwd_ws(int B, int H, int W, int which);
 int ppst_lpips_backward(const void* pack, const void* ws, const void* gout, int B, int H, int W, int which, void* ga, void* gb,
                         void* bws, void* stream);
 
+/* ------------------------------------------------ image-quality metrics ---- */
+/* SSIM (Wang et al. 2004, Gaussian form), MS-SSIM (Wang et al. 2003) and PSNR of two image batches a, b (B, C, H, W), C >= 1,
+ * data range L (csrc/ssim.hip).
+ *   window g: 11 taps exp(-(i - 5)^2 / (2 * 1.5^2)), normalised to sum 1 in float64, rounded once to fp32; separable, applied
+ *   "valid": the maps are (H - 10) x (W - 10).  Per channel mu_a = g*a, mu_b = g*b, s_a = g*(a^2) - mu_a^2, s_b likewise,
+ *   s_ab = g*(ab) - mu_a mu_b;  C1 = (0.01 L)^2, C2 = (0.03 L)^2;  cs = (2 s_ab + C2) / (s_a + s_b + C2),
+ *   ssim = (2 mu_a mu_b + C1) / (mu_a^2 + mu_b^2 + C1) * cs;  per (image, channel) the mean over the valid pixels, per image the
+ *   mean of that over the channels.
+ * The kernels work at L = 1 on inputs divided by data_range (SSIM is invariant under a common scale of a, b and L: for uint8
+ * input that keeps the g*(a^2) - mu^2 cancellation at the size it has for [-1, 1] images).  fp32 arithmetic; the per-block partial sums are added in a fixed order in float64: repeated
+ * calls are bit-identical, and no floating-point atomic is used.  The caller owns every buffer.
+ * Inputs: `u8` = 0: fp32; 1: uint8 (forward only).  *_strides: 4 ELEMENT strides (n, c, y, x) of the source tensor, any layout
+ * (a uint8 (B, H, W, C) image is the strides (H W C, 1, W C, C)).
+ *   ppst_ssim_ws        bytes of the forward workspace (block partial sums)
+ *   ppst_ssim_forward   ssim_bc[B * C], cs_bc[B * C] = the per-(image, channel) means of ssim and cs; out[B] (may be null) = the
+ *                       per-image SSIM
+ *   ppst_ssim_backward  grad (B, C, H, W) contiguous fp32 = d(sum_b gout[b] * out[b]) / d a (the first argument only; fp32
+ *                       inputs).  With A = d ssim / d mu_a, Bm = d ssim / d (g*a^2), Cm = d ssim / d (g*ab) on the valid grid:
+ *                       grad(q) = (g^T*A)(q) + 2 a(q) (g^T*Bm)(q) + b(q) (g^T*Cm)(q) (the full correlation of the zero-extended
+ *                       maps) times gout[b] / (C (H - 10)(W - 10)).  One launch: every block recomputes the moments that reach
+ *                       its tile; no map reaches memory, no workspace
+ *   ppst_pool2x2        out (B, C, H / 2, W / 2) contiguous fp32 = the 2 x 2 mean with stride 2 (an odd trailing row / column is
+ *                       dropped), in the input's own units: the step between two MS-SSIM scales
+ *   ppst_msssim_combine vals[5][B * C]: rows 0..3 the mean cs of scales 1..4, row 4 the mean ssim of scale 5;
+ *                       out[B] = mean_c prod_j max(vals[j], 0)^w_j, w = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+ *   ppst_sqerr_ws       bytes of the squared-error pass's workspace
+ *   ppst_sqerr          out[B][3] = (mean (a - b)^2, mean |a - b|, 10 log10(L^2 / mean (a - b)^2): +inf for equal images), in
+ *                       the inputs' own units
+ * B < 0, C < 1, H or W < 11 (ppst_pool2x2: < 2; ppst_sqerr, ppst_msssim_combine: < 1), data_range <= 0, u8 outside {0, 1} or
+ * B * C * H * W > 2^32 - 1: PPST_EINVAL (the *_ws functions return it as a negative size); B == 0 is a no-op (PPST_OK) before
+ * any pointer is looked at; null pointers PPST_ENULL. */
+int64_t ppst_ssim_ws(int B, int C, int H, int W);
+int ppst_ssim_forward(const void* a, const int64_t* a_strides, const void* b, const int64_t* b_strides, int u8, int B, int C, int H,
+                      int W, float data_range, void* out, void* ssim_bc, void* cs_bc, void* ws, void* stream);
+int ppst_ssim_backward(const void* a, const int64_t* a_strides, const void* b, const int64_t* b_strides, const void* gout, int B,
+                       int C, int H, int W, float data_range, void* grad, void* stream);
+int ppst_pool2x2(const void* x, const int64_t* strides, int u8, int B, int C, int H, int W, void* out, void* stream);
+int ppst_msssim_combine(const void* vals, int B, int C, void* out, void* stream);
+int64_t ppst_sqerr_ws(int B, int C, int H, int W);
+int ppst_sqerr(const void* a, const int64_t* a_strides, const void* b, const int64_t* b_strides, int u8, int B, int C, int H, int W,
+               float data_range, void* out, void* ws, void* stream);
+
 /* ------------------------------------------------------- post-process ---- */
 /* util.tensor2im quantisation (util/util.py:98-131): NCHW fp32 [-1,1] ->
  * HWC uint8, ((x+1)/2*255) clipped and truncated. */

@@ -194,6 +194,13 @@ _SIGS = {
     "ppst_lpips_tail": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "ppst_lpips_bwd_ws": (i64, [i32, i32, i32, i32]),
     "ppst_lpips_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "ppst_ssim_ws": (i64, [i32, i32, i32, i32]),
+    "ppst_ssim_forward": (i32, [vp, ctypes.POINTER(i64), vp, ctypes.POINTER(i64), i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
+    "ppst_ssim_backward": (i32, [vp, ctypes.POINTER(i64), vp, ctypes.POINTER(i64), vp, i32, i32, i32, i32, f32, vp, vp]),
+    "ppst_pool2x2": (i32, [vp, ctypes.POINTER(i64), i32, i32, i32, i32, i32, vp, vp]),
+    "ppst_msssim_combine": (i32, [vp, i32, i32, vp, vp]),
+    "ppst_sqerr_ws": (i64, [i32, i32, i32, i32]),
+    "ppst_sqerr": (i32, [vp, ctypes.POINTER(i64), vp, ctypes.POINTER(i64), i32, i32, i32, i32, i32, f32, vp, vp, vp]),
     "ppst_guided_filter_ws": (i64, [i32, i32, i32]),
     "ppst_guided_filter": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),
     "ppst_smooth_local_affine_ws": (i64, [i32, i32, i32]),

@@ -695,6 +695,26 @@ class LpipsFn(Function):
         return ga, gb, None
 
 
+class SsimFn(Function):
+    """SSIM of two fp32 (B,C,H,W) batches (any layout) -> (B,) (csrc/ssim.hip).  The gradient goes to the FIRST argument only (the
+    Cycwarp term's use: metric(image_rec, real)); asking for the second one's is an error, not a silent zero.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, a, b, data_range):
+        out, _, _ = ops.ssim_forward(a, b, data_range)
+        ctx.save_for_backward(a, b)
+        ctx.data_range = data_range
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if ctx.needs_input_grad[1]:
+            raise RuntimeError("SsimFn: the gradient to the second image is not implemented (detach it)")
+        a, b = ctx.saved_tensors
+        return ops.ssim_backward(a, b, _c(g), ctx.data_range), None, None
+
+
 class LsganFn(Function):
     """weight * mean((pred - target)^2) (models/networks/loss.py:11-18)."""
 

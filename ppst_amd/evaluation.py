@@ -217,6 +217,54 @@ def swapping_grid(model, contents, styles, rank=0, world=1, smooth=True, pair_ba
     return grid_pair_pass(model, contents, styles, table_c, table_s, rank, world, smooth, pair_batch)
 
 
+# ------------------------------------------------------------------------------------------------- numbers about images
+def evaluate_reconstruction(model, images, batch=8):
+    """How well the auto-encoder path returns held-out images: under ``no_grad``, ``rec = decode(*encode(x))`` (no target, so no
+    guided filter) in batches of ``batch``, compared with ``x`` by the HIP metrics (ppst_amd/metrics.py) at data range 2.
+    ``images``: (N, 3, H, W) in [-1, 1] on the GPU.  Returns {"l1", "psnr", "ssim"}, plus "ms_ssim" where min(H, W) >= 176, plus
+    "lpips" where ``model.perceptual_metric`` is an LPIPSAlex; every entry an (N,) fp32 tensor."""
+    from . import metrics
+    from .lpips import LPIPSAlex
+    N, _, H, W = images.shape
+    names = ["l1", "psnr", "ssim"]
+    if min(H, W) >= ops.MS_SSIM_MIN_SIDE:
+        names.append("ms_ssim")
+    lp = model.perceptual_metric if isinstance(getattr(model, "perceptual_metric", None), LPIPSAlex) else None
+    if lp is not None:
+        names.append("lpips")
+    out = {k: torch.empty((N,), device=images.device, dtype=torch.float32) for k in names}
+    with torch.no_grad():
+        for i in range(0, N, batch):
+            x = images[i:i + batch]
+            sp, gl = model(x, command="encode")
+            rec = model(sp, gl, target=None, command="decode")
+            err = ops.sqerr(rec, x, 2.0)
+            out["l1"][i:i + batch] = err[:, 1]
+            out["psnr"][i:i + batch] = err[:, 2]
+            out["ssim"][i:i + batch] = metrics.ssim(rec, x, 2.0)
+            if "ms_ssim" in out:
+                out["ms_ssim"][i:i + batch] = metrics.ms_ssim(rec, x, 2.0)
+            if lp is not None:
+                out["lpips"][i:i + batch] = lp(rec, x).flatten()
+    return out
+
+
+def content_preservation(contents, outputs):
+    """SSIM(content, swap) per pair, the content-preservation number of a swap.  ``outputs``: a tensor (K, C, H, W) paired with
+    ``contents`` (K, C, H, W) one to one -> (K,) tensor; or what ``swapping_grid`` returns, {(i, j): image (3, H, W)}, in which
+    case pair (i, j) is compared with ``contents[i]`` and the result is {(i, j): float}.  Images in [-1, 1] (data range 2)."""
+    from . import metrics
+    if isinstance(outputs, dict):
+        keys = sorted(outputs)
+        if not keys:
+            return {}
+        with torch.no_grad():
+            vals = metrics.ssim(torch.stack([outputs[k] for k in keys]), torch.stack([contents[i] for i, _ in keys]))
+        return dict(zip(keys, vals.cpu().tolist()))
+    with torch.no_grad():
+        return metrics.ssim(outputs, contents)
+
+
 # ------------------------------------------------------------------------------------------------- file front ends
 _IMG_EXT = (".jpg", ".jpeg", ".png", ".bmp", ".webp")
 

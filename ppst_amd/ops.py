@@ -2118,6 +2118,114 @@ def lpips_backward(pack, ws, gout, B, H, W, need_a, need_b):
     return ga, gb
 
 
+# ------------------------------------------------------ image-quality metrics ----
+MS_SSIM_SCALES = 5
+MS_SSIM_MIN_SIDE = 11 << (MS_SSIM_SCALES - 1)        # 176: the fifth scale must still hold the 11-tap window
+
+
+def _metric_img(t, name):
+    """-> (u8 flag, (B, C, H, W), the four element strides (n, c, y, x)): fp32 (B, C, H, W) in any layout, or uint8 (B, H, W, C)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("%s must be a CUDA (HIP) tensor (no CPU fallback)" % name)
+    if t.dim() != 4:
+        raise RuntimeError("%s must have four dimensions, got %s" % (name, tuple(t.shape)))
+    if t.dtype == torch.uint8:
+        B, H, W, C = t.shape
+        sn, sy, sx, sc = t.stride()
+        return 1, (B, C, H, W), (ctypes.c_int64 * 4)(sn, sc, sy, sx)
+    if t.dtype != torch.float32:
+        raise RuntimeError("%s must be float32 (B, C, H, W) or uint8 (B, H, W, C), got %s" % (name, t.dtype))
+    return 0, tuple(t.shape), (ctypes.c_int64 * 4)(*t.stride())
+
+
+def _metric_pair(a, b, what):
+    ua, shape, sa = _metric_img(a, what + " input")
+    ub, shape_b, sb = _metric_img(b, what + " input")
+    if ua != ub or shape != shape_b:
+        raise RuntimeError("%s inputs differ: %s %s and %s %s" % (what, a.dtype, tuple(a.shape), b.dtype, tuple(b.shape)))
+    return ua, shape, sa, sb
+
+
+def default_data_range(t, data_range=None):
+    """2.0 for float tensors (the model's [-1, 1]), 255 for uint8"""
+    if data_range is None:
+        return 255.0 if t.dtype == torch.uint8 else 2.0
+    if not float(data_range) > 0.0:
+        raise ValueError("data_range must be positive, got %r" % (data_range,))
+    return float(data_range)
+
+
+def ssim_forward(a, b, data_range=None):
+    """SSIM (11-tap Gaussian window, sigma 1.5, valid) of two fp32 (B, C, H, W) batches in any layout, or two uint8 (B, H, W, C)
+    ones -> (per-image SSIM (B,), per-(image, channel) mean ssim (B, C), mean cs (B, C)); csrc/ssim.hip."""
+    u8, (B, C, H, W), sa, sb = _metric_pair(a, b, "ssim")
+    L = default_data_range(a, data_range)
+    nbytes = lib.ppst_ssim_ws(B, C, H, W)
+    if nbytes < 0:
+        raise ValueError("ssim: unsupported shape %s (H and W of at least 11, at least one channel)" % ((B, C, H, W),))
+    ws = torch.empty(nbytes, device=a.device, dtype=torch.uint8)
+    out = torch.empty((B,), device=a.device, dtype=torch.float32)
+    s_bc = torch.empty((B, C), device=a.device, dtype=torch.float32)
+    cs_bc = torch.empty((B, C), device=a.device, dtype=torch.float32)
+    check(lib.ppst_ssim_forward(_p(a), sa, _p(b), sb, u8, B, C, H, W, L, _p(out), _p(s_bc), _p(cs_bc), _p(ws), _stream()), "ppst_ssim_forward")
+    return out, s_bc, cs_bc
+
+
+def ssim_backward(a, b, gout, data_range=None):
+    """d(sum_b gout[b] * ssim[b]) / d a, (B, C, H, W) contiguous fp32; fp32 inputs only"""
+    u8, (B, C, H, W), sa, sb = _metric_pair(a, b, "ssim")
+    if u8:
+        raise RuntimeError("ssim_backward: uint8 images are forward only")
+    _chk(gout, "ssim grad_output")
+    gout = gout.reshape(-1).contiguous()
+    if gout.numel() != B:
+        raise RuntimeError("ssim grad_output must have %d elements" % B)
+    L = default_data_range(a, data_range)
+    grad = torch.empty((B, C, H, W), device=a.device, dtype=torch.float32)
+    check(lib.ppst_ssim_backward(_p(a), sa, _p(b), sb, _p(gout), B, C, H, W, L, _p(grad), _stream()), "ppst_ssim_backward")
+    return grad
+
+
+def pool2x2(x):
+    """the 2 x 2 mean with stride 2 between two MS-SSIM scales (F.avg_pool2d(x, 2)): fp32 (B, C, H, W) in any layout or uint8
+    (B, H, W, C) -> contiguous fp32 (B, C, H // 2, W // 2), in the input's units"""
+    u8, (B, C, H, W), sx = _metric_img(x, "pool2x2 input")
+    out = torch.empty((B, C, H // 2, W // 2), device=x.device, dtype=torch.float32)
+    check(lib.ppst_pool2x2(_p(x), sx, u8, B, C, H, W, _p(out), _stream()), "ppst_pool2x2")
+    return out
+
+
+def ms_ssim_forward(a, b, data_range=None):
+    """five-scale MS-SSIM -> (B,); min(H, W) >= 176"""
+    u8, (B, C, H, W), _, _ = _metric_pair(a, b, "ms_ssim")
+    if min(H, W) < MS_SSIM_MIN_SIDE:
+        raise ValueError("ms_ssim needs images of at least %d x %d (five scales, the last one must still hold the 11-tap window), "
+                         "got %d x %d" % (MS_SSIM_MIN_SIDE, MS_SSIM_MIN_SIDE, H, W))
+    L = default_data_range(a, data_range)
+    vals = torch.empty((MS_SSIM_SCALES, B, C), device=a.device, dtype=torch.float32)
+    for j in range(MS_SSIM_SCALES):
+        _, s_bc, cs_bc = ssim_forward(a, b, L)
+        vals[j].copy_(s_bc if j == MS_SSIM_SCALES - 1 else cs_bc)
+        if j < MS_SSIM_SCALES - 1:
+            a, b = pool2x2(a), pool2x2(b)
+    out = torch.empty((B,), device=vals.device, dtype=torch.float32)
+    check(lib.ppst_msssim_combine(_p(vals), B, C, _p(out), _stream()), "ppst_msssim_combine")
+    return out
+
+
+def sqerr(a, b, data_range=None):
+    """-> (B, 3) fp32: per image mean (a - b)^2, mean |a - b|, PSNR = 10 log10(L^2 / mse) (+inf for equal images)"""
+    u8, (B, C, H, W), sa, sb = _metric_pair(a, b, "sqerr")
+    L = default_data_range(a, data_range)
+    nbytes = lib.ppst_sqerr_ws(B, C, H, W)
+    if nbytes < 0:
+        raise ValueError("sqerr: unsupported shape %s" % ((B, C, H, W),))
+    ws = torch.empty(nbytes, device=a.device, dtype=torch.uint8)
+    out = torch.empty((B, 3), device=a.device, dtype=torch.float32)
+    check(lib.ppst_sqerr(_p(a), sa, _p(b), sb, u8, B, C, H, W, L, _p(out), _p(ws), _stream()), "ppst_sqerr")
+    return out
+
+
 # --------------------------------------------------------------- profiling ----
 PROF_ON = {"value": False}
 

@@ -249,8 +249,14 @@ class PPSTModel(nn.Module):
         checkpoint the reference wrote).  Opt-in, and outside the module registry either way: ``state_dict()`` and ``save()``
         never see it."""
         if isinstance(fn, str):
+            if fn == "ssim":
+                # 1 - SSIM (ppst_amd/metrics.py): no weights, so no state dict -- the built-in metric for lambda_Cycwarp > 0
+                # where no reference-written checkpoint (and so no LPIPS weights) is at hand
+                from .metrics import SSIMLoss
+                self.__dict__["perceptual_metric"] = SSIMLoss()
+                return self
             if fn != "lpips":
-                raise ValueError("unknown perceptual metric %r (\"lpips\" or a callable)" % fn)
+                raise ValueError("unknown perceptual metric %r (\"lpips\", \"ssim\" or a callable)" % fn)
             if state_dict is None:
                 raise ValueError("set_perceptual_metric(\"lpips\") needs the state_dict that holds the metric's weights")
             from .lpips import LPIPSAlex

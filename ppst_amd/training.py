@@ -333,10 +333,42 @@ def load_optimizer_state(optimizer, path):
     return optimizer
 
 
-def train_loop(opt, model, dataset, optimizer, iter_counter=None, log=print, max_iterations=None):
+class HeldOutEvaluator:
+    """Reconstruction quality on a FIXED set of held-out images, for ``train_loop(evaluator=...)`` -- the place where the
+    reference's train.py runs its evaluators (train.py:52-56).  ``__call__(model, steps)`` returns the means of
+    ``evaluation.evaluate_reconstruction`` over the images as {name: float}, appends one line to ``log_path`` (None: the loop
+    resolves it to <checkpoints_dir>/<name>/eval_log.txt) and keeps (steps, result) in ``.history``.  It issues no collective:
+    only rank 0 calls it, the other ranks simply reach their next all-reduce first."""
+
+    def __init__(self, images, log_path=None, batch=8):
+        self.images, self.log_path, self.batch = images, log_path, batch
+        self.history = []
+
+    @staticmethod
+    def format(steps, result):
+        return "(eval iters: %d) %s" % (steps, " ".join("%s: %.5f" % kv for kv in sorted(result.items())))
+
+    def __call__(self, model, steps):
+        from . import evaluation
+        per_image = evaluation.evaluate_reconstruction(model, self.images, batch=self.batch)
+        result = {k: float(v.double().mean().item()) for k, v in per_image.items()}
+        self.history.append((int(steps), result))
+        if self.log_path is not None:
+            os.makedirs(os.path.dirname(os.path.abspath(self.log_path)), exist_ok=True)
+            with open(self.log_path, "a") as f:
+                f.write(self.format(steps, result) + "\n")
+        return result
+
+
+def train_loop(opt, model, dataset, optimizer, iter_counter=None, log=print, max_iterations=None, evaluator=None):
     """train.py:24-60: while not done: batch -> train_one_step (D / G alternation) -> EMA metrics -> rank 0 prints / saves
-    (model checkpoint in the reference's layout + optimiser state + iter.txt).  Returns the metric tracker."""
+    (model checkpoint in the reference's layout + optimiser state + iter.txt).  Returns the metric tracker.
+    ``evaluator``: a callable (model, steps) -> {name: number}, e.g. ``HeldOutEvaluator``; rank 0 calls it where
+    ``iter_counter.needs_evaluation()`` fires (train.py:52-56) and prints its line through ``log``.  None (the default): nothing
+    is evaluated and ``opt.evaluation_freq`` is never read."""
     iter_counter = iter_counter or IterationCounter(opt)
+    if evaluator is not None and getattr(evaluator, "log_path", "") is None:
+        evaluator.log_path = os.path.join(opt.checkpoints_dir, opt.name, "eval_log.txt")
     tracker = MetricTracker()
     rank0 = getattr(opt, "local_rank", 0) == 0
     n = 0
@@ -351,6 +383,9 @@ def train_loop(opt, model, dataset, optimizer, iter_counter=None, log=print, max
                 tm = iter_counter.time_measurements
                 log("(iters: %d) %s | %s" % (iter_counter.steps_so_far, " ".join("%s: %.3f" % kv for kv in tm.items()),
                                               " ".join("%s: %.3f" % kv for kv in sorted(tracker.current_metrics().items()))))
+            if evaluator is not None and iter_counter.needs_evaluation():
+                result = evaluator(model, iter_counter.steps_so_far)
+                log(HeldOutEvaluator.format(iter_counter.steps_so_far, result))
             if iter_counter.needs_saving():
                 save_all(opt, optimizer, iter_counter.steps_so_far)
         n += 1
