@@ -878,6 +878,46 @@ int64_t ppst_sqerr_ws(int B, int C, int H, int W);
 int ppst_sqerr(const void* a, const int64_t* a_strides, const void* b, const int64_t* b_strides, int u8, int B, int C, int H, int W,
                float data_range, void* out, void* ws, void* stream);
 
+/* ---------------------------------------------------- colour statistics ---- */
+/* Per-region colour statistics of uint8 RGB images and exact 1-Wasserstein distances between their histograms
+ * (csrc/colour_stats.hip): what the style-fidelity metrics of ppst_amd/metrics.py are made of.
+ *   img     (B, H, W, 3) uint8; ELEMENT strides img_sn (image), img_sy (row), img_sx (pixel: must be 3, the channels are
+ *           adjacent), so a crop view of a larger image is read in place
+ *   labels  (B, H, W) uint8 with strides lab_sn, lab_sy (pixels adjacent), or null: one region that holds every pixel.  A
+ *           pixel whose label is >= R belongs to no region (255 = "ignore")
+ *   dirs    HOST pointer, P rows of 3 int16 with sum_c |d_c| <= 4096 each (validated here, passed to the kernel by value)
+ * Per image b and region r < R:
+ *   hist[b][r][p][256] uint32  the exact histogram of t = (d_p . (r, g, b) + 255 * sum_{d_c < 0} |d_c|) >> 12, all integer;
+ *                       0 <= t <= 255 by construction, and the row (4096, 0, 0) gives the red channel itself
+ *   count[b][r] uint32  pixels of the region
+ *   lab_mean[b][r][3], lab_cov[b][r][6] float64: mean and POPULATION covariance (divided by count; entries LL, La, Lb, aa,
+ *                       ab, bb) of the pixels' CIELAB values.  Per pixel, in fp32: channel c -> lin(c) by a 256-entry table,
+ *                       lin(c) = c / 255 / 12.92 below 0.04045, else ((c / 255 + 0.055) / 1.055)^2.4, built in float64 and
+ *                       rounded once to fp32; (X / Xn, Y / Yn, Z / Zn) = M lin with M = the sRGB (D65) matrix rows
+ *                       (0.4124564 0.3575761 0.1804375; 0.2126729 0.7151522 0.0721750; 0.0193339 0.1191920 0.9503041) divided
+ *                       by the white point (0.95047, 1, 1.08883) in float64 and rounded once to fp32;
+ *                       f(t) = cbrt(t) above (6/29)^3, else t * 841 / 108 + 4 / 29; L = 116 f(Y) - 16, a = 500 (f(X) - f(Y)),
+ *                       b = 200 (f(Y) - f(Z)).  A wave of the kernel owns 1024 consecutive pixels: it sums (lab - pivot) and
+ *                       its products per region, the pivot being the Lab value of the region's mean colour there (rounded to
+ *                       integers: a flat region cancels exactly), and writes those sums to the workspace; a finishing launch
+ *                       combines them in a fixed order in float64.  No floating-point atomic: repeats are bit-identical and an
+ *                       image's numbers do not depend on its batch.  An empty region: count 0, moments 0
+ *   ppst_colour_stats_ws  bytes of the workspace (partial sums and the constant tables)
+ *   ppst_hist_w1    hist_a (Ba, R, P, 256), hist_b (Bb, R, P, 256) uint32; pairs (K, 2) int32 on the device.  num[k][r][p]
+ *                   int64 = sum_{v = 0..255} |cumA(v) nB - cumB(v) nA| of histograms i_k of a and j_k of b: W1 in grey
+ *                   levels is num / (nA nB), the caller's division.  Exact for n <= 2^22 (the sum stays below 2^52).  0 where a
+ *                   side is empty; -1 where an index is outside [0, Ba) x [0, Bb) (nothing is read)
+ * B < 0, H or W < 1, H * W > 2^22, R outside [1, 4], P outside [1, 16], img_sx != 3 (ppst_hist_w1: Ba, Bb or K < 0, R, P
+ * likewise): PPST_EINVAL (ppst_colour_stats_ws returns it as a negative size); B == 0 (K == 0) is a no-op (PPST_OK) before any
+ * pointer is looked at; null pointers (labels excepted) PPST_ENULL; then a row of
+ * dirs with sum |d_c| > 4096: PPST_EINVAL.  Nothing is launched in any of these cases. */
+int64_t ppst_colour_stats_ws(int B, int H, int W);
+int ppst_colour_stats(const void* img, int64_t img_sn, int64_t img_sy, int64_t img_sx, const void* labels, int64_t lab_sn,
+                      int64_t lab_sy, int B, int H, int W, int R, const int16_t* dirs, int P, void* hist, void* count, void* lab_mean,
+                      void* lab_cov, void* ws, void* stream);
+int ppst_hist_w1(const void* hist_a, int Ba, const void* hist_b, int Bb, const void* pairs, int K, int R, int P, void* num,
+                 void* stream);
+
 /* ------------------------------------------------------- post-process ---- */
 /* util.tensor2im quantisation (util/util.py:98-131): NCHW fp32 [-1,1] ->
  * HWC uint8, ((x+1)/2*255) clipped and truncated. */

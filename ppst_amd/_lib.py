@@ -201,6 +201,9 @@ _SIGS = {
     "ppst_msssim_combine": (i32, [vp, i32, i32, vp, vp]),
     "ppst_sqerr_ws": (i64, [i32, i32, i32, i32]),
     "ppst_sqerr": (i32, [vp, ctypes.POINTER(i64), vp, ctypes.POINTER(i64), i32, i32, i32, i32, i32, f32, vp, vp, vp]),
+    "ppst_colour_stats_ws": (i64, [i32, i32, i32]),
+    "ppst_colour_stats": (i32, [vp, i64, i64, i64, vp, i64, i64, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int16), i32, vp, vp, vp, vp, vp, vp]),
+    "ppst_hist_w1": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp]),
     "ppst_guided_filter_ws": (i64, [i32, i32, i32]),
     "ppst_guided_filter": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),
     "ppst_smooth_local_affine_ws": (i64, [i32, i32, i32]),

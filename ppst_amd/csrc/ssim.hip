@@ -56,11 +56,6 @@ template <int U8> __device__ __forceinline__ float ss_ld(const void* p, int64_t 
   if (U8) return (float)((const unsigned char*)p)[i];
   return ((const float*)p)[i];
 }
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ssim, cs and what the gradient needs of them at one pixel, from the means, variances and covariance of the range-1 inputs
 struct SsPoint { float s, cs, l, D1, D2; };

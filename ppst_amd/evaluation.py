@@ -265,6 +265,33 @@ def content_preservation(contents, outputs):
         return metrics.ssim(outputs, contents)
 
 
+def style_fidelity(styles, outputs, style_labels=None, content_labels=None, regions=3):
+    """Did the style arrive?  ``metrics.colour_distance`` between each style image and its swap, per region: the twin of
+    ``content_preservation`` (which a swap that returns the content unchanged passes perfectly).  ``outputs``: a tensor paired
+    with ``styles`` one to one -> {metric: float64 (K, R) tensor}; or what ``swapping_grid`` returns, {(i, j): image (3, H, W)},
+    in which case pair (i, j) is compared with ``styles[j]`` and the result is {(i, j): {metric: [per region]}}.  Labels are
+    integer (N, H, W) maps or one-hot (N, R, H, W) masks: ``style_labels`` those of ``styles``; ``content_labels`` those of the
+    outputs -- with the dict, of the CONTENTS (``content_labels[i]`` for pair (i, j): the output has the content's geometry).
+    Without both label sets the whole image is one region.  Images: fp32 in [-1, 1] or uint8 (N, H, W, 3).  The statistics of
+    every distinct style image and of every output are computed once, not once per pair."""
+    from . import metrics
+    if (style_labels is None) != (content_labels is None):
+        raise ValueError("style_fidelity needs the labels of both sides, or of neither")
+    R = regions if style_labels is not None else 1
+    with torch.no_grad():
+        if isinstance(outputs, dict):
+            keys = sorted(outputs)
+            if not keys:
+                return {}
+            used = sorted({j for _, j in keys})
+            st_s = metrics.colour_stats(styles[used], None if style_labels is None else style_labels[used], R)
+            st_o = metrics.colour_stats(torch.stack([outputs[k] for k in keys]),
+                                        None if content_labels is None else torch.stack([content_labels[i] for i, _ in keys]), R)
+            dist = metrics.colour_distance(st_s, st_o, [(used.index(j), n) for n, (_, j) in enumerate(keys)])
+            return {k: {name: v[n].tolist() for name, v in dist.items()} for n, k in enumerate(keys)}
+        return metrics.colour_distance(metrics.colour_stats(styles, style_labels, R), metrics.colour_stats(outputs, content_labels, R))
+
+
 # ------------------------------------------------------------------------------------------------- file front ends
 _IMG_EXT = (".jpg", ".jpeg", ".png", ".bmp", ".webp")
 

@@ -6,6 +6,10 @@ Images are fp32 (B, C, H, W) in any layout, or uint8 (B, H, W, C) as ``glue.tens
 them.  ``data_range`` defaults to 2.0 for float tensors (the model's [-1, 1]) and to 255 for uint8.  Every function returns one
 fp32 number per image, (B,).  ``ssim`` is differentiable in its FIRST argument (fp32 only); MS-SSIM and PSNR are forward only.
 There is no CPU fallback: CPU tensors raise RuntimeError.
+
+The second half of this file holds the style-fidelity metrics (csrc/colour_stats.hip; include/ppst_hip.h "colour statistics"):
+``colour_stats`` / ``colour_distance``, distances between the colour distributions of two images per label region, held to
+integer and float64 restatements (tests/colour_cases.py).
 """
 import torch
 
@@ -59,3 +63,116 @@ class SSIMLoss:
 
     def __call__(self, a, b):
         return (1.0 - ssim(a, b, self.data_range)).view(-1, 1, 1, 1)
+
+
+# ------------------------------------------------------------------------------------------------- style fidelity
+# Did the STYLE arrive?  Distances between the colour distributions of two images, taken per region of a label map (skin, hair,
+# background: CelebAMaskDataset's three classes).  They need no weights and are defined by formulas (include/ppst_hip.h "colour
+# statistics"; DESIGN.md "Style-fidelity metrics"), so the tests hold them to integer and float64 restatements.
+_DIRECTIONS = {}
+LUMA_601 = (1225, 2404, 467)            # BT.601 luma in 1/4096: 0.299, 0.587, 0.114
+
+
+def colour_directions(k=12, seed=0):
+    """The projection table of the colour histograms, int16 (4 + k, 3) on the CPU: rows 0-2 the channel axes (4096 on one
+    channel), row 3 BT.601 luma, rows 4.. ``k`` seeded random directions, theta normal in float64 (a CPU generator) and
+    d = trunc(theta / |theta|_1 * 4096): truncation toward zero keeps sum |d| <= 4096.  Cached per (k, seed); do not write to it."""
+    key = (int(k), int(seed))
+    if key not in _DIRECTIONS:
+        if not 0 <= key[0] <= ops.COLOUR_MAX_DIRS - 4:
+            raise ValueError("colour_directions: 0 <= k <= %d, got %r" % (ops.COLOUR_MAX_DIRS - 4, k))
+        theta = torch.randn(key[0], 3, generator=torch.Generator().manual_seed(key[1]), dtype=torch.float64)
+        rand = torch.trunc(theta / theta.abs().sum(1, keepdim=True) * 4096.0).to(torch.int16)
+        _DIRECTIONS[key] = torch.cat((torch.tensor(ops.COLOUR_AXES + (LUMA_601,), dtype=torch.int16), rand), 0)
+    return _DIRECTIONS[key]
+
+
+class ColourStats:
+    """What ``colour_stats`` returns: ``hist`` (B, R, P, 256) int32, ``count`` (B, R) int32, ``lab_mean`` (B, R, 3) and
+    ``lab_cov`` (B, R, 3, 3) float64 on the device, and the ``dirs`` (P, 3) int16 (CPU) the histograms were taken along."""
+
+    def __init__(self, hist, count, lab_mean, lab_cov, dirs):
+        self.hist, self.count, self.lab_mean, self.lab_cov, self.dirs = hist, count, lab_mean, lab_cov, dirs
+
+    def __len__(self):
+        return int(self.hist.shape[0])
+
+    def __getitem__(self, idx):
+        """the entries ``idx`` (a slice, a list or a tensor of indices) as a ColourStats"""
+        if isinstance(idx, (list, tuple)):
+            idx = torch.tensor(idx, dtype=torch.int64, device=self.hist.device)
+        return ColourStats(self.hist[idx], self.count[idx], self.lab_mean[idx], self.lab_cov[idx], self.dirs)
+
+
+_COV_INDEX = ((0, 1, 2), (1, 3, 4), (2, 4, 5))          # the six unique entries LL, La, Lb, aa, ab, bb as a 3 x 3
+
+
+def colour_stats(images, labels=None, regions=1, dirs=None):
+    """``images``: uint8 (B, H, W, 3), or fp32 (B, 3, H, W) in [-1, 1] (quantised by ``glue.tensor2im``).  ``labels``: None (one
+    region: the image), an integer (B, H, W) map (a value >= ``regions`` -- 255, say -- belongs to no region) or a one-hot
+    (B, R, H, W) mask (arg-max).  ``dirs``: ``colour_directions()`` by default.  -> ColourStats."""
+    from . import glue
+    _on_device(images)
+    if images.dtype != torch.uint8:
+        images = glue.tensor2im(images)
+    if labels is not None:
+        _on_device(labels)
+        if labels.dim() == 4:
+            labels = labels.argmax(dim=1)
+        labels = labels.to(torch.uint8)
+    dirs = colour_directions() if dirs is None else dirs
+    hist, count, mean, cov6 = ops.colour_stats(images, labels, regions, dirs)
+    return ColourStats(hist, count, mean, cov6[..., torch.tensor(_COV_INDEX, device=cov6.device)], torch.as_tensor(dirs).cpu())
+
+
+def _sqrtm_psd(m):
+    """the symmetric square root of a batch of 3 x 3 positive semi-definite matrices, float64 on the host"""
+    w, v = torch.linalg.eigh(m)
+    return (v * w.clamp(min=0.0).sqrt().unsqueeze(-2)) @ v.transpose(-1, -2)
+
+
+def gaussian_w2_squared(mean_a, cov_a, mean_b, cov_b):
+    """|mu_a - mu_b|^2 + tr(Sa + Sb - 2 (Sa^1/2 Sb Sa^1/2)^1/2) of Gaussians (..., 3), (..., 3, 3): float64 on the host (nine
+    numbers per entry: two 3 x 3 eigen-decompositions)"""
+    mean_a, cov_a, mean_b, cov_b = (t.detach().double().cpu() for t in (mean_a, cov_a, mean_b, cov_b))
+    ra = _sqrtm_psd(cov_a)
+    cross = _sqrtm_psd(ra @ cov_b @ ra)
+    tr = lambda m: m.diagonal(dim1=-2, dim2=-1).sum(-1)
+    return ((mean_a - mean_b) ** 2).sum(-1) + tr(cov_a) + tr(cov_b) - 2.0 * tr(cross)
+
+
+def w1_from_numerators(num, count_a, count_b):
+    """W1 in grey levels from ppst_hist_w1's numerators (K, R, P) and the two sides' counts (K, R): float64, NaN where a side is
+    empty"""
+    den = (count_a.double() * count_b.double()).unsqueeze(-1)
+    return torch.where(den > 0, num.double() / den.clamp(min=1.0), torch.full_like(num, float("nan"), dtype=torch.float64))
+
+
+def colour_distance(stats_a, stats_b, pairs=None):
+    """Distances between entry i of ``stats_a`` and entry j of ``stats_b`` for every (i, j) of ``pairs`` (None: n with n), per
+    region: {name: float64 (K, R) on the host}.  ``w1_rgb``: mean W1 of the three channel histograms, in levels; ``w1_luma``: W1
+    of BT.601 luma; ``swd``: mean over the random directions of W1 * 4096 / |d|_2, a sliced 1-Wasserstein distance in Euclidean
+    RGB levels (NaN without random rows); ``delta_e``: CIE76 between the regions' mean Lab; ``frechet``: the Gaussian
+    2-Wasserstein distance squared between the regions' Lab Gaussians.  NaN wherever the region is empty on either side."""
+    if not torch.equal(stats_a.dirs, stats_b.dirs):
+        raise ValueError("colour_distance: the two statistics were taken along different directions")
+    if pairs is None:
+        if len(stats_a) != len(stats_b):
+            raise ValueError("colour_distance without pairs needs as many entries on both sides (%d and %d)" % (len(stats_a), len(stats_b)))
+        pairs = [(n, n) for n in range(len(stats_a))]
+    pr = torch.as_tensor(pairs).reshape(-1, 2).to(torch.int64).cpu()
+    num = ops.hist_w1(stats_a.hist, stats_b.hist, pr)
+    ia, ib = pr[:, 0].to(num.device), pr[:, 1].to(num.device)
+    ca, cb = stats_a.count[ia], stats_b.count[ib]
+    w1 = w1_from_numerators(num, ca, cb).cpu()                                        # (K, R, P)
+    d = stats_a.dirs.double()
+    P = d.shape[0]
+    empty = ((ca == 0) | (cb == 0)).cpu()
+    nan = torch.full(empty.shape, float("nan"), dtype=torch.float64)
+    out = {"w1_rgb": w1[..., :3].mean(-1) if P >= 3 else nan.clone(),
+           "w1_luma": w1[..., 3] if P >= 4 else nan.clone(),
+           "swd": (w1[..., 4:] * (4096.0 / d[4:].norm(dim=1))).mean(-1) if P > 4 else nan.clone()}
+    ma, mb = stats_a.lab_mean[ia].cpu(), stats_b.lab_mean[ib].cpu()
+    out["delta_e"] = torch.where(empty, nan, (ma - mb).norm(dim=-1))
+    out["frechet"] = torch.where(empty, nan, gaussian_w2_squared(ma, stats_a.lab_cov[ia], mb, stats_b.lab_cov[ib]))
+    return out

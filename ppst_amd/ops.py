@@ -2226,6 +2226,80 @@ def sqerr(a, b, data_range=None):
     return out
 
 
+# --------------------------------------------------------- colour statistics ----
+COLOUR_MAX_REGIONS, COLOUR_MAX_DIRS, COLOUR_MAX_PIXELS = 4, 16, 1 << 22
+COLOUR_AXES = ((4096, 0, 0), (0, 4096, 0), (0, 0, 4096))
+
+
+def _u8_dev(t, name, dims):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("%s must be a CUDA (HIP) tensor (no CPU fallback)" % name)
+    if t.dtype != torch.uint8 or t.dim() != dims:
+        raise RuntimeError("%s must be uint8 with %d dimensions, got %s %s" % (name, dims, t.dtype, tuple(t.shape)))
+
+
+def colour_stats(u8, labels=None, regions=1, dirs=None):
+    """Per-image, per-region colour statistics (csrc/colour_stats.hip).  ``u8``: (B, H, W, 3) uint8 whose pixels are contiguous
+    (any batch and row stride: a crop view is read in place, anything else is copied); ``labels``: (B, H, W) uint8 or None (one
+    region); a label >= ``regions`` belongs to no region; ``dirs``: (P, 3) int16 rows with sum |d| <= 4096 (default: the three
+    channel axes).  -> (hist (B, R, P, 256) int32 -- the kernel's uint32 counts, all below 2^22 --, count (B, R) int32,
+    lab_mean (B, R, 3) float64, lab_cov (B, R, 6) float64: LL, La, Lb, aa, ab, bb)."""
+    _u8_dev(u8, "colour_stats images", 4)
+    B, H, W, C = u8.shape
+    if C != 3:
+        raise RuntimeError("colour_stats images must be (B, H, W, 3), got %s" % (tuple(u8.shape),))
+    if u8.stride(3) != 1 or (W > 1 and u8.stride(2) != 3):      # (the stride of a dimension of size 1 says nothing)
+        u8 = u8.contiguous()
+    if labels is not None:
+        _u8_dev(labels, "colour_stats labels", 3)
+        if tuple(labels.shape) != (B, H, W) or labels.device != u8.device:
+            raise RuntimeError("colour_stats labels must be (B, H, W) = %s on the images' device, got %s" % ((B, H, W), tuple(labels.shape)))
+        if W > 1 and labels.stride(2) != 1:
+            labels = labels.contiguous()
+    d = torch.tensor(COLOUR_AXES, dtype=torch.int16) if dirs is None else torch.as_tensor(dirs).detach().cpu()
+    if d.dtype != torch.int16 or d.dim() != 2 or d.shape[1] != 3:
+        raise ValueError("colour_stats directions must be int16 (P, 3), got %s %s" % (d.dtype, tuple(d.shape)))
+    d = d.contiguous()
+    R, P = int(regions), int(d.shape[0])
+    nbytes = lib.ppst_colour_stats_ws(B, H, W)
+    if nbytes < 0 or not 1 <= R <= COLOUR_MAX_REGIONS or not 1 <= P <= COLOUR_MAX_DIRS or int(d.to(torch.int32).abs().sum(1).max()) > 4096:
+        raise ValueError("colour_stats: H * W <= 2^22, 1 .. 4 regions, 1 .. 16 directions with sum |d| <= 4096 each; got %s, %d regions, "
+                         "directions %s" % ((B, H, W), R, tuple(d.shape)))
+    dev = u8.device
+    hist = torch.empty((B, R, P, 256), device=dev, dtype=torch.int32)
+    count = torch.empty((B, R), device=dev, dtype=torch.int32)
+    mean = torch.empty((B, R, 3), device=dev, dtype=torch.float64)
+    cov = torch.empty((B, R, 6), device=dev, dtype=torch.float64)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    dptr = ctypes.cast(ctypes.c_void_p(d.data_ptr()), ctypes.POINTER(ctypes.c_int16))
+    check(lib.ppst_colour_stats(_p(u8), u8.stride(0), u8.stride(1), 3, _p(labels), 0 if labels is None else labels.stride(0),
+                                0 if labels is None else labels.stride(1), B, H, W, R, dptr, P, _p(hist), _p(count), _p(mean), _p(cov),
+                                _p(ws), _stream()), "ppst_colour_stats")
+    return hist, count, mean, cov
+
+
+def hist_w1(hist_a, hist_b, pairs):
+    """The exact 1-Wasserstein numerators between histograms ``hist_a[i]`` and ``hist_b[j]`` for every (i, j) of ``pairs`` (a
+    list of index pairs or a (K, 2) integer tensor), per region and projection: (K, R, P) int64 =
+    sum_v |cumA(v) nB - cumB(v) nA|; W1 in grey levels is that over nA nB (0 where a side is empty)."""
+    for t, name in ((hist_a, "hist_a"), (hist_b, "hist_b")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("hist_w1 %s must be a CUDA (HIP) tensor (no CPU fallback)" % name)
+        if t.dtype != torch.int32 or t.dim() != 4 or t.shape[3] != 256:
+            raise RuntimeError("hist_w1 %s must be int32 (B, R, P, 256), got %s %s" % (name, t.dtype, tuple(t.shape)))
+    if hist_a.shape[1:] != hist_b.shape[1:] or hist_a.device != hist_b.device:
+        raise RuntimeError("hist_w1: the two histogram tensors differ: %s and %s" % (tuple(hist_a.shape), tuple(hist_b.shape)))
+    pr = torch.as_tensor(pairs).detach().cpu().reshape(-1, 2).to(torch.int64)
+    K, (Ba, R, P), Bb = int(pr.shape[0]), hist_a.shape[:3], hist_b.shape[0]
+    if K and (int(pr.min()) < 0 or int(pr[:, 0].max()) >= Ba or int(pr[:, 1].max()) >= Bb):
+        raise ValueError("hist_w1: a pair index is outside the histograms' batches (%d and %d)" % (Ba, Bb))
+    hist_a, hist_b = hist_a.contiguous(), hist_b.contiguous()
+    pr = pr.to(torch.int32).contiguous().to(hist_a.device)
+    num = torch.empty((K, R, P), device=hist_a.device, dtype=torch.int64)
+    check(lib.ppst_hist_w1(_p(hist_a), Ba, _p(hist_b), Bb, _p(pr), K, R, P, _p(num), _stream()), "ppst_hist_w1")
+    return num
+
+
 # --------------------------------------------------------------- profiling ----
 PROF_ON = {"value": False}
 

@@ -338,11 +338,43 @@ class HeldOutEvaluator:
     reference's train.py runs its evaluators (train.py:52-56).  ``__call__(model, steps)`` returns the means of
     ``evaluation.evaluate_reconstruction`` over the images as {name: float}, appends one line to ``log_path`` (None: the loop
     resolves it to <checkpoints_dir>/<name>/eval_log.txt) and keeps (steps, result) in ``.history``.  It issues no collective:
-    only rank 0 calls it, the other ranks simply reach their next all-reduce first."""
+    only rank 0 calls it, the other ranks simply reach their next all-reduce first.
+    ``swaps=True`` (at least two images): it also runs ``evaluation.simple_swap`` of image i with style (i + 1) mod N under
+    ``no_grad`` and adds ``swap_content_ssim`` (``evaluation.content_preservation``), ``swap_style_w1`` / ``swap_style_swd`` /
+    ``swap_style_delta_e`` (``evaluation.style_fidelity``'s w1_rgb, swd and delta_e: means over the pairs and the non-empty
+    regions) and ``identity_style_w1``, the same w1 between each content and its style BEFORE the swap: what no transfer at all
+    scores on these images.  ``labels`` (integer (N, H, W) maps or one-hot masks of the images, three regions): the distances are
+    taken per region, and the three style numbers are also reported per region as ``..._r0``, ``_r1``, ``_r2``."""
 
-    def __init__(self, images, log_path=None, batch=8):
-        self.images, self.log_path, self.batch = images, log_path, batch
+    STYLE_KEYS = (("swap_style_w1", "w1_rgb"), ("swap_style_swd", "swd"), ("swap_style_delta_e", "delta_e"))
+
+    def __init__(self, images, log_path=None, batch=8, swaps=False, labels=None):
+        if swaps and images.shape[0] < 2:
+            raise ValueError("HeldOutEvaluator(swaps=True) needs at least two images, got %d" % images.shape[0])
+        self.images, self.log_path, self.batch, self.swaps, self.labels = images, log_path, batch, swaps, labels
         self.history = []
+
+    def evaluate_swaps(self, model):
+        """the swap numbers of ``swaps=True`` as {name: float}"""
+        from . import evaluation
+        N = self.images.shape[0]
+        style_of = [(i + 1) % N for i in range(N)]
+        styles = self.images[style_of]
+        lab = self.labels
+        lab_s = None if lab is None else lab[style_of]
+        with torch.no_grad():
+            out = torch.cat([evaluation.simple_swap(model, self.images[i:i + self.batch], styles[i:i + self.batch])[1.0]
+                             for i in range(0, N, self.batch)], 0)
+        nanmean = lambda t: float(t[~t.isnan()].mean().item())
+        res = {"swap_content_ssim": float(evaluation.content_preservation(self.images, out).double().mean().item())}
+        fid = evaluation.style_fidelity(styles, out, lab_s, lab)
+        for key, name in self.STYLE_KEYS:
+            res[key] = nanmean(fid[name])
+            if lab is not None:
+                for r in range(fid[name].shape[1]):
+                    res["%s_r%d" % (key, r)] = nanmean(fid[name][:, r])
+        res["identity_style_w1"] = nanmean(evaluation.style_fidelity(styles, self.images, lab_s, lab)["w1_rgb"])
+        return res
 
     @staticmethod
     def format(steps, result):
@@ -352,6 +384,8 @@ class HeldOutEvaluator:
         from . import evaluation
         per_image = evaluation.evaluate_reconstruction(model, self.images, batch=self.batch)
         result = {k: float(v.double().mean().item()) for k, v in per_image.items()}
+        if self.swaps:
+            result.update(self.evaluate_swaps(model))
         self.history.append((int(steps), result))
         if self.log_path is not None:
             os.makedirs(os.path.dirname(os.path.abspath(self.log_path)), exist_ok=True)
