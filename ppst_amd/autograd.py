@@ -57,23 +57,17 @@ def prelu_bwd(g, y, prelu, scale_shift=None, res=None):
 
 
 # ---- parameter gradients go straight into the trainer's flat gradient buffer -------------------------------------------
-# FlatParams / DiscriminatorTrainer bind ``p.grad`` of every parameter to a view of ONE flat buffer per network and mark the
-# parameter (``_ppst_direct``).  A block's backward then lets the producing kernel add into that view (the ``accumulate`` flag
-# of the C ABI) and returns None for the parameter: no temporary, no zero fill and no AccumulateGrad ``add`` launch per
-# (parameter, use) -- 866 + 320 launches per train step before.  ``_ppst_on_grad`` tells the trainer that one more
+# train.FlatParams binds ``p.grad`` of every parameter to a view of ONE flat buffer per network and marks the parameters of the
+# generator-side networks (``_ppst_direct``).  A block's backward then lets the producing kernel add into that view (the
+# ``accumulate`` flag of the C ABI) and returns None for the parameter: no temporary, no zero fill and no AccumulateGrad ``add``
+# launch per (parameter, use) -- 866 + 320 launches per train step before.  ``_ppst_on_grad`` tells the trainer that one more
 # contribution has landed (it counts them to launch a network's gradient all-reduce from inside backward()).
 # Consequence: EVERY pass through a block's backward -- also torch.autograd.grad(..., inputs=[some activation]) -- adds that
 # block's parameter gradients to the flat buffer, exactly as a second .backward() would.  The reference's pattern (zero_grad ->
-# one backward -> step, ppst_optimizer.py:73-94) is what the trainers run; ``DIRECT["value"] = False`` restores returned
-# gradients (autograd accumulates them) for code that walks a graph more than once.
-DIRECT = {"value": True}
-# round 5: LinearFn's backward in two or three launches instead of seven (ReLU gates, relu(x) and the bias column sums folded into the
-# two gradient kernels); off while the gate tape records / replays (its gates go through gates.sign_gate)
-FUSE_LINEAR = {"value": True}
-
-
+# one backward -> step, ppst_optimizer.py:73-94) is what the trainers run; a parameter without the mark (one no FlatParams owns)
+# gets its gradient returned, and autograd accumulates it.
 def _direct(p):
-    if not DIRECT["value"] or p is None or not getattr(p, "_ppst_direct", False) or not p.requires_grad:
+    if p is None or not getattr(p, "_ppst_direct", False) or not p.requires_grad:
         return None
     return p.grad
 
@@ -496,7 +490,9 @@ class LinearFn(Function):
         w2 = w.reshape(w.shape[0], -1)
         dx = dw = db = None
         wp, bp = ctx.refs
-        fused = FUSE_LINEAR["value"] and gates.MODE["value"] is None and w2.shape[1] % 4 == 0
+        # two or three launches instead of seven (ReLU gates, relu(x) and the bias column sums folded into the two gradient kernels);
+        # not while the gate tape records / replays (its gates go through gates.sign_gate)
+        fused = gates.MODE["value"] is None and w2.shape[1] % 4 == 0
         if ctx.needs_input_grad[0]:
             if relu_in and fused:          # the ReLU's backward rides on the slice reduction of the input gradient
                 dx = ops.linear_dgrad_gate(g, w2, x, wscale)

@@ -426,7 +426,7 @@ class PPSTModel(nn.Module):
         with torch.no_grad():
             tr = self.__dict__.get("_trainer")
             if tr is not None:                     # parameters live in flat buffers: one broadcast per network
-                for f in list(tr.fp.values()) + ([tr.d_trainer] if tr.d_trainer is not None else []):
+                for f in tr.owners().values():
                     dist.broadcast(f.flat, 0)
             else:
                 for p in self.parameters():

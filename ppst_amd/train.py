@@ -23,8 +23,6 @@ from .networks.base_network import to_nhwc
 
 SQRT2 = math.sqrt(2.0)
 INV_SQRT2 = 1.0 / SQRT2
-# round 5: elementwise passes of D's backward folded into the convs beside them (tests/train_ab.py flips them for same-process A/B)
-TRAIN_FUSE = {"d_fanin": True, "d_skip_scale": True}
 
 
 def _lrelu_bwd(g, out, scale=1.0):
@@ -33,7 +31,105 @@ def _lrelu_bwd(g, out, scale=1.0):
     return ops.fused_bias_act_raw(g, None, gates.sign_gate(out, "lrelu"), 3, 1, 0.2, SQRT2 * scale)
 
 
-class DiscriminatorTrainer:
+class FlatParams:
+    """Parameters of one network as views into a flat buffer, with flat gradient and Adam state: the all-reduce and Adam are
+    single launches.  ``autograd``: the parameters are autograd leaves whose ``.grad`` views autograd accumulates into and the
+    backward kernels add into directly (G, E1, E2); False for D, whose parameters stay ``requires_grad=False`` and unmarked
+    because its gradients are written by the taped backward through ``g(name)``."""
+
+    def __init__(self, net, lr, beta1, beta2, autograd=True):
+        self.net, self.autograd = net, autograd
+        self.names = [n for n, _ in net.named_parameters()]
+        params = [p for _, p in net.named_parameters()]
+        self.params = params
+        self.sizes = [p.numel() for p in params]
+        flat = torch.cat([p.detach().reshape(-1) for p in params]).contiguous()
+        self.flat, self.grad = flat, torch.zeros_like(flat)
+        self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat)
+        self.offsets, off = {}, 0
+        for n_, p, sz in zip(self.names, params, self.sizes):
+            p.data = flat[off:off + sz].view_as(p)
+            if autograd:
+                p.requires_grad_(True)
+                p._ppst_direct = True                       # the backward kernels add straight into p.grad (autograd._direct)
+                p._ppst_on_grad = self._on_grad
+            p.grad = self.grad[off:off + sz].view_as(p)     # what the optimisers of the reference read: views of the flat gradient
+            self.offsets[n_] = (off, sz)
+            off += sz
+        self.on_event = None                                # set by the trainer: called once per gradient contribution
+        net._flat.clear(); net._cache.clear()
+        self.eps, self.step_count = 1e-8, 0
+        FlatParams.set_hyper(self, lr, beta1, beta2)        # (not the subclass's: DiscriminatorTrainer applies its own after this)
+
+    def set_hyper(self, lr, beta1, beta2):
+        self.lr, self.b1, self.b2 = lr, beta1, beta2
+
+    def _on_grad(self):
+        if self.on_event is not None:
+            self.on_event()
+
+    def g(self, name):
+        off, sz = self.offsets[name]
+        return self.grad[off:off + sz]
+
+    def scalar(self, name):
+        """Host value of a one-element parameter (the 14 NoiseInjection weights: the conv kernel takes them by value).  All
+        of them come over in ONE device-to-host copy per parameter update -- `float(param)` per StyledConv call was a
+        stream synchronisation each (50-80 per train step, each draining the launch queue)."""
+        key = (self.step_count, self.flat._version)
+        if getattr(self, "_scalar_key", None) != key:
+            names = [n_ for n_, sz in zip(self.names, self.sizes) if sz == 1]
+            if not hasattr(self, "_scalar_idx"):
+                self._scalar_idx = torch.tensor([self.offsets[n_][0] for n_ in names], dtype=torch.long, device=self.flat.device)
+            vals = self.flat.index_select(0, self._scalar_idx).cpu().tolist() if names else []
+            self._scalars, self._scalar_key = dict(zip(names, vals)), key
+        return self._scalars[name]
+
+    def derived(self, key, build):
+        """A value computed from the parameters under no_grad (the folded StyledConv bias), kept until the parameters change --
+        same lifetime as the host scalars: one parameter update.  (The three-bias sum alone was 2 aten launches per StyledConv
+        call, ~170 per train step.)"""
+        ver = (self.step_count, self.flat._version)
+        if getattr(self, "_derived_key", None) != ver:
+            self._derived, self._derived_key = {}, ver
+        hit = self._derived.get(key)
+        if hit is None:
+            hit = self._derived[key] = build()
+        return hit
+
+    def invalidate(self):
+        """Forget host-side copies of parameter values (the noise-weight scalars) and the network's packed weights: call after
+        ANY write to the parameters that did not go through adam() -- load_state_dict / PPSTModel.load copy into the parameter
+        views, which bumps their version counters, not the flat buffer's."""
+        self._scalar_key = self._derived_key = None
+        self.net._cache.clear()
+
+    def owns_parameters(self):
+        """True while the parameters still alias the flat buffer (``.to()`` / ``.cuda()`` or another owner's constructor break
+        the aliasing) and, for autograd leaves, their ``.grad`` the flat gradient."""
+        off = 0
+        for p, n in zip(self.params, self.sizes):
+            if p.data_ptr() != self.flat.data_ptr() + 4 * off:
+                return False
+            if self.autograd and (p.grad is None or p.grad.data_ptr() != self.grad.data_ptr() + 4 * off):
+                return False
+            off += n
+        return True
+
+    def zero_grad(self):
+        self.grad.zero_()
+
+    def adam(self):
+        if not self.owns_parameters():
+            raise RuntimeError("parameters / gradients no longer alias the flat buffers of this owner (a second one was built on "
+                               "the same network, or .to()/.cuda() moved it): the update would be lost")
+        self.step_count += 1
+        ops.adam_step_(self.flat, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, self.step_count)
+        self._scalar_key = self._derived_key = None      # host scalars / folded biases are stale; the conv plans are re-packed in place (two launches)
+        self.net.refresh_plans()
+
+
+class DiscriminatorTrainer(FlatParams):
     """Owns D's parameters (views into one flat buffer), their gradients and Adam state."""
 
     @classmethod
@@ -46,55 +142,25 @@ class DiscriminatorTrainer:
             tr = cls(D, **kw)
         return tr
 
-    def owns_parameters(self):
-        """True while D's parameters still alias this trainer's flat buffer (``.to()`` / ``.cuda()`` or another
-        trainer's constructor break the aliasing)."""
-        params = [p for _, p in self.D.named_parameters()]
-        off = 0
-        for p, n in zip(params, self.sizes):
-            if p.data_ptr() != self.flat.data_ptr() + 4 * off:
-                return False
-            off += n
-        return True
-
     def __init__(self, D, lr=1e-3, beta1=0.0, beta2=0.99, R1_once_every=16, world=1):
+        super().__init__(D, lr, beta1, beta2, autograd=False)
         self.D = D
         D.__dict__["_trainer"] = self
         self.size = D.size
-        c = R1_once_every / (1 + R1_once_every)
-        self.lr, self.b1, self.b2, self.eps = lr * c, beta1 ** c, beta2 ** c, 1e-8
-        self.step_count = 0
+        self.set_hyper(lr, beta1, beta2, R1_once_every)
         self.iter_counter = 0            # discriminator_iter_counter (ppst_optimizer.py:103)
-        self.R1_once_every = R1_once_every
         self.world = world
-        # flatten parameters so the all-reduce and Adam are single launches
-        self.names = [n for n, _ in D.named_parameters()]
-        params = [p for _, p in D.named_parameters()]
-        self.sizes = [p.numel() for p in params]
-        flat = torch.cat([p.detach().reshape(-1) for p in params]).contiguous()
-        self.flat = flat
-        off = 0
-        for p, n in zip(params, self.sizes):
-            p.data = flat[off:off + n].view_as(p)
-            off += n
-        D._flat.clear(); D._cache.clear()
-        self.grad = torch.zeros_like(flat)
-        self.m = torch.zeros_like(flat)
-        self.v = torch.zeros_like(flat)
-        self.offsets = {}
-        off = 0
-        for n_, p, sz in zip(self.names, params, self.sizes):
-            self.offsets[n_] = (off, sz)
-            p.grad = self.grad[off:off + sz].view_as(p)      # what optimizer_D reads in the reference: views of the flat gradient
-            off += sz
         # the facade's loss tensors hang on this leaf (ppst_model.compute_discriminator_losses / compute_R1_loss): D's
         # parameters themselves are not autograd inputs, their gradients are written by the taped backward below
-        self.anchor = torch.zeros(1, device=flat.device, requires_grad=True)
+        self.anchor = torch.zeros(1, device=self.flat.device, requires_grad=True)
         self._pending = None                                  # async gradient all-reduce whose Adam step is still owed
 
-    def g(self, name):
-        off, sz = self.offsets[name]
-        return self.grad[off:off + sz]
+    def set_hyper(self, lr, beta1, beta2, R1_once_every):
+        """Adam's settings under lazy regularisation (ppst_optimizer.py:46-49): the R1 pass on every ``R1_once_every``-th iteration
+        counts as a step of its own, so lr and the betas are corrected by c = R1 / (1 + R1)."""
+        c = R1_once_every / (1 + R1_once_every)
+        super().set_hyper(lr * c, beta1 ** c, beta2 ** c)
+        self.R1_once_every = R1_once_every
 
     # ---------------------------------------------------------------- forward
     def forward(self, img):
@@ -113,14 +179,19 @@ class DiscriminatorTrainer:
             B, S, _, cin = x.shape
             k = D.p(q + "conv2.Blur.kernel")
             sc1, scs = 1.0 / math.sqrt(cin * 9), 1.0 / math.sqrt(cin)
-            y1 = D.plan(q + "conv1.Conv.weight", scale=sc1)(x, bias=D.p(q + "conv1.Act.bias"), act=ops.ACT_LRELU)
+            conv1 = D.plan(q + "conv1.Conv.weight", scale=sc1)
+            y1 = conv1(x, bias=D.p(q + "conv1.Act.bias"), act=ops.ACT_LRELU)
             xs, _ = ops.blur_nhwc(x, D.p(q + "skip.Blur.kernel"), 1, 1, ops.PAD_ZERO, down=2)
-            skip = D.plan(q + "skip.Conv.weight", scale=scs)(xs)
+            skipc = D.plan(q + "skip.Conv.weight", scale=scs)
+            skip = skipc(xs)
             xb, bhw = ops.blur_nhwc(y1, k, 2, 2, ops.PAD_ZERO, s2d=True)
             ohw = ((bhw[0] - 3) // 2 + 1, (bhw[1] - 3) // 2 + 1)
-            a2 = D.plan(q + "conv2.Conv.weight", "s2d", sc1)(xb, bias=D.p(q + "conv2.Act.bias"), act=ops.ACT_LRELU, out_hw=ohw)
+            conv2 = D.plan(q + "conv2.Conv.weight", "s2d", sc1)
+            a2 = conv2(xb, bias=D.p(q + "conv2.Act.bias"), act=ops.ACT_LRELU, out_hw=ohw)
             out = ops.affine_act(a2, None, res=skip, out_scale=INV_SQRT2)
-            blocks.append(dict(q=q, x=x, y1=y1, xs=xs, xb=xb, bhw=bhw, a2=a2, cin=cin, S=S))
+            # (name, scales and forward plans: what backward / r1_backward need of this block besides its activations)
+            blocks.append(dict(q=q, name="convs.%s." % name, sc1=sc1, scs=scs, conv1=conv1, conv2=conv2, skipc=skipc,
+                               x=x, y1=y1, xs=xs, xb=xb, bhw=bhw, a2=a2, S=S))
             x = out
         tape["blocks"] = blocks
         cin = x.shape[3]
@@ -170,18 +241,15 @@ class DiscriminatorTrainer:
             # (bias gradients = column sums of the same gradient tensor: out of the weight-gradient kernel's staging pass)
             ops.conv_wgrad(D.plan(p + "final_conv.Conv.weight", scale=scf), tape["x_last"], gpre, out=G("final_conv.Conv.weight"), accumulate=True,
                            bias_out=G("final_conv.Act.bias"), bias_accumulate=True)
-        dx = self._dgrad(p + "final_conv.Conv.weight", "dgrad", scf)(gpre)
+        dx = D.plan(p + "final_conv.Conv.weight", "dgrad", scf)(gpre)
         if keep is not None:
             keep["dpred"], keep["gpre_h"], keep["gpre_fc"], keep["blocks"] = dpred, gpre_h, gpre, []
         for blk in reversed(tape["blocks"]):
-            q, cin = blk["q"], blk["cin"]
-            name = q[len(p):]
-            sc1, scs = 1.0 / math.sqrt(cin * 9), 1.0 / math.sqrt(cin)
-            cout = blk["a2"].shape[3]
+            q, name, sc1, scs = blk["q"], blk["name"], blk["sc1"], blk["scs"]
             # out = (a2 + skip)/sqrt2 ;  a2 = lrelu(conv2 + b)*sqrt2
             g2 = _lrelu_bwd(dx, blk["a2"], INV_SQRT2)
             if pg:
-                ops.conv_wgrad(D.plan(q + "conv2.Conv.weight", "s2d", sc1), blk["xb"], g2, out=G(name + "conv2.Conv.weight"), accumulate=True,
+                ops.conv_wgrad(blk["conv2"], blk["xb"], g2, out=G(name + "conv2.Conv.weight"), accumulate=True,
                                bias_out=G(name + "conv2.Act.bias"), bias_accumulate=True)
             d_xb = ops.dgrad_s2d(self.D, q + "conv2.Conv.weight", sc1, g2, blk["bhw"])
             # blur backward: upfirdn2d with the flipped (symmetric) taps and g_pad = (1, 1)
@@ -190,22 +258,21 @@ class DiscriminatorTrainer:
             d_y1, _ = ops.blur_nhwc(d_xb, kf, 1, 1, ops.PAD_ZERO)
             g1 = _lrelu_bwd(d_y1, blk["y1"])
             if pg:
-                ops.conv_wgrad(D.plan(q + "conv1.Conv.weight", scale=sc1), blk["x"], g1, out=G(name + "conv1.Conv.weight"), accumulate=True,
+                ops.conv_wgrad(blk["conv1"], blk["x"], g1, out=G(name + "conv1.Conv.weight"), accumulate=True,
                                bias_out=G(name + "conv1.Act.bias"), bias_accumulate=True)
             # skip branch: 1x1 conv on the blurred + decimated input, no bias / activation.  Its upstream gradient is dx / sqrt2: the
             # factor rides on the two kernels that consume it (round 5: no pass that materialises gs) -- unless the R1 sweep wants
             # gs itself (``keep``)
-            if keep is not None or not TRAIN_FUSE["d_skip_scale"]:
+            if keep is not None:
                 gs = ops.affine_act(dx, None, out_scale=INV_SQRT2)
                 if pg:
-                    ops.conv_wgrad(D.plan(q + "skip.Conv.weight", scale=scs), blk["xs"], gs, out=G(name + "skip.Conv.weight"), accumulate=True)
-                d_xs = self._dgrad(q + "skip.Conv.weight", "dgrad", scs)(gs)
+                    ops.conv_wgrad(blk["skipc"], blk["xs"], gs, out=G(name + "skip.Conv.weight"), accumulate=True)
+                d_xs = D.plan(q + "skip.Conv.weight", "dgrad", scs)(gs)
             else:
                 gs = None
                 if pg:
-                    ops.conv_wgrad(D.plan(q + "skip.Conv.weight", scale=scs), blk["xs"], dx, out=G(name + "skip.Conv.weight"), accumulate=True,
-                                   dy_scale=INV_SQRT2)
-                d_xs = self._dgrad(q + "skip.Conv.weight", "dgrad", scs)(dx, out_scale=INV_SQRT2)
+                    ops.conv_wgrad(blk["skipc"], blk["xs"], dx, out=G(name + "skip.Conv.weight"), accumulate=True, dy_scale=INV_SQRT2)
+                d_xs = D.plan(q + "skip.Conv.weight", "dgrad", scs)(dx, out_scale=INV_SQRT2)
             # blur(down=2, pad (1,1)) backward = zero-insert x2 then FIR with g_pad (upfirdn2d.py:116-121)
             S = blk["S"]
             ks = D.p(q + "skip.Blur.kernel")
@@ -216,11 +283,7 @@ class DiscriminatorTrainer:
             ksf = D.cached(("flip", q + "skip.Blur.kernel"), [ks], lambda: torch.flip(D.p(q + "skip.Blur.kernel"), [0, 1]).contiguous())
             d_xb2 = ops.upfirdn2d_raw(d_xs, ksf, 2, 2, 1, 1, gp0, gp1, gp0, gp1)
             # dx = d_xa + d_xb2: the fan-in add rides on the epilogue of conv1's input-gradient conv (its ``residual``)
-            if TRAIN_FUSE["d_fanin"]:
-                dx = self._dgrad(q + "conv1.Conv.weight", "dgrad", sc1)(g1, residual=d_xb2)
-            else:
-                d_xa = self._dgrad(q + "conv1.Conv.weight", "dgrad", sc1)(g1)
-                dx = ops.affine_act(d_xa, None, res=d_xb2)
+            dx = D.plan(q + "conv1.Conv.weight", "dgrad", sc1)(g1, residual=d_xb2)
             if keep is not None:
                 keep["blocks"].append(dict(g1=g1, g2=g2, gs=gs))
         # FromRGB: 1x1 conv (no bias) + fused lrelu
@@ -239,10 +302,6 @@ class DiscriminatorTrainer:
             keep["d_img"] = ops.conv1x1_small_cout(g0, wt, None, wscale=sc0)
 
     # -------------------------------------------------------------- R1 penalty
-    def r1_penalty(self, real, lambda_R1=10.0):
-        """compute_R1_loss value only: per-sample 0.5*lambda*||d sum(D(x))/dx||^2 (forward + backward to the image)."""
-        return self.r1_forward(real, lambda_R1)[0]
-
     def r1_forward(self, real, lambda_R1=10.0):
         """compute_R1_loss (ppst_model.py:140-159): per-sample penalty 0.5*lambda*||d sum(D(x)) / dx||^2 -> (pen (B,), state)."""
         pred, tape = self.forward(real)
@@ -277,19 +336,17 @@ class DiscriminatorTrainer:
         t = ops.conv1x1_small_cin(t, w, None, sc0, ops.ACT_NONE, out_dtype=tape["x0"].dtype)
         t = _lrelu_bwd(t, tape["x0"])
         for blk, kb in zip(tape["blocks"], keep["blocks"]):
-            q, cin = blk["q"], blk["cin"]
-            name = q[len(p):]
-            sc1, scs = 1.0 / math.sqrt(cin * 9), 1.0 / math.sqrt(cin)
-            ops.conv_wgrad(D.plan(q + "conv1.Conv.weight", scale=sc1), t, kb["g1"], out=G(name + "conv1.Conv.weight"), accumulate=True)
-            t1 = D.plan(q + "conv1.Conv.weight", scale=sc1)(t)
+            q, name, conv1, conv2, skipc = blk["q"], blk["name"], blk["conv1"], blk["conv2"], blk["skipc"]
+            ops.conv_wgrad(conv1, t, kb["g1"], out=G(name + "conv1.Conv.weight"), accumulate=True)
+            t1 = conv1(t)
             t1 = _lrelu_bwd(t1, blk["y1"])
             ts, _ = ops.blur_nhwc(t, D.p(q + "skip.Blur.kernel"), 1, 1, ops.PAD_ZERO, down=2)
-            ops.conv_wgrad(D.plan(q + "skip.Conv.weight", scale=scs), ts, kb["gs"], out=G(name + "skip.Conv.weight"), accumulate=True)
-            tskip = D.plan(q + "skip.Conv.weight", scale=scs)(ts)
+            ops.conv_wgrad(skipc, ts, kb["gs"], out=G(name + "skip.Conv.weight"), accumulate=True)
+            tskip = skipc(ts)
             tb, bhw = ops.blur_nhwc(t1, D.p(q + "conv2.Blur.kernel"), 2, 2, ops.PAD_ZERO, s2d=True)
-            ops.conv_wgrad(D.plan(q + "conv2.Conv.weight", "s2d", sc1), tb, kb["g2"], out=G(name + "conv2.Conv.weight"), accumulate=True)
+            ops.conv_wgrad(conv2, tb, kb["g2"], out=G(name + "conv2.Conv.weight"), accumulate=True)
             ohw = ((bhw[0] - 3) // 2 + 1, (bhw[1] - 3) // 2 + 1)
-            t2 = D.plan(q + "conv2.Conv.weight", "s2d", sc1)(tb, out_hw=ohw)
+            t2 = conv2(tb, out_hw=ohw)
             t2 = _lrelu_bwd(t2, blk["a2"])
             t = ops.affine_act(t2, None, res=tskip, out_scale=INV_SQRT2)
         scf = 1.0 / math.sqrt(t.shape[3] * 9)
@@ -312,9 +369,6 @@ class DiscriminatorTrainer:
         B = pen.shape[0]
         self.r1_backward(state, torch.full((B,), R1_once_every / B, device=pen.device))
         return {"D_R1": pen}
-
-    def _dgrad(self, wname, kind, scale):
-        return self.D.plan(wname, kind, scale)
 
     # ------------------------------------------------------------------- step
     def d_forward(self, real, rec, mix, lambda_GAN=1.0):
@@ -350,7 +404,7 @@ class DiscriminatorTrainer:
 
     def zero_grad(self):
         self.finish_pending()
-        self.grad.zero_()
+        super().zero_grad()
 
     def all_reduce(self):
         """DDP gradient averaging: one flat all-reduce (RCCL when the tensors are on the GPU)."""
@@ -359,12 +413,7 @@ class DiscriminatorTrainer:
 
     def adam(self):
         self.finish_pending()     # (an owed step is applied first, in order; no-op when called from finish_pending itself)
-        if not self.owns_parameters():
-            raise RuntimeError("D's parameters no longer alias this trainer's flat buffer (a second trainer was built "
-                               "on the same network, or .to()/.cuda() moved it): the update would be lost")
-        self.step_count += 1
-        ops.adam_step_(self.flat, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, self.step_count)
-        self.D.refresh_plans()  # packed weights are stale: re-packed in place, two launches
+        super().adam()
 
     # Data parallel, overlapped: the discriminator iteration ends with its 116-MB gradient all-reduce; nothing else in that
     # iteration needs D any more, and the generator iteration that follows does not touch D before its GAN terms.  So the

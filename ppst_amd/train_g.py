@@ -16,103 +16,14 @@ import torch
 from . import autograd as A
 from . import glue, ops
 from .networks.base_network import to_nhwc
-from .train import DiscriminatorTrainer, ddp_average_
+from .train import DiscriminatorTrainer, FlatParams
 
 SQRT2 = math.sqrt(2.0)
 INV_SQRT2 = 1.0 / SQRT2
-# tuning switches of the differentiable generator (tests/train_ab.py flips them for same-process A/B timing)
-# "gate": StyledConv's leaky-ReLU gate rides on the norm backward's apply pass (round 5; off while the gate tape records / replays)
-# "gmp_multi": the four poolings of a feature map (plain + three class masks) as one multi-head launch, forward and backward
-TRAIN_FUSE = {"merge": True, "res_up2": True, "gate": True, "gmp_multi": True}
 HEAD_CH = [(256, 256), (256, 256), (256, 384), (384, 512)]
 UP = [(16, 512, 512), (32, 512, 256), (64, 256, 128)]
 TAGS = ["9", "0", "1", "2"]
 CH = [32, 64, 128, 256]
-
-
-class FlatParams:
-    """Parameters of one network as views into a flat buffer, with flat gradient and Adam state."""
-
-    def __init__(self, net, lr, beta1, beta2):
-        self.net = net
-        self.names = [n for n, _ in net.named_parameters()]
-        params = [p for _, p in net.named_parameters()]
-        self.params = params
-        self.sizes = [p.numel() for p in params]
-        flat = torch.cat([p.detach().reshape(-1) for p in params]).contiguous()
-        self.flat, self.grad = flat, torch.zeros_like(flat)
-        self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat)
-        self.offsets, off = {}, 0
-        for n_, p, sz in zip(self.names, params, self.sizes):
-            p.data = flat[off:off + sz].view_as(p)
-            p.requires_grad_(True)
-            p.grad = self.grad[off:off + sz].view_as(p)     # autograd accumulates in place into the flat gradient
-            p._ppst_direct = True                           # ... and the backward kernels add straight into it (autograd._direct)
-            p._ppst_on_grad = self._on_grad
-            self.offsets[n_] = (off, sz)
-            off += sz
-        self.on_event = None                                # set by the trainer: called once per gradient contribution
-        net._flat.clear(); net._cache.clear()
-        self.lr, self.b1, self.b2, self.eps, self.step_count = lr, beta1, beta2, 1e-8, 0
-
-    def _on_grad(self):
-        if self.on_event is not None:
-            self.on_event()
-
-    def g(self, name):
-        off, sz = self.offsets[name]
-        return self.grad[off:off + sz]
-
-    def scalar(self, name):
-        """Host value of a one-element parameter (the 14 NoiseInjection weights: the conv kernel takes them by value).  All
-        of them come over in ONE device-to-host copy per parameter update -- `float(param)` per StyledConv call was a
-        stream synchronisation each (50-80 per train step, each draining the launch queue)."""
-        key = (self.step_count, self.flat._version)
-        if getattr(self, "_scalar_key", None) != key:
-            names = [n_ for n_, sz in zip(self.names, self.sizes) if sz == 1]
-            if not hasattr(self, "_scalar_idx"):
-                self._scalar_idx = torch.tensor([self.offsets[n_][0] for n_ in names], dtype=torch.long, device=self.flat.device)
-            vals = self.flat.index_select(0, self._scalar_idx).cpu().tolist() if names else []
-            self._scalars, self._scalar_key = dict(zip(names, vals)), key
-        return self._scalars[name]
-
-    def derived(self, key, build):
-        """A value computed from the parameters under no_grad (the folded StyledConv bias), kept until the parameters change --
-        same lifetime as the host scalars: one parameter update.  (The three-bias sum alone was 2 aten launches per StyledConv
-        call, ~170 per train step.)"""
-        ver = (self.step_count, self.flat._version)
-        if getattr(self, "_derived_key", None) != ver:
-            self._derived, self._derived_key = {}, ver
-        hit = self._derived.get(key)
-        if hit is None:
-            hit = self._derived[key] = build()
-        return hit
-
-    def invalidate(self):
-        """Forget host-side copies of parameter values (the noise-weight scalars) and the network's packed weights: call after
-        ANY write to the parameters that did not go through adam() -- load_state_dict / PPSTModel.load copy into the parameter
-        views, which bumps their version counters, not the flat buffer's."""
-        self._scalar_key = self._derived_key = None
-        self.net._cache.clear()
-
-    def owns_parameters(self):
-        off = 0
-        for p, n in zip(self.params, self.sizes):
-            if p.data_ptr() != self.flat.data_ptr() + 4 * off or p.grad is None or p.grad.data_ptr() != self.grad.data_ptr() + 4 * off:
-                return False
-            off += n
-        return True
-
-    def zero_grad(self):
-        self.grad.zero_()
-
-    def adam(self):
-        if not self.owns_parameters():
-            raise RuntimeError("parameters / gradients no longer alias the flat buffers of this trainer")
-        self.step_count += 1
-        ops.adam_step_(self.flat, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, self.step_count)
-        self._scalar_key = self._derived_key = None      # host scalars / folded biases are stale; the conv plans are re-packed in place (two launches)
-        self.net.refresh_plans()
 
 
 class GeneratorTrainer:
@@ -127,11 +38,13 @@ class GeneratorTrainer:
             tr = cls(model, **kw)
         return tr
 
+    def owners(self):
+        """Every flat-parameter owner of the model by network: G, E2, E1 and, where the model has one, D."""
+        return dict(self.fp, D=self.d_trainer) if self.d_trainer is not None else dict(self.fp)
+
     def invalidate(self):
-        for f in self.fp.values():
+        for f in self.owners().values():
             f.invalidate()
-        if self.d_trainer is not None:
-            self.d_trainer.D._cache.clear()
 
     def __init__(self, model, lr=1e-3, beta1=0.0, beta2=0.99, world=1):
         self.model = model
@@ -218,10 +131,9 @@ class GeneratorTrainer:
         levels = net._mask_planes(mask) if mask is not None else None
         sw = net._mask_planes(glue.swap(mask)) if (mask is not None and warped is not None) else None
         vectors, vectors_w, pm, pmw = [], [], [], []
-        multi = TRAIN_FUSE["gmp_multi"] and mask is not None      # (under the gate tape its backward walks the heads one by one)
         for lvl, (t, f) in enumerate(zip(TAGS, feats)):
             # every head of this level in one batch, in the reference's order of use
-            if multi and (f.shape[1] * f.shape[2]) % 16 == 0:
+            if mask is not None and (f.shape[1] * f.shape[2]) % 16 == 0:      # (under the gate tape its backward walks the heads one by one)
                 # the four poolings of a map (plain + three class masks) in ONE read of it, their gradients written as one sum
                 B = f.shape[0]
                 vf = A.GapGmpMultiFn.apply(f, levels[lvl])                       # rows [plain | mask 0 | mask 1 | mask 2] x B
@@ -290,12 +202,13 @@ class GeneratorTrainer:
             B, H, W = x.shape[0], x.shape[1] * (2 if upsample else 1), x.shape[2] * (2 if upsample else 1)
             nz = torch.randn(B, 1, H, W, device=x.device)          # NoiseInjection draws N(0,1) (stylegan2_layers.py:388-390)
         wn = p + "conv.weight"
-        fuse_gate = TRAIN_FUSE["gate"]     # (`a` has exactly one consumer: the norm below; under the gate tape the norm's backward runs the gate pass itself)
+        # the leaky-ReLU gate rides on the norm backward's apply pass: `a` has exactly one consumer, the norm below (under the gate tape
+        # the norm's backward runs the gate pass itself)
         a, st = A.conv(x, P(wn), net, wn, bias=bias, kind=kind, act=A.LRELU, noise_w=P(p + "noise.weight"), noise=nz.contiguous(), stats=True,
-                       noise_w_host=self.fp["G"].scalar(p + "noise.weight"), bias_params=bias_params, gate_downstream=fuse_gate)
+                       noise_w_host=self.fp["G"].scalar(p + "noise.weight"), bias_params=bias_params, gate_downstream=True)
         wl = P(p + "epi1.style_mod.lin.weight")
         style = A.linear(code, wl, P(p + "epi1.style_mod.lin.bias"), wscale=wl.shape[1] ** -0.5)
-        return A.instance_norm(a, st, style=style, res=res, out_scale=out_scale, res_up2=res_up2, post_gate=fuse_gate)     # res: the block's (skip + res) / sqrt2 merge
+        return A.instance_norm(a, st, style=style, res=res, out_scale=out_scale, res_up2=res_up2, post_gate=True)     # res: the block's (skip + res) / sqrt2 merge
 
     def generator(self, sp, global_codes, noise=None, extract_features=False):
         """sp NHWC (B,h,w,256), codes 4 x (B,2048) -> rgb NCHW (B,3,8h,8w) [, feat NHWC, feat1 NHWC]."""
@@ -325,10 +238,7 @@ class GeneratorTrainer:
             sw = q + "skip.Conv.weight"
             skip = x if ci == co else A.conv(x, P(sw), net, sw, scale=1.0 / math.sqrt(ci))
             r = self._styled_conv(x, q + "conv1.", g, "HeadResnetBlock%d.conv1" % i, noise)
-            if TRAIN_FUSE["merge"]:
-                x = self._styled_conv(r, q + "conv2.", g, "HeadResnetBlock%d.conv2" % i, noise, res=skip, out_scale=INV_SQRT2)
-            else:
-                x = A.AddScaleFn.apply(skip, self._styled_conv(r, q + "conv2.", g, "HeadResnetBlock%d.conv2" % i, noise), INV_SQRT2)
+            x = self._styled_conv(r, q + "conv2.", g, "HeadResnetBlock%d.conv2" % i, noise, res=skip, out_scale=INV_SQRT2)
         feas = []
         if extract_features:
             feas.append(self._feat_head(x.detach().float(), "layer32.", 3))
@@ -341,15 +251,8 @@ class GeneratorTrainer:
                 sw = q + "skip.Conv.weight"
                 skip = A.conv(x, P(sw), net, sw, bias=P(q + "skip.Act.bias"), scale=1.0 / math.sqrt(ci), act=A.LRELU)
             # (the x2 bilinear upsample of the skip is sampled on the fly by the merge pass, as in the inference path)
-            up2 = TRAIN_FUSE["res_up2"] and TRAIN_FUSE["merge"]
-            if not up2:
-                skip = A.BilinearFn.apply(skip, 2 * skip.shape[1], 2 * skip.shape[2])
             r = self._styled_conv(x, q + "conv1.", g, "UpsamplingResBlock%d.conv1" % key, noise, upsample=True)
-            if TRAIN_FUSE["merge"]:
-                x = self._styled_conv(r, q + "conv2.", g, "UpsamplingResBlock%d.conv2" % key, noise, res=skip, out_scale=INV_SQRT2,
-                                      res_up2=up2)
-            else:
-                x = A.AddScaleFn.apply(skip, self._styled_conv(r, q + "conv2.", g, "UpsamplingResBlock%d.conv2" % key, noise), INV_SQRT2)
+            x = self._styled_conv(r, q + "conv2.", g, "UpsamplingResBlock%d.conv2" % key, noise, res=skip, out_scale=INV_SQRT2, res_up2=True)
             if extract_features:
                 feas.append(self._feat_head(x.detach().float(), "layer%d." % (2 ** (j + 6)), 3 if j < 2 else 1))
         wr = P("ToRGB.conv.weight")
@@ -605,12 +508,6 @@ class GeneratorTrainer:
         for k in ("G", "E2", "E1"):          # optimizer_G.step(); optimizer_E2.step(); optimizer_E1.step()
             self.fp[k].adam()
 
-    def train_step(self, real, mask=None):
-        losses = self.losses_and_grads(real, mask)
-        self.all_reduce()
-        self.adam()
-        return losses
-
 
 class FlatAdam:
     """torch.optim.Adam of one network for the restated PPSTOptimizer: ``zero_grad()`` / ``step()`` on the network's flat
@@ -643,10 +540,11 @@ class PPSTOptimizer:
         self.train_mode_counter = 0
         self.discriminator_iter_counter = 0
         self.R1_once_every = R1_once_every
+        # (for_model may hand back a trainer that was built with other settings: they are applied again here)
         self.gen = GeneratorTrainer.for_model(model, lr=lr, beta1=beta1, beta2=beta2, world=world)
         self.gen.world = world
         for f in self.gen.fp.values():
-            f.lr, f.b1, f.b2 = lr, beta1, beta2
+            f.set_hyper(lr, beta1, beta2)
         self.dis = self.gen.d_trainer
         # the generator-side all-reduces are launched from inside backward(); the first step() of an iteration completes them
         self.optimizer_G = FlatAdam(self.gen.fp["G"], reduce=self.gen.all_reduce)
@@ -654,9 +552,8 @@ class PPSTOptimizer:
         self.optimizer_E1 = FlatAdam(self.gen.fp["E1"])
         self.optimizer_D = None
         if self.dis is not None:
-            c = R1_once_every / (1 + R1_once_every)
-            self.dis.lr, self.dis.b1, self.dis.b2 = lr * c, beta1 ** c, beta2 ** c
-            self.dis.R1_once_every, self.dis.world = R1_once_every, world
+            self.dis.set_hyper(lr, beta1, beta2, R1_once_every)
+            self.dis.world = world
             self.optimizer_D = self.dis
         # DistributedDataParallel's constructor broadcasts rank 0's parameters and buffers (models/__init__.py:88): without it the
         # per-process torch.randn NCE queues (and any unseeded parameter) differ between the ranks

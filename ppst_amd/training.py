@@ -310,11 +310,10 @@ def save_optimizer_state(optimizer, path):
     """Adam moments + step counts of all four networks and the D / G alternation state.  The reference saves the model
     only (base_model.py:33-41) and resumes with zero moments; this makes a resumed run continue the same trajectory."""
     st = {"train_mode_counter": optimizer.train_mode_counter}
-    for k, f in optimizer.gen.fp.items():
+    for k, f in optimizer.gen.owners().items():
         st[k] = {"m": f.m.detach().cpu(), "v": f.v.detach().cpu(), "step": f.step_count}
-    d = optimizer.dis
-    if d is not None:
-        st["D"] = {"m": d.m.detach().cpu(), "v": d.v.detach().cpu(), "step": d.step_count, "iter_counter": d.iter_counter}
+        if k == "D":
+            st[k]["iter_counter"] = f.iter_counter
     torch.save(st, path)
     return path
 
@@ -322,14 +321,14 @@ def save_optimizer_state(optimizer, path):
 def load_optimizer_state(optimizer, path):
     st = torch.load(path, map_location="cpu", weights_only=True)        # nested dicts of tensors / ints only: nothing is executed
     optimizer.train_mode_counter = int(st["train_mode_counter"])
-    for k, f in optimizer.gen.fp.items():
+    for k, f in optimizer.gen.owners().items():
+        if k == "D" and "D" not in st:          # (a file written for a model without a discriminator)
+            continue
         if f.m.numel() != st[k]["m"].numel():
             raise ValueError("optimizer state of %s has %d entries, the network has %d" % (k, st[k]["m"].numel(), f.m.numel()))
         f.m.copy_(st[k]["m"]); f.v.copy_(st[k]["v"]); f.step_count = int(st[k]["step"])
-    if optimizer.dis is not None and "D" in st:
-        d = optimizer.dis
-        d.m.copy_(st["D"]["m"]); d.v.copy_(st["D"]["v"])
-        d.step_count, d.iter_counter = int(st["D"]["step"]), int(st["D"]["iter_counter"])
+        if k == "D":
+            f.iter_counter = int(st[k]["iter_counter"])
     return optimizer
 
 

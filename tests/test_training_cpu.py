@@ -273,3 +273,93 @@ def test_scalar_cache_invalidated_by_weight_load():
     assert abs(f.scalar(name) - 0.25) < 1e-7
     m.load_weights(W.make_state_dict(2, with_D=False, with_nce=False, noise_weight=0.5))
     assert abs(f.scalar(name) - 0.5) < 1e-7 and f.owns_parameters()
+
+
+def test_flat_owners_who_accumulates_into_what():
+    """One FlatParams class owns all four networks.  G / E1 / E2 are autograd leaves whose ``.grad`` views the backward kernels add
+    into (marked ``_ppst_direct``); D's parameters stay ``requires_grad=False`` and unmarked -- the taped backward writes their
+    gradients through ``g(name)`` -- and its ownership check looks at the parameter storage only."""
+    from ppst_amd.ppst_model import Options, PPSTModel
+    from ppst_amd.train import DiscriminatorTrainer, FlatParams
+    from ppst_amd import train_g
+    assert train_g.FlatParams is FlatParams and issubclass(DiscriminatorTrainer, FlatParams)
+    m = PPSTModel(Options(), with_D=True, with_nce=True)
+    tr = m.trainer()
+    assert list(tr.owners()) == ["G", "E2", "E1", "D"] and tr.owners()["D"] is tr.d_trainer
+    for key, f in tr.owners().items():
+        assert type(f) is (DiscriminatorTrainer if key == "D" else FlatParams)
+        assert [n for n, _ in f.net.named_parameters()] == f.names and len(f.names) > 0
+        for n, p in f.net.named_parameters():
+            off, sz = f.offsets[n]
+            assert p.data_ptr() == f.flat.data_ptr() + 4 * off and p.numel() == sz, (key, n)
+            assert p.grad is not None and p.grad.data_ptr() == f.grad.data_ptr() + 4 * off and p.grad.shape == p.shape, (key, n)
+            assert f.g(n).data_ptr() == p.grad.data_ptr() and f.g(n).numel() == sz
+            if key == "D":
+                assert p.requires_grad is False and not hasattr(p, "_ppst_direct") and not hasattr(p, "_ppst_on_grad"), n
+            else:
+                assert p.requires_grad is True and p._ppst_direct is True and p._ppst_on_grad == f._on_grad, (key, n)
+        assert f.owns_parameters()
+    next(iter(m.D.parameters())).grad = None
+    assert tr.d_trainer.owns_parameters()
+    next(iter(m.G.parameters())).grad = None
+    assert not tr.fp["G"].owns_parameters() and tr.fp["E1"].owns_parameters() and tr.fp["E2"].owns_parameters()
+
+
+def test_optimizer_hyper_parameters_are_applied_and_reapplied():
+    """G / E1 / E2 take lr and the betas as given; D takes them corrected for lazy regularisation (ppst_optimizer.py:46-49,
+    c = R1 / (1 + R1)).  A second PPSTOptimizer on the same model finds the same trainers and applies its own values."""
+    from ppst_amd.ppst_model import Options, PPSTModel
+    from ppst_amd.train_g import PPSTOptimizer
+    m = PPSTModel(Options(), with_D=True, with_nce=True)
+    opt = PPSTOptimizer(m, lr=2e-3, beta1=0.5, beta2=0.9, R1_once_every=4)
+    c = 4 / 5
+    for f in opt.gen.fp.values():
+        assert (f.lr, f.b1, f.b2, f.eps) == (2e-3, 0.5, 0.9, 1e-8)
+    d = opt.dis
+    assert (d.lr, d.b1, d.b2, d.eps) == (2e-3 * c, 0.5 ** c, 0.9 ** c, 1e-8) and d.R1_once_every == 4 and d.world == 1
+    opt2 = PPSTOptimizer(m, lr=5e-4, beta1=0.0, beta2=0.99, R1_once_every=16, world=2)
+    assert opt2.gen is opt.gen and opt2.dis is d and all(opt2.gen.fp[k] is opt.gen.fp[k] for k in ("G", "E2", "E1"))
+    c = 16 / 17
+    for f in opt2.gen.fp.values():
+        assert (f.lr, f.b1, f.b2) == (5e-4, 0.0, 0.99)
+    assert (d.lr, d.b1, d.b2) == (5e-4 * c, 0.0 ** c, 0.99 ** c) and d.R1_once_every == 16 and d.world == 2 and opt2.gen.world == 2
+
+
+def test_optimizer_state_file_layout(tmp_path):
+    """The file keeps its layout: train_mode_counter, then m / v / step per network, D with its iter_counter on top."""
+    from ppst_amd.ppst_model import Options, PPSTModel
+    from ppst_amd.train_g import PPSTOptimizer
+    from ppst_amd.training import save_optimizer_state
+    opt = PPSTOptimizer(PPSTModel(Options(), with_D=True, with_nce=True))
+    opt.dis.iter_counter, opt.dis.step_count, opt.train_mode_counter = 5, 6, 1
+    st = torch.load(save_optimizer_state(opt, str(tmp_path / "o.pth")), map_location="cpu", weights_only=True)
+    assert list(st) == ["train_mode_counter", "G", "E2", "E1", "D"] and st["train_mode_counter"] == 1
+    for k, f in opt.gen.owners().items():
+        assert list(st[k]) == ["m", "v", "step"] + (["iter_counter"] if k == "D" else []), k
+        assert st[k]["m"].shape == f.m.shape and st[k]["v"].shape == f.v.shape and st[k]["m"].dtype == torch.float32
+        assert type(st[k]["step"]) is int
+    assert st["D"]["step"] == 6 and st["D"]["iter_counter"] == 5 and type(st["D"]["iter_counter"]) is int
+
+
+def test_removed_train_switches_and_leftovers_are_gone_everywhere():
+    """The fusion switches of the train step (every one was on, nothing set one off), the tool that flipped them and the three
+    methods without a caller left the package together (92afa9f is the last commit with them): no attribute, and no file of the
+    package or the tests still names one."""
+    import re
+    from ppst_amd import autograd, train, train_g
+    for mod, name in ((train, "TRAIN_FUSE"), (train_g, "TRAIN_FUSE"), (autograd, "FUSE_LINEAR"), (autograd, "DIRECT")):
+        assert not hasattr(mod, name), (mod.__name__, name)
+    assert not hasattr(train.DiscriminatorTrainer, "r1_penalty") and not hasattr(train.DiscriminatorTrainer, "_dgrad")
+    assert not hasattr(train_g.GeneratorTrainer, "train_step") and hasattr(train.DiscriminatorTrainer, "train_step")
+    assert not os.path.exists(os.path.join(ROOT, "tests", "train_ab.py"))
+    gone = re.compile(r"\bTRAIN_FUSE\b|\bFUSE_LINEAR\b|\.DIRECT\b|\bDIRECT\s*(\[|=[^=])|\br1_penalty\b|\._dgrad\b|\bdef _dgrad\b|\btrain_ab\b")
+    seen = 0
+    for top in ("ppst_amd", "tests"):
+        for d, _, files in os.walk(os.path.join(ROOT, top)):
+            for f in files:
+                path = os.path.join(d, f)
+                if f.endswith(".py") and not os.path.samefile(path, __file__):
+                    seen += 1
+                    hit = gone.search(open(path, encoding="utf-8", errors="replace").read())
+                    assert hit is None, (path, hit.group(0))
+    assert seen > 50

@@ -1,10 +1,11 @@
 """Tuning aid (GPU): how long the host takes to ISSUE one train step (D + G iteration, batch 2) against how long the GPU takes
-to run it.  The loss read-outs of train_one_step synchronise once per iteration; the issue time is measured with those
-replaced by no-ops (PPST_HOST_TIME only inside this script).  python tests/train_host_time.py"""
+to run it.  The loss read-outs of train_one_step synchronise once per iteration; the issue time is measured on the two
+iterations called directly, without the read-outs (what is left inside is the one device-to-host copy of the NoiseInjection
+scalars per generator iteration).  python tests/train_host_time.py"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from ppst_amd import weights as W
+from ppst_amd import ops, weights as W
 from ppst_amd.ppst_model import Options, create_model
 from ppst_amd.train_g import PPSTOptimizer
 
@@ -27,6 +28,13 @@ for _ in range(N):
     opt.train_one_step(data, 0); opt.train_one_step(data, 0)
 torch.cuda.synchronize()
 wall = (time.perf_counter() - t0) / N * 1e3
+t0 = time.perf_counter()
+for _ in range(N):
+    with ops.batch_aware():
+        opt.train_discriminator_one_step(real, mask); opt.train_generator_one_step(real, mask)
+issue = (time.perf_counter() - t0) / N * 1e3
+torch.cuda.synchronize()
+print("wall per step %.2f ms, host issue per step %.2f ms" % (wall, issue), flush=True)
 # host-only: profile with cProfile where the time goes
 import cProfile, pstats, io
 pr = cProfile.Profile()
