@@ -935,6 +935,19 @@ int ppst_guided_filter(const void* guide_u8, const void* src_u8, void* out, void
  * 0 = the library's default for that radius, 32 / 64 / 128 = forced.  Results do not depend on it beyond the rounding of the sliding
  * fp32 sums of the second launch. */
 int ppst_guided_filter_tune(int vs1, int vs2);
+/* native-size output of the filter (He and Sun, "Fast Guided Filter", arXiv:1505.00996): the mean coefficient planes of the filter
+ * at (h, w), then their bilinear upsample applied to a guide of (H, W) >= (h, w).
+ * ppst_guided_filter_coeffs: guide, src uint8 [B][h][w][3] -> coeffs fp32 [B][12][h][w], plane 4c + k: k = 0..2 the mean of a_ck,
+ * k = 3 the mean of b_c (q_c = sum_k a_ck I_k + b_c).  Five launches through fp32 planes at every radius it accepts; work:
+ * >= ppst_guided_filter_ws(B, h, w) bytes.  PPST_EINVAL, with nothing written: r <= 0, r > 64 (90 included), r >= h, r >= w, w > 2048.
+ * ppst_guided_filter_apply: coeffs [B][12][h][w], guide uint8 [B][H][W][3] -> out_u8 [B][H][W][3] and / or out_f32 NCHW
+ * (q/255 - 0.5)*2 of the stored byte (either may be NULL, not both).  Bilinear taps with half-pixel centres and edge replication
+ * (F.interpolate(mode="bilinear", align_corners=False)) at positions computed in integers, horizontally then vertically; any ratio
+ * H/h >= 1 and W/w >= 1 per axis.  PPST_EINVAL, with nothing written: H < h, W < w, H W > 2^28. */
+int ppst_guided_filter_coeffs(const void* guide_u8, const void* src_u8, void* coeffs, int B, int h, int w, int r, float eps,
+                              void* work, void* stream);
+int ppst_guided_filter_apply(const void* coeffs, int h, int w, const void* guide_u8, void* out_u8, void* out_f32,
+                             int B, int H, int W, void* stream);
 
 /* local-affine photo smoothing (smooth_filter.py:332-378 smooth_local_affine and its three NVRTC kernels :149-321):
  * output (stylised), input (content = guide), result: planar fp32 [B][3][H][W]; model_ws: >= ppst_smooth_local_affine_ws()

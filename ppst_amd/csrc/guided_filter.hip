@@ -474,5 +474,265 @@ extern "C" int ppst_guided_filter(const void* guide_u8, const void* src_u8, void
   return PPST_LAUNCH_CHECK();
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// Native-size output (He and Sun, "Fast Guided Filter", arXiv:1505.00996): the mean planes (mean a, mean b) of a filter solved at
+// (h, w) are smooth by construction, so they are upsampled bilinearly and applied to the guide at ITS size (H, W) >= (h, w).
+//   ppst_guided_filter_coeffs: the 12 mean planes [B][12][h][w] fp32 (plane 4c + k: k = 0..2 mean a_ck, k = 3 mean b_c), by the
+//     fp32-plane route at EVERY accepted radius (30 and 60 included: the fused launches never store the means): gf_h<true>, V pass,
+//     solve, gf_h<false>, V pass into the caller's buffer -- the V pass and the solve in the forms at the entry point (gfc_*).
+//   ppst_guided_filter_apply -> gf_apply_up_kernel: q_c = A_c0 I0 + A_c1 I1 + A_c2 I2 + B_c per native pixel, (A, B) the bilinear
+//     interpolation of the mean planes (half-pixel centres, edge replication: F.interpolate(mode="bilinear", align_corners=False)),
+//     horizontally first, then vertically; rounded and stored like gf_store.  The 12 upsampled planes never exist in memory.
+// Tap positions are INTEGERS: along an axis of n coefficient and N output samples, output Y has num = (2Y + 1) n - N,
+// i0 = floor(num / 2N) (>= -1 since num > -2N), f = (num - 2N i0) / 2N, taps clamp(i0, 0, n - 1) and clamp(i0 + 1, 0, n - 1): no
+// float position is ever floored, so a tap index cannot differ from a float64 judge's at any size.
+// Geometry: a block of 256 threads owns a tile of GA_TW = 64 output columns x GA_TH = 16 rows, looping over the images of the
+// batch that its blockIdx.y owns.  n <= N makes i0 grow by 0 or 1 per output sample, so the tile's taps lie in at most
+// (GA_TH + 1) x (GA_TW + 1) coefficient samples -- the footprint, largest at scale 1: 17 x 65 x 12 floats = 53,040 B of LDS
+// (60,080 B with the row buffers and tables: two blocks per CU).  At scale >= 2 on both axes it is at most 10 x 34 samples, and a
+// second instance of the same body declares only that (23,360 B: five blocks per CU by registers, 92 VGPRs; measured 62 -> 45 us
+// at 512^2 -> 1024^2 and 194 -> 102 us at -> 2048^2, B = 4).  Both instances compute the same bytes.  The footprint is staged
+// PIXEL-MAJOR ([row][column][12 planes], edge replication resolved while staging: the compute phase never clamps) so that one
+// thread's 2 taps x 12 planes are 24 consecutive floats = six 16-byte LDS reads (lane stride 12 dwords at scale 1: 16 lanes cover
+// the 64 banks once; at scale >= 2 neighbours share a column and the read broadcasts).
+// Thread = output column; a wave walks 4 consecutive rows and keeps the horizontally interpolated coefficient rows i0 and i0 + 1
+// in registers: a row is read from LDS only when i0 advances (wave-uniform).  LDS words read per output pixel: 24 (1 + rows
+// advanced) / 4 -- 30 at scale 1, 18 to 24 at scale 2, 12 at scale >= 4, against 48 of the form that reads four taps per pixel.
+// Guide and output bytes move as ALIGNED DWORDS over each tile row's byte span through two small LDS row buffers (the bytes of a
+// span that do not fill a dword -- at most 3 at either end -- move as bytes), whatever the alignment of the tensors.
+// Every staged index is clamped to the plane and every local index to the footprint in the kernel itself.
+#define GA_TW 64
+#define GA_TH 16
+#define GA_FC (GA_TW + 1)       // footprint of a tile at any scale >= 1 ...
+#define GA_FR (GA_TH + 1)
+#define GA_FC2 (GA_TW / 2 + 2)  // ... and at scale >= 2 on both axes: i0 advances at most every other sample (10 x 34 at exactly 2)
+#define GA_FR2 (GA_TH / 2 + 2)
+#define GA_NT 256
+#define GA_RDW ((GA_TW * 3 + 3 + 3) / 4 + 1)   // dwords of one staged byte row: 192 B + up to 3 B of misalignment, rounded up: 50
+#define GA_MAXPIX ((int64_t)1 << 28)
+
+// tap of output sample Y along an axis of n coefficient and N >= n output samples
+__device__ __forceinline__ void ga_tap(int Y, int n, int N, int& i0, float& f) {
+  const int64_t num = (2 * (int64_t)Y + 1) * n - N, den = 2 * (int64_t)N;
+  const int64_t q = num < 0 ? -1 : num / den;                          // floor: num > -den
+  i0 = (int)q;
+  f = (float)(num - q * den) / (float)den;
+}
+
+// the horizontally interpolated 12 coefficients of footprint row lr at the column pair (lc, lc + 1)
+template <int FC>
+__device__ __forceinline__ void ga_hrow(const float* fp, int lr, int lc, float fx, float (&v)[12]) {
+  const float4* p = (const float4*)(fp + (lr * FC + lc) * 12);
+  float4 q[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) q[i] = p[i];
+  const float* a = (const float*)q;
+  const float gx = 1.f - fx;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) v[i] = gx * a[i] + fx * a[12 + i];
+}
+
+// FR x FC: the footprint the instance has LDS for (its local indices are clamped to it: a launch with the wrong instance would
+// give wrong values, never an access outside)
+template <int FR, int FC>
+__global__ __launch_bounds__(GA_NT) void gf_apply_up_kernel(const float* __restrict__ coef, int h, int w,
+                                                            const unsigned char* __restrict__ guide, unsigned char* __restrict__ out_u8,
+                                                            float* __restrict__ out, int B, int H, int W, int tiles_x) {
+  __shared__ __attribute__((aligned(16))) float fp[FR * FC * 12];
+  __shared__ unsigned gsh[GA_TH][GA_RDW], osh[GA_TH][GA_RDW];
+  __shared__ int rowi[GA_TH], coli[GA_TW];
+  __shared__ float rowf[GA_TH], colf[GA_TW];
+  const int t = threadIdx.x;
+  const int X0 = (int)(blockIdx.x % tiles_x) * GA_TW, Y0 = (int)(blockIdx.x / tiles_x) * GA_TH;
+  const int ncols = min(GA_TW, W - X0), nrows = min(GA_TH, H - Y0);
+  // the tile's tap tables, once (absolute i0; samples past the image repeat its last one and are never stored)
+  if (t < GA_TH) ga_tap(min(Y0 + t, H - 1), h, H, rowi[t], rowf[t]);
+  else if (t >= 64 && t < 64 + GA_TW) ga_tap(min(X0 + t - 64, W - 1), w, W, coli[t - 64], colf[t - 64]);
+  __syncthreads();
+  const int ilo = rowi[0], jlo = coli[0];
+  const int fr = min(rowi[nrows - 1] - ilo + 2, FR), fc = min(coli[ncols - 1] - jlo + 2, FC);
+  const int64_t p = (int64_t)h * w, P = (int64_t)H * W;
+  const int lane = t & 63, wv = t >> 6;
+  const int xc = min(lane, ncols - 1);
+  const int lc = min(coli[xc] - jlo, FC - 2);
+  const float fx = colf[xc];
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    // ---- stage the footprint: thread = (column, row mod 4), 12 plane reads in flight; column 64 (scale 1 only) by a second loop
+    const float* cb = coef + (int64_t)b * 12 * p;
+    if (lane < fc) {
+      const int gx = min(max(jlo + lane, 0), w - 1);
+      for (int lr = wv; lr < fr; lr += GA_NT / 64) {
+        const float* s = cb + (int64_t)min(max(ilo + lr, 0), h - 1) * w + gx;
+        float v[12];
+#pragma unroll
+        for (int pl = 0; pl < 12; ++pl) v[pl] = s[pl * p];
+        float4* d = (float4*)(fp + (lr * FC + lane) * 12);
+        d[0] = make_float4(v[0], v[1], v[2], v[3]);
+        d[1] = make_float4(v[4], v[5], v[6], v[7]);
+        d[2] = make_float4(v[8], v[9], v[10], v[11]);
+      }
+    }
+    if (FC > 64 && fc > 64) {
+      const int gx = min(max(jlo + 64, 0), w - 1);
+      for (int i = t; i < fr * 12; i += GA_NT) {
+        const int lr = i / 12, pl = i - lr * 12;
+        fp[(lr * FC + 64) * 12 + pl] = cb[pl * p + (int64_t)min(max(ilo + lr, 0), h - 1) * w + gx];
+      }
+    }
+    // ---- stage the guide bytes of the tile's rows: dword k of row y is the ALIGNED dword k of the row span's address range
+    for (int i = t; i < nrows * 64; i += GA_NT) {
+      const int y = i >> 6, k = i & 63;
+      const unsigned char* a = guide + (((int64_t)b * H + Y0 + y) * W + X0) * 3;
+      const int mis = (int)((uintptr_t)a & 3), n = ncols * 3, lo = 4 * k - mis;      // span bytes lo .. lo + 3
+      if (k < GA_RDW && lo < n && lo + 4 > 0) {
+        if (lo >= 0 && lo + 4 <= n) gsh[y][k] = *(const unsigned*)(a + lo);
+        else
+          for (int j = max(lo, 0); j < min(lo + 4, n); ++j) ((unsigned char*)gsh[y])[mis + j] = a[j];
+      }
+    }
+    __syncthreads();
+    // ---- compute: lane = column, the wave's 4 rows top to bottom
+    {
+      float top[12], bot[12];
+      int cur = -2;
+      for (int yy = 0; yy < GA_TH / 4; ++yy) {
+        const int y = wv * (GA_TH / 4) + yy;
+        if (y >= nrows) break;
+        const int lr = __builtin_amdgcn_readfirstlane(min(rowi[y] - ilo, FR - 2));
+        const float fy = rowf[y], gy = 1.f - fy;
+        if (lr != cur) {
+          if (lr == cur + 1) {
+#pragma unroll
+            for (int i = 0; i < 12; ++i) top[i] = bot[i];
+          } else {
+            ga_hrow<FC>(fp, lr, lc, fx, top);
+          }
+          ga_hrow<FC>(fp, lr + 1, lc, fx, bot);
+          cur = lr;
+        }
+        const int64_t row = ((int64_t)b * H + Y0 + y) * W + X0;
+        const unsigned char* g = (const unsigned char*)gsh[y] + (int)((uintptr_t)(guide + row * 3) & 3) + xc * 3;
+        const float I0 = g[0], I1 = g[1], I2 = g[2];
+        unsigned char* o = out_u8 ? (unsigned char*)osh[y] + (int)((uintptr_t)(out_u8 + row * 3) & 3) + xc * 3 : nullptr;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float A0 = gy * top[c * 4] + fy * bot[c * 4], A1 = gy * top[c * 4 + 1] + fy * bot[c * 4 + 1];
+          const float A2 = gy * top[c * 4 + 2] + fy * bot[c * 4 + 2], Bc = gy * top[c * 4 + 3] + fy * bot[c * 4 + 3];
+          const float qv = A0 * I0 + A1 * I1 + A2 * I2 + Bc;
+          const float rq = fminf(fmaxf(rintf(qv), 0.f), 255.f);          // as gf_store
+          if (lane < ncols) {
+            if (o) o[c] = (unsigned char)rq;
+            if (out) out[((int64_t)b * 3 + c) * P + (int64_t)(Y0 + y) * W + X0 + lane] = (rq / 255.0f - 0.5f) * 2.f;
+          }
+        }
+      }
+    }
+    __syncthreads();
+    // ---- store the output bytes: aligned dwords over each row's span, bytes where the span does not fill one
+    if (out_u8) {
+      for (int i = t; i < nrows * 64; i += GA_NT) {
+        const int y = i >> 6, k = i & 63;
+        unsigned char* a = out_u8 + (((int64_t)b * H + Y0 + y) * W + X0) * 3;
+        const int mis = (int)((uintptr_t)a & 3), n = ncols * 3, lo = 4 * k - mis;
+        if (k < GA_RDW && lo < n && lo + 4 > 0) {
+          if (lo >= 0 && lo + 4 <= n) *(unsigned*)(a + lo) = osh[y][k];
+          else
+            for (int j = max(lo, 0); j < min(lo + 4, n); ++j) a[j] = ((const unsigned char*)osh[y])[mis + j];
+        }
+      }
+    }
+    // (the next image's staging writes fp and gsh, which nobody reads after the barrier above; osh is written again only
+    //  behind the next barrier)
+  }
+}
+
+// The coefficient entry's own V pass and solve.  Its planes are judged ALONE against float64 (twice the error of a float32 run whose
+// window means are float64 means rounded once, tests/gf_native_cases.py:plane_ref), and the generic path's gf_v_kernel / gf_solve_kernel
+// do not meet that: gf_v sums 2r + 1 row sums in fp32 (exact only up to r = 7: 255^2 (2r + 1)^2 < 2^24) and multiplies by a ROUNDED
+// 1 / (2r + 1)^2, gf_solve compiles with contraction, and an ill-conditioned covariance amplifies both (measured with them: 3.39e-3
+// against a bar of 2.47e-3 at r = 7, 2.65e-4 against 2.50e-4 at r = 30).  Those two keep their bytes for ppst_guided_filter; these are
+// beside them:
+//   gfc_v_kernel      the same pass with a double accumulator and a true division, rounded once -- on the integer moment sums of
+//                     stage 1 (gf_h<true>'s row sums are exact in fp32: 255^2 (2 GF_MAXR + 1) < 2^24) the mean is the correctly rounded one;
+//   gfc_solve_kernel  gf_solve_kernel's text (the shared GF_SOLVE_* macros, six divisions) with contraction off: every operation
+//                     rounds once, in the order written.
+__global__ __launch_bounds__(256) void gfc_v_kernel(const float* __restrict__ in, float* __restrict__ out, int H, int W, int r, int64_t total) {
+  const double n2 = (double)((2 * r + 1) * (2 * r + 1));
+  const int64_t P = (int64_t)H * W;
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
+    int x = (int)(t % W);
+    int64_t q = t / W;
+    int y = (int)(q % H);
+    int64_t bp = q / H;
+    const float* col = in + bp * P + x;
+    double s = 0.0;
+    for (int k = -r; k <= r; ++k) s += (double)col[(int64_t)reflect_idx(y + k, H) * W];
+    out[t] = (float)(s / n2);
+  }
+}
+
+__global__ __launch_bounds__(256) void gfc_solve_kernel(const float* __restrict__ m, float* __restrict__ ab, int64_t P, float eps, int64_t total) {
+#pragma clang fp contract(off)
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
+    int64_t b = t / P, p = t - b * P;
+    const float* mp = m + b * 21 * P + p;
+#define GF_M(i) mp[(i) * P]
+    GF_SOLVE_DET(GF_M, eps);
+    const float i00 = c00 / det, i01 = c01 / det, i02 = c02 / det, i11 = c11 / det, i12 = c12 / det, i22 = c22 / det;
+    float* o = ab + b * 12 * P + p;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      GF_SOLVE_AB(GF_M, c);
+      o[(c * 4 + 0) * P] = A0; o[(c * 4 + 1) * P] = A1; o[(c * 4 + 2) * P] = A2; o[(c * 4 + 3) * P] = bb;
+    }
+#undef GF_M
+  }
+}
+
+extern "C" int ppst_guided_filter_coeffs(const void* guide_u8, const void* src_u8, void* coeffs, int B, int h, int w, int r, float eps,
+                                         void* work, void* stream) {
+  // (the generic path's rule without the fused radius above GF_MAXR: r = 90 has no fp32-plane form)
+  if (B < 0 || h <= 0 || w <= 0 || w > GF_MAXW || r <= 0 || r > GF_MAXR || r >= h || r >= w) return PPST_EINVAL;
+  if (B == 0) return PPST_OK;
+  if (!guide_u8 || !src_u8 || !coeffs || !work) return PPST_ENULL;
+  hipStream_t st = as_stream(stream);
+  const int64_t P = (int64_t)h * w;
+  const unsigned char* g = (const unsigned char*)guide_u8;
+  const unsigned char* s = (const unsigned char*)src_u8;
+  float* bufA = (float*)work;                // [B][21][P]
+  float* bufB = bufA + (int64_t)B * 21 * P;  // [B][21][P]
+  auto blocks_for = [](int64_t total) { int64_t b = cdiv64(total, 256); return (unsigned)(b > 256 * 32 ? 256 * 32 : b); };
+  int e;
+  PPST_LAUNCH(gf_h_kernel<true>, dim3(h, 21, B), dim3(256), 0, st, g, s, (const float*)nullptr, bufA, h, w, r, 21);
+  if ((e = PPST_LAUNCH_CHECK())) return e;
+  const int64_t t21 = (int64_t)B * 21 * P, t12 = (int64_t)B * 12 * P;
+  PPST_LAUNCH(gfc_v_kernel, dim3(blocks_for(t21)), dim3(256), 0, st, (const float*)bufA, bufB, h, w, r, t21);
+  if ((e = PPST_LAUNCH_CHECK())) return e;
+  PPST_LAUNCH(gfc_solve_kernel, dim3(blocks_for(B * P)), dim3(256), 0, st, (const float*)bufB, bufA, P, eps, (int64_t)B * P);
+  if ((e = PPST_LAUNCH_CHECK())) return e;
+  PPST_LAUNCH(gf_h_kernel<false>, dim3(h, 12, B), dim3(256), 0, st, g, s, (const float*)bufA, bufB, h, w, r, 12);
+  if ((e = PPST_LAUNCH_CHECK())) return e;
+  PPST_LAUNCH(gfc_v_kernel, dim3(blocks_for(t12)), dim3(256), 0, st, (const float*)bufB, (float*)coeffs, h, w, r, t12);
+  return PPST_LAUNCH_CHECK();
+}
+
+extern "C" int ppst_guided_filter_apply(const void* coeffs, int h, int w, const void* guide_u8, void* out_u8, void* out_f32, int B, int H,
+                                        int W, void* stream) {
+  if (B < 0 || h <= 0 || w <= 0 || H < h || W < w || (int64_t)H * W > GA_MAXPIX) return PPST_EINVAL;
+  if (B == 0) return PPST_OK;
+  if (!coeffs || !guide_u8 || (!out_u8 && !out_f32)) return PPST_ENULL;
+  const int tiles_x = cdiv(W, GA_TW);
+  const int64_t tiles = (int64_t)tiles_x * cdiv(H, GA_TH);     // <= 2^28: H W <= 2^28
+  const dim3 grid((unsigned)tiles, (unsigned)(B > 65535 ? 65535 : B));
+  // two instances of one body: at scale >= 2 on both axes the footprint is a quarter and three times the blocks fit a CU
+  if (2 * (int64_t)h <= H && 2 * (int64_t)w <= W)
+    PPST_LAUNCH((gf_apply_up_kernel<GA_FR2, GA_FC2>), grid, dim3(GA_NT), 0, as_stream(stream), (const float*)coeffs, h, w,
+                (const unsigned char*)guide_u8, (unsigned char*)out_u8, (float*)out_f32, B, H, W, tiles_x);
+  else
+    PPST_LAUNCH((gf_apply_up_kernel<GA_FR, GA_FC>), grid, dim3(GA_NT), 0, as_stream(stream), (const float*)coeffs, h, w,
+                (const unsigned char*)guide_u8, (unsigned char*)out_u8, (float*)out_f32, B, H, W, tiles_x);
+  return PPST_LAUNCH_CHECK();
+}
+
 // (the revision history is at PPST_ABI_VERSION in include/ppst_hip.h; callers built against another revision must rebuild)
 extern "C" int ppst_version(void) { return PPST_ABI_VERSION; }

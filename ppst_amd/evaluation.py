@@ -34,10 +34,10 @@ def above_code_grid(*images):
     return any(max(int(t.shape[-2]), int(t.shape[-1])) > CORR_SIDE for t in images)
 
 
-def simple_swap_full_size(model, content, style, alphas=(1.0,)):
-    """``simple_swap`` above 512 x 512: spatial code, global codes and the decode at full size, the correspondence from the
-    512 x 512 resamples of both images (PPSTModel.correspondence_features); E2's warp pools every level of the full-size style
-    pass to the 64 x 64 grid, applies the matrix and resizes back."""
+def swap_codes_full_size(model, content, style):
+    """``swap_codes`` above 512 x 512: spatial code and global codes at full size, the correspondence from the 512 x 512 resamples
+    of both images (PPSTModel.correspondence_features); E2's warp pools every level of the full-size style pass to the 64 x 64
+    grid, applies the matrix and resizes back."""
     sp, gl_c = model(content, command="encode")
     if content.shape == style.shape:
         # both 512 x 512 passes as one batch: contents, then styles (bit-identical: nothing depends on the batch size)
@@ -50,16 +50,24 @@ def simple_swap_full_size(model, content, style, alphas=(1.0,)):
         fea_s = model(style, command="correspondence_features")
     corr = model(fea_s, fea_c, command="corrm")
     _, gl_w = model(style, corr, command="encode2")
+    return sp, gl_c, gl_w
+
+
+def simple_swap_full_size(model, content, style, alphas=(1.0,)):
+    """``simple_swap`` above 512 x 512: the codes of ``swap_codes_full_size``, decoded at full size."""
+    sp, gl_c, gl_w = swap_codes_full_size(model, content, style)
     out = {}
     for alpha in alphas:
         out[alpha] = model(sp, glue.lerp(gl_c, gl_w, alpha), target=None, command="decode")
     return out
 
 
-def simple_swap(model, content, style, alphas=(1.0,)):
-    """content, style: (B,3,H,W) in [-1,1] on the GPU.  Returns {alpha: image (B,3,H,W)}."""
+def swap_codes(model, content, style):
+    """The recipe of ``simple_swap`` up to its codes: -> (sp, gl_c, gl_w), the content's spatial code, its global codes and the
+    style's warped ones; every alpha decodes from ``(sp, lerp(gl_c, gl_w, alpha))``.  Shared by ``simple_swap`` and
+    ``simple_swap_native``."""
     if above_code_grid(content, style):
-        return simple_swap_full_size(model, content, style, alphas)
+        return swap_codes_full_size(model, content, style)
     if content.shape == style.shape:
         # the encoder passes of the recipe (encode(content) + the E1 / E2 inside the two extract_feat_from_image) as one batch of
         # 3B images, the two generator feature passes as one of 2B: the same work, bit-identical (nothing depends on the batch size)
@@ -77,10 +85,48 @@ def simple_swap(model, content, style, alphas=(1.0,)):
         fea_s = torch.cat((fea_s, model(fea_s1, command="Rselfcorr")), dim=1)
     corr = model(fea_s, fea_c, command="corrm")
     _, gl_w = model(style, corr, command="encode2")
+    return sp, gl_c, gl_w
+
+
+def simple_swap(model, content, style, alphas=(1.0,)):
+    """content, style: (B,3,H,W) in [-1,1] on the GPU.  Returns {alpha: image (B,3,H,W)}."""
+    if above_code_grid(content, style):
+        return simple_swap_full_size(model, content, style, alphas)
+    sp, gl_c, gl_w = swap_codes(model, content, style)
     out = {}
     for alpha in alphas:
         code = glue.lerp(gl_c, gl_w, alpha)
         out[alpha] = model(sp, code, target=None, command="decode")
+    return out
+
+
+def native_size_rule(native_shape, load_size):
+    """The size rule of ``simple_swap_native`` from shapes alone: ValueError unless the native images (B,H,W,3) are square with a
+    side >= load_size and load_size is a side the model runs at (``ppst_model.correspondence_side``)."""
+    from .ppst_model import correspondence_side
+    if len(native_shape) != 4 or native_shape[3] != 3:
+        raise ValueError("simple_swap_native takes native images as (B,H,W,3) uint8, got shape %s" % (tuple(native_shape),))
+    correspondence_side(int(load_size), int(load_size))
+    H, W = int(native_shape[1]), int(native_shape[2])
+    if H != W or H < load_size:
+        raise ValueError("simple_swap_native: native images must be square with a side of at least load_size = %d (the model runs "
+                         "at load_size x load_size and its filter coefficients are upsampled, never reduced), got %d x %d"
+                         % (load_size, H, W))
+
+
+def simple_swap_native(model, content_native_u8, style, alphas=(1.0,), load_size=512):
+    """``simple_swap`` + guided filter, delivered at the content file's own size.  content_native_u8: (B,H,W,3) uint8 on the GPU,
+    square, H >= load_size; style: (B,3,h,w) in [-1,1] as today.  The model runs at load_size on
+    ``imageio.preprocess(content_native_u8, load_size)`` (the tensor the file front end feeds it), the codes are ``simple_swap``'s,
+    and each alpha is decoded by ``decode_native``: the filter's coefficients at load_size, upsampled and applied to the native
+    image.  Returns {alpha: uint8 (B,H,W,3)}."""
+    native_size_rule(tuple(content_native_u8.shape), load_size)
+    from . import imageio
+    content = imageio.preprocess(content_native_u8, load_size)
+    sp, gl_c, gl_w = swap_codes(model, content, style)
+    out = {}
+    for alpha in alphas:
+        out[alpha] = model(sp, glue.lerp(gl_c, gl_w, alpha), content, content_native_u8, command="decode_native")
     return out
 
 
@@ -466,6 +512,70 @@ def evaluate_swap_files(model, structure_path, texture_path, out_dir, alphas=(1.
         path = os.path.join(out_dir, "%s_%s_%.2f%s" % (stem(structure_path), stem(texture_path), alpha, FORMATS[format]))
         paths += write_png_batch(to_uint8_image(outs[alpha])[:1], [path], None, png, format, jpeg_quality, jpeg_subsampling)
     return paths
+
+
+def load_native(paths, device="cuda", pool=None):
+    """Files -> list of (H,W,3) uint8 device tensors at the files' own sizes, decoded where ``evaluation.decoder`` says: on the
+    host (Pillow), or by the HIP decoders with Pillow for whatever they do not take (the rule of ``load_images``)."""
+    decode = current_decoder()
+    _check_decoder(decode)
+    imgs = [None] * len(paths)
+    if decode == "device":
+        blobs = list(pool.map(_read_file, paths)) if pool is not None else [_read_file(p) for p in paths]
+        imgs = decode_files_device(blobs, paths, device)
+    rest = [i for i, v in enumerate(imgs) if v is None]
+    host = list(pool.map(_decode, [paths[i] for i in rest])) if pool is not None else [_decode(paths[i]) for i in rest]
+    for i, a in zip(rest, host):
+        imgs[i] = torch.from_numpy(a).to(device)
+    return imgs
+
+
+def _device_encoder_takes(shape, format, jpeg_subsampling):
+    """whether the device encoder of ``format`` has a bound for images of this (H, W, C) (ops.png_encode / jpeg_encode refuse otherwise)"""
+    from ._lib import lib
+    H, W, C = (int(v) for v in shape)
+    if format == "jpeg":
+        return lib.ppst_jpeg_bound(H, W, C, ops.JPEG_SUBSAMPLING[jpeg_subsampling]) >= 0
+    return lib.ppst_png_bound(H, W, C) >= 0
+
+
+def evaluate_swap_files_native(model, structure_path, texture_path, out_dir, alphas=(1.0,), load_size=512, device="cuda", png="host",
+                               format="png", jpeg_quality=90, jpeg_subsampling="4:2:0"):
+    """``evaluate_swap_files`` with every output at the size of its structure FILE (``simple_swap_native``: the model runs at
+    load_size, the guided filter's coefficients are applied to the file's own pixels).  ``structure_path`` / ``texture_path``: one
+    path or a list of paths each -- one texture serves every structure, otherwise the two lists pair up.  Structure files are read
+    at their own size (square, side >= load_size) where ``evaluation.decoder`` says, textures as today (load_images); structures
+    of one size run as one batch.  Files are written through write_png_batch, named as evaluate_swap_files names them; a size the
+    device encoder has no bound for is encoded on the host.  Returns the paths, structure by structure, alpha by alpha."""
+    import os
+    _check_encoder(png)
+    _check_format(format, jpeg_quality, jpeg_subsampling)
+    _check_decoder(current_decoder())
+    as_list = lambda p: [p] if isinstance(p, (str, bytes, os.PathLike)) else list(p)
+    structures, textures = as_list(structure_path), as_list(texture_path)
+    if len(textures) == 1:
+        textures = textures * len(structures)
+    if len(textures) != len(structures):
+        raise ValueError("evaluate_swap_files_native pairs structures and textures: %d structure and %d texture paths"
+                         % (len(structures), len(textures)))
+    os.makedirs(out_dir, exist_ok=True)
+    natives = load_native([os.path.expanduser(p) for p in structures], device)
+    for n in natives:                                          # (before any model pass: a wrong size fails at once)
+        native_size_rule((1,) + tuple(n.shape), load_size)
+    styles = load_images([os.path.expanduser(p) for p in textures], load_size, device)
+    stem = lambda p: os.path.splitext(os.path.basename(p))[0]
+    groups = {}
+    for i, n in enumerate(natives):                            # structures of one size (and one texture size) share a batch
+        groups.setdefault((tuple(n.shape), tuple(styles[i].shape)), []).append(i)
+    paths = {}
+    for (shape, _), idx in groups.items():
+        outs = simple_swap_native(model, torch.stack([natives[i] for i in idx]), torch.cat([styles[i] for i in idx], 0), alphas, load_size)
+        encoder = png if png == "host" or _device_encoder_takes(shape, format, jpeg_subsampling) else "host"
+        for alpha in alphas:
+            names = [os.path.join(out_dir, "%s_%s_%.2f%s" % (stem(structures[i]), stem(textures[i]), alpha, FORMATS[format])) for i in idx]
+            for i, p in zip(idx, write_png_batch(outs[alpha], names, None, encoder, format, jpeg_quality, jpeg_subsampling)):
+                paths.setdefault(i, []).append(p)
+    return [p for i in range(len(structures)) for p in paths[i]]
 
 
 def evaluate_grid_folder(model, dataroot, out_dir, rank=0, world=1, smooth=True, load_size=512, device="cuda", workers=8,

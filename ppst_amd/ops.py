@@ -1760,6 +1760,47 @@ def guided_filter(guide_u8, src_u8, r=30, eps=(0.02 * 255) ** 2, want_u8=False):
     return (out, out_u8) if want_u8 else out
 
 
+def guided_filter_coeffs(guide_u8, src_u8, r=30, eps=(0.02 * 255) ** 2):
+    """guide/src (B,h,w,3) uint8 -> (B,12,h,w) fp32: the filter's mean coefficient planes (plane 4c + k: k = 0..2 mean a_ck,
+    k = 3 mean b_c), what ``guided_filter_apply`` upsamples.  Five launches through fp32 planes at every radius: 0 < r <= 64
+    (30 and 60 included, 90 refused), r < h, r < w, w <= 2048."""
+    for t in (guide_u8, src_u8):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
+            raise RuntimeError("guided_filter_coeffs needs CUDA uint8 tensors")
+    if guide_u8.dim() != 4 or guide_u8.shape[3] != 3 or src_u8.shape != guide_u8.shape:
+        raise RuntimeError("guided_filter_coeffs needs guide and source of one shape (B,h,w,3), got %s and %s"
+                           % (tuple(guide_u8.shape), tuple(src_u8.shape)))
+    guide_u8, src_u8 = guide_u8.contiguous(), src_u8.contiguous()
+    B, h, w, _ = guide_u8.shape
+    ws = torch.empty(lib.ppst_guided_filter_ws(B, h, w), device=guide_u8.device, dtype=torch.uint8)
+    coeffs = torch.empty((B, 12, h, w), device=guide_u8.device, dtype=torch.float32)
+    check(lib.ppst_guided_filter_coeffs(_p(guide_u8), _p(src_u8), _p(coeffs), B, h, w, int(r), float(eps), _p(ws), _stream()),
+          "ppst_guided_filter_coeffs")
+    return coeffs
+
+
+def guided_filter_apply(coeffs, guide_full_u8, want_f32=False):
+    """coeffs (B,12,h,w) fp32 (``guided_filter_coeffs``), guide (B,H,W,3) uint8 with H >= h, W >= w -> uint8 (B,H,W,3): the
+    coefficients upsampled bilinearly (half-pixel centres, any ratio per axis) and applied to the guide at its own size, one
+    launch; ``want_f32``: also the fp32 NCHW image (q/255 - 0.5)*2 of those bytes.  H < h, W < w and H W > 2^28 are refused."""
+    if not isinstance(coeffs, torch.Tensor) or not coeffs.is_cuda or coeffs.dtype != torch.float32:
+        raise RuntimeError("guided_filter_apply needs CUDA float32 coefficients")
+    if not isinstance(guide_full_u8, torch.Tensor) or not guide_full_u8.is_cuda or guide_full_u8.dtype != torch.uint8:
+        raise RuntimeError("guided_filter_apply needs a CUDA uint8 guide")
+    if (coeffs.dim() != 4 or coeffs.shape[1] != 12 or guide_full_u8.dim() != 4 or guide_full_u8.shape[3] != 3
+            or guide_full_u8.shape[0] != coeffs.shape[0]):
+        raise RuntimeError("guided_filter_apply needs coefficients (B,12,h,w) and a guide (B,H,W,3) of one batch, got %s and %s"
+                           % (tuple(coeffs.shape), tuple(guide_full_u8.shape)))
+    coeffs, guide_full_u8 = coeffs.contiguous(), guide_full_u8.contiguous()
+    B, _, h, w = coeffs.shape
+    _, H, W, _ = guide_full_u8.shape
+    out_u8 = torch.empty((B, H, W, 3), device=coeffs.device, dtype=torch.uint8)
+    out = torch.empty((B, 3, H, W), device=coeffs.device, dtype=torch.float32) if want_f32 else None
+    check(lib.ppst_guided_filter_apply(_p(coeffs), h, w, _p(guide_full_u8), _p(out_u8), _p(out), B, H, W, _stream()),
+          "ppst_guided_filter_apply")
+    return (out_u8, out) if want_f32 else out_u8
+
+
 def _encode(name, u8, limits, geom=(), settings=()):
     """What png_encode and jpeg_encode do: the slots from the library's bound, the workspace from torch's allocator, one call.
     ``geom``: the codec's arguments behind (H, W, C) of its bound and workspace; ``settings``: those of its encode call."""

@@ -342,6 +342,21 @@ class PPSTModel(nn.Module):
             return ops.guided_filter(glue.tensor2im(target), glue.tensor2im(out), r, (0.02 * 255) ** 2)
         return out
 
+    def decode_native(self, spatial_code, global_code, target, native_u8):
+        """``decode(target=...)`` delivered at the size of the content FILE (He and Sun, "Fast Guided Filter"): the filter's mean
+        coefficients are solved at the model's size from the pair decode filters -- tensor2im(target), tensor2im(G's output) -- at
+        ``guided_filter_radius``, upsampled bilinearly and applied to ``native_u8`` (B,H,W,3) uint8, the image ``target`` was made
+        from, H >= h, W >= w.  -> uint8 (B,H,W,3).  The coefficient entry runs radii up to 64: ValueError for any other
+        ("scaled" at 1536^2 gives 90)."""
+        h, w = int(target.shape[-2]), int(target.shape[-1])
+        r = guided_filter_radius(self.opt, h, w)
+        if not 0 < r <= 64 or r >= h or r >= w or w > 2048:           # (from shapes alone, before the generator runs)
+            raise ValueError("decode_native: the coefficient planes are computed at radii 0 < r <= 64 with r < h, r < w and "
+                             "w <= 2048, got r = %d at %d x %d" % (r, h, w))
+        out = self.G(spatial_code, global_code, noise=self.noise)
+        coeffs = ops.guided_filter_coeffs(glue.tensor2im(target), glue.tensor2im(out), r, (0.02 * 255) ** 2)
+        return ops.guided_filter_apply(coeffs, native_u8)
+
     def discriminate(self, x):
         return self.D(x)
 
