@@ -579,6 +579,19 @@ int ppst_resample_f32(const void* x, void* y, int B, int in_h, int in_w, int out
                       const void* bounds_h, const void* coef_h, int ksize_h,
                       const void* bounds_v, const void* coef_v, int ksize_v,
                       int clamp, float lo, float hi, void* stream);
+/* An aligned square crop of a photograph under a similarity transform, antialiased: photo uint8 [B][H][W][3] -> out uint8
+ * [B][n][n][3].  A transform is four int64 (a, b, cu, cv): the photo pixel in column X, row Y (centre X + 1/2, Y + 1/2) lies at
+ *   U = a (2X + 1) + b (2Y + 1) + cu,   V = -b (2X + 1) + a (2Y + 1) + cv      (units of 2^-24 crop pixel)
+ * in the crop's frame; the crop is 0 <= U, V < n 2^24 and s = 2^23 / sqrt(a^2 + b^2) is photo pixels per crop pixel
+ * (ppst_amd/imageio.py: crop_transform).  xf_host [B][4] is read by the entry point (rule, tile choice), xf_dev is the same table
+ * on the device (read by the kernel).  out[j][i][c] = clamp(rint(sum w photo[clamp(Y)][clamp(X)][c] / sum w), 0, 255) with
+ * w = k((U - (2i + 1) 2^23) / 2^24) k((V - (2j + 1) 2^23) / 2^24), k Pillow's bicubic (Keys a = -0.5), over every integer (X, Y),
+ * inside the photo or not (edge replication), with both arguments below 2 in magnitude: Pillow's antialiased bicubic in the
+ * crop's frame.  No float position is floored: which pixels enter a sum is decided in integers.
+ * PPST_EINVAL, with nothing written: n <= 0, n > 4096, H W > 2^28, a transform with s < 1 or s > 8 (2^40 <= a^2 + b^2 <= 2^46
+ * required: the upper end of s bounds the staged footprint of a tile) or |cu|, |cv| > 2^56. */
+int ppst_extract_similarity(const void* photo_u8, int B, int H, int W, const void* xf_host, const void* xf_dev, int n,
+                            void* out_u8, void* stream);
 
 /* PNG encode on the device (ppst_amd/csrc/png.hip): uint8 HWC [B][H][W][C], C = 1 (grey) or 3 (RGB), 8 bits per sample, ->
  * B complete PNG files.  Per row the filter with the smallest sum of absolute signed bytes (libpng's heuristic, ties to the
@@ -948,6 +961,19 @@ int ppst_guided_filter_coeffs(const void* guide_u8, const void* src_u8, void* co
                               void* work, void* stream);
 int ppst_guided_filter_apply(const void* coeffs, int h, int w, const void* guide_u8, void* out_u8, void* out_f32,
                              int B, int H, int W, void* stream);
+/* the filter's coefficients applied INSIDE a photograph: coeffs fp32 [B][12][n][n] (ppst_guided_filter_coeffs of an n x n crop
+ * taken by ppst_extract_similarity), photo uint8 [B][H][W][3], the crop's transforms (xf_host / xf_dev as there) -> out_u8
+ * [B][H][W][3], which may be photo_u8 itself.  Only photo pixels inside the crop square 0 <= U, V < n 2^24 are written: the
+ * caller's out_u8 keeps every other byte (copy the photo into it first, or work in place); one launch over the tiles of the
+ * quads' bounding boxes.  Inside: the 12 coefficients by bilinear interpolation at (U / 2^24 - 1/2, V / 2^24 - 1/2) -- tap
+ * floor by an arithmetic shift of the integer, fraction = its low 24 bits / 2^24, taps clamped to [0, n - 1], horizontally
+ * first, then vertically --, q_c = A_c0 I0 + A_c1 I1 + A_c2 I2 + B_c on the photo's own pixel I, and
+ * out = clamp(rint(g q + (1 - g) I), 0, 255), g = t^2 (3 - 2t), t = clamp(d / feather, 0, 1),
+ * d = min(U, n 2^24 - U, V, n 2^24 - V) / 2^24; feather = 0: g = 1.
+ * PPST_EINVAL, with nothing written: n <= 0, n > 4096, feather < 0, 2 feather > n, H W > 2^28, a transform refused by
+ * ppst_extract_similarity. */
+int ppst_guided_filter_paste(const void* coeffs, int n, const void* photo_u8, void* out_u8, int B, int H, int W,
+                             const void* xf_host, const void* xf_dev, int feather, void* stream);
 
 /* local-affine photo smoothing (smooth_filter.py:332-378 smooth_local_affine and its three NVRTC kernels :149-321):
  * output (stylised), input (content = guide), result: planar fp32 [B][3][H][W]; model_ws: >= ppst_smooth_local_affine_ws()

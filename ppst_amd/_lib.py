@@ -208,6 +208,8 @@ _SIGS = {
     "ppst_guided_filter": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),
     "ppst_guided_filter_coeffs": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),
     "ppst_guided_filter_apply": (i32, [vp, i32, i32, vp, vp, vp, i32, i32, i32, vp]),
+    "ppst_guided_filter_paste": (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp, i32, vp]),
+    "ppst_extract_similarity": (i32, [vp, i32, i32, i32, vp, vp, i32, vp, vp]),
     "ppst_smooth_local_affine_ws": (i64, [i32, i32, i32]),
     "ppst_smooth_local_affine": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]),
     "ppst_conv_wgrad_f32": (i32, [vp, vp, vp, vp, vp] + [i32] * 11 + [vp]),

@@ -30,7 +30,7 @@ def _hipcc():
 
 
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "rscl_common.h"), os.path.join(CSRC, "png_common.h"),
-           os.path.join(CSRC, "codec_common.h"), os.path.join(CSRC, "jpeg_common.h"), os.path.join(CSRC, "parse_reader.h"),
+           os.path.join(CSRC, "codec_common.h"), os.path.join(CSRC, "jpeg_common.h"), os.path.join(CSRC, "parse_reader.h"), os.path.join(CSRC, "sim_xf.h"),
            os.path.join(HERE, "..", "include", "ppst_hip.h")]
 
 

@@ -734,5 +734,135 @@ extern "C" int ppst_guided_filter_apply(const void* coeffs, int h, int w, const 
   return PPST_LAUNCH_CHECK();
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// The coefficients applied INSIDE a photograph (ppst_guided_filter_paste; the transform and its integer units are in sim_xf.h):
+// gf_apply_up_kernel's arithmetic along a similarity map instead of an axis-aligned one, plus a feathered edge.  For the photo
+// pixel (X, Y): U, V in int64; inside iff 0 <= U, V < n 2^24; taps from Ui = U - 2^23: i0 = Ui >> 24 (>= -1), fraction
+// (Ui & (2^24 - 1)) / 2^24 (exact in fp32), clamped to [0, n - 1]; horizontally, then vertically; q = A I + B on the photo's own
+// pixel; out = rint(g q + (1 - g) I), g the smoothstep of the distance to the crop's edge over ``feather`` crop pixels.  Pixels
+// outside the crop are not written.
+// Geometry: photo tiles of GP_T x GP_T pixels on the photo's own grid (multiples of GP_T), one thread per pixel, over the box of
+// the quad only: a block derives the box of its image from the transform (sx_box, margin 1; the entry point sizes the grid with
+// margin 2, so it never has fewer tiles than a block counts) and leaves if its index is past it.  A tile's taps lie between the
+// floors of Ui, Vi at its four corner pixels (both are linear in X, Y): 15 (|cos| + |sin|) / s <= 21.3 coefficient samples apart,
+// so at most GP_FS = 24 a side with the + 1 tap.  That footprint is staged pixel-major in LDS (24 x 24 x 12 floats = 27,648 B;
+// rows and columns limited to the plane, so fewer near the crop's edge), a thread reads its 4 taps x 12 planes as 12 16-byte
+// reads.  A 32 x 16 tile would need up to 37 x 37 samples at 45 degrees and s = 1 -- 65.7 KB, more than a block may declare.
+// Every staged index is clamped to the plane and every local index to the footprint.
+#include "sim_xf.h"
+#define GP_T 16
+#define GP_FS 24
+
+__global__ __launch_bounds__(GP_T * GP_T) void gf_paste_kernel(const float* __restrict__ coef, int n, const unsigned char* photo,
+                                                               unsigned char* out, int B, int H, int W,
+                                                               const int64_t* __restrict__ xf, int feather) {
+  __shared__ __attribute__((aligned(16))) float fp[GP_FS * GP_FS * 12];
+  const int t = threadIdx.x;
+  const int64_t p = (int64_t)n * n, side = (int64_t)n * SX_ONE;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const SimXf f = {xf[4 * b], xf[4 * b + 1], xf[4 * b + 2], xf[4 * b + 3]};
+    int bx0, by0, bx1, by1;
+    sx_box(f, 0, side, 0, side, 1, bx0, by0, bx1, by1);
+    bx0 = max(bx0, 0); by0 = max(by0, 0); bx1 = min(bx1, W - 1); by1 = min(by1, H - 1);
+    if (bx0 > bx1 || by0 > by1) continue;                                      // (block-uniform, like every exit below)
+    const int tx0 = bx0 / GP_T, ty0 = by0 / GP_T, ntx = bx1 / GP_T - tx0 + 1, nty = by1 / GP_T - ty0 + 1;
+    if ((int64_t)blockIdx.x >= (int64_t)ntx * nty) continue;
+    const int X0 = (tx0 + (int)(blockIdx.x % ntx)) * GP_T, Y0 = (ty0 + (int)(blockIdx.x / ntx)) * GP_T;
+    const int XL = min(X0 + GP_T - 1, W - 1), YL = min(Y0 + GP_T - 1, H - 1);
+    // ---- the tile's footprint: extremes of Ui, Vi over the corner pixels
+    int64_t ulo = INT64_MAX, uhi = INT64_MIN, vlo = INT64_MAX, vhi = INT64_MIN;
+    for (int k = 0; k < 4; ++k) {
+      const int64_t px = 2 * (int64_t)((k & 1) ? XL : X0) + 1, py = 2 * (int64_t)((k & 2) ? YL : Y0) + 1;
+      const int64_t Ui = f.a * px + f.b * py + f.cu - SX_HALF, Vi = -f.b * px + f.a * py + f.cv - SX_HALF;
+      ulo = sx_min(ulo, Ui); uhi = sx_max(uhi, Ui); vlo = sx_min(vlo, Vi); vhi = sx_max(vhi, Vi);
+    }
+    // U and V are linear in (X, Y): a tile whose corners all lie on the outer side of one edge of the square has no pixel in it
+    // (the box of a turned square is up to twice its area)
+    if (uhi + SX_HALF < 0 || ulo + SX_HALF >= side || vhi + SX_HALF < 0 || vlo + SX_HALF >= side) continue;
+    const int64_t nm1 = n - 1;
+    const int ilo = (int)sx_min(sx_max(ulo >> 24, 0), nm1), ihi = (int)sx_min(sx_max((uhi >> 24) + 1, 0), nm1);
+    const int jlo = (int)sx_min(sx_max(vlo >> 24, 0), nm1), jhi = (int)sx_min(sx_max((vhi >> 24) + 1, 0), nm1);
+    const int fc = min(ihi - ilo + 1, GP_FS), fr = min(jhi - jlo + 1, GP_FS);
+    const float* cb = coef + (int64_t)b * 12 * p;
+    for (int k = t; k < fr * fc; k += GP_T * GP_T) {
+      const int lr = k / fc, lc = k - lr * fc;
+      const float* s = cb + (int64_t)min(jlo + lr, n - 1) * n + min(ilo + lc, n - 1);
+      float v[12];
+#pragma unroll
+      for (int pl = 0; pl < 12; ++pl) v[pl] = s[pl * p];
+      float4* d = (float4*)(fp + (lr * GP_FS + lc) * 12);
+      d[0] = make_float4(v[0], v[1], v[2], v[3]);
+      d[1] = make_float4(v[4], v[5], v[6], v[7]);
+      d[2] = make_float4(v[8], v[9], v[10], v[11]);
+    }
+    __syncthreads();
+    const int X = X0 + (t % GP_T), Y = Y0 + (t / GP_T);
+    if (X < W && Y < H) {
+      const int64_t U = f.a * (2 * (int64_t)X + 1) + f.b * (2 * (int64_t)Y + 1) + f.cu;
+      const int64_t V = -f.b * (2 * (int64_t)X + 1) + f.a * (2 * (int64_t)Y + 1) + f.cv;
+      if (U >= 0 && U < side && V >= 0 && V < side) {
+        const int64_t Ui = U - SX_HALF, Vi = V - SX_HALF;
+        const int i0 = (int)(Ui >> 24), j0 = (int)(Vi >> 24);
+        const float fx = (float)(int)(Ui & (SX_ONE - 1)) * (1.f / 16777216.f), fy = (float)(int)(Vi & (SX_ONE - 1)) * (1.f / 16777216.f);
+        const float gx = 1.f - fx, gy = 1.f - fy;
+        const int c0 = min(max(min(max(i0, 0), n - 1) - ilo, 0), fc - 1), c1 = min(max(min(max(i0 + 1, 0), n - 1) - ilo, 0), fc - 1);
+        const int r0 = min(max(min(max(j0, 0), n - 1) - jlo, 0), fr - 1), r1 = min(max(min(max(j0 + 1, 0), n - 1) - jlo, 0), fr - 1);
+        float top[12], bot[12];
+        {
+          const float4* a0 = (const float4*)(fp + (r0 * GP_FS + c0) * 12);
+          const float4* a1 = (const float4*)(fp + (r0 * GP_FS + c1) * 12);
+          const float4* b0 = (const float4*)(fp + (r1 * GP_FS + c0) * 12);
+          const float4* b1 = (const float4*)(fp + (r1 * GP_FS + c1) * 12);
+          float4 q[12];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) { q[k] = a0[k]; q[3 + k] = a1[k]; q[6 + k] = b0[k]; q[9 + k] = b1[k]; }
+          const float* a = (const float*)q;
+#pragma unroll
+          for (int k = 0; k < 12; ++k) { top[k] = gx * a[k] + fx * a[12 + k]; bot[k] = gx * a[24 + k] + fx * a[36 + k]; }
+        }
+        const int64_t at = (((int64_t)b * H + Y) * W + X) * 3;
+        const float I0 = photo[at], I1 = photo[at + 1], I2 = photo[at + 2];
+        float g = 1.f;
+        if (feather > 0) {
+          const int64_t d = sx_min(sx_min(U, side - U), sx_min(V, side - V));
+          const float tt = fminf(fmaxf((float)d * (1.f / 16777216.f) / (float)feather, 0.f), 1.f);
+          g = tt * tt * (3.f - 2.f * tt);
+        }
+        const float I[3] = {I0, I1, I2};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float A0 = gy * top[c * 4] + fy * bot[c * 4], A1 = gy * top[c * 4 + 1] + fy * bot[c * 4 + 1];
+          const float A2 = gy * top[c * 4 + 2] + fy * bot[c * 4 + 2], Bc = gy * top[c * 4 + 3] + fy * bot[c * 4 + 3];
+          const float qv = A0 * I0 + A1 * I1 + A2 * I2 + Bc;
+          out[at + c] = (unsigned char)fminf(fmaxf(rintf(g * qv + (1.f - g) * I[c]), 0.f), 255.f);
+        }
+      }
+    }
+    __syncthreads();                                                          // (the next image's staging overwrites fp)
+  }
+}
+
+extern "C" int ppst_guided_filter_paste(const void* coeffs, int n, const void* photo_u8, void* out_u8, int B, int H, int W,
+                                        const void* xf_host, const void* xf_dev, int feather, void* stream) {
+  if (B < 0 || n <= 0 || n > SX_NMAX || H <= 0 || W <= 0 || (int64_t)H * W > SX_MAXPIX || feather < 0 || 2 * feather > n) return PPST_EINVAL;
+  if (B == 0) return PPST_OK;
+  if (!coeffs || !photo_u8 || !out_u8 || !xf_host || !xf_dev) return PPST_ENULL;
+  const SimXf* f = (const SimXf*)xf_host;
+  int64_t tiles = 0;
+  for (int b = 0; b < B; ++b) {
+    if (!sx_rule(f[b])) return PPST_EINVAL;
+    int x0, y0, x1, y1;
+    sx_box(f[b], 0, (int64_t)n * SX_ONE, 0, (int64_t)n * SX_ONE, 2, x0, y0, x1, y1);
+    x0 = x0 < 0 ? 0 : x0; y0 = y0 < 0 ? 0 : y0; x1 = x1 > W - 1 ? W - 1 : x1; y1 = y1 > H - 1 ? H - 1 : y1;
+    if (x0 > x1 || y0 > y1) continue;
+    const int64_t nt = (int64_t)(x1 / GP_T - x0 / GP_T + 1) * (y1 / GP_T - y0 / GP_T + 1);
+    tiles = nt > tiles ? nt : tiles;
+  }
+  if (tiles == 0) return PPST_OK;                                             // no quad meets its photo
+  PPST_LAUNCH(gf_paste_kernel, dim3((unsigned)tiles, (unsigned)(B > 65535 ? 65535 : B)), dim3(GP_T * GP_T), 0, as_stream(stream),
+              (const float*)coeffs, n, (const unsigned char*)photo_u8, (unsigned char*)out_u8, B, H, W, (const int64_t*)xf_dev, feather);
+  return PPST_LAUNCH_CHECK();
+}
+
 // (the revision history is at PPST_ABI_VERSION in include/ppst_hip.h; callers built against another revision must rebuild)
 extern "C" int ppst_version(void) { return PPST_ABI_VERSION; }

@@ -172,3 +172,103 @@ extern "C" int ppst_resample_f32(const void* x, void* y, int B, int in_h, int in
               make_fastdiv((unsigned)tiles_x), make_fastdiv((unsigned)tiles_y));
   return PPST_LAUNCH_CHECK();
 }
+
+// ------------------------------------------------------------------------------------------------------------------------
+// An aligned crop of a photograph under a similarity transform (ppst_extract_similarity; the transform and its integer units are
+// in sim_xf.h): Pillow's antialiased bicubic stated in the CROP's frame.  Crop pixel (i, j) has its centre at
+// (Uc, Vc) = ((2i + 1) 2^23, (2j + 1) 2^23); every photo pixel (X, Y) with |U - Uc| < 2^25 and |V - Vc| < 2^25 -- decided on the
+// int64 values, never on a float -- contributes w = k((U - Uc) / 2^24) k((V - Vc) / 2^24); the output is sum w p / sum w.  The
+// arguments are converted to fp32 from integers below 2^25 and the weights are fp32; a row of taps is summed on its own and the
+// row sums are added up (at s = 8 a pixel has 1024 taps: one running sum would carry their roundings).
+// Geometry: a block owns T x T crop pixels, one per thread.  The taps of the tile lie in the box of the rotated square of
+// (T + 3) crop pixels a side: at most (T + 3) s sqrt(2) + 3 photo pixels a side with the margin of sx_box -- 111 at T = 16, s <= 4
+// and 128 at T = 8, s <= 8, which is what the rule s <= 8 is for.  Its bytes are staged in LDS (EX_FS16^2 x 3 = 37,632 B,
+// EX_FS8^2 x 3 = 49,152 B) with the edge replication resolved while staging; a thread then walks the box of its own support
+// (limited to the staged box: a tap outside it -- there is none -- would be dropped, never read) with U, V advanced by
+// additions.
+#include "sim_xf.h"
+#define EX_FS16 112
+#define EX_FS8 128
+
+__device__ __forceinline__ float ex_bicubic(float x) {
+  x = fabsf(x);
+  const float a = -0.5f;
+  return x < 1.f ? ((a + 2.f) * x - (a + 3.f)) * x * x + 1.f : (x < 2.f ? (((x - 5.f) * x + 8.f) * x - 4.f) * a : 0.f);
+}
+
+template <int T, int FS>
+__global__ __launch_bounds__(T * T) void extract_similarity_kernel(const unsigned char* __restrict__ photo, const int64_t* __restrict__ xf,
+                                                                   unsigned char* __restrict__ out, int B, int H, int W, int n, int tiles_x) {
+  __shared__ unsigned char sh[FS * FS * 3];
+  const int t = threadIdx.x;
+  const int i0 = (int)(blockIdx.x % tiles_x) * T, j0 = (int)(blockIdx.x / tiles_x) * T;
+  const int i = i0 + (t % T), j = j0 + (t / T);
+  const int64_t R = (int64_t)1 << 25;                                         // the filter's support: 2 crop pixels
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const SimXf f = {xf[4 * b], xf[4 * b + 1], xf[4 * b + 2], xf[4 * b + 3]};
+    // ---- the tile's box and its bytes
+    const int il = min(i0 + T - 1, n - 1), jl = min(j0 + T - 1, n - 1);
+    int X0, Y0, X1, Y1;
+    sx_box(f, (2 * (int64_t)i0 + 1) * SX_HALF - R, (2 * (int64_t)il + 1) * SX_HALF + R, (2 * (int64_t)j0 + 1) * SX_HALF - R,
+           (2 * (int64_t)jl + 1) * SX_HALF + R, 1, X0, Y0, X1, Y1);
+    const int bw = min(X1 - X0 + 1, FS), bh = min(Y1 - Y0 + 1, FS);
+    const unsigned char* pb = photo + (int64_t)b * H * W * 3;
+    for (int k = t; k < bw * bh; k += T * T) {
+      const int ly = k / bw, lx = k - ly * bw;
+      const unsigned char* p = pb + ((int64_t)min(max(Y0 + ly, 0), H - 1) * W + min(max(X0 + lx, 0), W - 1)) * 3;
+      sh[k * 3] = p[0]; sh[k * 3 + 1] = p[1]; sh[k * 3 + 2] = p[2];
+    }
+    __syncthreads();
+    if (i < n && j < n) {
+      const int64_t Uc = (2 * (int64_t)i + 1) * SX_HALF, Vc = (2 * (int64_t)j + 1) * SX_HALF;
+      int x0, y0, x1, y1;
+      sx_box(f, Uc - R, Uc + R, Vc - R, Vc + R, 1, x0, y0, x1, y1);
+      x0 = max(x0, X0); y0 = max(y0, Y0); x1 = min(x1, X0 + bw - 1); y1 = min(y1, Y0 + bh - 1);
+      float n0 = 0.f, n1 = 0.f, n2 = 0.f, den = 0.f;
+      for (int Y = y0; Y <= y1; ++Y) {
+        int64_t dU = f.a * (2 * (int64_t)x0 + 1) + f.b * (2 * (int64_t)Y + 1) + f.cu - Uc;
+        int64_t dV = -f.b * (2 * (int64_t)x0 + 1) + f.a * (2 * (int64_t)Y + 1) + f.cv - Vc;
+        const unsigned char* row = sh + ((Y - Y0) * bw + (x0 - X0)) * 3;
+        float r0 = 0.f, r1 = 0.f, r2 = 0.f, rw = 0.f;
+        for (int X = x0; X <= x1; ++X, dU += 2 * f.a, dV -= 2 * f.b, row += 3) {
+          if (dU > -R && dU < R && dV > -R && dV < R) {
+            const float w = ex_bicubic((float)(int)dU * (1.f / 16777216.f)) * ex_bicubic((float)(int)dV * (1.f / 16777216.f));
+            r0 += w * (float)row[0]; r1 += w * (float)row[1]; r2 += w * (float)row[2]; rw += w;
+          }
+        }
+        n0 += r0; n1 += r1; n2 += r2; den += rw;
+      }
+      unsigned char* o = out + (((int64_t)b * n + j) * n + i) * 3;
+      o[0] = (unsigned char)fminf(fmaxf(rintf(n0 / den), 0.f), 255.f);
+      o[1] = (unsigned char)fminf(fmaxf(rintf(n1 / den), 0.f), 255.f);
+      o[2] = (unsigned char)fminf(fmaxf(rintf(n2 / den), 0.f), 255.f);
+    }
+    __syncthreads();                                                          // (the next image's staging overwrites sh)
+  }
+}
+
+extern "C" int ppst_extract_similarity(const void* photo_u8, int B, int H, int W, const void* xf_host, const void* xf_dev, int n,
+                                       void* out_u8, void* stream) {
+  if (B < 0 || H <= 0 || W <= 0 || n <= 0 || n > SX_NMAX || (int64_t)H * W > SX_MAXPIX) return PPST_EINVAL;
+  if (B == 0) return PPST_OK;
+  if (!photo_u8 || !xf_host || !xf_dev || !out_u8) return PPST_ENULL;
+  const SimXf* f = (const SimXf*)xf_host;
+  int64_t dmin = (int64_t)1 << 46;
+  for (int b = 0; b < B; ++b) {
+    if (!sx_rule(f[b])) return PPST_EINVAL;
+    const int64_t D = f[b].a * f[b].a + f[b].b * f[b].b;
+    dmin = D < dmin ? D : dmin;
+  }
+  const unsigned gy = (unsigned)(B > 65535 ? 65535 : B);
+  // s <= 4 for every image (a^2 + b^2 >= 2^42): 16 x 16 tiles; else 8 x 8, whose box fits up to s = 8.  Same bytes either way.
+  if (dmin >= ((int64_t)1 << 42)) {
+    const int tx = cdiv(n, 16);
+    PPST_LAUNCH((extract_similarity_kernel<16, EX_FS16>), dim3((unsigned)(tx * tx), gy), dim3(256), 0, as_stream(stream),
+                (const unsigned char*)photo_u8, (const int64_t*)xf_dev, (unsigned char*)out_u8, B, H, W, n, tx);
+  } else {
+    const int tx = cdiv(n, 8);
+    PPST_LAUNCH((extract_similarity_kernel<8, EX_FS8>), dim3((unsigned)(tx * tx), gy), dim3(64), 0, as_stream(stream),
+                (const unsigned char*)photo_u8, (const int64_t*)xf_dev, (unsigned char*)out_u8, B, H, W, n, tx);
+  }
+  return PPST_LAUNCH_CHECK();
+}

@@ -578,6 +578,92 @@ def evaluate_swap_files_native(model, structure_path, texture_path, out_dir, alp
     return [p for i in range(len(structures)) for p in paths[i]]
 
 
+def region_rule(photo_shape, xf, load_size):
+    """What ``simple_swap_region`` refuses from shapes and integers alone: photos that are not (B,H,W,3), a load_size the model does
+    not run at, crop transforms outside 1 <= s <= 8 (``imageio.crop_transform_rule``)."""
+    from . import imageio
+    from .ppst_model import correspondence_side
+    if len(photo_shape) != 4 or photo_shape[3] != 3:
+        raise ValueError("simple_swap_region takes photos as (B,H,W,3) uint8, got shape %s" % (tuple(photo_shape),))
+    correspondence_side(int(load_size), int(load_size))
+    imageio.crop_transform_rule(xf, load_size)
+
+
+def simple_swap_region(model, photo_u8, xf, style, alphas=(1.0,), load_size=512, feather=16, style_xf=None):
+    """A swap INSIDE a photograph: photo_u8 (B,H,W,3) uint8 on the GPU, of any shape; ``xf`` the crop transforms of the region
+    (``imageio.crop_transform``: centre, side and angle of the aligned square, 1 <= side / load_size <= 8).  The content is
+    ``to_tensor_normalized(extract_similarity(photo, xf, load_size))``; ``style`` is a (B,3,h,w) tensor in [-1,1] as for
+    ``simple_swap`` or, with ``style_xf``, a uint8 photo whose region is extracted the same way.  The codes are ``swap_codes``',
+    and each alpha goes through ``decode_region``: the guided filter's coefficients at load_size, applied to the photo's own
+    pixels inside the square and feathered over ``feather`` crop pixels at its edge.  Returns {alpha: uint8 (B,H,W,3)}; every
+    byte outside the square is the photo's."""
+    region_rule(tuple(photo_u8.shape), xf, load_size)
+    from . import imageio
+    if style_xf is not None:
+        imageio.crop_transform_rule(style_xf, load_size)
+        style = imageio.to_tensor_normalized(ops.extract_similarity(style, style_xf, load_size))
+    content = imageio.to_tensor_normalized(ops.extract_similarity(photo_u8, xf, load_size))
+    sp, gl_c, gl_w = swap_codes(model, content, style)
+    out = {}
+    for alpha in alphas:
+        out[alpha] = model(sp, glue.lerp(gl_c, gl_w, alpha), content, photo_u8, xf, feather, command="decode_region")
+    return out
+
+
+def evaluate_swap_files_region(model, structure_path, texture_path, out_dir, structure_box, texture_box=None, alphas=(1.0,), load_size=512,
+                               feather=16, device="cuda", png="host", format="png", jpeg_quality=90, jpeg_subsampling="4:2:0"):
+    """``evaluate_swap_files`` for a face inside a photograph (``simple_swap_region``): the structure FILE keeps its size and
+    every pixel outside the box.  A box is (cx, cy, side, angle_deg) in the file's pixels (``imageio.crop_transform``).
+    ``structure_path`` / ``texture_path``: one path or a list each, ``structure_box`` / ``texture_box``: one box or one per path --
+    one texture (and one box) serves every structure, otherwise the lists pair up.  ``texture_box=None`` loads the texture as
+    ``evaluate_swap_files`` does (the whole file at load_size); with a box its region is extracted like the structure's.  Files
+    are read at their own size by ``load_native`` and written through write_png_batch, named as evaluate_swap_files names them;
+    a size the device encoder has no bound for is encoded on the host.  Returns the paths, structure by structure, alpha by
+    alpha."""
+    import os
+    from . import imageio
+    _check_encoder(png)
+    _check_format(format, jpeg_quality, jpeg_subsampling)
+    _check_decoder(current_decoder())
+    as_list = lambda p: [p] if isinstance(p, (str, bytes, os.PathLike)) else list(p)
+    boxes = lambda b: [tuple(b)] if not hasattr(b[0], "__len__") else [tuple(v) for v in b]
+    structures, textures, sboxes = as_list(structure_path), as_list(texture_path), boxes(structure_box)
+    tboxes = None if texture_box is None else boxes(texture_box)
+    spread = lambda v: v * len(structures) if len(v) == 1 else v
+    textures, sboxes = spread(textures), spread(sboxes)
+    tboxes = None if tboxes is None else spread(tboxes)
+    for v, what in ((textures, "texture paths"), (sboxes, "structure boxes"), (tboxes, "texture boxes")):
+        if v is not None and len(v) != len(structures):
+            raise ValueError("evaluate_swap_files_region pairs its lists: %d structure paths and %d %s" % (len(structures), len(v), what))
+    os.makedirs(out_dir, exist_ok=True)
+    to_xf = lambda box: imageio.crop_transform((box[0], box[1]), box[2], box[3] if len(box) > 3 else 0.0, load_size)
+    sxf = [to_xf(b) for b in sboxes]
+    txf = None if tboxes is None else [to_xf(b) for b in tboxes]
+    imageio.crop_transform_rule(sxf, load_size)                # (before any file is read: a bad box fails at once)
+    if txf is not None:
+        imageio.crop_transform_rule(txf, load_size)
+    photos = load_native([os.path.expanduser(p) for p in structures], device)
+    if txf is None:
+        styles = load_images([os.path.expanduser(p) for p in textures], load_size, device)
+    else:
+        tphotos = load_native([os.path.expanduser(p) for p in textures], device)
+        styles = [imageio.to_tensor_normalized(ops.extract_similarity(t[None], [x], load_size)) for t, x in zip(tphotos, txf)]
+    stem = lambda p: os.path.splitext(os.path.basename(p))[0]
+    groups = {}
+    for i, n in enumerate(photos):                             # structures of one size (and one texture size) share a batch
+        groups.setdefault((tuple(n.shape), tuple(styles[i].shape)), []).append(i)
+    paths = {}
+    for (shape, _), idx in groups.items():
+        outs = simple_swap_region(model, torch.stack([photos[i] for i in idx]), [sxf[i] for i in idx], torch.cat([styles[i] for i in idx], 0),
+                                  alphas, load_size, feather)
+        encoder = png if png == "host" or _device_encoder_takes(shape, format, jpeg_subsampling) else "host"
+        for alpha in alphas:
+            names = [os.path.join(out_dir, "%s_%s_%.2f%s" % (stem(structures[i]), stem(textures[i]), alpha, FORMATS[format])) for i in idx]
+            for i, p in zip(idx, write_png_batch(outs[alpha], names, None, encoder, format, jpeg_quality, jpeg_subsampling)):
+                paths.setdefault(i, []).append(p)
+    return [p for i in range(len(structures)) for p in paths[i]]
+
+
 def evaluate_grid_folder(model, dataroot, out_dir, rank=0, world=1, smooth=True, load_size=512, device="cuda", workers=8,
                          pair_batch=8, image_batch=8, png="host", format="png", jpeg_quality=90, jpeg_subsampling="4:2:0"):
     """evaluation/content_style_grid_generation_evaluator.py:36-99 over <dataroot>/content/* and <dataroot>/style/*: every

@@ -167,6 +167,69 @@ def preprocess_resize(img, load_size=512):
     return to_tensor_normalized(x)
 
 
+XF_ONE = 1 << 24              # one crop pixel in the integer units of a crop transform (csrc/sim_xf.h)
+
+
+def crop_transform(centre, side, angle_deg=0.0, n=512):
+    """The similarity transform of a square crop inside a photograph, as four Python ints ``(a, b, cu, cv)``: the photo pixel in
+    column X, row Y (centre X + 1/2, Y + 1/2) lies at
+
+        U =  a (2X + 1) + b (2Y + 1) + cu,     V = -b (2X + 1) + a (2Y + 1) + cv      (units of 2^-24 crop pixel)
+
+    in the frame of the n x n crop, which is the half-open square 0 <= U, V < n 2^24.  ``centre`` = (x, y) in photo pixels (pixel
+    X spans [X, X + 1)) maps to the crop's centre (n/2, n/2); ``side`` is the side of the crop square in photo pixels, so
+    s = side / n photo pixels make one crop pixel; (u, v) = R(angle) ((x, y) - centre) / s + n/2 with R = [[cos, sin], [-sin, cos]].
+    a = round(2^23 cos / s), b = round(2^23 sin / s); cu, cv put ``centre`` at (n/2, n/2) under the ROUNDED a, b, rounded at 2^-24
+    crop pixel: the map is a similarity by construction and exact at the centre, and the rounding of a, b moves a point 8192
+    photo pixels from the centre by at most 2^-10 crop pixel.
+
+    Direction: image rows grow downwards, so with a positive angle the crop SQUARE is turned clockwise on screen about its centre
+    (its top edge runs from upper left to lower right), and what it shows appears turned counter-clockwise by the same angle in the
+    crop: a face whose top leans to the viewer's right by t degrees is upright in the crop at angle_deg = t.
+
+    ``crop_transform_rule`` judges the ROUNDED integers: a turned crop of exactly s = 1 or s = 8 can land a few units of
+    a^2 + b^2 outside it (axis-aligned ones are exact); give such a crop a side 2^-20 inside the range."""
+    x, y = float(centre[0]), float(centre[1])
+    s = float(side) / n
+    if not s > 0:
+        raise ValueError("crop_transform: side must be positive, got %r" % (side,))
+    th = math.radians(float(angle_deg))
+    q = round(float(angle_deg) / 90.0)
+    if float(angle_deg) == 90.0 * q:                       # whole quarter turns: exact cos / sin
+        co, si = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[q % 4]
+    else:
+        co, si = math.cos(th), math.sin(th)
+    a, b = round((1 << 23) * co / s), round((1 << 23) * si / s)
+    cu = round(n * (1 << 23) - 2.0 * (a * x + b * y))
+    cv = round(n * (1 << 23) - 2.0 * (-b * x + a * y))
+    return a, b, cu, cv
+
+
+def crop_transform_rule(xf, n):
+    """ValueError, from the integers alone, unless every transform of ``xf`` ((4,) or (B,4) ints) has 1 <= s <= 8 photo pixels per
+    crop pixel -- 2^40 <= a^2 + b^2 <= 2^46 -- and n is a size the kernels take.  The rule of ``evaluation.native_size_rule``: the
+    filter's coefficients are upsampled, never reduced; the upper end bounds the footprint a tile of the crop kernel stages."""
+    rows = np.asarray(xf.cpu() if isinstance(xf, torch.Tensor) else xf, dtype=object).reshape(-1, 4)
+    if not 1 <= int(n) <= 4096:
+        raise ValueError("crop size n = %r is outside 1 .. 4096" % (n,))
+    for a, b, cu, cv in rows:
+        a, b, cu, cv = int(a), int(b), int(cu), int(cv)
+        d = a * a + b * b
+        if d > 1 << 46:
+            raise ValueError("crop transform (%d, %d, ..): the crop has fewer photo pixels than crop pixels (s = %.4f < 1): "
+                             "coefficients are upsampled, never reduced" % (a, b, (1 << 23) / math.sqrt(d)))
+        if d < 1 << 40:
+            raise ValueError("crop transform (%d, %d, ..): more than 8 photo pixels per crop pixel (s = %s > 8)"
+                             % (a, b, "%.4f" % ((1 << 23) / math.sqrt(d)) if d else "inf"))
+        if max(abs(cu), abs(cv)) > 1 << 56:
+            raise ValueError("crop transform offsets (%d, %d) are beyond 2^56" % (cu, cv))
+
+
+def extract_similarity(photo_u8, xf, n=512):
+    """(B,H,W,3) uint8 photo on the GPU + crop transforms -> (B,n,n,3) uint8 aligned crops (ops.extract_similarity)."""
+    return ops.extract_similarity(photo_u8, xf, n)
+
+
 def encode_png(u8):
     """(B,H,W,C) uint8 on the device (C = 1: grey, 3: RGB) -> list of B ``bytes``, each a complete PNG file.
     Two device-to-host copies per batch: the B sizes, then the batch's file slots cut at the longest file."""

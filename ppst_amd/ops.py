@@ -1801,6 +1801,77 @@ def guided_filter_apply(coeffs, guide_full_u8, want_f32=False):
     return (out_u8, out) if want_f32 else out_u8
 
 
+def _crop_transforms(xf, B, device, who):
+    """crop transforms (imageio.crop_transform) as ((B,4) int64 on the host, the same table on ``device``); one transform serves
+    every image of the batch"""
+    if isinstance(xf, torch.Tensor):
+        if xf.dtype != torch.int64:
+            raise RuntimeError("%s needs int64 crop transforms, got %s" % (who, xf.dtype))
+        host = xf.detach().cpu()
+    else:
+        host = torch.tensor([[int(v) for v in row] for row in (xf if len(xf) and hasattr(xf[0], "__len__") else [xf])], dtype=torch.int64)
+    host = host.reshape(-1, 4)
+    if host.shape[0] == 1 and B != 1:
+        host = host.expand(B, 4)
+    if host.shape[0] != B:
+        raise RuntimeError("%s needs one crop transform (a, b, cu, cv) per image: %d for a batch of %d" % (who, host.shape[0], B))
+    host = host.contiguous()
+    return host, host.to(device)
+
+
+def extract_similarity(photo_u8, xf, n=512):
+    """photo (B,H,W,3) uint8 on the GPU, ``xf`` (B,4) int64 crop transforms (imageio.crop_transform; a tensor or nested ints, one
+    row serves a whole batch) -> (B,n,n,3) uint8: the n x n crop of each photo under its similarity transform, Pillow's
+    antialiased bicubic in the crop's frame, the photo read with edge replication (csrc/imageio.hip
+    extract_similarity_kernel).  Transforms with s < 1 or s > 8 photo pixels per crop pixel are refused."""
+    if not isinstance(photo_u8, torch.Tensor) or not photo_u8.is_cuda or photo_u8.dtype != torch.uint8:
+        raise RuntimeError("extract_similarity needs a CUDA uint8 photo")
+    if photo_u8.dim() != 4 or photo_u8.shape[3] != 3:
+        raise RuntimeError("extract_similarity needs a photo (B,H,W,3), got %s" % (tuple(photo_u8.shape),))
+    photo_u8 = photo_u8.contiguous()
+    B, H, W, _ = photo_u8.shape
+    host, dev = _crop_transforms(xf, B, photo_u8.device, "extract_similarity")
+    out = torch.empty((B, int(n), int(n), 3), device=photo_u8.device, dtype=torch.uint8)
+    check(lib.ppst_extract_similarity(_p(photo_u8), B, H, W, _p(host), _p(dev), int(n), _p(out), _stream()), "ppst_extract_similarity")
+    return out
+
+
+def guided_filter_paste(coeffs, photo_u8, xf, feather=0, out=None):
+    """coeffs (B,12,n,n) fp32 (``guided_filter_coeffs`` of the crops ``extract_similarity`` took), photo (B,H,W,3) uint8, the same
+    crop transforms -> uint8 (B,H,W,3): inside each crop square the photo's own pixels re-coloured by the bilinearly interpolated
+    coefficients, blended towards the photo over ``feather`` crop pixels from the square's edge (0 <= feather <= n/2; 0: a hard
+    edge); every byte outside the square is the photo's.  One launch over the tiles of the squares' bounding boxes.  ``out``:
+    None clones the photo first; ``out=photo_u8`` works in place; any other contiguous uint8 tensor of the photo's shape is
+    filled with the photo first."""
+    if not isinstance(coeffs, torch.Tensor) or not coeffs.is_cuda or coeffs.dtype != torch.float32:
+        raise RuntimeError("guided_filter_paste needs CUDA float32 coefficients")
+    if not isinstance(photo_u8, torch.Tensor) or not photo_u8.is_cuda or photo_u8.dtype != torch.uint8:
+        raise RuntimeError("guided_filter_paste needs a CUDA uint8 photo")
+    if (coeffs.dim() != 4 or coeffs.shape[1] != 12 or coeffs.shape[2] != coeffs.shape[3] or photo_u8.dim() != 4 or photo_u8.shape[3] != 3
+            or photo_u8.shape[0] != coeffs.shape[0]):
+        raise RuntimeError("guided_filter_paste needs coefficients (B,12,n,n) and a photo (B,H,W,3) of one batch, got %s and %s"
+                           % (tuple(coeffs.shape), tuple(photo_u8.shape)))
+    B, _, n, _ = coeffs.shape
+    _, H, W, _ = photo_u8.shape
+    if out is None:
+        out = photo_u8.clone(memory_format=torch.contiguous_format)
+        photo_u8 = out                                        # (a pixel reads only its own bytes: in place is the cloned form)
+    elif out is photo_u8:
+        if not out.is_contiguous():
+            raise RuntimeError("guided_filter_paste in place needs a contiguous photo")
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.shape != photo_u8.shape or not out.is_contiguous() \
+                or out.device != photo_u8.device:
+            raise RuntimeError("guided_filter_paste: out must be a contiguous uint8 tensor of the photo's shape on its device")
+        out.copy_(photo_u8)
+        photo_u8 = out
+    host, dev = _crop_transforms(xf, B, out.device, "guided_filter_paste")
+    coeffs = coeffs.contiguous()
+    check(lib.ppst_guided_filter_paste(_p(coeffs), n, _p(photo_u8), _p(out), B, H, W, _p(host), _p(dev), int(feather), _stream()),
+          "ppst_guided_filter_paste")
+    return out
+
+
 def _encode(name, u8, limits, geom=(), settings=()):
     """What png_encode and jpeg_encode do: the slots from the library's bound, the workspace from torch's allocator, one call.
     ``geom``: the codec's arguments behind (H, W, C) of its bound and workspace; ``settings``: those of its encode call."""

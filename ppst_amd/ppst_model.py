@@ -357,6 +357,23 @@ class PPSTModel(nn.Module):
         coeffs = ops.guided_filter_coeffs(glue.tensor2im(target), glue.tensor2im(out), r, (0.02 * 255) ** 2)
         return ops.guided_filter_apply(coeffs, native_u8)
 
+    def decode_region(self, spatial_code, global_code, target, photo_u8, xf, feather=0):
+        """``decode_native`` for a crop INSIDE a photograph: ``target`` (B,3,n,n) is the normalised crop that
+        ``ops.extract_similarity(photo_u8, xf, n)`` took, and the filter's coefficients, solved at n x n as in ``decode_native``, are
+        applied to the photo's own pixels inside the crop square through the same transforms (``ops.guided_filter_paste``), blended
+        over ``feather`` crop pixels at its edge.  -> uint8 (B,H,W,3), every byte outside the square the photo's.  The radius rule
+        is ``decode_native``'s, raised from shapes before the generator runs."""
+        h, w = int(target.shape[-2]), int(target.shape[-1])
+        r = guided_filter_radius(self.opt, h, w)
+        if not 0 < r <= 64 or r >= h or r >= w or w > 2048:           # (from shapes alone, before the generator runs)
+            raise ValueError("decode_region: the coefficient planes are computed at radii 0 < r <= 64 with r < h, r < w and "
+                             "w <= 2048, got r = %d at %d x %d" % (r, h, w))
+        if h != w:
+            raise ValueError("decode_region: the crop is a square, got a target of %d x %d" % (h, w))
+        out = self.G(spatial_code, global_code, noise=self.noise)
+        coeffs = ops.guided_filter_coeffs(glue.tensor2im(target), glue.tensor2im(out), r, (0.02 * 255) ** 2)
+        return ops.guided_filter_paste(coeffs, photo_u8, xf, feather)
+
     def discriminate(self, x):
         return self.D(x)
 
