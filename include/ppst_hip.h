@@ -382,18 +382,30 @@ int ppst_conv1x1_small_cin(const void* x, const void* w, const void* bias, void*
 int ppst_conv1x1_small_cin_st(const void* x, const void* w, const void* bias, void* y,
                               int64_t npix, int cin, int in_ld, int cout, float wscale,
                               int act, int y_st /* x stays fp32: the image */, void* stream);
+/* the same conv reading the NCHW image x [B][cin][hw] itself (no layout pass in front): the same products in the same order */
+int ppst_conv1x1_small_cin_nchw_st(const void* x, const void* w, const void* bias, void* y, int B, int64_t hw, int cin, int cout,
+                                   float wscale, int act, int y_st, void* stream);
 /* ToRGB-type conv: 1x1, Cout <= 4 (stylegan2_layers.py:487-489); y NHWC [npix][cout] */
 int ppst_conv1x1_small_cout(const void* x, const void* w, const void* bias, void* y,
                             int64_t npix, int cin, int cout, float wscale, void* stream);
 int ppst_conv1x1_small_cout_st(const void* x, const void* w, const void* bias, void* y,
                                int64_t npix, int cin, int cout, float wscale, int x_st /* y stays fp32 */, void* stream);
-/* ToRGB's 1x1 conv (stylegan2_layers.py:477-495, Cout = 3) with the merge pass of the block in front of it applied ON LOAD (round 5):
- * the input is read as (a[b][c] * x + s[b][c] + bilinear_x2(res)) * out_scale -- (IN + StyleMod of conv2 + the x2-upsampled skip) /
- * sqrt2 of the last UpsamplingResnetBlock (generator.py:63-78), whose only consumer in the image pass is this conv.
- * x [B][H][W][cin] dense (storage type x_st), scale_shift [B][cin][2], res [B][H/2][W/2][res_ld] (type x_st) or NULL,
- * w [3][cin], bias [3] or NULL -> y [B][H][W][3] fp32.  Equal to ppst_affine_act (res_up2) followed by ppst_conv1x1_small_cout. */
-int ppst_torgb_apply_st(const void* x, const void* scale_shift, const void* res, int res_ld, float out_scale, const void* w,
-                        const void* bias, void* y, int B, int H, int W, int cin, float wscale, int x_st, void* stream);
+/* the same with a pixel stride in_ld (>= cin, % 4 == 0) of x: a channel slice of a wider tensor is read in place */
+int ppst_conv1x1_small_cout_ld_st(const void* x, const void* w, const void* bias, void* y, int64_t npix, int cin, int in_ld, int cout,
+                                  float wscale, int x_st, void* stream);
+/* ToRGB's 1x1 conv (stylegan2_layers.py:477-495, Cout = 3) reading the merge of the block in front of it,
+ *   (a[b][c] * x + s[b][c] + bilinear_x2(res)) * out_scale      (IN + StyleMod of conv2 + the x2-upsampled skip, / sqrt2:
+ * the last UpsamplingResnetBlock, generator.py:63-78, whose only consumer in the image pass is this conv), by linearity: the skip's
+ * share is proj = ppst_conv1x1_small_cout_ld_st(res, w, no bias, scale wscale * out_scale), [B][H/2][W/2][3] fp32, sampled x2-bilinearly
+ * where the three outputs are stored; the 128-channel merge is never formed.
+ * x [B][H][W][cin] dense (storage type x_st), scale_shift [B][cin][2] or NULL (a = 1, s = 0), proj or NULL, w [3][cin], bias [3] or
+ * NULL -> y [B][H][W][3] fp32; partial != NULL: also the instance-norm partials of y, [B][*n_partials][3][2] as ppst_in_finalize
+ * reads them.  x == y == NULL: size query (*n_partials only).  Equal to ppst_affine_act (res_up2) followed by
+ * ppst_conv1x1_small_cout up to the order of one sum.  (Replaces ppst_torgb_apply_st, which sampled res per channel of every pixel.) */
+int ppst_torgb_linear_st(const void* x, const void* scale_shift, const void* proj, float out_scale, const void* w, const void* bias,
+                        void* y, void* partial, int* n_partials, int B, int H, int W, int cin, float wscale, int x_st, void* stream);
+/* ToRGB's end: out [B][3][hw] (NCHW) = a * y + s of y [B][hw][3], scale_shift [B][3][2]: ppst_affine_act then ppst_nhwc_to_nchw */
+int ppst_rgb_affine_nchw(const void* y, const void* scale_shift, void* out, int B, int64_t hw, void* stream);
 
 /* ------------------------------------------- instance norm / style mod ---
  * nn.InstanceNorm2d (eps 1e-5, biased var) + StyleMod (stylegan2_layers.py:361-374,

@@ -917,12 +917,13 @@ extern "C" int ppst_maxpool2(const void* x, void* y, int B, int H, int W, int C,
 // --------------------------------------------------------- small 1x1 convs --
 // Cin <= 4 (FromRGB): thread = (pixel, 4 output channels).  The grid stride is a multiple of
 // cout/4, so a thread keeps its output-channel group: its 4 x cin weights and biases are loaded
-// once, the loop is one pixel read + one 16-B store.
-template <int YS = PPST_ST_F32>
+// once, the loop is one pixel read + one 16-B store.  PLANES: x is the NCHW image [B][cin][hw] itself (d_hw divides by hw) -- a
+// wave's read of a plane is contiguous, and the encoders need no layout pass in front; the same products in the same order.
+template <int YS = PPST_ST_F32, bool PLANES = false>
 __global__ __launch_bounds__(256) void conv1x1_small_cin_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                 const float* __restrict__ bias, void* __restrict__ y,
                                                                 int64_t npix, int cin, int in_ld, int cout, float wscale,
-                                                                int act, FastDiv d_c) {
+                                                                int act, FastDiv d_c, FastDiv d_hw) {
   const unsigned t0 = blockIdx.x * 256 + threadIdx.x;
   unsigned cq;
   int64_t p = fd_divmod(t0, d_c, cq);
@@ -937,8 +938,15 @@ __global__ __launch_bounds__(256) void conv1x1_small_cin_kernel(const float* __r
   }
   for (; p < npix; p += pstep) {
     float xv[4];
+    if constexpr (PLANES) {
+      unsigned pix;
+      const int64_t b = fd_divmod((unsigned)p, d_hw, pix);
 #pragma unroll
-    for (int ci = 0; ci < 4; ++ci) xv[ci] = ci < cin ? x[p * in_ld + ci] : 0.f;
+      for (int ci = 0; ci < 4; ++ci) xv[ci] = ci < cin ? x[(b * cin + ci) * d_hw.d + pix] : 0.f;
+    } else {
+#pragma unroll
+      for (int ci = 0; ci < 4; ++ci) xv[ci] = ci < cin ? x[p * in_ld + ci] : 0.f;
+    }
     float o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -950,10 +958,12 @@ __global__ __launch_bounds__(256) void conv1x1_small_cin_kernel(const float* __r
     st_st4<YS>(y, p * cout + co, make_float4(o[0], o[1], o[2], o[3]));
   }
 }
-extern "C" int ppst_conv1x1_small_cin_st(const void* x, const void* w, const void* bias, void* y, int64_t npix, int cin,
-                                         int in_ld, int cout, float wscale, int act, int y_st, void* stream) {
+// hw > 0: x is NCHW [npix / hw][cin][hw] (in_ld unused), else NHWC with pixel stride in_ld
+static int small_cin_launch(const void* x, const void* w, const void* bias, void* y, int64_t npix, int cin, int in_ld, int64_t hw,
+                            int cout, float wscale, int act, int y_st, void* stream) {
   if ((unsigned)y_st > 2u) return PPST_EINVAL;
-  if (npix < 0 || cin <= 0 || cin > 4 || in_ld < cin || cout <= 0 || cout % 4) return PPST_EINVAL;
+  if (npix < 0 || cin <= 0 || cin > 4 || cout <= 0 || cout % 4) return PPST_EINVAL;
+  if (hw > 0 ? (npix % hw != 0 || npix > PPST_IDX32_MAX) : in_ld < cin) return PPST_EINVAL;
   if (npix == 0) return PPST_OK;
   if (!x || !w || !y) return PPST_ENULL;
   const int c4n = cout / 4;
@@ -964,9 +974,24 @@ extern "C" int ppst_conv1x1_small_cin_st(const void* x, const void* w, const voi
   const int unit = c4n / g;
   int64_t blocks = (int64_t)grid_for(total);
   blocks = ((blocks + unit - 1) / unit) * unit;
-  PPST_ST_SWITCH(y_st, PPST_LAUNCH(conv1x1_small_cin_kernel<ST_>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const float*)x,
-                                   (const float*)w, (const float*)bias, y, npix, cin, in_ld, cout, wscale, act, make_fastdiv(c4n)));
+  if (hw > 0)
+    PPST_ST_SWITCH(y_st, PPST_LAUNCH((conv1x1_small_cin_kernel<ST_, true>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream),
+                                     (const float*)x, (const float*)w, (const float*)bias, y, npix, cin, in_ld, cout, wscale, act,
+                                     make_fastdiv(c4n), make_fastdiv((unsigned)hw)));
+  else
+    PPST_ST_SWITCH(y_st, PPST_LAUNCH((conv1x1_small_cin_kernel<ST_, false>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream),
+                                     (const float*)x, (const float*)w, (const float*)bias, y, npix, cin, in_ld, cout, wscale, act,
+                                     make_fastdiv(c4n), make_fastdiv(1u)));
   return PPST_LAUNCH_CHECK();
+}
+extern "C" int ppst_conv1x1_small_cin_st(const void* x, const void* w, const void* bias, void* y, int64_t npix, int cin,
+                                         int in_ld, int cout, float wscale, int act, int y_st, void* stream) {
+  return small_cin_launch(x, w, bias, y, npix, cin, in_ld, 0, cout, wscale, act, y_st, stream);
+}
+extern "C" int ppst_conv1x1_small_cin_nchw_st(const void* x, const void* w, const void* bias, void* y, int B, int64_t hw, int cin,
+                                              int cout, float wscale, int act, int y_st, void* stream) {
+  if (B < 0 || hw <= 0 || hw > PPST_IDX32_MAX) return PPST_EINVAL;
+  return small_cin_launch(x, w, bias, y, (int64_t)B * hw, cin, 0, hw, cout, wscale, act, y_st, stream);
 }
 extern "C" int ppst_conv1x1_small_cin(const void* x, const void* w, const void* bias, void* y, int64_t npix, int cin,
                                       int in_ld, int cout, float wscale, int act, void* stream) {
@@ -978,14 +1003,14 @@ extern "C" int ppst_conv1x1_small_cin(const void* x, const void* w, const void* 
 template <int XS = PPST_ST_F32>
 __global__ __launch_bounds__(256) void conv1x1_small_cout_kernel(const void* __restrict__ x, const float* __restrict__ w,
                                                                  const float* __restrict__ bias, float* __restrict__ y,
-                                                                 int64_t npix, int cin, int cout, float wscale) {
+                                                                 int64_t npix, int cin, int in_ld, int cout, float wscale) {
   const int hl = threadIdx.x & 31;
   const int64_t half_id = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 5;
   const int64_t nhalf = ((int64_t)gridDim.x * 256) >> 5;
   for (int64_t p = half_id; p < npix; p += nhalf) {
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int c = hl * 4; c < cin; c += 128) {
-      float4 v = st_ld4<XS>(x, p * cin + c);
+      float4 v = st_ld4<XS>(x, p * in_ld + c);
       for (int j = 0; j < cout; ++j) {
         float4 ww = *(const float4*)(w + (int64_t)j * cin + c);
         acc[j] += v.x * ww.x + v.y * ww.y + v.z * ww.z + v.w * ww.w;
@@ -1013,7 +1038,7 @@ __device__ __forceinline__ float dot4(const float4& a, const float4& b) {
 template <int XS = PPST_ST_F32>
 __global__ __launch_bounds__(256) void conv1x1_cout3_kernel(const void* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ bias, float* __restrict__ y,
-                                                            int64_t npix, int cin, float wscale) {
+                                                            int64_t npix, int cin, int in_ld, float wscale) {
   const int hl = threadIdx.x & 31;
   const int64_t half_id = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 5;
   const int64_t nhalf = ((int64_t)gridDim.x * 256) >> 5;
@@ -1028,7 +1053,7 @@ __global__ __launch_bounds__(256) void conv1x1_cout3_kernel(const void* __restri
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const int64_t p = p0 + k < npix ? p0 + k : npix - 1;
-        xv[k] = st_ld4<XS>(x, p * cin + c);
+        xv[k] = st_ld4<XS>(x, p * in_ld + c);
       }
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
@@ -1065,70 +1090,99 @@ __global__ __launch_bounds__(256) void conv1x1_cout3_kernel(const void* __restri
   }
 }
 
-extern "C" int ppst_conv1x1_small_cout_st(const void* x, const void* w, const void* bias, void* y, int64_t npix, int cin,
-                                          int cout, float wscale, int x_st, void* stream) {
+extern "C" int ppst_conv1x1_small_cout_ld_st(const void* x, const void* w, const void* bias, void* y, int64_t npix, int cin,
+                                             int in_ld, int cout, float wscale, int x_st, void* stream) {
   if ((unsigned)x_st > 2u || (x_st && (uintptr_t)x % 8)) return PPST_EINVAL;
-  if (npix < 0 || cin <= 0 || cin % 4 || cout <= 0 || cout > 4) return PPST_EINVAL;
+  if (npix < 0 || cin <= 0 || cin % 4 || in_ld < cin || in_ld % 4 || cout <= 0 || cout > 4) return PPST_EINVAL;
   if (npix == 0) return PPST_OK;
   if (!x || !w || !y) return PPST_ENULL;
   if (cout == 3 && ((uintptr_t)x % (x_st ? 8 : 16)) == 0 && ((uintptr_t)w % 16) == 0) {
     PPST_ST_SWITCH(x_st, PPST_LAUNCH(conv1x1_cout3_kernel<ST_>, dim3(grid_for(cdiv64(npix, 8) * 32)), dim3(256), 0, as_stream(stream), x,
-                                     (const float*)w, (const float*)bias, (float*)y, npix, cin, wscale));
+                                     (const float*)w, (const float*)bias, (float*)y, npix, cin, in_ld, wscale));
     return PPST_LAUNCH_CHECK();
   }
   PPST_ST_SWITCH(x_st, PPST_LAUNCH(conv1x1_small_cout_kernel<ST_>, dim3(grid_for(npix * 32)), dim3(256), 0, as_stream(stream),
-                                   x, (const float*)w, (const float*)bias, (float*)y, npix, cin, cout, wscale));
+                                   x, (const float*)w, (const float*)bias, (float*)y, npix, cin, in_ld, cout, wscale));
   return PPST_LAUNCH_CHECK();
+}
+extern "C" int ppst_conv1x1_small_cout_st(const void* x, const void* w, const void* bias, void* y, int64_t npix, int cin,
+                                          int cout, float wscale, int x_st, void* stream) {
+  return ppst_conv1x1_small_cout_ld_st(x, w, bias, y, npix, cin, cin, cout, wscale, x_st, stream);
 }
 extern "C" int ppst_conv1x1_small_cout(const void* x, const void* w, const void* bias, void* y, int64_t npix, int cin,
                                        int cout, float wscale, void* stream) {
-  return ppst_conv1x1_small_cout_st(x, w, bias, y, npix, cin, cout, wscale, PPST_ST_F32, stream);
+  return ppst_conv1x1_small_cout_ld_st(x, w, bias, y, npix, cin, cin, cout, wscale, PPST_ST_F32, stream);
 }
 
 
-// ToRGB's 1x1 conv (Cout = 3) with the producer's merge pass applied ON LOAD (round 5): the input is read as
-//   x_eff = (a[b][c] * x + s[b][c] + bilinear_up2(res)) * out_scale
-// -- the (IN + StyleMod of conv2 + x2-upsampled skip) / sqrt2 of the last UpsamplingResnetBlock (generator.py:63-78), whose only
-// consumer in the image pass is this conv: the 128-channel 512^2 tensor is neither written nor read back.  Same lane / butterfly
-// scheme as conv1x1_cout3_kernel; the apply arithmetic is affine_act_kernel's, in its order.
+// ToRGB (Cout = 3) of the image pass with the last upsampling block's merge taken apart by linearity.  The block's output is
+//   m = (a[b][c] * x + s[b][c] + up2(res)) * out_scale                      (IN + StyleMod of conv2, + the x2-bilinear skip, / sqrt2)
+// and ToRGB is its only consumer there.  The conv and the fixed-weight x2 bilinear are both linear, so they commute:
+//   y_j = wscale * sum_c w_jc (a x + s) out_scale  +  up2(P)_j  +  bias_j ,   P_j = wscale * out_scale * sum_c w_jc res_c
+// P [B][H/2][W/2][3] is conv1x1_cout3_kernel over the skip at ITS resolution (a quarter of the pixels); this kernel keeps
+// affine_act_kernel's a*x + s per element, in its order, and samples a 3-channel tensor once per stored value: the merged
+// 128-channel tensor is neither written nor read, and no skip element is sampled per channel (the round-5 form of this kernel did
+// that: four 16-byte loads per lane per pixel, 256 registers, one wave per SIMD, 1.09 ms against 0.59 + 0.22 for the two passes).
+// Lane and butterfly scheme of conv1x1_cout3_kernel.  A block owns TORGB_CHUNK pixels of ONE image (grid y = image): a group of 8
+// pixels never crosses an image (the last group of an image is ragged, its pixels clamped), the (a, s) pairs and weights of a lane's
+// channel slice are loaded once per block when cin <= 128 (once per channel iteration beyond), and the block can emit the
+// instance-norm partials (sum, sum of squares) of its three outputs as ppst_in_finalize reads them: [B][n][3][2].
+// ss == NULL: a = 1, s = 0 (with out_scale = 1 and P == NULL the plain ToRGB conv, with the partials).
+#define TORGB_CHUNK 512
 template <int XS = PPST_ST_F32>
-__global__ __launch_bounds__(256) void conv1x1_cout3_apply_kernel(const void* __restrict__ x, const float* __restrict__ ss,
-                                                                  const void* __restrict__ res, int res_ld, float out_scale,
-                                                                  const float* __restrict__ w, const float* __restrict__ bias,
-                                                                  float* __restrict__ y, int64_t npix, int H, int W, int cin, float wscale,
-                                                                  FastDiv d_hw, FastDiv d_w) {
-  const int hl = threadIdx.x & 31;
-  const int64_t half_id = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 5;
-  const int64_t nhalf = ((int64_t)gridDim.x * 256) >> 5;
+__global__ __launch_bounds__(256) void conv1x1_cout3_lin_kernel(const void* __restrict__ x, const float* __restrict__ ss,
+                                                                const float* __restrict__ proj, float out_scale,
+                                                                const float* __restrict__ w, const float* __restrict__ bias,
+                                                                float* __restrict__ y, float* __restrict__ partial, int H, int W, int cin,
+                                                                float wscale, FastDiv d_w) {
+  __shared__ float sm[4][3][2];
+  const int hl = threadIdx.x & 31, half = threadIdx.x >> 5;
+  const int b = blockIdx.y;
+  const int hw = H * W;
+  const int pbeg = blockIdx.x * TORGB_CHUNK;
+  const int pend = pbeg + TORGB_CHUNK < hw ? pbeg + TORGB_CHUNK : hw;
+  const int64_t img = (int64_t)b * hw;
   const int b4 = (hl >> 4) & 1, b3 = (hl >> 3) & 1, b2 = (hl >> 2) & 1;
-  const unsigned hw = (unsigned)H * (unsigned)W;
-  for (int64_t p0 = half_id * 8; p0 < npix; p0 += nhalf * 8) {
+  const int k = b4 * 4 + b3 * 2 + b2, j = hl & 3;
+  const bool once = cin <= 128;
+  float4 w0, w1, w2, q0 = make_float4(1.f, 0.f, 1.f, 0.f), q1 = q0;
+  w0 = w1 = w2 = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (once && hl * 4 < cin) {
+    const int c = hl * 4;
+    w0 = *(const float4*)(w + c); w1 = *(const float4*)(w + (int64_t)cin + c); w2 = *(const float4*)(w + 2 * (int64_t)cin + c);
+    if (ss) {
+      const float4* q = (const float4*)(ss + ((int64_t)b * cin + c) * 2);
+      q0 = q[0]; q1 = q[1];
+    }
+  }
+  const float bj = (bias && j < 3) ? bias[j] : 0.f;
+  float st_s = 0.f, st_q = 0.f;
+  for (int p0 = pbeg + half * 8; p0 < pend; p0 += 64) {
     float v[24];
 #pragma unroll
     for (int i = 0; i < 24; ++i) v[i] = 0.f;
     for (int c = hl * 4; c < cin; c += 128) {
-      const float4 w0 = *(const float4*)(w + c), w1 = *(const float4*)(w + (int64_t)cin + c), w2 = *(const float4*)(w + 2 * (int64_t)cin + c);
+      if (!once) {
+        w0 = *(const float4*)(w + c); w1 = *(const float4*)(w + (int64_t)cin + c); w2 = *(const float4*)(w + 2 * (int64_t)cin + c);
+        if (ss) {
+          const float4* q = (const float4*)(ss + ((int64_t)b * cin + c) * 2);
+          q0 = q[0]; q1 = q[1];
+        }
+      }
       float4 xv[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int64_t p = p0 + k < npix ? p0 + k : npix - 1;
-        unsigned pix, oxu;
-        const int b = (int)fd_divmod((unsigned)p, d_hw, pix);
-        const int oy = (int)fd_divmod(pix, d_w, oxu);
-        const float4 xr = st_ld4<XS>(x, p * cin + c);
-        const float4* q = (const float4*)(ss + ((int64_t)b * cin + c) * 2);
-        const float4 q0 = q[0], q1 = q[1];
-        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (res) r = res_up2_sample<XS>(res, b, oy, (int)oxu, H, W, res_ld, c);
-        float t0 = q0.x * xr.x + q0.y, t1 = q0.z * xr.y + q0.w, t2 = q1.x * xr.z + q1.y, t3 = q1.z * xr.w + q1.w;
-        t0 += r.x; t1 += r.y; t2 += r.z; t3 += r.w;
-        xv[k] = make_float4(t0 * out_scale, t1 * out_scale, t2 * out_scale, t3 * out_scale);
+      for (int kk = 0; kk < 8; ++kk) {
+        const int p = p0 + kk < hw ? p0 + kk : hw - 1;
+        xv[kk] = st_ld4<XS>(x, (img + p) * cin + c);
       }
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        v[k * 3 + 0] += dot4(xv[k], w0);
-        v[k * 3 + 1] += dot4(xv[k], w1);
-        v[k * 3 + 2] += dot4(xv[k], w2);
+      for (int kk = 0; kk < 8; ++kk) {
+        const float4 xr = xv[kk];
+        const float t0 = q0.x * xr.x + q0.y, t1 = q0.z * xr.y + q0.w, t2 = q1.x * xr.z + q1.y, t3 = q1.z * xr.w + q1.w;
+        const float4 xe = make_float4(t0 * out_scale, t1 * out_scale, t2 * out_scale, t3 * out_scale);
+        v[kk * 3 + 0] += dot4(xe, w0);
+        v[kk * 3 + 1] += dot4(xe, w1);
+        v[kk * 3 + 2] += dot4(xe, w2);
       }
     }
 #pragma unroll
@@ -1151,27 +1205,89 @@ __global__ __launch_bounds__(256) void conv1x1_cout3_apply_kernel(const void* __
       v[i] += __shfl_xor(v[i], 2, 64);
       v[i] += __shfl_xor(v[i], 1, 64);
     }
-    const int k = b4 * 4 + b3 * 2 + b2, j = hl & 3;
-    if (j < 3 && p0 + k < npix) {
+    const int p = p0 + k;
+    if (j < 3 && p < hw) {
       const float r = j == 0 ? v[0] : (j == 1 ? v[1] : v[2]);
-      y[(p0 + k) * 3 + j] = r * wscale + (bias ? bias[j] : 0.f);
+      float o = fmaf(r, wscale, bj);                // (conv1x1_cout3_kernel's r * wscale + bias, as hipcc contracts it)
+      if (proj) {                                   // res_up2_sample's four taps and edge clamps, on the 3-channel P
+        unsigned oxu;
+        const int oy = (int)fd_divmod((unsigned)p, d_w, oxu), ox = (int)oxu;
+        const int h2 = H >> 1, w2n = W >> 1;
+        const float fy = fmaxf(((float)oy + 0.5f) * 0.5f - 0.5f, 0.f), fx = fmaxf(((float)ox + 0.5f) * 0.5f - 0.5f, 0.f);
+        const int y0 = (int)fy, x0 = (int)fx;
+        const int y1 = y0 + (y0 < h2 - 1), x1 = x0 + (x0 < w2n - 1);
+        const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
+        const float* pb = proj + (int64_t)b * h2 * w2n * 3 + j;
+        const float v00 = pb[((int64_t)y0 * w2n + x0) * 3], v01 = pb[((int64_t)y0 * w2n + x1) * 3];
+        const float v10 = pb[((int64_t)y1 * w2n + x0) * 3], v11 = pb[((int64_t)y1 * w2n + x1) * 3];
+        o = fmaf(r, wscale, hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11)) + bj;
+      }
+      y[(img + p) * 3 + j] = o;
+      st_s += o;
+      st_q += o * o;
+    }
+  }
+  if (partial) {        // (kernel argument: the whole block takes the branch)
+#pragma unroll
+    for (int o = 4; o < 64; o <<= 1) {              // the 2 x 8 pixel slots of a wave; the channel j = lane & 3 stays
+      st_s += __shfl_xor(st_s, o, 64);
+      st_q += __shfl_xor(st_q, o, 64);
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane < 3) { sm[wave][lane][0] = st_s; sm[wave][lane][1] = st_q; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+      float s = sm[0][threadIdx.x][0], q = sm[0][threadIdx.x][1];
+#pragma unroll
+      for (int r = 1; r < 4; ++r) { s += sm[r][threadIdx.x][0]; q += sm[r][threadIdx.x][1]; }
+      float* o = partial + (((int64_t)b * gridDim.x + blockIdx.x) * 3 + threadIdx.x) * 2;
+      o[0] = s; o[1] = q;
     }
   }
 }
-// x [B][H][W][cin] (storage x_st, dense), scale_shift [B][cin][2], res [B][H/2][W/2][res_ld] or NULL (same storage type),
-// w [3][cin], bias [3] or NULL -> y [B][H][W][3] fp32
-extern "C" int ppst_torgb_apply_st(const void* x, const void* scale_shift, const void* res, int res_ld, float out_scale, const void* w,
-                                   const void* bias, void* y, int B, int H, int W, int cin, float wscale, int x_st, void* stream) {
+// x [B][H][W][cin] (storage x_st, dense), scale_shift [B][cin][2] or NULL, proj [B][H/2][W/2][3] fp32 or NULL (the skip's projection:
+// ppst_conv1x1_small_cout_ld_st on it with scale wscale * out_scale and no bias), w [3][cin], bias [3] or NULL -> y [B][H][W][3] fp32 and,
+// with partial != NULL, its instance-norm partials [B][*n_partials][3][2].  x == y == NULL: only *n_partials is set.
+extern "C" int ppst_torgb_linear_st(const void* x, const void* scale_shift, const void* proj, float out_scale, const void* w,
+                                    const void* bias, void* y, void* partial, int* n_partials, int B, int H, int W, int cin,
+                                   float wscale, int x_st, void* stream) {
   if ((unsigned)x_st > 2u) return PPST_EINVAL;
-  if (B < 0 || H <= 0 || W <= 0 || cin <= 0 || cin % 4 || (res && (H % 2 || W % 2 || res_ld < cin || res_ld % 4))) return PPST_EINVAL;
+  if (B < 0 || B > 65535 || H <= 0 || W <= 0 || cin <= 0 || cin % 4 || (proj && (H % 2 || W % 2))) return PPST_EINVAL;
+  if ((int64_t)H * W > 0x7fffffffll - TORGB_CHUNK) return PPST_EINVAL;
+  const int nchunks = (int)cdiv64((int64_t)H * W, TORGB_CHUNK);
+  if (n_partials) *n_partials = nchunks;
+  if (!x && !y) return PPST_OK;  // size query
   if (B == 0) return PPST_OK;
-  if (!x || !scale_shift || !w || !y) return PPST_ENULL;
-  const int64_t npix = (int64_t)B * H * W;
-  if (npix > PPST_IDX32_MAX) return PPST_EINVAL;
-  if (((uintptr_t)x | (uintptr_t)res) % (x_st ? 8 : 16) || ((uintptr_t)w | (uintptr_t)scale_shift) % 16) return PPST_EINVAL;
-  PPST_ST_SWITCH(x_st, PPST_LAUNCH(conv1x1_cout3_apply_kernel<ST_>, dim3(grid_for(cdiv64(npix, 8) * 32)), dim3(256), 0, as_stream(stream), x,
-                                   (const float*)scale_shift, res, res_ld, out_scale, (const float*)w, (const float*)bias, (float*)y, npix,
-                                   H, W, cin, wscale, make_fastdiv((unsigned)H * (unsigned)W), make_fastdiv((unsigned)W)));
+  if (!x || !w || !y) return PPST_ENULL;
+  if ((uintptr_t)x % (x_st ? 8 : 16) || ((uintptr_t)w | (uintptr_t)scale_shift) % 16) return PPST_EINVAL;
+  PPST_ST_SWITCH(x_st, PPST_LAUNCH(conv1x1_cout3_lin_kernel<ST_>, dim3(nchunks, B), dim3(256), 0, as_stream(stream), x,
+                                   (const float*)scale_shift, (const float*)proj, out_scale, (const float*)w, (const float*)bias, (float*)y,
+                                   (float*)partial, H, W, cin, wscale, make_fastdiv((unsigned)W)));
+  return PPST_LAUNCH_CHECK();
+}
+
+// The end of ToRGB: y [B][hw][3] (the conv's output) normalised as ppst_affine_act does it (a * y + s, scale_shift [B][3][2]) and
+// stored as the NCHW image [B][3][hw] -- the apply pass and the layout pass in one; a thread per pixel, three coalesced plane stores.
+__global__ __launch_bounds__(256) void rgb_affine_nchw_kernel(const float* __restrict__ y, const float* __restrict__ ss,
+                                                              float* __restrict__ out, unsigned hw, unsigned total, FastDiv d_hw) {
+  for (uint64_t t64 = (uint64_t)blockIdx.x * 256 + threadIdx.x; t64 < total; t64 += (uint64_t)gridDim.x * 256) {
+    const unsigned t = (unsigned)t64;
+    unsigned pix;
+    const int b = (int)fd_divmod(t, d_hw, pix);
+    const float* sp = ss + (int64_t)b * 6;
+    const float* yp = y + (int64_t)t * 3;
+    float* op = out + (int64_t)b * 3 * hw + pix;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) op[(int64_t)i * hw] = sp[i * 2] * yp[i] + sp[i * 2 + 1];
+  }
+}
+extern "C" int ppst_rgb_affine_nchw(const void* y, const void* scale_shift, void* out, int B, int64_t hw, void* stream) {
+  if (B < 0 || hw <= 0 || (int64_t)B * hw > PPST_IDX32_MAX) return PPST_EINVAL;
+  if (B == 0) return PPST_OK;
+  if (!y || !scale_shift || !out) return PPST_ENULL;
+  const int64_t total = (int64_t)B * hw;
+  PPST_LAUNCH(rgb_affine_nchw_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), (const float*)y, (const float*)scale_shift,
+              (float*)out, (unsigned)hw, (unsigned)total, make_fastdiv((unsigned)hw));
   return PPST_LAUNCH_CHECK();
 }
 

@@ -138,6 +138,14 @@ class BaseNetwork(nn.Module):
         w = self.p(p + "Conv.weight")
         return ops.conv1x1_small_cin(x, w, self.p(p + "Act.bias"), 1.0 / math.sqrt(w.shape[1]), ops.ACT_LRELU, out_dtype=out_dtype)
 
+    def from_rgb_image(self, img, p, out_dtype=torch.float32):
+        """from_rgb of the NCHW image itself: a contiguous NCHW tensor is read plane by plane by the conv (no layout pass in front);
+        a permuted NHWC tensor takes the NHWC form as before."""
+        if img.dim() == 4 and img.is_contiguous() and not img.permute(0, 2, 3, 1).is_contiguous():
+            w = self.p(p + "Conv.weight")
+            return ops.conv1x1_small_cin_nchw(img, w, self.p(p + "Act.bias"), 1.0 / math.sqrt(w.shape[1]), ops.ACT_LRELU, out_dtype=out_dtype)
+        return self.from_rgb(to_nhwc(img), p, out_dtype=out_dtype)
+
     def _norm_act(self, y, st, count, act_bias=None, act=ops.ACT_NONE, **kw):
         ss = ops.in_finalize(st, count, post_bias=act_bias)
         return ops.affine_act(y, ss, act=act, **kw), ss

@@ -39,7 +39,7 @@ class StyleGAN2ResnetEncodercol(BaseNetwork):
         return ops.l2norm_rows_grouped(v, 1e-12, 1)
 
     def trunk(self, x, dtype=torch.float32):
-        feats = [self.from_rgb(to_nhwc(x), "FromRGB.", out_dtype=dtype)]
+        feats = [self.from_rgb_image(x, "FromRGB.", out_dtype=dtype)]
         for i in range(3):
             feats.append(self.res_block(feats[-1], "DownToGlobalCode1.ResBlockDownBy%d." % (2 ** i), ops.PAD_REFLECT, norm=False))
         return feats

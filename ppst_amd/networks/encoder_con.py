@@ -7,14 +7,14 @@ import math
 import torch
 
 from .. import ops
-from .base_network import BaseNetwork, as_nchw, to_nhwc
+from .base_network import BaseNetwork, as_nchw
 
 
 class StyleGAN2ResnetEncodercon(BaseNetwork):
     prefix = "E1."
 
     def forward(self, x, extract_features=False, patch_ids=None):
-        x = self.from_rgb(to_nhwc(x), "FromRGB.", out_dtype=ops.act_dtype())
+        x = self.from_rgb_image(x, "FromRGB.", out_dtype=ops.act_dtype())
         for i in range(3):
             x = self.res_block(x, "DownToSpatialCode.ResBlockDownBy%d." % (2 ** i), ops.PAD_REFLECT, norm=True)
         B, H, W, C = x.shape

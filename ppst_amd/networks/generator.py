@@ -237,12 +237,18 @@ class StyleGAN2ResnetGenerator(BaseNetwork):
         wr = self.p("ToRGB.conv.weight")
         brgb = self.cached(("rgbb",), [self.p("ToRGB.conv.bias"), self.p("ToRGB.bias")],
                            lambda: (self.p("ToRGB.conv.bias") + self.p("ToRGB.bias").reshape(-1)).contiguous())
-        if last_merge is not None:
-            y = ops.torgb_apply(x, last_merge[0], last_merge[1], INV_SQRT2, wr, brgb, 1.0 / math.sqrt(wr.shape[1]))
+        wsc = 1.0 / math.sqrt(wr.shape[1])
+        if ops.FUSE_TAIL["value"]:
+            # the conv leaves the instance-norm partials of its three outputs; one pass normalises them and stores the NCHW image
+            if last_merge is not None:
+                y, st = ops.torgb_apply(x, last_merge[0], last_merge[1], INV_SQRT2, wr, brgb, wsc, stats=True)
+            else:
+                y, st = ops.torgb_apply(x, None, None, 1.0, wr, brgb, wsc, stats=True)
+            rgb = ops.rgb_affine_nchw(y, ops.in_finalize(st, y.shape[1] * y.shape[2], style=styles["ToRGB."]))
         else:
-            y = ops.conv1x1_small_cout(x, wr, brgb, 1.0 / math.sqrt(wr.shape[1]))
-        ss = ops.in_finalize(ops.in_stats(y), y.shape[1] * y.shape[2], style=styles["ToRGB."])
-        rgb = ops.nhwc_to_nchw(ops.affine_act(y, ss))
+            y = ops.conv1x1_small_cout(x, wr, brgb, wsc)
+            ss = ops.in_finalize(ops.in_stats(y), y.shape[1] * y.shape[2], style=styles["ToRGB."])
+            rgb = ops.nhwc_to_nchw(ops.affine_act(y, ss))
         if not extract_features:
             return rgb
         for i in range(3):

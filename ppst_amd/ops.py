@@ -90,10 +90,13 @@ class batch_aware:
 # with S = 2 -- its 128 accumulator registers per thread make the hand-over twice as large; tests/conv_ksplit_time.py)
 WINO = {"value": True, "min_blocks": 16, "fill": 0, "ksplit_fill": 64}
 # round 5: apply passes whose only consumer is a 1x1 conv are applied by that conv while it loads -- layert1's resnet merge by
-# layert1.1 (ConvPlan in_res), the last upsampling block's merge by ToRGB in the image pass (torgb_apply).  Off: the round-4 passes.
-# "torgb": measured SLOWER (rocprofv3, batch-8 swap step: 1.09 ms against 0.56 + 0.23 for the pass + the conv -- the 32-lanes-per-pixel ToRGB
-# kernel becomes instruction-bound with the bilinear skip sampled per element) -- built, tested (t_fuse_tail), off
-FUSE_TAIL = {"value": os.environ.get("PPST_FUSE_TAIL", "1") != "0", "torgb": os.environ.get("PPST_FUSE_TORGB", "0") == "1"}
+# layert1.1 (ConvPlan in_res), the last upsampling block's merge by ToRGB in the image pass (torgb_apply); ToRGB's conv leaves the
+# instance-norm partials of its output and one pass normalises them into the NCHW image.  Off: the round-4 passes.
+# "torgb": ToRGB is linear and so is the x2 bilinear, so the skip is projected to 3 channels at its own resolution and the projection
+# sampled where the outputs are stored (rocprofv3, batch-8 swap step: 0.07 + 0.19 ms against 0.59 + 0.22 for the merge pass + the conv;
+# the round-5 form sampled the skip per channel of every pixel and took 1.09 ms).  On: swap step 48.79 -> 48.00 ms, fp16 36.85 ->
+# 35.99, hires 39.52 -> 37.23 (profiles/torgb_linear_ab.txt).  PPST_FUSE_TORGB=0: the merge pass + the plain conv.
+FUSE_TAIL = {"value": os.environ.get("PPST_FUSE_TAIL", "1") != "0", "torgb": os.environ.get("PPST_FUSE_TORGB", "1") != "0"}
 FAT_MIN_BLOCKS = 32         # take the 256-channel tile only when ONE image still gives >= this many blocks (B = 8: one per CU)
 
 
@@ -1019,38 +1022,73 @@ def conv1x1_small_cin(x, w, bias, wscale, act, out_dtype=torch.float32):
     return y
 
 
+def conv1x1_small_cin_nchw(x, w, bias, wscale, act, out_dtype=torch.float32):
+    """conv1x1_small_cin reading the NCHW image x (B,cin,H,W) itself -> (B,H,W,cout): no layout pass in front."""
+    _chk(x, "x")
+    B, cin, H, W = x.shape
+    if not x.is_contiguous():
+        raise RuntimeError("conv1x1_small_cin_nchw needs a contiguous NCHW tensor")
+    cout = w.shape[0]
+    y = torch.empty((B, H, W, cout), device=x.device, dtype=out_dtype)
+    w2 = w.detach().reshape(cout, cin).contiguous()
+    check(lib.ppst_conv1x1_small_cin_nchw_st(_p(x), _p(w2), _p(bias), _p(y), B, H * W, cin, cout, float(wscale), act, _ST[out_dtype],
+                                             _stream()), "ppst_conv1x1_small_cin_nchw")
+    return y
+
+
 def conv1x1_small_cout(x, w, bias, wscale):
+    """x (B,H,W,cin) or a channel slice of a wider tensor (pixel stride a multiple of 4)"""
     ld = _nhwc_ld(x, half_ok=True)
     B, H, W, cin = x.shape
-    assert ld == cin
     cout = w.shape[0]
     y = torch.empty((B, H, W, cout), device=x.device, dtype=torch.float32)
     w2 = w.detach().reshape(cout, cin).contiguous()
-    check(lib.ppst_conv1x1_small_cout_st(_p(x), _p(w2), _p(bias), _p(y), B * H * W, cin, cout, float(wscale), _ST[x.dtype], _stream()),
+    check(lib.ppst_conv1x1_small_cout_ld_st(_p(x), _p(w2), _p(bias), _p(y), B * H * W, cin, ld, cout, float(wscale), _ST[x.dtype], _stream()),
           "ppst_conv1x1_small_cout")
     return y
 
 
-def torgb_apply(x, scale_shift, res, out_scale, w, bias, wscale):
-    """ToRGB's 1x1 conv reading (a*x + s + bilinear_x2(res)) * out_scale (ppst_torgb_apply_st): x (B,H,W,C) dense, res (B,H/2,W/2,C)
-    or None (x's storage type) -> (B,H,W,3) fp32."""
+def torgb_apply(x, scale_shift, res, out_scale, w, bias, wscale, stats=False):
+    """ToRGB's 1x1 conv reading (a*x + s + bilinear_x2(res)) * out_scale: x (B,H,W,C) dense, scale_shift (B,C,2) or None, res
+    (B,H/2,W/2,C) (x's storage type; may be a channel slice) or None -> (B,H,W,3) fp32.  By linearity (ppst_torgb_linear_st): the skip
+    is projected to 3 channels at its own resolution (conv1x1_small_cout, scale wscale * out_scale) and that projection is sampled
+    where the outputs are stored.  stats: also returns the instance-norm partials (B, n, 3, 2) of the output."""
     ld = _nhwc_ld(x, half_ok=True)
     B, H, W, cin = x.shape
     if ld != cin or w.shape[0] != 3:
         raise RuntimeError("torgb_apply needs a dense input and a 3-channel weight")
     _chk(scale_shift, "scale_shift"); _chk(bias, "bias")
-    res_ld = 0
+    proj = None
     if res is not None:
-        res_ld = _nhwc_ld(res, "res", half_ok=True)
-        if res.dtype != x.dtype or tuple(res.shape) != (B, H // 2, W // 2, cin):
+        if res.dtype != x.dtype or tuple(res.shape) != (B, H // 2, W // 2, cin) or H % 2 or W % 2:
             raise RuntimeError("torgb_apply: res must be the half-resolution tensor of x's type")
-    if tuple(scale_shift.shape) != (B, cin, 2) or not scale_shift.is_contiguous():
+        proj = conv1x1_small_cout(res, w, None, float(wscale) * float(out_scale))
+    if scale_shift is not None and (tuple(scale_shift.shape) != (B, cin, 2) or not scale_shift.is_contiguous()):
         raise RuntimeError("torgb_apply: scale_shift must be a contiguous (B, C, 2) table")
     y = torch.empty((B, H, W, 3), device=x.device, dtype=torch.float32)
     w2 = w.detach().reshape(3, cin).contiguous()
-    check(lib.ppst_torgb_apply_st(_p(x), _p(scale_shift), _p(res), res_ld, float(out_scale), _p(w2), _p(bias), _p(y), B, H, W, cin,
-                                  float(wscale), _ST[x.dtype], _stream()), "ppst_torgb_apply")
-    return y
+    if w2.data_ptr() % 16:          # a view into a flat parameter buffer (the trainers'): the kernel loads 16-byte weight items
+        w2 = w2.clone()
+    n = ctypes.c_int(0)
+    part = None
+    if stats:
+        check(lib.ppst_torgb_linear_st(None, None, None, 1.0, None, None, None, None, ctypes.byref(n), B, H, W, cin, 1.0, 0, None),
+              "ppst_torgb_linear(size)")
+        part = torch.empty((B, n.value, 3, 2), device=x.device, dtype=torch.float32)
+    check(lib.ppst_torgb_linear_st(_p(x), _p(scale_shift), _p(proj), float(out_scale), _p(w2), _p(bias), _p(y), _p(part), ctypes.byref(n),
+                                  B, H, W, cin, float(wscale), _ST[x.dtype], _stream()), "ppst_torgb_linear")
+    return (y, part) if stats else y
+
+
+def rgb_affine_nchw(y, scale_shift):
+    """ToRGB's end: y (B,H,W,3), scale_shift (B,3,2) -> the image (B,3,H,W) = nhwc_to_nchw(affine_act(y, scale_shift)) in one pass."""
+    _chk(y, "y"); _chk(scale_shift, "scale_shift")
+    B, H, W, C = y.shape
+    if C != 3 or not y.is_contiguous() or tuple(scale_shift.shape) != (B, 3, 2) or not scale_shift.is_contiguous():
+        raise RuntimeError("rgb_affine_nchw needs a dense (B,H,W,3) tensor and a contiguous (B,3,2) table")
+    out = torch.empty((B, 3, H, W), device=y.device, dtype=torch.float32)
+    check(lib.ppst_rgb_affine_nchw(_p(y), _p(scale_shift), _p(out), B, H * W, _stream()), "ppst_rgb_affine_nchw")
+    return out
 
 
 def upscale_weight_bwd(dw4, cout, cin, scale=1.0, out=None, accumulate=False):
