@@ -102,7 +102,8 @@ int ppst_upfirdn2d(const void* x, const void* k, void* y,
  * in_scale_shift (optional, [B][C][2] (a, s)) + in_act (PPST_ACT_NONE / PPST_ACT_LRELU):
  * the input is read as in_act(a*x + s) -- the InstanceNorm + FusedLeakyReLU that
  * ConvLayer(norm='in') puts in front of the Blur (:542-549) without a pass of its own;
- * zero-padding positions stay 0. */
+ * zero-padding positions stay 0.  x and y: 16-byte aligned in fp32, 8-byte aligned in a
+ * half type, or PPST_EINVAL -- there is no one-channel form behind this entry. */
 int ppst_blur_nhwc(const void* x, const void* k, void* y, int B, int in_h, int in_w, int C,
                    int ksize, int pad0, int pad1, int pad_mode, int down, int s2d,
                    const void* in_scale_shift, int in_act, void* stream);

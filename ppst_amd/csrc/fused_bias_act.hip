@@ -41,7 +41,12 @@ __global__ __launch_bounds__(256) void fused_bias_act_kernel(const void* __restr
       float v = st_ld1<ST>(x, i);
       if (b) v += st_ld1<ST>(b, (i / step_b) % size_b);
       float r = ref ? st_ld1<ST>(ref, i) : 0.f;
-      st_st1<ST>(y, i, fba_one(v, r, mode, alpha) * scale);
+      float o = fba_one(v, r, mode, alpha) * scale;
+      // fp16: the product is an fp32 value before it is rounded to the storage type.  Left to itself the compiler fuses the multiply
+      // and the conversion into one v_fma_mixlo_f16 (o * scale + 0, rounded once to fp16): another value next to a tie and +0 where
+      // the product is -0 -- not the fp32 launch on the widened input rounded once (include/ppst_hip.h), which the vec form is
+      if (ST == PPST_ST_F16) asm volatile("" : "+v"(o));
+      st_st1<ST>(y, i, o);
     }
   }
 }

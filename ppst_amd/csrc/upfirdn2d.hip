@@ -556,12 +556,14 @@ extern "C" int ppst_upfirdn2d(const void* x, const void* k, void* y, int major, 
     UF_HALF(PPST_ST_BF16);
 #undef UF_HALF
   }
+  // the four-channel forms read and write float4: off the 16-byte grid the call falls to the generic kernel (the planes form is scalar)
+  const bool al16 = (((uintptr_t)x | (uintptr_t)y) % 16) == 0;
+  if (minor != 1 && !al16) fast = down2 = false;
   if (fast && kh == 3) return launch_fast<3, 3>(xf, yf, p, st);
   if (fast && kh == 4) return launch_fast<4, 4>(xf, yf, p, st);
   if (down2 && kh == 3) return launch_chan<3, 3>(xf, yf, p, 2, false, st);
   if (down2 && kh == 4) return launch_chan<4, 4>(xf, yf, p, 2, false, st);
-  if (up_x == 2 && up_y == 2 && down_x == 1 && down_y == 1 && minor % 4 == 0 && n / 4 <= PPST_IDX32_MAX &&
-      (((uintptr_t)x | (uintptr_t)y) % 16) == 0) {
+  if (up_x == 2 && up_y == 2 && down_x == 1 && down_y == 1 && minor % 4 == 0 && n / 4 <= PPST_IDX32_MAX && al16) {
     int64_t b4 = cdiv64(n / 4, 256);
     if (b4 > 256 * 32) b4 = 256 * 32;
     PPST_LAUNCH(upfirdn2d_up2_chan<PPST_ST_F32>, dim3((unsigned)b4), dim3(256), 0, st, (const void*)xf, (void*)yf, p, (unsigned)(n / 4),
@@ -605,7 +607,8 @@ extern "C" int ppst_blur_nhwc_st(const void* x, const void* k, void* y, int B, i
   static const bool c8_4x4 = getenv("PPST_UF_C8_4X4") != nullptr;
   const bool c8 = st != PPST_ST_F32 && C % 8 == 0 && (((uintptr_t)x | (uintptr_t)y) % 16) == 0 && (ksize == 3 || c8_4x4);
   if (st != PPST_ST_F32 && (((uintptr_t)x | (uintptr_t)y) % 8)) return PPST_EINVAL;
-#define UF_GO(K_)                                                                                             \
+  if (st == PPST_ST_F32 && (((uintptr_t)x | (uintptr_t)y) % 16)) return PPST_EINVAL;   // float4 items and no generic form here
+#define UF_GO(K_)                                                                                            \
   do {                                                                                                        \
     if (st == PPST_ST_F16) return c8 ? launch_chan<K_, K_, PPST_ST_F16, 8>(x, y, p, down, s2d != 0, as_stream(stream))   \
                                      : launch_chan<K_, K_, PPST_ST_F16, 4>(x, y, p, down, s2d != 0, as_stream(stream));  \

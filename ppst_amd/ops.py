@@ -228,11 +228,21 @@ def _chk_op(t, name):
         raise RuntimeError("%s must be float32, float16, bfloat16 or float64, got %s" % (name, t.dtype))
 
 
-def upfirdn2d_raw(x4, kernel, up_x, up_y, down_x, down_y, px0, px1, py0, py1):
+def _raw_out(out, shape, like):
+    """the destination of a native op: a fresh tensor, or the caller's dense ``out`` of that shape and type"""
+    if out is None:
+        return torch.empty(shape, device=like.device, dtype=like.dtype)
+    _chk_op(out, "out")
+    if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or not out.is_contiguous():
+        raise RuntimeError("out must be a dense %s tensor of shape %s" % (like.dtype, tuple(shape)))
+    return out
+
+
+def upfirdn2d_raw(x4, kernel, up_x, up_y, down_x, down_y, px0, px1, py0, py1, out=None):
     """x4: [major, H, W, minor] contiguous (upfirdn2d.cpp:4-23). Returns [major, oh, ow, minor].  float32, float16, bfloat16
     or float64 like the reference's AT_DISPATCH_FLOATING_TYPES_AND_HALF (upfirdn2d_kernel.cu:225); for the 16- and 32-bit types
     the taps are used as fp32 and the products accumulate in fp32 (the reference accumulates in the tensor's type), rounded once
-    to the input's type; float64: taps and accumulation in double."""
+    to the input's type; float64: taps and accumulation in double.  ``out``: write into this tensor."""
     _chk_op(x4, "input")
     _chk_op(kernel, "kernel")
     x4 = x4.contiguous()
@@ -242,7 +252,7 @@ def upfirdn2d_raw(x4, kernel, up_x, up_y, down_x, down_y, px0, px1, py0, py1):
     kh, kw = kernel.shape
     out_h = (in_h * up_y + py0 + py1 - kh + down_y) // down_y
     out_w = (in_w * up_x + px0 + px1 - kw + down_x) // down_x
-    y = torch.empty((major, out_h, out_w, minor), device=x4.device, dtype=x4.dtype)
+    y = _raw_out(out, (major, out_h, out_w, minor), x4)
     check(lib.ppst_upfirdn2d(_p(x4), _p(kernel), _p(y), major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y,
                              px0, px1, py0, py1, _DT_F64 if f64 else _ST[x4.dtype], _stream()), "ppst_upfirdn2d")
     return y
@@ -267,17 +277,17 @@ def blur_nhwc(x, kernel, pad0, pad1, pad_mode=PAD_ZERO, down=1, s2d=False, in_ss
     return y, (oh, ow)
 
 
-def fused_bias_act_raw(x, b, ref, act, grad, alpha, scale):
+def fused_bias_act_raw(x, b, ref, act, grad, alpha, scale, out=None):
     """fused.fused_bias_act (fused_bias_act.cpp:4-20): empty tensor == absent.  float32, float16 or bfloat16 (the reference:
     AT_DISPATCH_FLOATING_TYPES_AND_HALF, fused_bias_act_kernel.cu:79): bias and refer take the input's type, fp32 arithmetic,
-    one rounding.  float64 (round 5): arithmetic in double."""
+    one rounding.  float64 (round 5): arithmetic in double.  ``out``: write into this tensor."""
     _chk_op(x, "input")
     x = x.contiguous()
     b = None if (b is None or b.numel() == 0) else b.to(x.dtype).contiguous()
     ref = None if (ref is None or ref.numel() == 0) else ref.to(x.dtype).contiguous()
     _chk_op(b, "bias")
     _chk_op(ref, "refer")
-    y = torch.empty_like(x)
+    y = _raw_out(out, x.shape, x)
     step_b = 1
     for i in range(2, x.dim()):
         step_b *= x.size(i)

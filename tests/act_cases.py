@@ -1233,6 +1233,20 @@ _FACETS = {"in_stats": _is_facets, "affine_act_stats": _as_facets, "gap_gmp": _g
            "blur_nhwc": _bn_facets}
 
 
+def register(op, spec, cases, out_st=None, border=None, facets=None):
+    """another table's op (tests/fir_cases.py) judged by this module's machinery: its cases resolve through ``by_id`` -- and so through
+    ``inputs``, ``reference``, ``bar``, ``judge``, ``mutations`` -- without joining CASES, the table of tests/test_gpu_act.py"""
+    assert op not in OPS and not any(c.id in _BY_ID for c in cases)
+    OPS[op] = spec
+    _BY_ID.update((c.id, c) for c in cases)
+    if out_st is not None:
+        OUT_ST[op] = out_st
+    if border is not None:
+        BORDER[op] = border
+    if facets is not None:
+        _FACETS[op] = facets
+
+
 def by_id(cid):
     return _BY_ID[cid]
 

@@ -1,0 +1,276 @@
+"""No GPU: the references, the inputs and the bars of tests/test_gpu_fir.py are proven here before the device is trusted by them
+(tests/fir_cases.py): 105 cases (71 of ppst_upfirdn2d, 34 of ppst_fused_bias_act), 34 launch forms (27 + 7), 53 facets, 22 kinds
+of seeded defect (13 + 9).
+  * ``upfirdn_ref`` equals the oracle's upfirdn2d_full on every case, its output-side twin ``upfirdn_gather`` equals it on every
+    small case, and both references reproduce the stored outputs of tests/golden/ops.npz and ops_f64.npz at the bars of
+    tests/test_oracle_golden.py;
+  * every form the two dispatchers can pick and every facet inside a form has a case: FORMS and FACETS are compared for equality;
+  * every seeded defect of every case is rejected by the comparison the GPU test uses, at the GPU test's bar, on the case's own
+    inputs -- and the float64 reference itself, rounded once to the output's storage type, passes it;
+  * the float32 evaluation of every reference passes the bar taken from it;
+  * gate operands stay off the boundary, the reference operand of mode 31 disagrees in sign with x on about half of the elements,
+    stored operands are what their storage type holds;
+  * ``fir._adjoint_pad`` equals float64 autograd of ``upfirdn_ref`` over a grid of geometries, most of whose adjoints crop.
+"""
+import itertools
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+import fir_cases as C  # noqa: E402
+
+IDS = [c.id for c in C.CASES]
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+FORMS = {"f64:generic", "generic:f32", "generic:f16", "generic:bf16", "up2_chan:f32", "up2_chan:f16", "up2_chan:bf16", "chan:k4:slide:f16",
+         "chan:k4:slide:bf16", "fba:f64"}
+FORMS |= {"planes:k%d:%s" % (k, s) for k in (3, 4) for s in ("f32", "f16", "bf16")}
+FORMS |= {"chan:k%d:%s:%s" % (k, f, s) for k in (3, 4) for f in ("plain", "down2") for s in ("f32", "f16", "bf16")}
+FORMS |= {"fba:%s:%s" % (f, s) for f in ("vec", "scalar") for s in ("f32", "f16", "bf16")}
+
+FACETS = {
+    "generic:kh!=kw", "generic:taps-1", "generic:taps-2", "generic:taps-5", "generic:taps-8", "generic:up2-minor1", "generic:up_x!=up_y",
+    "generic:down3", "generic:down_x!=down_y", "generic:minor6", "generic:up2-off-grid", "generic:blur-off-grid", "generic:down2-off-grid",
+    "generic:second-trip", "pad:pad0<0", "pad:pad1<0", "pad:both<0", "pad:px!=py", "planes:one-tile", "planes:32x64-exact",
+    "planes:33x65-seams", "planes:seams", "planes:1x1-out", "planes:input-smaller-than-the-taps", "up2:odd-in", "up2:even-in",
+    "up2:adjoint-k3-p10", "up2:adjoint-k4-p11", "up2:adjoint-k4-p21", "up2:adjoint-k4-p22", "up2:second-trip", "major=1",
+    "slide:last-band-partial", "slide:last-band-full",
+    "fba:mode-30", "fba:mode-31", "fba:mode-32", "fba:mode-10", "fba:mode-11", "fba:mode-12", "fba:no-bias", "fba:step_b%4==0", "fba:step_b-35",
+    "fba:2-D", "fba:scalar-by-n", "fba:scalar-by-step_b", "fba:scalar-by-pointer", "fba:alpha-0", "fba:alpha-0.2", "fba:alpha-1.5", "fba:scale!=1",
+    "fba:vec:second-trip", "fba:scalar:second-trip",
+}
+
+DEFECTS = {
+    "upfirdn2d": {"taps not flipped", "taps transposed", "px and py exchanged", "up_x and up_y exchanged", "a crop treated as zero padding",
+                  "zero-insert phase off by one", "decimation starting at sample 1", "last row not written", "last column not written",
+                  "the row after a 32-row seam taken from the row above", "the column after a 64-column seam taken from the column before",
+                  "last sliding band dropped", "second-trip elements left zero"},
+    "fba": {"gate by x instead of ref", "bias index without / step_b", "bias of element 0 of a 4-group used where step_b % 4 != 0",
+            "scale applied before the activation", "alpha ignored", "modes 12 and 32 returning x", "modes 12 and 32 taken as grad 0",
+            "last element not written", "second-trip elements left zero"},
+}
+
+
+def _of(op):
+    return [c for c in C.CASES if c.op == op]
+
+
+def _close(a, b, tol=1e-12):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    s = max(np.abs(b).max(), 1e-300)
+    assert np.abs(a - b).max() <= tol * s, np.abs(a - b).max() / s
+
+
+# ------------------------------------------------------------------------------------------------------ reference checks
+@pytest.mark.parametrize("c", _of("upfirdn2d"), ids=lambda c: c.id)
+def test_reference_is_the_oracle_upfirdn2d_full(c):
+    import ppst_oracle as O
+    inp, p = C.inputs(c.id), c.p
+    want = O.upfirdn2d_full(inp["x"].double().permute(0, 3, 1, 2), inp["k"].double(), *p["up"], *p["down"], *p["pads"])
+    assert tuple(want.shape[2:]) == C.uf_out_hw(p)
+    _close(C.reference(c.id)["y"], want.permute(0, 2, 3, 1).numpy())
+    if not C.is_big(c):
+        _close(C.upfirdn_gather(inp["x"], inp["k"], p["up"], p["down"], p["pads"], C.uf_out_hw(p)).numpy(), C.reference(c.id)["y"])
+
+
+@pytest.mark.parametrize("c", [c for c in _of("fba") if not C.is_big(c)], ids=lambda c: c.id)
+def test_fba_reference_is_the_element_loop(c):
+    """the kernel's contract written out element by element in Python floats (fused_bias_act_kernel.cu:19-49)"""
+    inp, p = C.inputs(c.id), c.p
+    n, step_b, size_b = C.fba_geom(p)
+    x = inp["x"].double().reshape(-1).tolist()
+    b = inp["b"].double().tolist() if "b" in inp else None
+    r = inp["ref"].double().reshape(-1).tolist() if "ref" in inp else None
+    alpha, scale, mode = float(np.float32(p["alpha"])), float(np.float32(p["scale"])), C.fba_mode(p)
+    want = []
+    for i in range(n):
+        v = x[i] + (b[(i // step_b) % size_b] if b is not None else 0.0)
+        f = {30: v if v > 0 else v * alpha, 31: (v if r[i] > 0 else v * alpha) if r is not None else None, 32: 0.0, 12: 0.0}.get(mode, v)
+        want.append(f * scale)
+    assert np.array_equal(C.reference(c.id)["y"].reshape(-1), np.asarray(want))
+
+
+def test_references_reproduce_the_golden_vectors():
+    g = np.load(os.path.join(GOLD, "ops.npz"))
+    g64 = np.load(os.path.join(GOLD, "ops_f64.npz"))
+    for gold, rtol, atol in ((g, 1e-5, 2e-6), (g64, 1e-13, 1e-14)):
+        assert int(gold["upfirdn2d.n"]) > 0
+        for i in range(int(gold["upfirdn2d.n"])):
+            x, k = torch.from_numpy(gold["upfirdn2d.%d.x" % i]), torch.from_numpy(gold["upfirdn2d.%d.k" % i])
+            u, d, p0, p1 = [int(v) for v in gold["upfirdn2d.%d.cfg" % i]]
+            N, Cc, H, W = x.shape
+            y = C.upfirdn_ref(x.reshape(N * Cc, H, W, 1), k, (u, u), (d, d), (p0, p1, p0, p1), x.dtype)
+            want = torch.from_numpy(gold["upfirdn2d.%d.y" % i])
+            assert torch.allclose(y.reshape(N, Cc, *y.shape[1:3]), want, rtol=rtol, atol=atol), (i, u, d, p0, p1)
+    # fused_leaky_relu = act 3, grad 0 (forward) and grad 1 gated by the saved output; the stored vectors come from the reference's
+    # Python fallback, which multiplies by Python doubles: abi=False (the C-float rounding of 2 ** 0.5 is 1.7e-8 away)
+    for gold, dt, rtol, atol in ((g, torch.float32, 1e-6, 1e-7), (g64, torch.float64, 1e-14, 1e-15)):
+        x, b = torch.from_numpy(gold["flrelu.x"]), torch.from_numpy(gold["flrelu.b"])
+        step_b = int(np.prod(x.shape[2:]))
+        y = C.fba_ref(x, b, None, 30, 0.2, 2 ** 0.5, step_b, dt, abi=False)
+        assert torch.allclose(y, torch.from_numpy(gold["flrelu.y"]), rtol=rtol, atol=atol)
+        gx = C.fba_ref(torch.from_numpy(gold["flrelu.g"]), None, y, 31, 0.2, 2 ** 0.5, step_b, dt, abi=False)
+        assert torch.allclose(gx, torch.from_numpy(gold["flrelu.gx"]), rtol=rtol, atol=atol)
+    x2, b2 = torch.from_numpy(g["flrelu2.x"]), torch.from_numpy(g["flrelu2.b"])
+    assert torch.allclose(C.fba_ref(x2, b2, None, 30, 0.1, 1.5, 1, torch.float32, abi=False), torch.from_numpy(g["flrelu2.y"]), rtol=1e-6, atol=1e-7)
+
+
+# ----------------------------------------------------------------------------------------------------------- sensitivity
+@pytest.mark.parametrize("cid", IDS)
+def test_bar_passes_the_reference_and_rejects_every_seeded_defect(cid):
+    c = C.by_id(cid)
+    ref = C.reference(cid)
+    for k, v in ref.items():
+        bad, _ = C.judge(c, k, C.as_stored(c, k, v))
+        assert not bad, "%s: the reference, rounded once to its storage type, misses its own bar: %s" % (k, bad)
+    muts = C.mutations(c)
+    assert len(muts) >= 2, "a case carries at least two seeded defects"
+    for name, out in muts:
+        assert name in DEFECTS[c.op], name
+        bad, _ = C.judge(c, "y", C.as_stored(c, "y", out["y"]))
+        assert bad, "the inputs of %s cannot show the defect '%s' at the bar" % (cid, name)
+
+
+@pytest.mark.parametrize("cid", [c.id for c in C.CASES if c.p["st"] != "f64"])
+def test_float32_evaluation_passes_its_own_bar(cid):
+    c = C.by_id(cid)
+    r32 = C.A.OPS[c.op].ref(c, C.inputs(cid), torch.float32)
+    for k, v in r32.items():
+        bad, _ = C.judge(c, k, C.as_stored(c, k, v.double().numpy()))
+        assert not bad, (k, bad)
+
+
+def test_every_listed_kind_of_defect_occurs():
+    kinds = {op: set() for op in DEFECTS}
+    for c in C.CASES:
+        kinds[c.op].update(n for n, _ in C.mutations(c))
+    assert kinds == DEFECTS
+
+
+def test_float64_bound_rejects_a_float32_evaluation():
+    """the derived bound is a bound of double arithmetic: the same reference evaluated in float32 is far outside it"""
+    for c in C.CASES:
+        if c.p["st"] != "f64" or (c.op == "fba" and C.fba_mode(c.p) in (12, 32)):
+            continue
+        r32 = C.A.OPS[c.op].ref(c, C.inputs(c.id), torch.float32)["y"].double().numpy()
+        assert C.judge(c, "y", r32)[0], c.id
+
+
+def test_bars_print():
+    for c in C.CASES:
+        if c.p["st"] != "f64":
+            b, e = C.bar(c, "y"), C.err32(c.id)["y"]
+            print("%-64s bar %.2e  (float32 reference error %.2e)  %s" % (c.id, b, e, C.branch_of(c)))
+            assert b < 1e-5, "a bar this wide says the case is ill-conditioned: fix the inputs"
+
+
+# ---------------------------------------------------------------------------------------------------------------- inputs
+def test_gate_operands_stay_off_the_boundary_and_ref_is_independent_of_x():
+    for c in _of("fba"):
+        inp, p = C.inputs(c.id), c.p
+        n, step_b, size_b = C.fba_geom(p)
+        if C.fba_mode(p) == 30:
+            v = inp["x"].reshape(-1)
+            if "b" in inp:
+                v = v + inp["b"][(torch.arange(n) // step_b) % size_b]          # in the operands' own type, as the kernel adds them
+            assert float(v.abs().min()) >= 1e-3, c.id
+        if C.fba_mode(p) == 31:
+            assert float(inp["ref"].abs().min()) >= 1e-3, c.id
+            v = inp["x"].double().reshape(-1)
+            if "b" in inp:
+                v = v + inp["b"].double()[(torch.arange(n) // step_b) % size_b]
+            differ = float(((v > 0) != (inp["ref"].reshape(-1) > 0)).double().mean())
+            assert 0.3 < differ < 0.7, (c.id, differ)
+
+
+def test_stored_operands_are_what_their_storage_type_holds():
+    for c in C.CASES:
+        st = c.p["st"]
+        for k, v in C.inputs(c.id).items():
+            assert v.dtype == (torch.float64 if st == "f64" else torch.float32), (c.id, k)
+            if st in C.A.HALF and k != "k":                    # (the taps cross the boundary as fp32)
+                assert torch.equal(v, v.to(C.A.HALF[st]).float()), (c.id, k)
+
+
+def test_taps_are_asymmetric():
+    for c in _of("upfirdn2d"):
+        k = C.inputs(c.id)["k"]
+        if k.numel() > 1:
+            assert not torch.equal(k, torch.flip(k, [0, 1])) and bool((k > 0).any()) and bool((k < 0).any()), c.id
+            assert k.shape[0] != k.shape[1] or not torch.equal(k, k.t()), c.id
+
+
+# -------------------------------------------------------------------------------------------------------------- coverage
+def test_every_form_and_every_facet_has_a_case():
+    assert {C.branch_of(c) for c in C.CASES} == FORMS and len(FORMS) == 34
+    assert {f for c in C.CASES for f in C.facets_of(c)} == FACETS
+
+
+def test_the_counts_of_the_module_docstring():
+    assert (len(C.CASES), len(_of("upfirdn2d")), len(_of("fba"))) == (105, 71, 34)
+    assert len({f for f in FORMS if not f.startswith("fba")}) == 27 and len({f for f in FORMS if f.startswith("fba")}) == 7
+    assert len(FACETS) == 53
+    assert (len(DEFECTS["upfirdn2d"]), len(DEFECTS["fba"])) == (13, 9)
+
+
+def test_the_table_of_the_issue_is_present():
+    uf, fb = _of("upfirdn2d"), _of("fba")
+    big = [c for c in C.CASES if C.is_big(c)]
+    assert len(big) == 4 and all("second-trip" in c.id for c in big)
+    assert all(C.out_numel(c) * C.ITEM[c.p["st"]] <= 35e6 for c in big)
+    assert all(C.out_numel(c) <= 1 << 15 for c in C.CASES if not C.is_big(c))
+    # each reason for the scalar form of fused_bias_act is the only reason of some case; alpha 0, 0.2, 1.5; a scale that is not 1
+    assert {tuple(C.fba_reasons(c.p)) for c in fb if c.p["st"] != "f64"} >= {(), ("n",), ("step_b",), ("pointer",)}
+    assert {c.p["alpha"] for c in fb} == {0.0, 0.2, 1.5} and any(c.p["scale"] < 0 for c in fb)
+    # the generic kernel on half storage: minor > 1, kh != kw, up_x != up_y, down = 3
+    for st in ("f16", "bf16"):
+        gen = [c for c in uf if C.branch_of(c) == "generic:" + st]
+        assert any(c.p["C"] > 1 for c in gen) and any(c.p["k"][0] != c.p["k"][1] for c in gen) and any(c.p["up"][0] != c.p["up"][1] for c in gen)
+        assert any(3 in c.p["down"] for c in gen)
+        assert any("planes:33x65-seams" in C.facets_of(c) and c.p["st"] == st for c in uf)
+    # the pad pairs BlurDownFn.backward emits at H, W in {8, 9}; most of them crop
+    adj = [c for c in uf if c.p.get("adj")]
+    assert {c.p["adj"][:3] for c in adj} == {(3, 1, 0), (4, 1, 1), (4, 2, 1), (4, 2, 2)} and {c.p["adj"][3:] for c in adj} == {(8, 9), (9, 8)}
+    assert all(C.branch_of(c).startswith("up2_chan") for c in adj)
+    for c in adj:
+        ks, p0, p1, H, W = c.p["adj"]
+        assert C.uf_out_hw(c.p) == (H, W)
+
+
+# ------------------------------------------------------------------------------------------------- fir._adjoint_pad
+_GRID_HW = ((5, 7), (6, 9), (1, 1), (2, 3), (11, 4))
+_GRID_K = ((1, 1), (2, 2), (3, 3), (4, 4), (5, 3), (2, 4))
+_GRID_PAD = ((0, 0), (1, 1), (2, 1), (1, 0), (2, 2), (-1, -1), (3, -1), (-1, 2))
+
+
+def test_adjoint_pad_is_float64_autograd_of_the_reference():
+    """the geometry every backward of the op is launched with (stylegan2_op/fir.py): the gradient of ``upfirdn_ref`` with respect to
+    its input IS ``upfirdn_ref`` of the output gradient with the flipped taps, up and down exchanged and ``_adjoint_pad``'s pads"""
+    from ppst_amd.stylegan2_op.fir import _adjoint_pad
+    g = torch.Generator().manual_seed(7)
+    seen = crops = 0
+    for (ih, iw), (kh, kw), u, d, (p0, p1) in itertools.product(_GRID_HW, _GRID_K, (1, 2, 3), (1, 2, 3), _GRID_PAD):
+        pads = (p0, p1, p0, p1)
+        oh, ow = C.uf_out_hw(dict(H=ih, W=iw, k=(kh, kw), up=(u, u), down=(d, d), pads=pads))
+        if oh <= 0 or ow <= 0 or ih * u + p0 + p1 < kh or iw * u + p0 + p1 < kw:
+            continue
+        x = torch.randn(2, ih, iw, 3, generator=g, dtype=torch.float64, requires_grad=True)
+        k = torch.randn(kh, kw, generator=g, dtype=torch.float64)
+        y = C.upfirdn_ref(x, k, (u, u), (d, d), pads)
+        assert tuple(y.shape[1:3]) == (oh, ow)
+        gy = torch.randn(y.shape, generator=g, dtype=torch.float64)
+        gx = torch.autograd.grad(y, x, gy)[0] if y.requires_grad else torch.zeros_like(x)      # (no sample inside the crop: y == 0)
+        gpad = _adjoint_pad((ih, iw), (oh, ow), (kh, kw), (u, u), (d, d), pads)
+        got = C.upfirdn_ref(gy, torch.flip(k, [0, 1]), (d, d), (u, u), gpad)
+        assert got.shape == gx.shape, ((ih, iw), (kh, kw), u, d, pads, gpad)
+        assert float((got - gx).abs().max()) <= 1e-12 * max(float(gx.abs().max()), 1e-300), ((ih, iw), (kh, kw), u, d, pads, gpad)
+        seen += 1
+        crops += min(gpad) < 0
+    print("%d geometries, %d of them with a negative adjoint pad" % (seen, crops))
+    assert seen > 1500 and crops > seen // 2
