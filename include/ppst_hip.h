@@ -987,6 +987,26 @@ int ppst_guided_filter_apply(const void* coeffs, int h, int w, const void* guide
  * ppst_extract_similarity. */
 int ppst_guided_filter_paste(const void* coeffs, int n, const void* photo_u8, void* out_u8, int B, int H, int W,
                              const void* xf_host, const void* xf_dev, int feather, void* stream);
+/* the same paste through a matte: matte_f32 fp32 [B][n][n] in the crop's frame (ppst_label_matte, or the caller's own, whose
+ * values the caller keeps in [0, 1]: nothing is clamped here).  ppst_guided_filter_paste's arithmetic with g = g_edge * m^, m^ the
+ * matte sampled by the same taps, fractions and clamps as the 12 coefficient planes (horizontally, then vertically);
+ * out = clamp(rint(g q + (1 - g) I), 0, 255).  A pixel with g == 0 is NOT written: its byte stays the caller's, and a non-finite
+ * coefficient where the matte is 0 cannot leak.  The refusals of ppst_guided_filter_paste, and PPST_ENULL for a null matte. */
+int ppst_guided_filter_paste_matte(const void* coeffs, const void* matte_f32, int n, const void* photo_u8, void* out_u8, int B, int H,
+                                   int W, const void* xf_host, const void* xf_dev, int feather, void* stream);
+/* a feathered matte from a label map: the exact, clipped, signed Euclidean distance transform of "label kept", then a smoothstep.
+ * labels_u8 uint8 [B][h][w]; a pixel is INSIDE iff its label L < 32 and bit L of ``keep`` is set (labels >= 32 are outside whatever
+ * keep says).  R = max(grow, max(feather - grow, 0)) + 1.  D2(p) = min(R^2, min |p - q|^2) over the pixels q OF THE PLANE whose
+ * inside-ness differs from p's (the plane's edge is no boundary; no such pixel: D2 = R^2).  sd2_i32 int32 [B][h][w] = + D2 for an
+ * inside pixel, - D2 for an outside one (exact).  sd = sign (sqrt(D2) - 1/2): the boundary lies midway between pixel centres.
+ * matte_f32 fp32 [B][h][w] (may be NULL): feather > 0: t = clamp((sd + grow) / feather, 0, 1), m = t^2 (3 - 2t); feather == 0:
+ * m = 1 if sd + grow > 0, else 0.  grow = 0 feathers inwards only (outside pixels get exactly 0); grow = feather / 2 centres the
+ * ramp on the boundary.  Clipping at R^2 never changes m (csrc/matte.hip shows why).  Two launches, nothing allocated: sd2_i32 is
+ * required and holds the packed column distances between them.
+ * PPST_EINVAL: B < 0, h or w outside [1, 4096], feather or grow outside [0, 255].  B == 0: PPST_OK before any pointer is looked
+ * at.  PPST_ENULL: labels_u8 or sd2_i32 NULL.  Nothing is launched in any of these cases. */
+int ppst_label_matte(const void* labels_u8, int B, int h, int w, unsigned int keep, int feather, int grow, void* sd2_i32,
+                     void* matte_f32, void* stream);
 
 /* local-affine photo smoothing (smooth_filter.py:332-378 smooth_local_affine and its three NVRTC kernels :149-321):
  * output (stylised), input (content = guide), result: planar fp32 [B][3][H][W]; model_ws: >= ppst_smooth_local_affine_ws()

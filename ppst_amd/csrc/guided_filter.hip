@@ -749,14 +749,19 @@ extern "C" int ppst_guided_filter_apply(const void* coeffs, int h, int w, const 
 // rows and columns limited to the plane, so fewer near the crop's edge), a thread reads its 4 taps x 12 planes as 12 16-byte
 // reads.  A 32 x 16 tile would need up to 37 x 37 samples at 45 degrees and s = 1 -- 65.7 KB, more than a block may declare.
 // Every staged index is clamped to the plane and every local index to the footprint.
+// Through a matte (ppst_guided_filter_paste_matte; MATTE = true, the same body): the matte plane [B][n][n] is a 13th plane with
+// the same footprint, staged in an array of its own (24 x 24 floats = 2,304 B: the 12-plane array keeps its 48-byte pixels and
+// 16-byte reads) and sampled by the same taps and fractions; g = g_edge m^, and a pixel with g == 0 is left unwritten.
 #include "sim_xf.h"
 #define GP_T 16
 #define GP_FS 24
 
-__global__ __launch_bounds__(GP_T * GP_T) void gf_paste_kernel(const float* __restrict__ coef, int n, const unsigned char* photo,
-                                                               unsigned char* out, int B, int H, int W,
+template <bool MATTE>
+__global__ __launch_bounds__(GP_T * GP_T) void gf_paste_kernel(const float* __restrict__ coef, const float* __restrict__ matte, int n,
+                                                               const unsigned char* photo, unsigned char* out, int B, int H, int W,
                                                                const int64_t* __restrict__ xf, int feather) {
   __shared__ __attribute__((aligned(16))) float fp[GP_FS * GP_FS * 12];
+  __shared__ float fm[MATTE ? GP_FS * GP_FS : 1];
   const int t = threadIdx.x;
   const int64_t p = (int64_t)n * n, side = (int64_t)n * SX_ONE;
   for (int b = blockIdx.y; b < B; b += gridDim.y) {
@@ -794,6 +799,7 @@ __global__ __launch_bounds__(GP_T * GP_T) void gf_paste_kernel(const float* __re
       d[0] = make_float4(v[0], v[1], v[2], v[3]);
       d[1] = make_float4(v[4], v[5], v[6], v[7]);
       d[2] = make_float4(v[8], v[9], v[10], v[11]);
+      if (MATTE) fm[lr * GP_FS + lc] = matte[(int64_t)b * p + (s - cb)];
     }
     __syncthreads();
     const int X = X0 + (t % GP_T), Y = Y0 + (t / GP_T);
@@ -828,9 +834,14 @@ __global__ __launch_bounds__(GP_T * GP_T) void gf_paste_kernel(const float* __re
           const float tt = fminf(fmaxf((float)d * (1.f / 16777216.f) / (float)feather, 0.f), 1.f);
           g = tt * tt * (3.f - 2.f * tt);
         }
+        if (MATTE) {
+          const float mt = gx * fm[r0 * GP_FS + c0] + fx * fm[r0 * GP_FS + c1], mb = gx * fm[r1 * GP_FS + c0] + fx * fm[r1 * GP_FS + c1];
+          g *= gy * mt + fy * mb;
+        }
         const float I[3] = {I0, I1, I2};
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
+          if (MATTE && g == 0.f) break;                                          // (unwritten: the byte stays the caller's)
           const float A0 = gy * top[c * 4] + fy * bot[c * 4], A1 = gy * top[c * 4 + 1] + fy * bot[c * 4 + 1];
           const float A2 = gy * top[c * 4 + 2] + fy * bot[c * 4 + 2], Bc = gy * top[c * 4 + 3] + fy * bot[c * 4 + 3];
           const float qv = A0 * I0 + A1 * I1 + A2 * I2 + Bc;
@@ -842,11 +853,12 @@ __global__ __launch_bounds__(GP_T * GP_T) void gf_paste_kernel(const float* __re
   }
 }
 
-extern "C" int ppst_guided_filter_paste(const void* coeffs, int n, const void* photo_u8, void* out_u8, int B, int H, int W,
-                                        const void* xf_host, const void* xf_dev, int feather, void* stream) {
+template <bool MATTE>
+static int gf_paste(const void* coeffs, const void* matte, int n, const void* photo_u8, void* out_u8, int B, int H, int W,
+                    const void* xf_host, const void* xf_dev, int feather, void* stream) {
   if (B < 0 || n <= 0 || n > SX_NMAX || H <= 0 || W <= 0 || (int64_t)H * W > SX_MAXPIX || feather < 0 || 2 * feather > n) return PPST_EINVAL;
   if (B == 0) return PPST_OK;
-  if (!coeffs || !photo_u8 || !out_u8 || !xf_host || !xf_dev) return PPST_ENULL;
+  if (!coeffs || (MATTE && !matte) || !photo_u8 || !out_u8 || !xf_host || !xf_dev) return PPST_ENULL;
   const SimXf* f = (const SimXf*)xf_host;
   int64_t tiles = 0;
   for (int b = 0; b < B; ++b) {
@@ -859,9 +871,20 @@ extern "C" int ppst_guided_filter_paste(const void* coeffs, int n, const void* p
     tiles = nt > tiles ? nt : tiles;
   }
   if (tiles == 0) return PPST_OK;                                             // no quad meets its photo
-  PPST_LAUNCH(gf_paste_kernel, dim3((unsigned)tiles, (unsigned)(B > 65535 ? 65535 : B)), dim3(GP_T * GP_T), 0, as_stream(stream),
-              (const float*)coeffs, n, (const unsigned char*)photo_u8, (unsigned char*)out_u8, B, H, W, (const int64_t*)xf_dev, feather);
+  PPST_LAUNCH((gf_paste_kernel<MATTE>), dim3((unsigned)tiles, (unsigned)(B > 65535 ? 65535 : B)), dim3(GP_T * GP_T), 0, as_stream(stream),
+              (const float*)coeffs, (const float*)matte, n, (const unsigned char*)photo_u8, (unsigned char*)out_u8, B, H, W,
+              (const int64_t*)xf_dev, feather);
   return PPST_LAUNCH_CHECK();
+}
+
+extern "C" int ppst_guided_filter_paste(const void* coeffs, int n, const void* photo_u8, void* out_u8, int B, int H, int W,
+                                        const void* xf_host, const void* xf_dev, int feather, void* stream) {
+  return gf_paste<false>(coeffs, nullptr, n, photo_u8, out_u8, B, H, W, xf_host, xf_dev, feather, stream);
+}
+
+extern "C" int ppst_guided_filter_paste_matte(const void* coeffs, const void* matte_f32, int n, const void* photo_u8, void* out_u8,
+                                              int B, int H, int W, const void* xf_host, const void* xf_dev, int feather, void* stream) {
+  return gf_paste<true>(coeffs, matte_f32, n, photo_u8, out_u8, B, H, W, xf_host, xf_dev, feather, stream);
 }
 
 // (the revision history is at PPST_ABI_VERSION in include/ppst_hip.h; callers built against another revision must rebuild)

@@ -596,9 +596,47 @@ def simple_swap_region(model, photo_u8, xf, style, alphas=(1.0,), load_size=512,
     ``simple_swap`` or, with ``style_xf``, a uint8 photo whose region is extracted the same way.  The codes are ``swap_codes``',
     and each alpha goes through ``decode_region``: the guided filter's coefficients at load_size, applied to the photo's own
     pixels inside the square and feathered over ``feather`` crop pixels at its edge.  Returns {alpha: uint8 (B,H,W,3)}; every
-    byte outside the square is the photo's."""
+    byte outside the square is the photo's.  ``simple_swap_region_matte`` blends through a matte of the face instead of the whole
+    square."""
+    return simple_swap_region_matte(model, photo_u8, xf, style, alphas, load_size, feather, style_xf)
+
+
+def crop_labels(labels, B, load_size):
+    """Label maps of the crops as (B,n,n) uint8, n == load_size: (B,n,n) uint8 / int64, or one-hot (B,C,n,n) arg-maxed as
+    ``metrics.colour_stats`` does.  Raises ValueError from shapes and dtypes alone."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() not in (3, 4):
+        raise ValueError("labels are a (B,n,n) uint8 / int64 tensor or one-hot (B,C,n,n), got %s"
+                         % (tuple(labels.shape) if isinstance(labels, torch.Tensor) else type(labels).__name__,))
+    if labels.dim() == 4:
+        if labels.shape[1] > 256:
+            raise ValueError("one-hot labels have at most 256 classes, got %d" % labels.shape[1])
+        labels = labels.argmax(1)
+    elif labels.dtype not in (torch.uint8, torch.int64):
+        raise ValueError("labels (B,n,n) are uint8 or int64, got %s" % labels.dtype)
+    if tuple(labels.shape) != (B, int(load_size), int(load_size)):
+        raise ValueError("labels lie in the crop's frame: (%d,%d,%d) for this batch and load_size, got %s"
+                         % (B, load_size, load_size, tuple(labels.shape)))
+    if labels.dtype != torch.uint8:
+        labels = labels.clamp(0, 255).to(torch.uint8)                              # (values >= 32 are outside any matte)
+    return labels
+
+
+def simple_swap_region_matte(model, photo_u8, xf, style, alphas=(1.0,), load_size=512, feather=16, style_xf=None, labels=None,
+                             keep=(1, 2), matte_feather=16, matte_grow=8, matte=None):
+    """``simple_swap_region`` blended through a matte of the face, so that the re-coloured background of the square does not reach
+    the photo.  ``labels``: per-pixel labels of the CROP (``crop_labels``: (B,n,n) uint8 / int64 or one-hot (B,C,n,n), n ==
+    load_size), turned into a matte by ``ops.label_matte(labels, keep, matte_feather, matte_grow)``: label values in ``keep`` are
+    the face, the ramp is ``matte_feather`` crop pixels wide and reaches ``matte_grow`` pixels outwards.  ``matte``: a ready fp32
+    (B,n,n) matte in [0, 1] instead; both together raise.  Neither: ``simple_swap_region``.  Photo pixels where the matte is 0 keep
+    their bytes."""
     region_rule(tuple(photo_u8.shape), xf, load_size)
+    if labels is not None and matte is not None:
+        raise ValueError("simple_swap_region_matte takes labels or a matte, not both")
+    if labels is not None:
+        labels = crop_labels(labels, int(photo_u8.shape[0]), load_size)
     from . import imageio
+    if labels is not None:
+        matte = ops.label_matte(labels.to(photo_u8.device), keep, matte_feather, matte_grow)
     if style_xf is not None:
         imageio.crop_transform_rule(style_xf, load_size)
         style = imageio.to_tensor_normalized(ops.extract_similarity(style, style_xf, load_size))
@@ -606,20 +644,28 @@ def simple_swap_region(model, photo_u8, xf, style, alphas=(1.0,), load_size=512,
     sp, gl_c, gl_w = swap_codes(model, content, style)
     out = {}
     for alpha in alphas:
-        out[alpha] = model(sp, glue.lerp(gl_c, gl_w, alpha), content, photo_u8, xf, feather, command="decode_region")
+        code = glue.lerp(gl_c, gl_w, alpha)
+        if matte is None:
+            out[alpha] = model(sp, code, content, photo_u8, xf, feather, command="decode_region")
+        else:
+            out[alpha] = model(sp, code, content, photo_u8, xf, feather, matte, command="decode_region_matte")
     return out
 
 
 def evaluate_swap_files_region(model, structure_path, texture_path, out_dir, structure_box, texture_box=None, alphas=(1.0,), load_size=512,
-                               feather=16, device="cuda", png="host", format="png", jpeg_quality=90, jpeg_subsampling="4:2:0"):
+                               feather=16, device="cuda", png="host", format="png", jpeg_quality=90, jpeg_subsampling="4:2:0",
+                               label_path=None, keep=(1, 2), matte_feather=16, matte_grow=8):
     """``evaluate_swap_files`` for a face inside a photograph (``simple_swap_region``): the structure FILE keeps its size and
     every pixel outside the box.  A box is (cx, cy, side, angle_deg) in the file's pixels (``imageio.crop_transform``).
     ``structure_path`` / ``texture_path``: one path or a list each, ``structure_box`` / ``texture_box``: one box or one per path --
     one texture (and one box) serves every structure, otherwise the lists pair up.  ``texture_box=None`` loads the texture as
     ``evaluate_swap_files`` does (the whole file at load_size); with a box its region is extracted like the structure's.  Files
     are read at their own size by ``load_native`` and written through write_png_batch, named as evaluate_swap_files names them;
-    a size the device encoder has no bound for is encoded on the host.  Returns the paths, structure by structure, alpha by
-    alpha."""
+    a size the device encoder has no bound for is encoded on the host.  ``label_path``: one grey label PNG per structure, in the
+    CROP's frame (the layout of the dataset's ``labels/``), read with ``convert("L")`` and resized NEAREST to load_size when it
+    differs (the dataset's rule); the lists pair up as the boxes do, and the swap is blended through
+    ``ops.label_matte(labels, keep, matte_feather, matte_grow)`` (``simple_swap_region_matte``).  Returns the paths, structure by
+    structure, alpha by alpha."""
     import os
     from . import imageio
     _check_encoder(png)
@@ -632,7 +678,8 @@ def evaluate_swap_files_region(model, structure_path, texture_path, out_dir, str
     spread = lambda v: v * len(structures) if len(v) == 1 else v
     textures, sboxes = spread(textures), spread(sboxes)
     tboxes = None if tboxes is None else spread(tboxes)
-    for v, what in ((textures, "texture paths"), (sboxes, "structure boxes"), (tboxes, "texture boxes")):
+    lpaths = None if label_path is None else spread(as_list(label_path))
+    for v, what in ((textures, "texture paths"), (sboxes, "structure boxes"), (tboxes, "texture boxes"), (lpaths, "label paths")):
         if v is not None and len(v) != len(structures):
             raise ValueError("evaluate_swap_files_region pairs its lists: %d structure paths and %d %s" % (len(structures), len(v), what))
     os.makedirs(out_dir, exist_ok=True)
@@ -648,14 +695,25 @@ def evaluate_swap_files_region(model, structure_path, texture_path, out_dir, str
     else:
         tphotos = load_native([os.path.expanduser(p) for p in textures], device)
         styles = [imageio.to_tensor_normalized(ops.extract_similarity(t[None], [x], load_size)) for t, x in zip(tphotos, txf)]
+    labels = None
+    if lpaths is not None:
+        import numpy as np
+        from PIL import Image
+
+        def read(p):
+            im = Image.open(os.path.expanduser(p)).convert("L")
+            return np.asarray(im if im.size == (load_size, load_size) else im.resize((load_size, load_size), Image.NEAREST))
+        labels = torch.from_numpy(np.stack([read(p) for p in lpaths])).to(device)
     stem = lambda p: os.path.splitext(os.path.basename(p))[0]
     groups = {}
     for i, n in enumerate(photos):                             # structures of one size (and one texture size) share a batch
         groups.setdefault((tuple(n.shape), tuple(styles[i].shape)), []).append(i)
     paths = {}
     for (shape, _), idx in groups.items():
-        outs = simple_swap_region(model, torch.stack([photos[i] for i in idx]), [sxf[i] for i in idx], torch.cat([styles[i] for i in idx], 0),
-                                  alphas, load_size, feather)
+        outs = simple_swap_region_matte(model, torch.stack([photos[i] for i in idx]), [sxf[i] for i in idx],
+                                        torch.cat([styles[i] for i in idx], 0), alphas, load_size, feather,
+                                        labels=None if labels is None else labels[idx], keep=keep, matte_feather=matte_feather,
+                                        matte_grow=matte_grow)
         encoder = png if png == "host" or _device_encoder_takes(shape, format, jpeg_subsampling) else "host"
         for alpha in alphas:
             names = [os.path.join(out_dir, "%s_%s_%.2f%s" % (stem(structures[i]), stem(textures[i]), alpha, FORMATS[format])) for i in idx]

@@ -1884,13 +1884,38 @@ def extract_similarity(photo_u8, xf, n=512):
     return out
 
 
-def guided_filter_paste(coeffs, photo_u8, xf, feather=0, out=None):
+def label_matte(labels, keep=(1, 2), feather=16, grow=8, want_distance=False):
+    """labels (B,h,w) uint8 on the GPU, ``keep`` the label values (0..31) that count as inside -> fp32 matte (B,h,w) in [0, 1]: the
+    smoothstep over ``feather`` pixels of the signed Euclidean distance to the kept region's boundary, moved outwards by ``grow``
+    pixels (csrc/matte.hip; the semantics are at ppst_label_matte in include/ppst_hip.h).  grow = 0 feathers inwards only,
+    grow = feather / 2 centres the ramp on the boundary; both in [0, 255].  ``want_distance``: also the exact int32 signed squared
+    distance (B,h,w), clipped to +-R^2, R = max(grow, max(feather - grow, 0)) + 1."""
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dtype != torch.uint8:
+        raise RuntimeError("label_matte needs CUDA uint8 labels")
+    if labels.dim() != 3:
+        raise RuntimeError("label_matte needs labels (B,h,w), got %s" % (tuple(labels.shape),))
+    mask = 0
+    for k in keep:
+        if int(k) != k or not 0 <= int(k) <= 31:
+            raise RuntimeError("label_matte keeps label values 0..31, got %r" % (k,))
+        mask |= 1 << int(k)
+    labels = labels.contiguous()
+    B, h, w = labels.shape
+    sd2 = torch.empty((B, h, w), device=labels.device, dtype=torch.int32)
+    matte = torch.empty((B, h, w), device=labels.device, dtype=torch.float32)
+    check(lib.ppst_label_matte(_p(labels), B, h, w, mask, int(feather), int(grow), _p(sd2), _p(matte), _stream()), "ppst_label_matte")
+    return (matte, sd2) if want_distance else matte
+
+
+def guided_filter_paste(coeffs, photo_u8, xf, feather=0, out=None, matte=None):
     """coeffs (B,12,n,n) fp32 (``guided_filter_coeffs`` of the crops ``extract_similarity`` took), photo (B,H,W,3) uint8, the same
     crop transforms -> uint8 (B,H,W,3): inside each crop square the photo's own pixels re-coloured by the bilinearly interpolated
     coefficients, blended towards the photo over ``feather`` crop pixels from the square's edge (0 <= feather <= n/2; 0: a hard
     edge); every byte outside the square is the photo's.  One launch over the tiles of the squares' bounding boxes.  ``out``:
     None clones the photo first; ``out=photo_u8`` works in place; any other contiguous uint8 tensor of the photo's shape is
-    filled with the photo first."""
+    filled with the photo first.  ``matte``: fp32 (B,n,n) on the photo's device, in the crop's frame (``label_matte``): the blend
+    weight is the edge feather times the matte sampled like the coefficients, and pixels of weight 0 keep the photo's byte (the
+    caller keeps its values in [0, 1]); None: no matte."""
     if not isinstance(coeffs, torch.Tensor) or not coeffs.is_cuda or coeffs.dtype != torch.float32:
         raise RuntimeError("guided_filter_paste needs CUDA float32 coefficients")
     if not isinstance(photo_u8, torch.Tensor) or not photo_u8.is_cuda or photo_u8.dtype != torch.uint8:
@@ -1901,6 +1926,11 @@ def guided_filter_paste(coeffs, photo_u8, xf, feather=0, out=None):
                            % (tuple(coeffs.shape), tuple(photo_u8.shape)))
     B, _, n, _ = coeffs.shape
     _, H, W, _ = photo_u8.shape
+    if matte is not None:
+        if not isinstance(matte, torch.Tensor) or matte.dtype != torch.float32 or matte.device != photo_u8.device \
+                or tuple(matte.shape) != (B, n, n):
+            raise RuntimeError("guided_filter_paste needs a float32 matte (B,n,n) = %s on the photo's device" % ((B, n, n),))
+        matte = matte.contiguous()
     if out is None:
         out = photo_u8.clone(memory_format=torch.contiguous_format)
         photo_u8 = out                                        # (a pixel reads only its own bytes: in place is the cloned form)
@@ -1915,6 +1945,10 @@ def guided_filter_paste(coeffs, photo_u8, xf, feather=0, out=None):
         photo_u8 = out
     host, dev = _crop_transforms(xf, B, out.device, "guided_filter_paste")
     coeffs = coeffs.contiguous()
+    if matte is not None:
+        check(lib.ppst_guided_filter_paste_matte(_p(coeffs), _p(matte), n, _p(photo_u8), _p(out), B, H, W, _p(host), _p(dev), int(feather),
+                                                 _stream()), "ppst_guided_filter_paste_matte")
+        return out
     check(lib.ppst_guided_filter_paste(_p(coeffs), n, _p(photo_u8), _p(out), B, H, W, _p(host), _p(dev), int(feather), _stream()),
           "ppst_guided_filter_paste")
     return out

@@ -363,6 +363,11 @@ class PPSTModel(nn.Module):
         applied to the photo's own pixels inside the crop square through the same transforms (``ops.guided_filter_paste``), blended
         over ``feather`` crop pixels at its edge.  -> uint8 (B,H,W,3), every byte outside the square the photo's.  The radius rule
         is ``decode_native``'s, raised from shapes before the generator runs."""
+        return self.decode_region_matte(spatial_code, global_code, target, photo_u8, xf, feather, None)
+
+    def decode_region_matte(self, spatial_code, global_code, target, photo_u8, xf, feather=0, matte=None):
+        """``decode_region`` blended through a matte: ``matte`` fp32 (B,n,n) in the crop's frame (``ops.label_matte``) multiplies the
+        edge feather, and photo pixels where it is 0 keep their bytes.  ``matte=None`` is ``decode_region``."""
         h, w = int(target.shape[-2]), int(target.shape[-1])
         r = guided_filter_radius(self.opt, h, w)
         if not 0 < r <= 64 or r >= h or r >= w or w > 2048:           # (from shapes alone, before the generator runs)
@@ -372,7 +377,7 @@ class PPSTModel(nn.Module):
             raise ValueError("decode_region: the crop is a square, got a target of %d x %d" % (h, w))
         out = self.G(spatial_code, global_code, noise=self.noise)
         coeffs = ops.guided_filter_coeffs(glue.tensor2im(target), glue.tensor2im(out), r, (0.02 * 255) ** 2)
-        return ops.guided_filter_paste(coeffs, photo_u8, xf, feather)
+        return ops.guided_filter_paste(coeffs, photo_u8, xf, feather, matte=matte)
 
     def discriminate(self, x):
         return self.D(x)
