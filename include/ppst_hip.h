@@ -407,6 +407,18 @@ int ppst_torgb_linear_st(const void* x, const void* scale_shift, const void* pro
                         void* y, void* partial, int* n_partials, int B, int H, int W, int cin, float wscale, int x_st, void* stream);
 /* ToRGB's end: out [B][3][hw] (NCHW) = a * y + s of y [B][hw][3], scale_shift [B][3][2]: ppst_affine_act then ppst_nhwc_to_nchw */
 int ppst_rgb_affine_nchw(const void* y, const void* scale_shift, void* out, int B, int64_t hw, void* stream);
+/* The encoders' first ResBlock without norm (stylegan2_layers.py:552-579, reflection_pad) in one launch, every intermediate in LDS:
+ *   y = (lrelu(conv2(blur(lrelu(conv1(x) + b1))) + b2) + skip(blur_down2(x))) / sqrt 2,  lrelu(t) = sqrt 2 * max(t, 0.2 t);
+ * conv1 3x3 reflect pad 1, blur = the 3x3 FIR `blur` (9 floats, as ppst_upfirdn2d takes it) with reflect pad (2, 1), conv2 3x3
+ * stride 2 on that extent, skip = `blur` with zero pad (1, 0) keeping every second sample, then the 1x1 conv.
+ * fp32 storage, precision mode 0 (bf16 hi + lo, three MFMAs per product), channels 32 -> 32 -> 64 only.
+ * x [B][H][W][32] dense (x_ld = 32 = its pixel stride, x_st = PPST_ST_F32), H and W even and >= 4 -> y [B][H/2][W/2][64].
+ * w1, w2, ws: the ppst_conv_pack blobs (bn = 64, precision 0, scale folded in) of the (32,32,3,3), (64,32,3,3) and (64,32,1,1)
+ * weights under the plain conv step table (one step per tap, ky-major); b1 [32], b2 [64].  x, y and the blobs 16-byte aligned.
+ * Anything else is PPST_EINVAL: the caller keeps such inputs on the unfused path.  Equal to that path up to the order of conv2's
+ * nine-tap sum. */
+int ppst_encoder_resblock(const void* x, int x_st, int B, int H, int W, int cin, int cmid, int cout, int x_ld, const void* w1, const void* w2,
+                          const void* ws, const void* b1, const void* b2, const void* blur, void* y, void* stream);
 
 /* ------------------------------------------- instance norm / style mod ---
  * nn.InstanceNorm2d (eps 1e-5, biased var) + StyleMod (stylegan2_layers.py:361-374,

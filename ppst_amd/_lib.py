@@ -136,6 +136,7 @@ _SIGS = {
     "ppst_conv1x1_small_cout_ld_st": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, f32, i32, vp]),
     "ppst_torgb_linear_st": (i32, [vp, vp, vp, f32, vp, vp, vp, vp, ctypes.POINTER(i32), i32, i32, i32, i32, f32, i32, vp]),
     "ppst_rgb_affine_nchw": (i32, [vp, vp, vp, i32, i64, vp]),
+    "ppst_encoder_resblock": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ppst_in_stats": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, ctypes.POINTER(i32), vp]),
     "ppst_in_finalize": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, f64, f32, vp]),
     "ppst_affine_act": (i32, [vp, vp, vp, vp, vp, i32, i64, i32, i32, i32, i32, i32, vp, f32, i32, vp]),

@@ -163,6 +163,13 @@ class BaseNetwork(nn.Module):
         conv_pad = ops.PAD_REFLECT if blur_pad_mode == ops.PAD_REFLECT else ops.PAD_ZERO
         pad_c = (ks - 2) + 2          # conv2: (len(k)-2)+(3-1)   (stylegan2_layers.py:515)
         pad_s = (ks - 2) + 0          # skip:  (len(k)-2)+(1-1)
+        if not norm and blur_pad_mode == ops.PAD_REFLECT and ks == 3 and ops.encoder_resblock_ok(x, w1.shape[0], w2.shape[0]) \
+                and self.cached(("one_blur", p), [k, self.p(p + "skip.Blur.kernel")],
+                                lambda: bool(torch.equal(k, self.p(p + "skip.Blur.kernel")))):
+            # inference, fp32-class mode, 32 -> 32 -> 64: the whole block in one launch, no intermediate in HBM
+            return ops.encoder_resblock(x, self.plan(p + "conv1.Conv.weight", scale=sc1), self.plan(p + "conv2.Conv.weight", scale=sc1),
+                                        self.plan(p + "skip.Conv.weight", scale=scs), self.p(p + "conv1.Act.bias"),
+                                        self.p(p + "conv2.Act.bias"), k)
         # skip: blur (zero pad) keeping every 2nd sample == blur then 1x1 stride-2 conv
         xs, _ = ops.blur_nhwc(x, self.p(p + "skip.Blur.kernel"), (pad_s + 1) // 2, pad_s // 2, ops.PAD_ZERO, down=2)
         if not norm:

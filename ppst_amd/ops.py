@@ -1090,6 +1090,35 @@ def torgb_apply(x, scale_shift, res, out_scale, w, bias, wscale, stats=False):
     return (y, part) if stats else y
 
 
+def encoder_resblock_ok(x, cmid, cout):
+    """May ``x`` (B,H,W,C) take encoder_resblock?  Inference in the fp32-class mode on a dense, 16-byte aligned fp32 tensor, channels
+    32 -> 32 -> 64, even extents of at least 4 (what ppst_encoder_resblock accepts)."""
+    if torch.is_grad_enabled() or PRECISION["value"] != 0 or x.dtype != torch.float32 or not x.is_cuda or x.dim() != 4:
+        return False
+    B, H, W, cin = x.shape
+    return (x.is_contiguous() and x.data_ptr() % 16 == 0 and (cin, cmid, cout) == (32, 32, 64) and B >= 1 and H >= 4 and W >= 4
+            and H % 2 == 0 and W % 2 == 0 and H * W * 32 < 2 ** 31)
+
+
+def encoder_resblock(x, plan1, plan2, plan_s, b1, b2, blur):
+    """The no-norm ResBlock 32 -> 32 -> 64 with downsampling in one launch (ppst_encoder_resblock): x (B,H,W,32) dense fp32 ->
+    (B,H/2,W/2,64).  plan1 / plan2 / plan_s: the 'conv' ConvPlans (scale folded in) of conv1, conv2 and the skip's 1x1; b1, b2: the two
+    activation biases; blur: the 3x3 FIR both branches use.  The entry refuses every other input (PPST_EINVAL)."""
+    _chk_act(x, "x"); _chk(b1, "b1"); _chk(b2, "b2"); _chk(blur, "blur")
+    B, H, W, cin = x.shape
+    dense = x.stride(3) == 1 and x.stride(2) == cin and x.stride(1) == W * cin and (B == 1 or x.stride(0) == H * W * cin)
+    if plan1.kind != "conv" or plan2.kind != "conv" or plan_s.kind != "conv" or (plan1.k, plan2.k, plan_s.k) != (3, 3, 1) \
+            or plan1.cin != cin or plan2.cin != plan1.cout or plan_s.cin != cin or plan_s.cout != plan2.cout \
+            or any(pl.precision != 0 for pl in (plan1, plan2, plan_s)) or blur.numel() != 9 or not blur.is_contiguous() \
+            or b1.numel() != plan1.cout or b2.numel() != plan2.cout or not b1.is_contiguous() or not b2.is_contiguous():
+        raise RuntimeError("encoder_resblock: plans must be the fp32-class 'conv' plans of a 3x3 / 3x3 / 1x1 ResBlock, blur a 3x3 FIR")
+    y = torch.empty((B, H // 2, W // 2, plan2.cout), device=x.device, dtype=torch.float32)
+    check(lib.ppst_encoder_resblock(_p(x), _ST[x.dtype], B, H, W, cin, plan1.cout, plan2.cout, x.stride(2) if dense else 0,
+                                    _p(plan1.pack_for(64)), _p(plan2.pack_for(64)), _p(plan_s.pack_for(64)), _p(b1), _p(b2), _p(blur), _p(y),
+                                    _stream()), "ppst_encoder_resblock")
+    return y
+
+
 def rgb_affine_nchw(y, scale_shift):
     """ToRGB's end: y (B,H,W,3), scale_shift (B,3,2) -> the image (B,3,H,W) = nhwc_to_nchw(affine_act(y, scale_shift)) in one pass."""
     _chk(y, "y"); _chk(scale_shift, "scale_shift")
