@@ -1006,6 +1006,28 @@ int ppst_guided_filter_paste(const void* coeffs, int n, const void* photo_u8, vo
  * coefficient where the matte is 0 cannot leak.  The refusals of ppst_guided_filter_paste, and PPST_ENULL for a null matte. */
 int ppst_guided_filter_paste_matte(const void* coeffs, const void* matte_f32, int n, const void* photo_u8, void* out_u8, int B, int H,
                                    int W, const void* xf_host, const void* xf_dev, int feather, void* stream);
+/* a matte refined by the photo's own pixels (He et al.'s "guided feathering": a coarse mask filtered with the image as guide; the
+ * refined alpha a . I + b follows the image's edges).
+ * ppst_guided_matte_coeffs: guide uint8 [B][h][w][3] (the crop), matte_f32 fp32 [B][h][w] -> mcoeffs fp32 [B][4][h][w]: plane
+ * k = 0..2 the window mean of a_k, plane 3 the window mean of b.  The source is p = rintf(255 fminf(fmaxf(m, 0), 1)): an integer
+ * in 0..255, ties to even, a NaN gives 0 (8 bits keep every stage-1 row sum an exact integer in fp32, as the colour entry relies
+ * on).  The filter is the colour guided filter of ppst_guided_filter_coeffs with this one source channel: the same windows
+ * (radius r, symmetric border), the same eps on the covariance diagonal, the same solve and the same second box mean, and the
+ * result is BIT-EQUAL to planes 0..3 of ppst_guided_filter_coeffs(guide, src) with src[..., c] = p for all three c -- a matte does
+ * not depend on which entry computed it -- through 13 of its 21 moment planes and 4 of its 12 coefficient planes.  work:
+ * >= ppst_guided_matte_ws(B, h, w) bytes; five launches, nothing allocated.  The refusals of ppst_guided_filter_coeffs, nothing
+ * written: PPST_EINVAL for r <= 0, r > 64, r >= h, r >= w, w > 2048; PPST_ENULL for a null pointer.
+ * ppst_guided_filter_paste_gmatte: ppst_guided_filter_paste_matte's arithmetic with one change: the four planes mcoeffs
+ * [B][4][n][n] are sampled at the photo pixel by the same taps, fractions and clamps as the 12 colour planes, giving
+ * (M0, M1, M2, Mb), and m^ = fminf(fmaxf((M0 I0 + M1 I1 + M2 I2 + Mb) (1/255), 0), 1) with I the photo's own pixel (a NaN gives
+ * 0); g = g_edge m^, and a pixel with g == 0 is not written.  weight_u8 uint8 [B][H][W] (NULL: no weight output) receives
+ * rint(255 g) for every pixel inside the square, 0 where g == 0 included; nothing is written outside the square.  The refusals of
+ * ppst_guided_filter_paste_matte. */
+int64_t ppst_guided_matte_ws(int B, int h, int w);
+int ppst_guided_matte_coeffs(const void* guide_u8, const void* matte_f32, void* mcoeffs, int B, int h, int w, int r, float eps,
+                             void* work, void* stream);
+int ppst_guided_filter_paste_gmatte(const void* coeffs, const void* mcoeffs, int n, const void* photo_u8, void* out_u8, void* weight_u8,
+                                    int B, int H, int W, const void* xf_host, const void* xf_dev, int feather, void* stream);
 /* a feathered matte from a label map: the exact, clipped, signed Euclidean distance transform of "label kept", then a smoothstep.
  * labels_u8 uint8 [B][h][w]; a pixel is INSIDE iff its label L < 32 and bit L of ``keep`` is set (labels >= 32 are outside whatever
  * keep says).  R = max(grow, max(feather - grow, 0)) + 1.  D2(p) = min(R^2, min |p - q|^2) over the pixels q OF THE PLANE whose

@@ -214,6 +214,9 @@ _SIGS = {
     "ppst_guided_filter_apply": (i32, [vp, i32, i32, vp, vp, vp, i32, i32, i32, vp]),
     "ppst_guided_filter_paste": (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp, i32, vp]),
     "ppst_guided_filter_paste_matte": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, i32, vp]),
+    "ppst_guided_matte_ws": (i64, [i32, i32, i32]),
+    "ppst_guided_matte_coeffs": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),
+    "ppst_guided_filter_paste_gmatte": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]),
     "ppst_label_matte": (i32, [vp, i32, i32, i32, ctypes.c_uint32, i32, i32, vp, vp, vp]),
     "ppst_extract_similarity": (i32, [vp, i32, i32, i32, vp, vp, i32, vp, vp]),
     "ppst_smooth_local_affine_ws": (i64, [i32, i32, i32]),

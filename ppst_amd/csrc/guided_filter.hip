@@ -716,6 +716,89 @@ extern "C" int ppst_guided_filter_coeffs(const void* guide_u8, const void* src_u
   return PPST_LAUNCH_CHECK();
 }
 
+// The same coefficients for a ONE-channel source: a matte (ppst_guided_matte_coeffs; He et al.'s guided feathering -- the refined
+// alpha is a . I + b).  The source is the fp32 matte quantised on load, p = rint(255 clamp(m, 0, 1)) (fmaxf drops a NaN: 0), an
+// integer in 0..255, so every stage-1 row sum stays an exact integer in fp32 as above.  Of the 21 moment planes a single channel
+// needs 13 -- plane 0..2 I, 3 p, 4..9 I_i I_j, 10..12 I_i p: the 21-plane order with P1, P2 and their products left out, i.e. moment
+// i of GF_SOLVE_* is plane i for i < 4 and plane i - 2 from 6 on (GFM_PLANE) -- and 4 of the 12 coefficient planes.  The launches
+// are those of ppst_guided_filter_coeffs with these plane counts: gfm_h_kernel (gf_h<true>'s body on the 13 planes), gfc_v_kernel,
+// gfm_solve_kernel (gfc_solve_kernel's text for channel 0 alone), gf_h<false>, gfc_v_kernel.  Every operation is the one the
+// 21-plane entry performs on channel 0, in its order, so the result is BIT-EQUAL to planes 0..3 of ppst_guided_filter_coeffs on
+// the source (p, p, p): a matte does not depend on the entry that computed it.
+#define GFM_PLANE(i) ((i) < 4 ? (i) : (i) - 2)
+
+__global__ __launch_bounds__(256) void gfm_h_kernel(const unsigned char* __restrict__ guide, const float* __restrict__ matte,
+                                                    float* __restrict__ out, int H, int W, int r) {
+  __shared__ float row[GF_MAXW + 2 * GF_MAXR];
+  const int y = blockIdx.x, pl = blockIdx.y, b = blockIdx.z;
+  const int64_t P = (int64_t)H * W;
+  for (int i = threadIdx.x; i < W + 2 * r; i += 256) {
+    const int64_t o = ((int64_t)b * H + y) * W + reflect_idx(i - r, W);
+    const unsigned char* g = guide + o * 3;
+    const float I0 = g[0], I1 = g[1], I2 = g[2];
+    const float p = rintf(255.f * fminf(fmaxf(matte[o], 0.f), 1.f));
+    float v;
+    switch (pl) {
+      case 0: v = I0; break; case 1: v = I1; break; case 2: v = I2; break; case 3: v = p; break;
+      case 4: v = I0 * I0; break; case 5: v = I0 * I1; break; case 6: v = I0 * I2; break;
+      case 7: v = I1 * I1; break; case 8: v = I1 * I2; break; case 9: v = I2 * I2; break;
+      case 10: v = I0 * p; break; case 11: v = I1 * p; break; default: v = I2 * p; break;
+    }
+    row[i] = v;
+  }
+  __syncthreads();
+  float* o = out + ((int64_t)b * 13 + pl) * P + (int64_t)y * W;
+  for (int x = threadIdx.x; x < W; x += 256) {
+    float s = 0.f;
+    for (int k = 0; k <= 2 * r; ++k) s += row[x + k];
+    o[x] = s;
+  }
+}
+
+// means: [B][13][P] -> ab: [B][4][P] (a_0, a_1, a_2, b)
+__global__ __launch_bounds__(256) void gfm_solve_kernel(const float* __restrict__ m, float* __restrict__ ab, int64_t P, float eps, int64_t total) {
+#pragma clang fp contract(off)
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
+    int64_t b = t / P, p = t - b * P;
+    const float* mp = m + b * 13 * P + p;
+#define GF_M(i) mp[GFM_PLANE(i) * P]
+    GF_SOLVE_DET(GF_M, eps);
+    const float i00 = c00 / det, i01 = c01 / det, i02 = c02 / det, i11 = c11 / det, i12 = c12 / det, i22 = c22 / det;
+    float* o = ab + b * 4 * P + p;
+    GF_SOLVE_AB(GF_M, 0);
+    o[0] = A0; o[P] = A1; o[2 * P] = A2; o[3 * P] = bb;
+#undef GF_M
+  }
+}
+
+// (26 planes: 13 + 13 fp32 planes handed through the workspace)
+extern "C" int64_t ppst_guided_matte_ws(int B, int h, int w) { return (int64_t)B * 26 * h * w * (int64_t)sizeof(float); }
+
+extern "C" int ppst_guided_matte_coeffs(const void* guide_u8, const void* matte_f32, void* mcoeffs, int B, int h, int w, int r, float eps,
+                                        void* work, void* stream) {
+  if (B < 0 || h <= 0 || w <= 0 || w > GF_MAXW || r <= 0 || r > GF_MAXR || r >= h || r >= w) return PPST_EINVAL;   // ppst_guided_filter_coeffs' rule
+  if (B == 0) return PPST_OK;
+  if (!guide_u8 || !matte_f32 || !mcoeffs || !work) return PPST_ENULL;
+  hipStream_t st = as_stream(stream);
+  const int64_t P = (int64_t)h * w;
+  const unsigned char* g = (const unsigned char*)guide_u8;
+  float* bufA = (float*)work;                // [B][13][P]
+  float* bufB = bufA + (int64_t)B * 13 * P;  // [B][13][P]
+  auto blocks_for = [](int64_t total) { int64_t b = cdiv64(total, 256); return (unsigned)(b > 256 * 32 ? 256 * 32 : b); };
+  int e;
+  PPST_LAUNCH(gfm_h_kernel, dim3(h, 13, B), dim3(256), 0, st, g, (const float*)matte_f32, bufA, h, w, r);
+  if ((e = PPST_LAUNCH_CHECK())) return e;
+  const int64_t t13 = (int64_t)B * 13 * P, t4 = (int64_t)B * 4 * P;
+  PPST_LAUNCH(gfc_v_kernel, dim3(blocks_for(t13)), dim3(256), 0, st, (const float*)bufA, bufB, h, w, r, t13);
+  if ((e = PPST_LAUNCH_CHECK())) return e;
+  PPST_LAUNCH(gfm_solve_kernel, dim3(blocks_for(B * P)), dim3(256), 0, st, (const float*)bufB, bufA, P, eps, (int64_t)B * P);
+  if ((e = PPST_LAUNCH_CHECK())) return e;
+  PPST_LAUNCH(gf_h_kernel<false>, dim3(h, 4, B), dim3(256), 0, st, g, g, (const float*)bufA, bufB, h, w, r, 4);
+  if ((e = PPST_LAUNCH_CHECK())) return e;
+  PPST_LAUNCH(gfc_v_kernel, dim3(blocks_for(t4)), dim3(256), 0, st, (const float*)bufB, (float*)mcoeffs, h, w, r, t4);
+  return PPST_LAUNCH_CHECK();
+}
+
 extern "C" int ppst_guided_filter_apply(const void* coeffs, int h, int w, const void* guide_u8, void* out_u8, void* out_f32, int B, int H,
                                         int W, void* stream) {
   if (B < 0 || h <= 0 || w <= 0 || H < h || W < w || (int64_t)H * W > GA_MAXPIX) return PPST_EINVAL;
@@ -749,19 +832,29 @@ extern "C" int ppst_guided_filter_apply(const void* coeffs, int h, int w, const 
 // rows and columns limited to the plane, so fewer near the crop's edge), a thread reads its 4 taps x 12 planes as 12 16-byte
 // reads.  A 32 x 16 tile would need up to 37 x 37 samples at 45 degrees and s = 1 -- 65.7 KB, more than a block may declare.
 // Every staged index is clamped to the plane and every local index to the footprint.
-// Through a matte (ppst_guided_filter_paste_matte; MATTE = true, the same body): the matte plane [B][n][n] is a 13th plane with
+// Through a matte (ppst_guided_filter_paste_matte; MATTE = GP_PLANE, the same body): the matte plane [B][n][n] is a 13th plane with
 // the same footprint, staged in an array of its own (24 x 24 floats = 2,304 B: the 12-plane array keeps its 48-byte pixels and
 // 16-byte reads) and sampled by the same taps and fractions; g = g_edge m^, and a pixel with g == 0 is left unwritten.
+// Through guided-matte coefficients (ppst_guided_filter_paste_gmatte; MATTE = GP_COEFFS): the four planes [B][4][n][n] of
+// ppst_guided_matte_coeffs are staged pixel-major in a third array (24 x 24 x 4 floats = 9,216 B, one 16-byte read per tap),
+// sampled like the 12 and evaluated on the photo's pixel: m^ = clamp((M . I + Mb) / 255, 0, 1); the optional weight plane gets
+// rint(255 g) for every pixel inside the square, written or not.  The kernel's ``matte`` pointer is the form's one extra input.
 #include "sim_xf.h"
 #define GP_T 16
 #define GP_FS 24
 
-template <bool MATTE>
+#define GP_NONE 0       // the three forms of the one body: no matte,
+#define GP_PLANE 1      // a matte plane [B][n][n],
+#define GP_COEFFS 2     // guided-matte coefficients [B][4][n][n]
+
+template <int MATTE>
 __global__ __launch_bounds__(GP_T * GP_T) void gf_paste_kernel(const float* __restrict__ coef, const float* __restrict__ matte, int n,
-                                                               const unsigned char* photo, unsigned char* out, int B, int H, int W,
+                                                               const unsigned char* photo, unsigned char* out,
+                                                               unsigned char* __restrict__ weight, int B, int H, int W,
                                                                const int64_t* __restrict__ xf, int feather) {
   __shared__ __attribute__((aligned(16))) float fp[GP_FS * GP_FS * 12];
-  __shared__ float fm[MATTE ? GP_FS * GP_FS : 1];
+  __shared__ float fm[MATTE == GP_PLANE ? GP_FS * GP_FS : 1];
+  __shared__ float4 fg[MATTE == GP_COEFFS ? GP_FS * GP_FS : 1];
   const int t = threadIdx.x;
   const int64_t p = (int64_t)n * n, side = (int64_t)n * SX_ONE;
   for (int b = blockIdx.y; b < B; b += gridDim.y) {
@@ -799,7 +892,11 @@ __global__ __launch_bounds__(GP_T * GP_T) void gf_paste_kernel(const float* __re
       d[0] = make_float4(v[0], v[1], v[2], v[3]);
       d[1] = make_float4(v[4], v[5], v[6], v[7]);
       d[2] = make_float4(v[8], v[9], v[10], v[11]);
-      if (MATTE) fm[lr * GP_FS + lc] = matte[(int64_t)b * p + (s - cb)];
+      if (MATTE == GP_PLANE) fm[lr * GP_FS + lc] = matte[(int64_t)b * p + (s - cb)];
+      if (MATTE == GP_COEFFS) {
+        const float* ms = matte + (int64_t)b * 4 * p + (s - cb);
+        fg[lr * GP_FS + lc] = make_float4(ms[0], ms[p], ms[2 * p], ms[3 * p]);
+      }
     }
     __syncthreads();
     const int X = X0 + (t % GP_T), Y = Y0 + (t / GP_T);
@@ -834,9 +931,18 @@ __global__ __launch_bounds__(GP_T * GP_T) void gf_paste_kernel(const float* __re
           const float tt = fminf(fmaxf((float)d * (1.f / 16777216.f) / (float)feather, 0.f), 1.f);
           g = tt * tt * (3.f - 2.f * tt);
         }
-        if (MATTE) {
+        if (MATTE == GP_PLANE) {
           const float mt = gx * fm[r0 * GP_FS + c0] + fx * fm[r0 * GP_FS + c1], mb = gx * fm[r1 * GP_FS + c0] + fx * fm[r1 * GP_FS + c1];
           g *= gy * mt + fy * mb;
+        }
+        if (MATTE == GP_COEFFS) {
+          const float4 t0 = fg[r0 * GP_FS + c0], t1 = fg[r0 * GP_FS + c1], u0 = fg[r1 * GP_FS + c0], u1 = fg[r1 * GP_FS + c1];
+          const float M0 = gy * (gx * t0.x + fx * t1.x) + fy * (gx * u0.x + fx * u1.x);
+          const float M1 = gy * (gx * t0.y + fx * t1.y) + fy * (gx * u0.y + fx * u1.y);
+          const float M2 = gy * (gx * t0.z + fx * t1.z) + fy * (gx * u0.z + fx * u1.z);
+          const float Mb = gy * (gx * t0.w + fx * t1.w) + fy * (gx * u0.w + fx * u1.w);
+          g *= fminf(fmaxf((M0 * I0 + M1 * I1 + M2 * I2 + Mb) * (1.f / 255.f), 0.f), 1.f);     // (fmaxf drops a NaN: 0)
+          if (weight) weight[((int64_t)b * H + Y) * W + X] = (unsigned char)rintf(255.f * g);
         }
         const float I[3] = {I0, I1, I2};
 #pragma unroll
@@ -853,8 +959,8 @@ __global__ __launch_bounds__(GP_T * GP_T) void gf_paste_kernel(const float* __re
   }
 }
 
-template <bool MATTE>
-static int gf_paste(const void* coeffs, const void* matte, int n, const void* photo_u8, void* out_u8, int B, int H, int W,
+template <int MATTE>
+static int gf_paste(const void* coeffs, const void* matte, int n, const void* photo_u8, void* out_u8, void* weight_u8, int B, int H, int W,
                     const void* xf_host, const void* xf_dev, int feather, void* stream) {
   if (B < 0 || n <= 0 || n > SX_NMAX || H <= 0 || W <= 0 || (int64_t)H * W > SX_MAXPIX || feather < 0 || 2 * feather > n) return PPST_EINVAL;
   if (B == 0) return PPST_OK;
@@ -872,19 +978,25 @@ static int gf_paste(const void* coeffs, const void* matte, int n, const void* ph
   }
   if (tiles == 0) return PPST_OK;                                             // no quad meets its photo
   PPST_LAUNCH((gf_paste_kernel<MATTE>), dim3((unsigned)tiles, (unsigned)(B > 65535 ? 65535 : B)), dim3(GP_T * GP_T), 0, as_stream(stream),
-              (const float*)coeffs, (const float*)matte, n, (const unsigned char*)photo_u8, (unsigned char*)out_u8, B, H, W,
-              (const int64_t*)xf_dev, feather);
+              (const float*)coeffs, (const float*)matte, n, (const unsigned char*)photo_u8, (unsigned char*)out_u8,
+              (unsigned char*)weight_u8, B, H, W, (const int64_t*)xf_dev, feather);
   return PPST_LAUNCH_CHECK();
 }
 
 extern "C" int ppst_guided_filter_paste(const void* coeffs, int n, const void* photo_u8, void* out_u8, int B, int H, int W,
                                         const void* xf_host, const void* xf_dev, int feather, void* stream) {
-  return gf_paste<false>(coeffs, nullptr, n, photo_u8, out_u8, B, H, W, xf_host, xf_dev, feather, stream);
+  return gf_paste<GP_NONE>(coeffs, nullptr, n, photo_u8, out_u8, nullptr, B, H, W, xf_host, xf_dev, feather, stream);
 }
 
 extern "C" int ppst_guided_filter_paste_matte(const void* coeffs, const void* matte_f32, int n, const void* photo_u8, void* out_u8,
                                               int B, int H, int W, const void* xf_host, const void* xf_dev, int feather, void* stream) {
-  return gf_paste<true>(coeffs, matte_f32, n, photo_u8, out_u8, B, H, W, xf_host, xf_dev, feather, stream);
+  return gf_paste<GP_PLANE>(coeffs, matte_f32, n, photo_u8, out_u8, nullptr, B, H, W, xf_host, xf_dev, feather, stream);
+}
+
+extern "C" int ppst_guided_filter_paste_gmatte(const void* coeffs, const void* mcoeffs, int n, const void* photo_u8, void* out_u8,
+                                               void* weight_u8, int B, int H, int W, const void* xf_host, const void* xf_dev, int feather,
+                                               void* stream) {
+  return gf_paste<GP_COEFFS>(coeffs, mcoeffs, n, photo_u8, out_u8, weight_u8, B, H, W, xf_host, xf_dev, feather, stream);
 }
 
 // (the revision history is at PPST_ABI_VERSION in include/ppst_hip.h; callers built against another revision must rebuild)

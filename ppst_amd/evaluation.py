@@ -628,10 +628,34 @@ def simple_swap_region_matte(model, photo_u8, xf, style, alphas=(1.0,), load_siz
     load_size), turned into a matte by ``ops.label_matte(labels, keep, matte_feather, matte_grow)``: label values in ``keep`` are
     the face, the ramp is ``matte_feather`` crop pixels wide and reaches ``matte_grow`` pixels outwards.  ``matte``: a ready fp32
     (B,n,n) matte in [0, 1] instead; both together raise.  Neither: ``simple_swap_region``.  Photo pixels where the matte is 0 keep
-    their bytes."""
+    their bytes.  ``simple_swap_region_gmatte`` refines the matte with the photo's own pixels."""
+    return _swap_region("simple_swap_region_matte", model, photo_u8, xf, style, alphas, load_size, feather, style_xf, labels, keep,
+                        matte_feather, matte_grow, matte, None)
+
+
+def simple_swap_region_gmatte(model, photo_u8, xf, style, alphas=(1.0,), load_size=512, feather=16, style_xf=None, labels=None,
+                              keep=(1, 2), matte_feather=16, matte_grow=8, matte=None, matte_radius=8, matte_eps=(0.01 * 255) ** 2,
+                              want_weight=False):
+    """``simple_swap_region_matte`` with the matte refined by the photo's own pixels (He et al.'s guided feathering): the matte of
+    the labels (or the ready ``matte``; one of the two is required) is filtered with the crop as guide at radius ``matte_radius``
+    and ``matte_eps`` (``ops.guided_matte_coeffs``) and evaluated from those coefficients on every photo pixel
+    (``PPSTModel.decode_region_gmatte``), so the blend edge follows hair, ears and the jaw line of the photo instead of a ramp
+    around the label boundary.  ``want_weight``: {alpha: (image, weight)}, the weight the uint8 (B,H,W) blend weight."""
+    if labels is None and matte is None:
+        raise ValueError("simple_swap_region_gmatte needs labels or a matte (simple_swap_region blends the whole square)")
+    return _swap_region("simple_swap_region_gmatte", model, photo_u8, xf, style, alphas, load_size, feather, style_xf, labels, keep,
+                        matte_feather, matte_grow, matte, (matte_radius, matte_eps, want_weight))
+
+
+def _swap_region(who, model, photo_u8, xf, style, alphas, load_size, feather, style_xf, labels, keep, matte_feather, matte_grow, matte,
+                 gmatte):
+    """the region swaps' one body.  ``gmatte``: None, or (matte_radius, matte_eps, want_weight) of the guided matte"""
     region_rule(tuple(photo_u8.shape), xf, load_size)
     if labels is not None and matte is not None:
-        raise ValueError("simple_swap_region_matte takes labels or a matte, not both")
+        raise ValueError("%s takes labels or a matte, not both" % who)
+    if gmatte is not None:
+        from .ppst_model import guided_matte_radius
+        guided_matte_radius(gmatte[0], int(load_size))         # (before any kernel runs)
     if labels is not None:
         labels = crop_labels(labels, int(photo_u8.shape[0]), load_size)
     from . import imageio
@@ -645,7 +669,9 @@ def simple_swap_region_matte(model, photo_u8, xf, style, alphas=(1.0,), load_siz
     out = {}
     for alpha in alphas:
         code = glue.lerp(gl_c, gl_w, alpha)
-        if matte is None:
+        if gmatte is not None:
+            out[alpha] = model(sp, code, content, photo_u8, xf, feather, matte, *gmatte, command="decode_region_gmatte")
+        elif matte is None:
             out[alpha] = model(sp, code, content, photo_u8, xf, feather, command="decode_region")
         else:
             out[alpha] = model(sp, code, content, photo_u8, xf, feather, matte, command="decode_region_matte")
@@ -665,8 +691,34 @@ def evaluate_swap_files_region(model, structure_path, texture_path, out_dir, str
     CROP's frame (the layout of the dataset's ``labels/``), read with ``convert("L")`` and resized NEAREST to load_size when it
     differs (the dataset's rule); the lists pair up as the boxes do, and the swap is blended through
     ``ops.label_matte(labels, keep, matte_feather, matte_grow)`` (``simple_swap_region_matte``).  Returns the paths, structure by
-    structure, alpha by alpha."""
+    structure, alpha by alpha.  ``evaluate_swap_files_region_gmatte`` refines that matte with the photo's own pixels."""
+    return _swap_files_region(model, structure_path, texture_path, out_dir, structure_box, texture_box, alphas, load_size, feather, device,
+                              png, format, jpeg_quality, jpeg_subsampling, label_path, keep, matte_feather, matte_grow, None)
+
+
+def evaluate_swap_files_region_gmatte(model, structure_path, texture_path, out_dir, structure_box, texture_box=None, alphas=(1.0,),
+                                      load_size=512, feather=16, device="cuda", png="host", format="png", jpeg_quality=90,
+                                      jpeg_subsampling="4:2:0", label_path=None, keep=(1, 2), matte_feather=16, matte_grow=8,
+                                      matte_radius=8, matte_eps=(0.01 * 255) ** 2):
+    """``evaluate_swap_files_region`` through ``simple_swap_region_gmatte``: the matte of each structure's label file is refined by
+    the photo's own pixels (guided filter of radius ``matte_radius`` and ``matte_eps`` with the crop as guide).  ``label_path`` is
+    required."""
+    if label_path is None:
+        raise ValueError("evaluate_swap_files_region_gmatte needs label_path (evaluate_swap_files_region blends the whole square)")
+    from .ppst_model import guided_matte_radius
+    guided_matte_radius(matte_radius, int(load_size))          # (before any file is read)
+    return _swap_files_region(model, structure_path, texture_path, out_dir, structure_box, texture_box, alphas, load_size, feather, device,
+                              png, format, jpeg_quality, jpeg_subsampling, label_path, keep, matte_feather, matte_grow,
+                              (matte_radius, matte_eps))
+
+
+def _swap_files_region(model, structure_path, texture_path, out_dir, structure_box, texture_box, alphas, load_size, feather, device, png,
+                       format, jpeg_quality, jpeg_subsampling, label_path, keep, matte_feather, matte_grow, gmatte):
+    """the region file front ends' one body.  ``gmatte``: None, or (matte_radius, matte_eps) of the guided matte"""
+    import functools
     import os
+    swap = simple_swap_region_matte if gmatte is None else functools.partial(simple_swap_region_gmatte, matte_radius=gmatte[0],
+                                                                             matte_eps=gmatte[1])
     from . import imageio
     _check_encoder(png)
     _check_format(format, jpeg_quality, jpeg_subsampling)
@@ -710,10 +762,9 @@ def evaluate_swap_files_region(model, structure_path, texture_path, out_dir, str
         groups.setdefault((tuple(n.shape), tuple(styles[i].shape)), []).append(i)
     paths = {}
     for (shape, _), idx in groups.items():
-        outs = simple_swap_region_matte(model, torch.stack([photos[i] for i in idx]), [sxf[i] for i in idx],
-                                        torch.cat([styles[i] for i in idx], 0), alphas, load_size, feather,
-                                        labels=None if labels is None else labels[idx], keep=keep, matte_feather=matte_feather,
-                                        matte_grow=matte_grow)
+        outs = swap(model, torch.stack([photos[i] for i in idx]), [sxf[i] for i in idx], torch.cat([styles[i] for i in idx], 0), alphas,
+                    load_size, feather, labels=None if labels is None else labels[idx], keep=keep, matte_feather=matte_feather,
+                    matte_grow=matte_grow)
         encoder = png if png == "host" or _device_encoder_takes(shape, format, jpeg_subsampling) else "host"
         for alpha in alphas:
             names = [os.path.join(out_dir, "%s_%s_%.2f%s" % (stem(structures[i]), stem(textures[i]), alpha, FORMATS[format])) for i in idx]

@@ -1936,6 +1936,23 @@ def label_matte(labels, keep=(1, 2), feather=16, grow=8, want_distance=False):
     return (matte, sd2) if want_distance else matte
 
 
+def _paste_out(photo_u8, out, who):
+    """the ``out`` rule of the pastes -> (the tensor the kernel reads, the one it writes): None clones the photo, the photo itself
+    works in place, any other contiguous uint8 tensor of its shape is filled with the photo first"""
+    if out is None:
+        out = photo_u8.clone(memory_format=torch.contiguous_format)
+        return out, out                                       # (a pixel reads only its own bytes: in place is the cloned form)
+    if out is photo_u8:
+        if not out.is_contiguous():
+            raise RuntimeError("%s in place needs a contiguous photo" % who)
+        return out, out
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.shape != photo_u8.shape or not out.is_contiguous() \
+            or out.device != photo_u8.device:
+        raise RuntimeError("%s: out must be a contiguous uint8 tensor of the photo's shape on its device" % who)
+    out.copy_(photo_u8)
+    return out, out
+
+
 def guided_filter_paste(coeffs, photo_u8, xf, feather=0, out=None, matte=None):
     """coeffs (B,12,n,n) fp32 (``guided_filter_coeffs`` of the crops ``extract_similarity`` took), photo (B,H,W,3) uint8, the same
     crop transforms -> uint8 (B,H,W,3): inside each crop square the photo's own pixels re-coloured by the bilinearly interpolated
@@ -1960,18 +1977,7 @@ def guided_filter_paste(coeffs, photo_u8, xf, feather=0, out=None, matte=None):
                 or tuple(matte.shape) != (B, n, n):
             raise RuntimeError("guided_filter_paste needs a float32 matte (B,n,n) = %s on the photo's device" % ((B, n, n),))
         matte = matte.contiguous()
-    if out is None:
-        out = photo_u8.clone(memory_format=torch.contiguous_format)
-        photo_u8 = out                                        # (a pixel reads only its own bytes: in place is the cloned form)
-    elif out is photo_u8:
-        if not out.is_contiguous():
-            raise RuntimeError("guided_filter_paste in place needs a contiguous photo")
-    else:
-        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.shape != photo_u8.shape or not out.is_contiguous() \
-                or out.device != photo_u8.device:
-            raise RuntimeError("guided_filter_paste: out must be a contiguous uint8 tensor of the photo's shape on its device")
-        out.copy_(photo_u8)
-        photo_u8 = out
+    photo_u8, out = _paste_out(photo_u8, out, "guided_filter_paste")
     host, dev = _crop_transforms(xf, B, out.device, "guided_filter_paste")
     coeffs = coeffs.contiguous()
     if matte is not None:
@@ -1981,6 +1987,57 @@ def guided_filter_paste(coeffs, photo_u8, xf, feather=0, out=None, matte=None):
     check(lib.ppst_guided_filter_paste(_p(coeffs), n, _p(photo_u8), _p(out), B, H, W, _p(host), _p(dev), int(feather), _stream()),
           "ppst_guided_filter_paste")
     return out
+
+
+def guided_matte_coeffs(guide_u8, matte, r=8, eps=(0.01 * 255) ** 2):
+    """guide (B,h,w,3) uint8, matte (B,h,w) fp32 on its device -> (B,4,h,w) fp32: the mean coefficient planes (mean a_0..2, mean b)
+    of the colour guided filter with the matte as its one source channel, quantised to rint(255 clamp(m, 0, 1)) on load (He et
+    al.'s guided feathering; ppst_guided_matte_coeffs in include/ppst_hip.h).  Bit-equal to planes 0..3 of
+    ``guided_filter_coeffs`` on the replicated source, through 13 of its 21 moment planes and 4 of its 12 coefficient planes; the
+    radius rule is ``guided_filter_coeffs``'."""
+    if not isinstance(guide_u8, torch.Tensor) or not guide_u8.is_cuda or guide_u8.dtype != torch.uint8:
+        raise RuntimeError("guided_matte_coeffs needs a CUDA uint8 guide")
+    if guide_u8.dim() != 4 or guide_u8.shape[3] != 3:
+        raise RuntimeError("guided_matte_coeffs needs a guide (B,h,w,3), got %s" % (tuple(guide_u8.shape),))
+    B, h, w, _ = guide_u8.shape
+    if not isinstance(matte, torch.Tensor) or matte.dtype != torch.float32 or matte.device != guide_u8.device \
+            or tuple(matte.shape) != (B, h, w):
+        raise RuntimeError("guided_matte_coeffs needs a float32 matte (B,h,w) = %s on the guide's device" % ((B, h, w),))
+    guide_u8, matte = guide_u8.contiguous(), matte.contiguous()
+    ws = torch.empty(lib.ppst_guided_matte_ws(B, h, w), device=guide_u8.device, dtype=torch.uint8)
+    mcoeffs = torch.empty((B, 4, h, w), device=guide_u8.device, dtype=torch.float32)
+    check(lib.ppst_guided_matte_coeffs(_p(guide_u8), _p(matte), _p(mcoeffs), B, h, w, int(r), float(eps), _p(ws), _stream()),
+          "ppst_guided_matte_coeffs")
+    return mcoeffs
+
+
+def guided_filter_paste_gmatte(coeffs, mcoeffs, photo_u8, xf, feather=0, out=None, want_weight=False):
+    """``guided_filter_paste`` through a guided matte: ``mcoeffs`` fp32 (B,4,n,n) on the photo's device (``guided_matte_coeffs``
+    of the crop) are sampled like the 12 colour planes and evaluated on the photo's own pixel, m^ = clamp((a . I + b) / 255, 0, 1),
+    so the matte follows the photo's edges; the blend weight is the edge feather times m^, and pixels of weight 0 keep the photo's
+    byte.  ``out`` as in ``guided_filter_paste``.  ``want_weight``: also the weight rint(255 g) as uint8 (B,H,W), 0 outside the
+    square."""
+    if not isinstance(coeffs, torch.Tensor) or not coeffs.is_cuda or coeffs.dtype != torch.float32:
+        raise RuntimeError("guided_filter_paste_gmatte needs CUDA float32 coefficients")
+    if not isinstance(photo_u8, torch.Tensor) or not photo_u8.is_cuda or photo_u8.dtype != torch.uint8:
+        raise RuntimeError("guided_filter_paste_gmatte needs a CUDA uint8 photo")
+    if (coeffs.dim() != 4 or coeffs.shape[1] != 12 or coeffs.shape[2] != coeffs.shape[3] or photo_u8.dim() != 4 or photo_u8.shape[3] != 3
+            or photo_u8.shape[0] != coeffs.shape[0]):
+        raise RuntimeError("guided_filter_paste_gmatte needs coefficients (B,12,n,n) and a photo (B,H,W,3) of one batch, got %s and %s"
+                           % (tuple(coeffs.shape), tuple(photo_u8.shape)))
+    B, _, n, _ = coeffs.shape
+    _, H, W, _ = photo_u8.shape
+    if not isinstance(mcoeffs, torch.Tensor) or mcoeffs.dtype != torch.float32 or mcoeffs.device != photo_u8.device \
+            or tuple(mcoeffs.shape) != (B, 4, n, n):
+        raise RuntimeError("guided_filter_paste_gmatte needs float32 matte coefficients (B,4,n,n) = %s on the photo's device" % ((B, 4, n, n),))
+    mcoeffs = mcoeffs.contiguous()
+    photo_u8, out = _paste_out(photo_u8, out, "guided_filter_paste_gmatte")
+    host, dev = _crop_transforms(xf, B, out.device, "guided_filter_paste_gmatte")
+    coeffs = coeffs.contiguous()
+    weight = torch.zeros((B, H, W), device=out.device, dtype=torch.uint8) if want_weight else None
+    check(lib.ppst_guided_filter_paste_gmatte(_p(coeffs), _p(mcoeffs), n, _p(photo_u8), _p(out), _p(weight), B, H, W, _p(host), _p(dev),
+                                              int(feather), _stream()), "ppst_guided_filter_paste_gmatte")
+    return (out, weight) if want_weight else out
 
 
 def _encode(name, u8, limits, geom=(), settings=()):

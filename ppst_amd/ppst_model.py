@@ -67,6 +67,16 @@ def guided_filter_radius(opt, h, w):
     return int(g)
 
 
+def guided_matte_radius(matte_radius, n):
+    """The radius rule of the guided matte (``ops.guided_matte_coeffs``) at an n x n crop, from integers alone: the radius as an
+    int, else ValueError."""
+    r = int(matte_radius)
+    if r != matte_radius or not 0 < r <= 64 or r >= n:
+        raise ValueError("the matte coefficients are computed at integer radii 0 < matte_radius <= 64 with matte_radius < n, "
+                         "got %r at n = %d" % (matte_radius, n))
+    return r
+
+
 class RsclQueues(nn.Module):
     """State + forward of rsclLoss (networks/rscl.py:17-90): four (2048, 128) key queues with their write pointers
     (checkpoint keys ``criterionNCE.queue_data_A{i}`` / ``queue_ptr_A{i}``)."""
@@ -368,6 +378,26 @@ class PPSTModel(nn.Module):
     def decode_region_matte(self, spatial_code, global_code, target, photo_u8, xf, feather=0, matte=None):
         """``decode_region`` blended through a matte: ``matte`` fp32 (B,n,n) in the crop's frame (``ops.label_matte``) multiplies the
         edge feather, and photo pixels where it is 0 keep their bytes.  ``matte=None`` is ``decode_region``."""
+        coeffs = self._region_coeffs(spatial_code, global_code, target)
+        return ops.guided_filter_paste(coeffs, photo_u8, xf, feather, matte=matte)
+
+    def decode_region_gmatte(self, spatial_code, global_code, target, photo_u8, xf, feather=0, matte=None, matte_radius=8,
+                             matte_eps=(0.01 * 255) ** 2, want_weight=False):
+        """``decode_region_matte`` with the matte refined by the photo's own pixels (He et al.'s guided feathering): ``matte`` fp32
+        (B,n,n) is filtered with the crop as guide (``ops.guided_matte_coeffs`` on the guide bytes of the colour filter, radius
+        ``matte_radius``, ``matte_eps``), and the paste evaluates it from those coefficients on each photo pixel
+        (``ops.guided_filter_paste_gmatte``), so the blend edge follows the photo's edges.  The matte is required; the radius rule
+        0 < matte_radius <= 64, matte_radius < n is raised from shapes before the generator runs.  ``want_weight``: also the
+        blend weight as uint8 (B,H,W)."""
+        if matte is None:
+            raise ValueError("decode_region_gmatte needs a matte (decode_region_matte blends without one)")
+        r = guided_matte_radius(matte_radius, min(int(target.shape[-2]), int(target.shape[-1])))
+        coeffs = self._region_coeffs(spatial_code, global_code, target)
+        mcoeffs = ops.guided_matte_coeffs(glue.tensor2im(target), matte, r, matte_eps)
+        return ops.guided_filter_paste_gmatte(coeffs, mcoeffs, photo_u8, xf, feather, want_weight=want_weight)
+
+    def _region_coeffs(self, spatial_code, global_code, target):
+        """the colour coefficients (B,12,n,n) of the region commands: ``decode_native``'s, at a square target"""
         h, w = int(target.shape[-2]), int(target.shape[-1])
         r = guided_filter_radius(self.opt, h, w)
         if not 0 < r <= 64 or r >= h or r >= w or w > 2048:           # (from shapes alone, before the generator runs)
@@ -376,8 +406,7 @@ class PPSTModel(nn.Module):
         if h != w:
             raise ValueError("decode_region: the crop is a square, got a target of %d x %d" % (h, w))
         out = self.G(spatial_code, global_code, noise=self.noise)
-        coeffs = ops.guided_filter_coeffs(glue.tensor2im(target), glue.tensor2im(out), r, (0.02 * 255) ** 2)
-        return ops.guided_filter_paste(coeffs, photo_u8, xf, feather, matte=matte)
+        return ops.guided_filter_coeffs(glue.tensor2im(target), glue.tensor2im(out), r, (0.02 * 255) ** 2)
 
     def discriminate(self, x):
         return self.D(x)
