@@ -956,6 +956,42 @@ int ppst_colour_stats(const void* img, int64_t img_sn, int64_t img_sy, int64_t i
 int ppst_hist_w1(const void* hist_a, int Ba, const void* hist_b, int Bb, const void* pairs, int K, int R, int P, void* num,
                  void* stream);
 
+/* ------------------------------------------------------- colour transfer ---- */
+/* Classical per-region colour transfer (csrc/colour_transfer.hip): the baselines the style-fidelity numbers are read against.
+ * Regions R <= 4; a label >= R belongs to no region and its pixel keeps its bytes.
+ *   ppst_hist_match_lut   exact histogram specification per RGB channel, in integers.  hist_c (Bc, R, P, 256), hist_s
+ *                   (Bs, R, P, 256) uint32 as ppst_colour_stats writes them (P >= 3; projections 0..2 must be the channel axes,
+ *                   the rest is not read); pairs (K, 2) int32 on the device.  luts[k][r][c][256] uint8: with hC, hS the
+ *                   histograms of (region, channel) of content i_k and style j_k, nC, nS their counts and cum the inclusive
+ *                   cumulative sum (cum(-1) = 0),
+ *                     LUT[v] = min{u in 0..255 : 2 cumS(u) nC >= (cumC(v - 1) + cumC(v)) nS}
+ *                   -- the mid-point form: a flat content region goes to the style's median, not to its maximum.  Every product
+ *                   is below 2^46 (counts <= 2^22) and is taken in int64.  nC == 0 or nS == 0, or an index outside
+ *                   [0, Bc) x [0, Bs) (nothing is read): the identity table
+ *   ppst_colour_transfer_apply   img (B, H, W, 3) uint8 and labels (B, H, W) uint8 or null (every pixel is region 0) with the
+ *                   stride rules of ppst_colour_stats; out uint8 [B][H][W][3], dense.  mode PPST_CT_LUT: maps = uint8
+ *                   [B][R][3][256], out_c = LUT[label][c][in_c].  mode PPST_CT_AFFINE: maps = fp32 [B][R][12], a row
+ *                   (T row-major | t): lab' = T lab + t in fp32 (fma chains, the offset innermost), with sRGB -> Lab as
+ *                   "colour statistics" defines it and Lab -> sRGB its inverse: fy = (L + 16) / 116, fx = fy + a / 500,
+ *                   fz = fy - b / 200; t = f^3 above 6/29, else (f - 4/29) * 108 / 841; linear RGB = Minv t, Minv the float64
+ *                   inverse of the float64 matrix rounded once to fp32; clamp to [0, 1]; s = 12.92 c up to 0.0031308, else
+ *                   1.055 c^(1/2.4) - 0.055; the byte is rint(255 s).
+ *                   weights (may be null): fp32 [B][R][H][W], >= 0, normalised per pixel here: with W = sum_r w_r > 0 the LUT
+ *                   mode gives rint(sum_r w_r LUT[r][c][in_c] / W) and the affine mode blends the 12 coefficients,
+ *                   sum_r w_r k_r / W, before its one conversion (sums in region order, fp32); W == 0 falls back to the pixel's
+ *                   label.  A pixel of no region is copied whatever its weights.  Pixels move as dwords, four pixels in three;
+ *                   no atomics: repeats are bit-identical and an image gives the same bits alone as inside a batch.
+ * B (K, Bc, Bs) < 0, H or W < 1, H * W > 2^22, R outside [1, 4], P outside [3, 16], img_sx != 3, a mode other than the two:
+ * PPST_EINVAL; B == 0 (K == 0) is a no-op (PPST_OK) before any pointer is looked at; null pointers (labels and weights
+ * excepted) PPST_ENULL.  Nothing is launched in any of these cases. */
+#define PPST_CT_LUT 0
+#define PPST_CT_AFFINE 1
+int ppst_hist_match_lut(const void* hist_c, int Bc, const void* hist_s, int Bs, const void* pairs, int K, int R, int P, void* luts,
+                        void* stream);
+int ppst_colour_transfer_apply(const void* img, int64_t img_sn, int64_t img_sy, int64_t img_sx, const void* labels, int64_t lab_sn,
+                               int64_t lab_sy, int B, int H, int W, int R, int mode, const void* maps, const void* weights, void* out,
+                               void* stream);
+
 /* ------------------------------------------------------- post-process ---- */
 /* util.tensor2im quantisation (util/util.py:98-131): NCHW fp32 [-1,1] ->
  * HWC uint8, ((x+1)/2*255) clipped and truncated. */

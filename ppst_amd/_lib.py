@@ -208,6 +208,8 @@ _SIGS = {
     "ppst_colour_stats_ws": (i64, [i32, i32, i32]),
     "ppst_colour_stats": (i32, [vp, i64, i64, i64, vp, i64, i64, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int16), i32, vp, vp, vp, vp, vp, vp]),
     "ppst_hist_w1": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp]),
+    "ppst_hist_match_lut": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp]),
+    "ppst_colour_transfer_apply": (i32, [vp, i64, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "ppst_guided_filter_ws": (i64, [i32, i32, i32]),
     "ppst_guided_filter": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),
     "ppst_guided_filter_coeffs": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),

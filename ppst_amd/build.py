@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libppst_hip.so")
 SOURCES = ["upfirdn2d.hip", "fused_bias_act.hip", "elementwise.hip", "linear.hip", "conv_mfma.hip", "conv_mfma2.hip", "conv1x1.hip", "conv_wino.hip", "conv_f32.hip", "encoder_block.hip",
-           "corr.hip", "guided_filter.hip", "train.hip", "train_g.hip", "imageio.hip", "smooth_filter.hip", "png.hip", "jpeg.hip", "jpeg_parse.hip", "jpeg_decode.hip", "png_parse.hip", "png_decode.hip", "lpips.hip", "ssim.hip", "colour_stats.hip", "matte.hip"]
+           "corr.hip", "guided_filter.hip", "train.hip", "train_g.hip", "imageio.hip", "smooth_filter.hip", "png.hip", "jpeg.hip", "jpeg_parse.hip", "jpeg_decode.hip", "png_parse.hip", "png_decode.hip", "lpips.hip", "ssim.hip", "colour_stats.hip", "matte.hip", "colour_transfer.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result"]
 # per-file flags.  conv_wino.hip: its staging arithmetic runs inside the MFMA stream and the kernel sits at 256 registers -- with SLP
 # vectorisation hipcc packs it into v_pk_* (operand pairs assembled with moves, 1 100 packed instructions, spills in the
@@ -30,7 +30,7 @@ def _hipcc():
 
 
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "rscl_common.h"), os.path.join(CSRC, "png_common.h"),
-           os.path.join(CSRC, "codec_common.h"), os.path.join(CSRC, "jpeg_common.h"), os.path.join(CSRC, "parse_reader.h"), os.path.join(CSRC, "sim_xf.h"),
+           os.path.join(CSRC, "codec_common.h"), os.path.join(CSRC, "jpeg_common.h"), os.path.join(CSRC, "parse_reader.h"), os.path.join(CSRC, "sim_xf.h"), os.path.join(CSRC, "colour_lab.h"),
            os.path.join(HERE, "..", "include", "ppst_hip.h")]
 
 

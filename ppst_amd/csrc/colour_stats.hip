@@ -21,6 +21,7 @@
 //               int64.
 // Nothing depends on the batch: the wave chunks and the blocks per image follow from H * W alone.
 #include "common.h"
+#include "colour_lab.h"                   // sRGB -> Lab: the table, the matrix, cs_lab
 #include <math.h>
 
 namespace {
@@ -35,29 +36,12 @@ namespace {
 #define CS_CONST_FLOATS (256 + 4 * CS_MAX_P)
 
 struct CsConst { float tab[256]; int dir[CS_MAX_P][4]; };   // (d0, d1, d2, 255 * sum of the negative |d_c|)
-struct CsMat { float m[3][3]; };
-struct CsLab { float L, a, b; };
 
 __global__ __launch_bounds__(64) void cs_setup_kernel(CsConst c, float* __restrict__ out) {
   for (int i = threadIdx.x; i < CS_CONST_FLOATS; i += 64)
     out[i] = i < 256 ? c.tab[i] : __int_as_float(c.dir[(i - 256) >> 2][(i - 256) & 3]);
 }
 
-__device__ __forceinline__ float cs_f(float t) {
-  return t > 0.008856451679035631f ? cbrtf(t) : fmaf(t, 7.787037037037037f, 0.13793103448275862f);
-}
-// (every multiply-add is an explicit fma: the pivot and the pixels go through the same arithmetic wherever this is inlined)
-__device__ __forceinline__ CsLab cs_lab(const float* __restrict__ tab, const CsMat& M, unsigned r, unsigned g, unsigned b) {
-  const float lr = tab[r], lg = tab[g], lb = tab[b];
-  const float fx = cs_f(fmaf(M.m[0][0], lr, fmaf(M.m[0][1], lg, M.m[0][2] * lb)));
-  const float fy = cs_f(fmaf(M.m[1][0], lr, fmaf(M.m[1][1], lg, M.m[1][2] * lb)));
-  const float fz = cs_f(fmaf(M.m[2][0], lr, fmaf(M.m[2][1], lg, M.m[2][2] * lb)));
-  CsLab o;
-  o.L = fmaf(116.f, fy, -16.f);
-  o.a = 500.f * (fx - fy);
-  o.b = 200.f * (fy - fz);
-  return o;
-}
 __device__ __forceinline__ int cs_wave_sum_i(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -275,10 +259,7 @@ int ppst_colour_stats(const void* img, int64_t img_sn, int64_t img_sy, int64_t i
   if (!img || !dirs || !hist || !count || !lab_mean || !lab_cov || !ws) return PPST_ENULL;
   static CsConst base;                                         // the table: built once (the same values every time)
   static const bool built = [] {
-    for (int i = 0; i < 256; ++i) {
-      const double c = i / 255.0;
-      base.tab[i] = (float)(c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4));
-    }
+    cs_srgb_table(base.tab);
     return true;
   }();
   (void)built;
@@ -294,11 +275,7 @@ int ppst_colour_stats(const void* img, int64_t img_sn, int64_t img_sy, int64_t i
     if (mag > 4096) return PPST_EINVAL;
     cst.dir[p][0] = d[0]; cst.dir[p][1] = d[1]; cst.dir[p][2] = d[2]; cst.dir[p][3] = 255 * neg;
   }
-  static const double XYZ[3][3] = {{0.4124564, 0.3575761, 0.1804375}, {0.2126729, 0.7151522, 0.0721750}, {0.0193339, 0.1191920, 0.9503041}};
-  static const double WHITE[3] = {0.95047, 1.0, 1.08883};
-  CsMat M;
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) M.m[r][c] = (float)(XYZ[r][c] / WHITE[r]);
+  const CsMat M = cs_lab_matrix();
   hipStream_t st = as_stream(stream);
   const int nwc = cs_wave_chunks(H, W), nb = cdiv(nwc, 4) < CS_MAX_BLOCKS ? cdiv(nwc, 4) : CS_MAX_BLOCKS;
   const size_t hist_bytes = (size_t)B * R * P * 256 * sizeof(unsigned);

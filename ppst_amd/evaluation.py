@@ -338,6 +338,72 @@ def style_fidelity(styles, outputs, style_labels=None, content_labels=None, regi
         return metrics.colour_distance(metrics.colour_stats(styles, style_labels, R), metrics.colour_stats(outputs, content_labels, R))
 
 
+# ------------------------------------------------------------------------------------------------- classical baselines
+def _baseline_inputs(images, labels):
+    """-> (uint8 (N, H, W, 3), uint8 (N, H, W) labels or None), as ``metrics.colour_stats`` reads them"""
+    from . import metrics
+    metrics._on_device(images)
+    u8 = images if images.dtype == torch.uint8 else glue.tensor2im(images)
+    if labels is not None:
+        metrics._on_device(labels)
+        labels = (labels.argmax(dim=1) if labels.dim() == 4 else labels).to(torch.uint8)
+    return u8, labels
+
+
+def _baseline_images(out_u8, guide_u8, smooth, gf_radius):
+    """uint8 (K, H, W, 3) -> fp32 (K, 3, H, W) in [-1, 1]: the guided filter of ``decode(target=...)`` with the content as guide,
+    or -- without it -- min((v + 0.5) / 127.5 - 1, 1), which stays in [-1, 1] and which ``glue.tensor2im`` takes back to v"""
+    if smooth:
+        return ops.guided_filter(guide_u8.contiguous(), out_u8, gf_radius, (0.02 * 255) ** 2)
+    return ((out_u8.permute(0, 3, 1, 2).float() + 0.5) / 127.5 - 1.0).clamp_(max=1.0)
+
+
+def baseline_swap(contents, styles, content_labels=None, style_labels=None, method="hist", regions=3, feather=0, smooth=False,
+                  gf_radius=30):
+    """What a CLASSICAL colour transfer makes of the pairs ``simple_swap`` is given: content n re-coloured towards style n per
+    region (``metrics.colour_transfer``: "hist" exact histogram specification per RGB channel, "mkl" the Monge-Kantorovich
+    linear map between the regions' Lab Gaussians, "reinhard" per-axis mean and deviation).  Images fp32 (B, 3, H, W) in [-1, 1] or
+    uint8 (B, H, W, 3); labels as ``style_fidelity`` takes them, of both sides or of neither (then the image is one region).
+    -> fp32 (B, 3, H, W) in [-1, 1] like ``simple_swap``'s images.  ``feather``: blend the regions through feathered mattes;
+    ``smooth``: run ``ops.guided_filter`` (radius ``gf_radius``) with the content as guide, as ``decode(target=...)`` does."""
+    from . import metrics
+    if (style_labels is None) != (content_labels is None):
+        raise ValueError("baseline_swap needs the labels of both sides, or of neither")
+    R = regions if style_labels is not None else 1
+    with torch.no_grad():
+        c_u8, c_lab = _baseline_inputs(contents, content_labels)
+        s_u8, s_lab = _baseline_inputs(styles, style_labels)
+        if c_u8.shape[0] != s_u8.shape[0]:
+            raise ValueError("baseline_swap pairs contents and styles one to one (%d and %d)" % (c_u8.shape[0], s_u8.shape[0]))
+        st_s = metrics.colour_stats(s_u8, s_lab, R)
+        out = metrics.colour_transfer(c_u8, st_s, c_lab, method, R, feather=feather)
+        return _baseline_images(out, c_u8, smooth, gf_radius)
+
+
+def baseline_grid(contents, styles, content_labels=None, style_labels=None, method="hist", regions=3, feather=0, smooth=False,
+                  gf_radius=30, pairs=None):
+    """``baseline_swap`` for every (content i, style j) (or the ``pairs`` given): {(i, j): image (3, H, W)}, shaped like
+    ``swapping_grid``'s dict, so ``content_preservation`` and ``style_fidelity`` take it as it is.  The statistics of every
+    distinct image are taken once."""
+    from . import metrics
+    if (style_labels is None) != (content_labels is None):
+        raise ValueError("baseline_grid needs the labels of both sides, or of neither")
+    R = regions if style_labels is not None else 1
+    with torch.no_grad():
+        c_u8, c_lab = _baseline_inputs(contents, content_labels)
+        s_u8, s_lab = _baseline_inputs(styles, style_labels)
+        if pairs is None:
+            pairs = [(i, j) for i in range(c_u8.shape[0]) for j in range(s_u8.shape[0])]
+        pairs = [(int(i), int(j)) for i, j in pairs]
+        if not pairs:
+            return {}
+        st_s = metrics.colour_stats(s_u8, s_lab, R)
+        st_c = metrics.colour_stats(c_u8, c_lab, R)
+        out = metrics.colour_transfer(c_u8, st_s, c_lab, method, R, pairs=pairs, feather=feather, content_stats=st_c)
+        img = _baseline_images(out, c_u8[[i for i, _ in pairs]], smooth, gf_radius)
+        return {k: img[n] for n, k in enumerate(pairs)}
+
+
 # ------------------------------------------------------------------------------------------------- file front ends
 _IMG_EXT = (".jpg", ".jpeg", ".png", ".bmp", ".webp")
 

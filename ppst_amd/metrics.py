@@ -10,6 +10,10 @@ There is no CPU fallback: CPU tensors raise RuntimeError.
 The second half of this file holds the style-fidelity metrics (csrc/colour_stats.hip; include/ppst_hip.h "colour statistics"):
 ``colour_stats`` / ``colour_distance``, distances between the colour distributions of two images per label region, held to
 integer and float64 restatements (tests/colour_cases.py).
+
+The last part holds the colour-transfer baselines (csrc/colour_transfer.hip; include/ppst_hip.h "colour transfer"):
+``colour_transfer_maps`` / ``colour_transfer``, classical per-region histogram specification, Monge-Kantorovich and Reinhard
+transfers, held to integer and float64 restatements (tests/transfer_cases.py).
 """
 import torch
 
@@ -176,3 +180,110 @@ def colour_distance(stats_a, stats_b, pairs=None):
     out["delta_e"] = torch.where(empty, nan, (ma - mb).norm(dim=-1))
     out["frechet"] = torch.where(empty, nan, gaussian_w2_squared(ma, stats_a.lab_cov[ia], mb, stats_b.lab_cov[ib]))
     return out
+
+
+# ------------------------------------------------------------------------------------------------- colour-transfer baselines
+# What does a CLASSICAL per-region colour transfer score on the same images with the same labels?  The other anchor of the style
+# numbers, beside "no transfer at all" (csrc/colour_transfer.hip; include/ppst_hip.h "colour transfer"; DESIGN.md "Colour-transfer
+# baselines").  The maps are built from two ColourStats; one HIP pass applies them to the content's pixels.
+TRANSFER_METHODS = ("hist", "mkl", "reinhard")
+
+
+def _pairs_or_diagonal(na, nb, pairs, who):
+    if pairs is None:
+        if na != nb:
+            raise ValueError("%s without pairs needs as many entries on both sides (%d and %d)" % (who, na, nb))
+        pairs = [(n, n) for n in range(na)]
+    return torch.as_tensor(pairs).reshape(-1, 2).to(torch.int64).cpu()
+
+
+def gaussian_transfer_rows(mean_c, cov_c, count_c, mean_s, cov_s, count_s, method="mkl", floor=1e-2, max_gain=8.0):
+    """The affine rows (T row-major | mu_S - T mu_C) that carry the Gaussian (mean_c, cov_c) onto (mean_s, cov_s): float64 on the
+    host, (..., 12).  ``"mkl"``: the Monge-Kantorovich linear map T = Sc^-1/2 (Sc^1/2 Ss Sc^1/2)^1/2 Sc^-1/2 (Pitie & Kokaram
+    2007), the optimal transport between the two Gaussians; ``"reinhard"``: T = diag(sigma_S / sigma_C) per Lab axis (Reinhard et
+    al. 2001).  ``floor`` is the lower clamp on Sc's eigenvalues (on its variances) before the inverse root, ``max_gain`` the
+    upper clamp on T's eigenvalues: both are PARAMETERS that keep a flat region from being amplified without bound, not findings.
+    A region that is empty on either side gets the identity row."""
+    mean_c, cov_c, mean_s, cov_s = (t.detach().double().cpu() for t in (mean_c, cov_c, mean_s, cov_s))
+    if method == "mkl":
+        w, v = torch.linalg.eigh(cov_c)
+        w = w.clamp(min=floor)
+        root = (v * w.sqrt().unsqueeze(-2)) @ v.transpose(-1, -2)
+        iroot = (v * w.rsqrt().unsqueeze(-2)) @ v.transpose(-1, -2)
+        T = iroot @ _sqrtm_psd(root @ cov_s @ root) @ iroot
+        T = 0.5 * (T + T.transpose(-1, -2))
+        w, v = torch.linalg.eigh(T)
+        T = (v * w.clamp(max=max_gain).unsqueeze(-2)) @ v.transpose(-1, -2)
+    elif method == "reinhard":
+        var_c, var_s = cov_c.diagonal(dim1=-2, dim2=-1), cov_s.diagonal(dim1=-2, dim2=-1)
+        T = torch.diag_embed((var_s.clamp(min=0.0) / var_c.clamp(min=floor)).sqrt().clamp(max=max_gain))
+    else:
+        raise ValueError("gaussian_transfer_rows: method 'mkl' or 'reinhard', got %r" % (method,))
+    off = mean_s - (T @ mean_c.unsqueeze(-1)).squeeze(-1)
+    rows = torch.cat((T.flatten(-2), off), -1)
+    eye = torch.cat((torch.eye(3, dtype=torch.float64).flatten(), torch.zeros(3, dtype=torch.float64)))
+    empty = ((count_c == 0) | (count_s == 0)).cpu().unsqueeze(-1)
+    return torch.where(empty, eye.expand_as(rows), rows)
+
+
+def colour_transfer_maps(stats_c, stats_s, method, pairs=None, floor=1e-2, max_gain=8.0):
+    """The maps that carry entry i of ``stats_c`` (the content) onto entry j of ``stats_s`` (the style) for every (i, j) of
+    ``pairs`` (None: n with n), per region.  ``"hist"``: uint8 (K, R, 3, 256) tables (``ops.hist_match_lut``; the statistics must
+    have been taken with ``ops.COLOUR_AXES`` as their first three directions); ``"mkl"`` / ``"reinhard"``: fp32 (K, R, 12) rows
+    (``gaussian_transfer_rows``; ``floor`` = 1e-2, the lower clamp on the content covariance's eigenvalues, and ``max_gain`` = 8,
+    the upper clamp on the map's, are parameters, not findings).  On the statistics' device."""
+    if method not in TRANSFER_METHODS:
+        raise ValueError("colour_transfer_maps: method one of %s, got %r" % (TRANSFER_METHODS, method))
+    pr = _pairs_or_diagonal(len(stats_c), len(stats_s), pairs, "colour_transfer_maps")
+    if method == "hist":
+        axes = torch.tensor(ops.COLOUR_AXES, dtype=torch.int16)
+        for st in (stats_c, stats_s):
+            if st.dirs.shape[0] < 3 or not torch.equal(st.dirs[:3].to(torch.int16), axes):
+                raise ValueError("colour_transfer_maps('hist') needs statistics whose first three directions are ops.COLOUR_AXES")
+        return ops.hist_match_lut(stats_c.hist, stats_s.hist, pr)
+    dev = stats_c.hist.device
+    ic, js = pr[:, 0].to(dev), pr[:, 1].to(dev)
+    rows = gaussian_transfer_rows(stats_c.lab_mean[ic], stats_c.lab_cov[ic], stats_c.count[ic], stats_s.lab_mean[js],
+                                  stats_s.lab_cov[js], stats_s.count[js], method, floor, max_gain)
+    return rows.float().to(dev)
+
+
+def region_weights(labels, regions, feather):
+    """fp32 (B, R, H, W): one ``ops.label_matte(labels, keep=(r,), feather, grow=feather // 2)`` per region"""
+    return torch.stack([ops.label_matte(labels, keep=(r,), feather=feather, grow=feather // 2) for r in range(regions)], 1)
+
+
+def colour_transfer(contents, style_stats, content_labels=None, method="hist", regions=1, pairs=None, feather=0, floor=1e-2,
+                    max_gain=8.0, content_stats=None):
+    """Content i re-coloured towards entry j of ``style_stats`` for every (i, j) of ``pairs`` (None: n with n), per region of the
+    content's labels: uint8 (K, H, W, 3).  ``contents`` / ``content_labels`` as ``colour_stats`` takes them; ``regions`` must be
+    that of ``style_stats``.  It takes the contents' statistics (or ``content_stats``, if the caller has them), builds the maps
+    (``colour_transfer_maps``) and applies them (``ops.colour_transfer_apply``).  ``feather`` > 0: the regions blend through
+    feathered mattes of the label map (``region_weights``) instead of switching at the label boundary."""
+    from . import glue
+    _on_device(contents)
+    if contents.dtype != torch.uint8:
+        contents = glue.tensor2im(contents)
+    lab = content_labels
+    if lab is not None:
+        _on_device(lab)
+        if lab.dim() == 4:
+            lab = lab.argmax(dim=1)
+        lab = lab.to(torch.uint8)
+    R = int(regions)
+    if style_stats.hist.shape[1] != R:
+        raise ValueError("colour_transfer: the style statistics have %d regions, not %d" % (style_stats.hist.shape[1], R))
+    if content_stats is None:
+        content_stats = colour_stats(contents, lab, R, style_stats.dirs)
+    pr = _pairs_or_diagonal(len(content_stats), len(style_stats), pairs, "colour_transfer")
+    maps = colour_transfer_maps(content_stats, style_stats, method, pr, floor, max_gain)
+    idx = pr[:, 0].to(contents.device)
+    diagonal = pr[:, 0].tolist() == list(range(contents.shape[0]))
+    u8 = contents if diagonal else contents[idx]
+    lab_k = lab if lab is None or diagonal else lab[idx]
+    weights = None
+    if feather > 0 and lab is not None:
+        w = region_weights(lab.contiguous(), R, int(feather))
+        weights = w if diagonal else w[idx]
+    key = "luts" if method == "hist" else "affine"
+    return ops.colour_transfer_apply(u8, lab_k, weights=weights, **{key: maps})

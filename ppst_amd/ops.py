@@ -2580,6 +2580,83 @@ def hist_w1(hist_a, hist_b, pairs):
     return num
 
 
+# ----------------------------------------------------------- colour transfer ----
+def hist_match_lut(hist_c, hist_s, pairs):
+    """The exact histogram-specification tables (csrc/colour_transfer.hip; include/ppst_hip.h "colour transfer") that send the
+    channel histograms ``hist_c[i]`` onto ``hist_s[j]`` for every (i, j) of ``pairs``, per region: uint8 (K, R, 3, 256).  Both
+    are ``colour_stats`` histograms (B, R, P, 256) int32 whose projections 0..2 are the channel axes (``COLOUR_AXES``; the rest
+    is not read).  ``LUT[v] = min{u : 2 cumS(u) nC >= (cumC(v - 1) + cumC(v)) nS}``; the identity where a side is empty."""
+    for t, name in ((hist_c, "hist_c"), (hist_s, "hist_s")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("hist_match_lut %s must be a CUDA (HIP) tensor (no CPU fallback)" % name)
+        if t.dtype != torch.int32 or t.dim() != 4 or t.shape[3] != 256 or t.shape[2] < 3:
+            raise RuntimeError("hist_match_lut %s must be int32 (B, R, P >= 3, 256), got %s %s" % (name, t.dtype, tuple(t.shape)))
+    if hist_c.shape[1:] != hist_s.shape[1:] or hist_c.device != hist_s.device:
+        raise RuntimeError("hist_match_lut: the two histogram tensors differ: %s and %s" % (tuple(hist_c.shape), tuple(hist_s.shape)))
+    pr = torch.as_tensor(pairs).detach().cpu().reshape(-1, 2).to(torch.int64)
+    K, (Bc, R, P), Bs = int(pr.shape[0]), hist_c.shape[:3], hist_s.shape[0]
+    if K and (int(pr.min()) < 0 or int(pr[:, 0].max()) >= Bc or int(pr[:, 1].max()) >= Bs):
+        raise ValueError("hist_match_lut: a pair index is outside the histograms' batches (%d and %d)" % (Bc, Bs))
+    if not 1 <= R <= COLOUR_MAX_REGIONS or P > COLOUR_MAX_DIRS:
+        raise ValueError("hist_match_lut: 1 .. 4 regions and 3 .. 16 projections, got %d and %d" % (R, P))
+    hist_c, hist_s = hist_c.contiguous(), hist_s.contiguous()
+    pr = pr.to(torch.int32).contiguous().to(hist_c.device)
+    luts = torch.empty((K, R, 3, 256), device=hist_c.device, dtype=torch.uint8)
+    check(lib.ppst_hist_match_lut(_p(hist_c), Bc, _p(hist_s), Bs, _p(pr), K, R, P, _p(luts), _stream()), "ppst_hist_match_lut")
+    return luts
+
+
+def colour_transfer_apply(u8, labels, luts=None, affine=None, weights=None, out=None):
+    """One pass that re-colours ``u8`` (B, H, W, 3) uint8 (strides as ``colour_stats``: a crop view is read in place) per region
+    of ``labels`` ((B, H, W) uint8, or None: one region) -> uint8 (B, H, W, 3).  Exactly one of ``luts`` (uint8 (B, R, 3, 256):
+    ``out_c = LUT[label][c][in_c]``) and ``affine`` (fp32 (B, R, 12) rows (T | t): ``lab' = T lab + t`` in CIELAB, converted back
+    and quantised once).  ``weights``: fp32 (B, R, H, W) >= 0, normalised per pixel in the kernel; the tables' outputs (the 12
+    coefficients) are blended by them, a pixel whose weights are all 0 follows its label.  A pixel whose label is >= R keeps its
+    bytes.  ``out``: a contiguous uint8 (B, H, W, 3) tensor to write to (and return)."""
+    _u8_dev(u8, "colour_transfer_apply images", 4)
+    B, H, W, C = u8.shape
+    if C != 3:
+        raise RuntimeError("colour_transfer_apply images must be (B, H, W, 3), got %s" % (tuple(u8.shape),))
+    if (luts is None) == (affine is None):
+        raise ValueError("colour_transfer_apply takes exactly one of luts and affine")
+    maps, mode = (luts, 0) if luts is not None else (affine, 1)
+    want = torch.uint8 if mode == 0 else torch.float32
+    if not isinstance(maps, torch.Tensor) or not maps.is_cuda:
+        raise RuntimeError("colour_transfer_apply maps must be a CUDA (HIP) tensor (no CPU fallback)")
+    ok = maps.dim() == 4 and maps.shape[2:] == (3, 256) if mode == 0 else maps.dim() == 3 and maps.shape[2] == 12
+    if maps.dtype != want or not ok or maps.shape[0] != B or maps.device != u8.device:
+        raise RuntimeError("colour_transfer_apply: luts must be uint8 (B, R, 3, 256), affine fp32 (B, R, 12), B = %d, on the images' "
+                           "device; got %s %s" % (B, maps.dtype, tuple(maps.shape)))
+    R = int(maps.shape[1])
+    if u8.stride(3) != 1 or (W > 1 and u8.stride(2) != 3):
+        u8 = u8.contiguous()
+    if labels is not None:
+        _u8_dev(labels, "colour_transfer_apply labels", 3)
+        if tuple(labels.shape) != (B, H, W) or labels.device != u8.device:
+            raise RuntimeError("colour_transfer_apply labels must be (B, H, W) = %s on the images' device, got %s" % ((B, H, W), tuple(labels.shape)))
+        if W > 1 and labels.stride(2) != 1:
+            labels = labels.contiguous()
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor) or not weights.is_cuda:
+            raise RuntimeError("colour_transfer_apply weights must be a CUDA (HIP) tensor (no CPU fallback)")
+        if weights.dtype != torch.float32 or tuple(weights.shape) != (B, R, H, W) or weights.device != u8.device:
+            raise RuntimeError("colour_transfer_apply weights must be fp32 (B, R, H, W) = %s, got %s %s" % ((B, R, H, W), weights.dtype, tuple(weights.shape)))
+        weights = weights.contiguous()
+    if H < 1 or W < 1 or H * W > COLOUR_MAX_PIXELS or not 1 <= R <= COLOUR_MAX_REGIONS:
+        raise ValueError("colour_transfer_apply: 1 <= H * W <= 2^22 and 1 .. 4 regions; got %s, %d regions" % ((B, H, W), R))
+    if out is None:
+        out = torch.empty((B, H, W, 3), device=u8.device, dtype=torch.uint8)
+    else:
+        _u8_dev(out, "colour_transfer_apply out", 4)
+        if tuple(out.shape) != (B, H, W, 3) or not out.is_contiguous() or out.device != u8.device:
+            raise RuntimeError("colour_transfer_apply out must be a contiguous (B, H, W, 3) = %s tensor on the images' device" % ((B, H, W, 3),))
+    maps = maps.contiguous()
+    check(lib.ppst_colour_transfer_apply(_p(u8), u8.stride(0), u8.stride(1), 3, _p(labels), 0 if labels is None else labels.stride(0),
+                                         0 if labels is None else labels.stride(1), B, H, W, R, mode, _p(maps), _p(weights), _p(out),
+                                         _stream()), "ppst_colour_transfer_apply")
+    return out
+
+
 # --------------------------------------------------------------- profiling ----
 PROF_ON = {"value": False}
 

@@ -343,15 +343,32 @@ class HeldOutEvaluator:
     ``swap_style_delta_e`` (``evaluation.style_fidelity``'s w1_rgb, swd and delta_e: means over the pairs and the non-empty
     regions) and ``identity_style_w1``, the same w1 between each content and its style BEFORE the swap: what no transfer at all
     scores on these images.  ``labels`` (integer (N, H, W) maps or one-hot masks of the images, three regions): the distances are
-    taken per region, and the three style numbers are also reported per region as ``..._r0``, ``_r1``, ``_r2``."""
+    taken per region, and the three style numbers are also reported per region as ``..._r0``, ``_r1``, ``_r2``.
+    ``set_baseline(method)`` (with ``swaps=True``; the constructor's parameter list is pinned, so the choice is made on the
+    object: ``HeldOutEvaluator(x, swaps=True).set_baseline("hist")``): "hist", "mkl" or "reinhard" -- the same pairs also go
+    through ``evaluation.baseline_swap`` with that method (no feather, no guided filter) and are scored the same way as
+    ``baseline_content_ssim``, ``baseline_style_w1``, ``baseline_style_swd`` and ``baseline_style_delta_e`` (per region with
+    labels): what a classical per-region colour transfer scores where the model scores ``swap_...``.  None adds nothing."""
 
     STYLE_KEYS = (("swap_style_w1", "w1_rgb"), ("swap_style_swd", "swd"), ("swap_style_delta_e", "delta_e"))
+
+    baseline = None
 
     def __init__(self, images, log_path=None, batch=8, swaps=False, labels=None):
         if swaps and images.shape[0] < 2:
             raise ValueError("HeldOutEvaluator(swaps=True) needs at least two images, got %d" % images.shape[0])
         self.images, self.log_path, self.batch, self.swaps, self.labels = images, log_path, batch, swaps, labels
         self.history = []
+
+    def set_baseline(self, method):
+        """choose the classical baseline reported beside the swap numbers (None: none); returns the evaluator"""
+        from .metrics import TRANSFER_METHODS
+        if method is not None and method not in TRANSFER_METHODS:
+            raise ValueError("HeldOutEvaluator.set_baseline takes None or one of %s, got %r" % (TRANSFER_METHODS, method))
+        if method is not None and not self.swaps:
+            raise ValueError("HeldOutEvaluator.set_baseline needs swaps=True: the baseline runs on the swap pairs")
+        self.baseline = method
+        return self
 
     def evaluate_swaps(self, model):
         """the swap numbers of ``swaps=True`` as {name: float}"""
@@ -373,6 +390,16 @@ class HeldOutEvaluator:
                 for r in range(fid[name].shape[1]):
                     res["%s_r%d" % (key, r)] = nanmean(fid[name][:, r])
         res["identity_style_w1"] = nanmean(evaluation.style_fidelity(styles, self.images, lab_s, lab)["w1_rgb"])
+        if self.baseline is not None:
+            base = evaluation.baseline_swap(self.images, styles, lab, lab_s, method=self.baseline)
+            res["baseline_content_ssim"] = float(evaluation.content_preservation(self.images, base).double().mean().item())
+            fid = evaluation.style_fidelity(styles, base, lab_s, lab)
+            for key, name in self.STYLE_KEYS:
+                key = key.replace("swap_", "baseline_")
+                res[key] = nanmean(fid[name])
+                if lab is not None:
+                    for r in range(fid[name].shape[1]):
+                        res["%s_r%d" % (key, r)] = nanmean(fid[name][:, r])
         return res
 
     @staticmethod
