@@ -11,13 +11,29 @@
 //     ppst_model.guided_filter_radius): TWO fused launches that keep every box sum on the chip --
 //     gf_s1_fused (uint8 -> exact uint32 moment sums -> 3x3 solve -> 12 half planes (a, b)), gf_s2_fused (means of (a, b),
 //     q = sum a_k I_k + b, round; uint8 + fp32 NCHW (q/255-0.5)*2).  Described at the kernels; each radius has its own strip geometry.
-//   every other radius up to GF_MAXR: FIVE launches of separable direct sums (no running sums: order-independent fp32 error) over
-//     [B][plane][H][W] fp32 planes in the caller's workspace --
-//     gf_h<true>  (uint8 -> 21 h-sums: I(3), p(3), I_i*I_j(6), I_i*p_c(9); one block per image row, row staged in LDS, reflected)
-//     gf_v        (21 means; lanes along x (coalesced), 2r+1 row reads per output served by L1/L2)
-//     gf_solve    (-> 12 planes a_c[3], b_c)
-//     gf_h<false> (12 h-sums)
-//     gf_v_final  (means of a, b; q; round; the two outputs)
+//   every other radius up to GF_MAXR: the PLANE ROUTE (gf_plane_route) and gf_v_final (means of a, b; q; round; the two outputs).
+// The plane route: four launches of separable direct sums (no running sums: order-independent fp32 error) over [B][plane][H][W]
+// fp32 planes in the caller's workspace, which leave the h-summed coefficient planes for the caller's last V pass --
+//     gf_h<source> (NM h-sums of the moments; one block per image row, row staged in LDS, reflected)
+//     gf_v         (NM means; lanes along x (coalesced), 2r+1 row reads per output served by L1/L2)
+//     solve        (-> 4 NC planes a_c[3], b_c)
+//     gf_h<planes> (4 NC h-sums)
+// It serves three entries.  ppst_guided_filter: a colour source (NM = 21 moments: I(3), p(3), I_i*I_j(6), I_i*p_c(9); NC = 3), the
+// V pass with a float accumulator and the contracting gf_solve_kernel, which keep this entry's bytes.  ppst_guided_filter_coeffs
+// (native-size output, below) and ppst_guided_matte_coeffs (a ONE-channel source, He et al.'s guided feathering -- the refined alpha
+// is a . I + b: NM = 13, NC = 1) run the EXACT forms and end in an exact V pass into the caller's buffer.  Their planes are judged
+// ALONE against float64 (twice the error of a float32 run whose window means are float64 means rounded once,
+// tests/gf_native_cases.py:plane_ref), and the first forms do not meet that: the float V pass sums 2r + 1 row sums in fp32 (exact only
+// up to r = 7: 255^2 (2r + 1)^2 < 2^24) and multiplies by a ROUNDED 1 / (2r + 1)^2, gf_solve_kernel compiles with contraction, and an
+// ill-conditioned covariance amplifies both (measured with them: 3.39e-3 against a bar of 2.47e-3 at r = 7, 2.65e-4 against 2.50e-4
+// at r = 30).  Exact: gf_v<double> accumulates in double and divides once, rounded once -- on the integer moment sums of stage 1
+// (every stage-1 value is an integer <= 255^2 and a row sum <= 255^2 (2 GF_MAXR + 1) < 2^24: exact in fp32 in any order) the mean is
+// the correctly rounded one; gf_solve_exact_kernel is gf_solve_kernel's text (the shared GF_SOLVE_* macros, six divisions) with
+// contraction off: every operation rounds once, in the order written.
+// The matte source is the fp32 matte quantised on load, p = rint(255 clamp(m, 0, 1)) (fmaxf drops a NaN: 0), an integer in 0..255,
+// and its 13 moments are those of the colour source (p, p, p) with P1, P2 and their products left out (GFM_PLANE).  Every operation
+// is the one the 21-plane entry performs on channel 0, in its order, so the result is BIT-EQUAL to planes 0..3 of
+// ppst_guided_filter_coeffs on the source (p, p, p): a matte does not depend on the entry that computed it.
 // The round-4 sliding-window forms of the radius-30 path (three and four launches through fp32 planes) were removed from the source;
 // bc82816 is the last commit that holds them, their measurements are in DESIGN.md section 4.
 #include "common.h"
@@ -31,10 +47,8 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {  // cv2.BORDER_REFLEC
   return i;
 }
 
-// plane value for stage 1 from the uint8 inputs at one pixel
-__device__ __forceinline__ float gf_plane_value(int pl, const unsigned char* g, const unsigned char* s) {
-  float I0 = g[0], I1 = g[1], I2 = g[2];
-  float P0 = s[0], P1 = s[1], P2 = s[2];
+// plane value for stage 1 from the guide (I) and source (P) bytes of one pixel: THE table of the 21 moments
+__device__ __forceinline__ float gf_plane_value(int pl, float I0, float I1, float I2, float P0, float P1, float P2) {
   switch (pl) {
     case 0: return I0; case 1: return I1; case 2: return I2;
     case 3: return P0; case 4: return P1; case 5: return P2;
@@ -48,6 +62,10 @@ __device__ __forceinline__ float gf_plane_value(int pl, const unsigned char* g, 
     }
   }
 }
+// A one-channel source needs 13 of them -- plane 0..2 I, 3 p, 4..9 I_i I_j, 10..12 I_i p: the 21-plane order with P1, P2 and their
+// products left out.  GFM_PLANE: moment i of the 21 -> its plane among the 13 (i < 4 or i >= 6); GFM_MOMENT: the inverse.
+#define GFM_PLANE(i) ((i) < 4 ? (i) : (i) - 2)
+#define GFM_MOMENT(j) ((j) < 4 ? (j) : (j) + 2)
 
 // the same 21 planes of one pixel as exact integers (plane order as above), from its six bytes
 __device__ __forceinline__ void gf_moments(unsigned I0, unsigned I1, unsigned I2, unsigned P0, unsigned P1, unsigned P2, unsigned (&m)[21]) {
@@ -88,22 +106,32 @@ __device__ __forceinline__ void gf_store(float qv, float* out, unsigned char* ou
   if (out) out[(b * 3 + c) * P + (int64_t)y * W + x] = (rq / 255.0f - 0.5f) * 2.f;  // ToTensor, (x-0.5)*2 (ppst_model.py:301-303)
 }
 
-// H pass.  grid = (H, nplanes, B).  STAGE1: read uint8 guide/src; else read fp32 planes.
-template <bool STAGE1>
-__global__ __launch_bounds__(256) void gf_h_kernel(const unsigned char* __restrict__ guide, const unsigned char* __restrict__ src,
-                                                   const float* __restrict__ in, float* __restrict__ out, int H, int W, int r,
-                                                   int nplanes) {
+// H pass.  grid = (H, nplanes, B).  ``src`` by SRC: [B][nplanes][H][W] fp32 planes (the guide is not read); a uint8 colour source
+// [B][H][W][3] beside the guide; an fp32 matte [B][H][W] beside the guide.
+#define GF_SRC_PLANES 0
+#define GF_SRC_COLOUR 1
+#define GF_SRC_MATTE 2
+template <int SRC>
+__global__ __launch_bounds__(256) void gf_h_kernel(const unsigned char* __restrict__ guide, const void* __restrict__ src,
+                                                   float* __restrict__ out, int H, int W, int r, int nplanes) {
   __shared__ float row[GF_MAXW + 2 * GF_MAXR];
   const int y = blockIdx.x, pl = blockIdx.y, b = blockIdx.z;
   const int64_t P = (int64_t)H * W;
   for (int i = threadIdx.x; i < W + 2 * r; i += 256) {
-    int x = reflect_idx(i - r, W);
+    const int x = reflect_idx(i - r, W);
+    const int64_t o = ((int64_t)b * H + y) * W + x;
     float v;
-    if (STAGE1) {
-      int64_t o = (((int64_t)b * H + y) * W + x) * 3;
-      v = gf_plane_value(pl, guide + o, src + o);
+    if (SRC == GF_SRC_PLANES) {
+      v = ((const float*)src)[((int64_t)b * nplanes + pl) * P + (int64_t)y * W + x];
     } else {
-      v = in[((int64_t)b * nplanes + pl) * P + (int64_t)y * W + x];
+      const unsigned char* g = guide + o * 3;
+      if (SRC == GF_SRC_COLOUR) {
+        const unsigned char* s = (const unsigned char*)src + o * 3;
+        v = gf_plane_value(pl, g[0], g[1], g[2], s[0], s[1], s[2]);
+      } else {
+        const float p = rintf(255.f * fminf(fmaxf(((const float*)src)[o], 0.f), 1.f));
+        v = gf_plane_value(GFM_MOMENT(pl), g[0], g[1], g[2], p, p, p);
+      }
     }
     row[i] = v;
   }
@@ -116,10 +144,14 @@ __global__ __launch_bounds__(256) void gf_h_kernel(const unsigned char* __restri
   }
 }
 
-// V pass: out = (sum over 2r+1 rows of in) / (2r+1)^2.  grid-stride over (b, plane, y, x).
+// V pass: out = (sum over 2r+1 rows of in) / (2r+1)^2.  grid-stride over (b, plane, y, x).  ACC is the arithmetic: a float
+// accumulator times the rounded reciprocal, or a double accumulator and a true division, rounded once (the exact form).
+__device__ __forceinline__ float gf_mean(float s, int n2) { return s * (1.f / (float)n2); }
+__device__ __forceinline__ float gf_mean(double s, int n2) { return (float)(s / (double)n2); }
+template <typename ACC>
 __global__ __launch_bounds__(256) void gf_v_kernel(const float* __restrict__ in, float* __restrict__ out, int H, int W, int r,
                                                    int64_t total) {
-  const float inv = 1.f / (float)((2 * r + 1) * (2 * r + 1));
+  const int n2 = (2 * r + 1) * (2 * r + 1);
   const int64_t P = (int64_t)H * W;
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
     int x = (int)(t % W);
@@ -127,9 +159,9 @@ __global__ __launch_bounds__(256) void gf_v_kernel(const float* __restrict__ in,
     int y = (int)(q % H);
     int64_t bp = q / H;
     const float* col = in + bp * P + x;
-    float s = 0.f;
-    for (int k = -r; k <= r; ++k) s += col[(int64_t)reflect_idx(y + k, H) * W];
-    out[t] = s * inv;
+    ACC s = 0;
+    for (int k = -r; k <= r; ++k) s += (ACC)col[(int64_t)reflect_idx(y + k, H) * W];
+    out[t] = gf_mean(s, n2);
   }
 }
 
@@ -149,6 +181,63 @@ __global__ __launch_bounds__(256) void gf_solve_kernel(const float* __restrict__
 #undef GF_M
     }
   }
+}
+
+// The same solve with contraction off (the pragma is lexical, which is why gf_solve_kernel is not an instance of this template:
+// it keeps its contracted bytes).  means: [B][NM][P], the 21 moments (NM = 21) or the 13 of a one-channel source (GFM_PLANE)
+// -> ab: [B][4 NC][P] for the NC = 3 or 1 channels of the source.
+template <int NM, int NC>
+__global__ __launch_bounds__(256) void gf_solve_exact_kernel(const float* __restrict__ m, float* __restrict__ ab, int64_t P, float eps,
+                                                             int64_t total) {
+#pragma clang fp contract(off)
+  static_assert((NM == 21 && NC == 3) || (NM == 13 && NC == 1), "moment planes of a colour or a one-channel source");
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
+    int64_t b = t / P, p = t - b * P;
+    const float* mp = m + b * NM * P + p;
+#define GF_M(i) mp[(NM == 21 ? (i) : GFM_PLANE(i)) * P]
+    GF_SOLVE_DET(GF_M, eps);
+    const float i00 = c00 / det, i01 = c01 / det, i02 = c02 / det, i11 = c11 / det, i12 = c12 / det, i22 = c22 / det;
+    float* o = ab + b * 4 * NC * P + p;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      GF_SOLVE_AB(GF_M, c);
+      o[(c * 4 + 0) * P] = A0; o[(c * 4 + 1) * P] = A1; o[(c * 4 + 2) * P] = A2; o[(c * 4 + 3) * P] = bb;
+    }
+#undef GF_M
+  }
+}
+
+// The plane route, H1 -> V -> solve -> H2, for a source of kind SRC with NM moment planes and NC channels; EXACT chooses the V pass
+// and the solve (the header comment).  It owns the argument rule the three entries share (``dst`` stands for the caller's output
+// and is only tested), the split of the workspace ([B][NM][P] twice) and the launches.  On PPST_OK *hs is the h-summed
+// coefficient planes [B][4 NC][P] for the caller's last V pass -- or null when B == 0 and nothing was launched.
+static unsigned gf_blocks_for(int64_t total) { int64_t b = cdiv64(total, 256); return (unsigned)(b > 256 * 32 ? 256 * 32 : b); }
+
+template <int SRC, int NM, int NC, bool EXACT>
+static int gf_plane_route(hipStream_t st, const void* guide_u8, const void* src, const void* dst, void* work, int B, int H, int W, int r,
+                          float eps, const float** hs) {
+  static_assert(EXACT || (NM == 21 && NC == 3), "gf_solve_kernel solves the colour source");
+  *hs = nullptr;
+  if (B < 0 || H <= 0 || W <= 0 || W > GF_MAXW || r <= 0 || r > GF_MAXR || r >= H || r >= W) return PPST_EINVAL;
+  if (B == 0) return PPST_OK;
+  if (!guide_u8 || !src || !dst || !work) return PPST_ENULL;
+  const int64_t P = (int64_t)H * W, tm = (int64_t)B * NM * P;
+  const unsigned char* g = (const unsigned char*)guide_u8;
+  float* bufA = (float*)work;  // [B][NM][P]
+  float* bufB = bufA + tm;     // [B][NM][P]
+  int e;
+  PPST_LAUNCH(gf_h_kernel<SRC>, dim3(H, NM, B), dim3(256), 0, st, g, src, bufA, H, W, r, NM);
+  if ((e = PPST_LAUNCH_CHECK())) return e;
+  PPST_LAUNCH((gf_v_kernel<std::conditional_t<EXACT, double, float>>), dim3(gf_blocks_for(tm)), dim3(256), 0, st, (const float*)bufA, bufB,
+              H, W, r, tm);
+  if ((e = PPST_LAUNCH_CHECK())) return e;
+  if constexpr (EXACT) PPST_LAUNCH((gf_solve_exact_kernel<NM, NC>), dim3(gf_blocks_for(B * P)), dim3(256), 0, st, (const float*)bufB, bufA, P, eps, (int64_t)B * P);
+  else PPST_LAUNCH(gf_solve_kernel, dim3(gf_blocks_for(B * P)), dim3(256), 0, st, (const float*)bufB, bufA, P, eps, (int64_t)B * P);
+  if ((e = PPST_LAUNCH_CHECK())) return e;
+  PPST_LAUNCH(gf_h_kernel<GF_SRC_PLANES>, dim3(H, 4 * NC, B), dim3(256), 0, st, g, (const void*)bufA, bufB, H, W, r, 4 * NC);
+  if ((e = PPST_LAUNCH_CHECK())) return e;
+  *hs = bufB;
+  return PPST_OK;
 }
 
 // final V pass over the 12 h-summed (a,b) planes + combination with the guide.
@@ -455,22 +544,12 @@ extern "C" int ppst_guided_filter(const void* guide_u8, const void* src_u8, void
   if (r == 30) return gf_fused<30, 32, 64>(st, g, s, (unsigned short*)work, out, out_u8, B, H, W, eps);
   if (r == 60) return gf_fused<60, 32, 32>(st, g, s, (unsigned short*)work, out, out_u8, B, H, W, eps);
   if (r == 90) return gf_fused<90, 64, 64>(st, g, s, (unsigned short*)work, out, out_u8, B, H, W, eps);
-  float* bufA = (float*)work;              // [B][21][P]
-  float* bufB = bufA + (int64_t)B * 21 * P;  // [B][21][P]
-  auto blocks_for = [](int64_t total) { int64_t b = cdiv64(total, 256); return (unsigned)(b > 256 * 32 ? 256 * 32 : b); };
-  PPST_LAUNCH(gf_h_kernel<true>, dim3(H, 21, B), dim3(256), 0, st, g, s, (const float*)nullptr, bufA, H, W, r, 21);
-  if ((e = PPST_LAUNCH_CHECK())) return e;
-  int64_t t21 = (int64_t)B * 21 * P;
-  PPST_LAUNCH(gf_v_kernel, dim3(blocks_for(t21)), dim3(256), 0, st, (const float*)bufA, bufB, H, W, r, t21);
-  if ((e = PPST_LAUNCH_CHECK())) return e;
-  PPST_LAUNCH(gf_solve_kernel, dim3(blocks_for(B * P)), dim3(256), 0, st, (const float*)bufB, bufA, P, eps, (int64_t)B * P);
-  if ((e = PPST_LAUNCH_CHECK())) return e;
-  PPST_LAUNCH(gf_h_kernel<false>, dim3(H, 12, B), dim3(256), 0, st, g, s, (const float*)bufA, bufB, H, W, r, 12);
-  if ((e = PPST_LAUNCH_CHECK())) return e;
+  const float* hs;
+  if ((e = gf_plane_route<GF_SRC_COLOUR, 21, 3, false>(st, g, s, out ? out : out_u8, work, B, H, W, r, eps, &hs))) return e;
   // (register blocking of this pass -- 12 planes x 8 rows per thread -- measured 3.5x SLOWER: 262 k threads with
   //  ~200 live registers each leave the chip empty; the plain form keeps one thread per pixel)
-  PPST_LAUNCH(gf_v_final_kernel, dim3(blocks_for(B * P)), dim3(256), 0, st, (const float*)bufB, g, (float*)out,
-                     (unsigned char*)out_u8, H, W, r, (int64_t)B * P);
+  PPST_LAUNCH(gf_v_final_kernel, dim3(gf_blocks_for(B * P)), dim3(256), 0, st, hs, g, (float*)out, (unsigned char*)out_u8, H, W, r,
+              (int64_t)B * P);
   return PPST_LAUNCH_CHECK();
 }
 
@@ -478,8 +557,8 @@ extern "C" int ppst_guided_filter(const void* guide_u8, const void* src_u8, void
 // Native-size output (He and Sun, "Fast Guided Filter", arXiv:1505.00996): the mean planes (mean a, mean b) of a filter solved at
 // (h, w) are smooth by construction, so they are upsampled bilinearly and applied to the guide at ITS size (H, W) >= (h, w).
 //   ppst_guided_filter_coeffs: the 12 mean planes [B][12][h][w] fp32 (plane 4c + k: k = 0..2 mean a_ck, k = 3 mean b_c), by the
-//     fp32-plane route at EVERY accepted radius (30 and 60 included: the fused launches never store the means): gf_h<true>, V pass,
-//     solve, gf_h<false>, V pass into the caller's buffer -- the V pass and the solve in the forms at the entry point (gfc_*).
+//     plane route (exact forms, the header comment) at EVERY accepted radius (30 and 60 included: the fused launches never store
+//     the means) and a last exact V pass into the caller's buffer (gf_coeffs).
 //   ppst_guided_filter_apply -> gf_apply_up_kernel: q_c = A_c0 I0 + A_c1 I1 + A_c2 I2 + B_c per native pixel, (A, B) the bilinear
 //     interpolation of the mean planes (half-pixel centres, edge replication: F.interpolate(mode="bilinear", align_corners=False)),
 //     horizontally first, then vertically; rounded and stored like gf_store.  The 12 upsampled planes never exist in memory.
@@ -646,129 +725,22 @@ __global__ __launch_bounds__(GA_NT) void gf_apply_up_kernel(const float* __restr
   }
 }
 
-// The coefficient entry's own V pass and solve.  Its planes are judged ALONE against float64 (twice the error of a float32 run whose
-// window means are float64 means rounded once, tests/gf_native_cases.py:plane_ref), and the generic path's gf_v_kernel / gf_solve_kernel
-// do not meet that: gf_v sums 2r + 1 row sums in fp32 (exact only up to r = 7: 255^2 (2r + 1)^2 < 2^24) and multiplies by a ROUNDED
-// 1 / (2r + 1)^2, gf_solve compiles with contraction, and an ill-conditioned covariance amplifies both (measured with them: 3.39e-3
-// against a bar of 2.47e-3 at r = 7, 2.65e-4 against 2.50e-4 at r = 30).  Those two keep their bytes for ppst_guided_filter; these are
-// beside them:
-//   gfc_v_kernel      the same pass with a double accumulator and a true division, rounded once -- on the integer moment sums of
-//                     stage 1 (gf_h<true>'s row sums are exact in fp32: 255^2 (2 GF_MAXR + 1) < 2^24) the mean is the correctly rounded one;
-//   gfc_solve_kernel  gf_solve_kernel's text (the shared GF_SOLVE_* macros, six divisions) with contraction off: every operation
-//                     rounds once, in the order written.
-__global__ __launch_bounds__(256) void gfc_v_kernel(const float* __restrict__ in, float* __restrict__ out, int H, int W, int r, int64_t total) {
-  const double n2 = (double)((2 * r + 1) * (2 * r + 1));
-  const int64_t P = (int64_t)H * W;
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-    int x = (int)(t % W);
-    int64_t q = t / W;
-    int y = (int)(q % H);
-    int64_t bp = q / H;
-    const float* col = in + bp * P + x;
-    double s = 0.0;
-    for (int k = -r; k <= r; ++k) s += (double)col[(int64_t)reflect_idx(y + k, H) * W];
-    out[t] = (float)(s / n2);
-  }
-}
-
-__global__ __launch_bounds__(256) void gfc_solve_kernel(const float* __restrict__ m, float* __restrict__ ab, int64_t P, float eps, int64_t total) {
-#pragma clang fp contract(off)
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-    int64_t b = t / P, p = t - b * P;
-    const float* mp = m + b * 21 * P + p;
-#define GF_M(i) mp[(i) * P]
-    GF_SOLVE_DET(GF_M, eps);
-    const float i00 = c00 / det, i01 = c01 / det, i02 = c02 / det, i11 = c11 / det, i12 = c12 / det, i22 = c22 / det;
-    float* o = ab + b * 12 * P + p;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      GF_SOLVE_AB(GF_M, c);
-      o[(c * 4 + 0) * P] = A0; o[(c * 4 + 1) * P] = A1; o[(c * 4 + 2) * P] = A2; o[(c * 4 + 3) * P] = bb;
-    }
-#undef GF_M
-  }
-}
-
-extern "C" int ppst_guided_filter_coeffs(const void* guide_u8, const void* src_u8, void* coeffs, int B, int h, int w, int r, float eps,
-                                         void* work, void* stream) {
-  // (the generic path's rule without the fused radius above GF_MAXR: r = 90 has no fp32-plane form)
-  if (B < 0 || h <= 0 || w <= 0 || w > GF_MAXW || r <= 0 || r > GF_MAXR || r >= h || r >= w) return PPST_EINVAL;
-  if (B == 0) return PPST_OK;
-  if (!guide_u8 || !src_u8 || !coeffs || !work) return PPST_ENULL;
+// The two coefficient entries: the exact plane route and its last V pass into the caller's buffer ([B][4 NC][h][w]).
+template <int SRC, int NM, int NC>
+static int gf_coeffs(const void* guide_u8, const void* src, void* coeffs, int B, int h, int w, int r, float eps, void* work, void* stream) {
   hipStream_t st = as_stream(stream);
-  const int64_t P = (int64_t)h * w;
-  const unsigned char* g = (const unsigned char*)guide_u8;
-  const unsigned char* s = (const unsigned char*)src_u8;
-  float* bufA = (float*)work;                // [B][21][P]
-  float* bufB = bufA + (int64_t)B * 21 * P;  // [B][21][P]
-  auto blocks_for = [](int64_t total) { int64_t b = cdiv64(total, 256); return (unsigned)(b > 256 * 32 ? 256 * 32 : b); };
-  int e;
-  PPST_LAUNCH(gf_h_kernel<true>, dim3(h, 21, B), dim3(256), 0, st, g, s, (const float*)nullptr, bufA, h, w, r, 21);
-  if ((e = PPST_LAUNCH_CHECK())) return e;
-  const int64_t t21 = (int64_t)B * 21 * P, t12 = (int64_t)B * 12 * P;
-  PPST_LAUNCH(gfc_v_kernel, dim3(blocks_for(t21)), dim3(256), 0, st, (const float*)bufA, bufB, h, w, r, t21);
-  if ((e = PPST_LAUNCH_CHECK())) return e;
-  PPST_LAUNCH(gfc_solve_kernel, dim3(blocks_for(B * P)), dim3(256), 0, st, (const float*)bufB, bufA, P, eps, (int64_t)B * P);
-  if ((e = PPST_LAUNCH_CHECK())) return e;
-  PPST_LAUNCH(gf_h_kernel<false>, dim3(h, 12, B), dim3(256), 0, st, g, s, (const float*)bufA, bufB, h, w, r, 12);
-  if ((e = PPST_LAUNCH_CHECK())) return e;
-  PPST_LAUNCH(gfc_v_kernel, dim3(blocks_for(t12)), dim3(256), 0, st, (const float*)bufB, (float*)coeffs, h, w, r, t12);
+  const float* hs;
+  const int e = gf_plane_route<SRC, NM, NC, true>(st, guide_u8, src, coeffs, work, B, h, w, r, eps, &hs);
+  if (e || !hs) return e;
+  const int64_t tc = (int64_t)B * 4 * NC * h * w;
+  PPST_LAUNCH(gf_v_kernel<double>, dim3(gf_blocks_for(tc)), dim3(256), 0, st, hs, (float*)coeffs, h, w, r, tc);
   return PPST_LAUNCH_CHECK();
 }
 
-// The same coefficients for a ONE-channel source: a matte (ppst_guided_matte_coeffs; He et al.'s guided feathering -- the refined
-// alpha is a . I + b).  The source is the fp32 matte quantised on load, p = rint(255 clamp(m, 0, 1)) (fmaxf drops a NaN: 0), an
-// integer in 0..255, so every stage-1 row sum stays an exact integer in fp32 as above.  Of the 21 moment planes a single channel
-// needs 13 -- plane 0..2 I, 3 p, 4..9 I_i I_j, 10..12 I_i p: the 21-plane order with P1, P2 and their products left out, i.e. moment
-// i of GF_SOLVE_* is plane i for i < 4 and plane i - 2 from 6 on (GFM_PLANE) -- and 4 of the 12 coefficient planes.  The launches
-// are those of ppst_guided_filter_coeffs with these plane counts: gfm_h_kernel (gf_h<true>'s body on the 13 planes), gfc_v_kernel,
-// gfm_solve_kernel (gfc_solve_kernel's text for channel 0 alone), gf_h<false>, gfc_v_kernel.  Every operation is the one the
-// 21-plane entry performs on channel 0, in its order, so the result is BIT-EQUAL to planes 0..3 of ppst_guided_filter_coeffs on
-// the source (p, p, p): a matte does not depend on the entry that computed it.
-#define GFM_PLANE(i) ((i) < 4 ? (i) : (i) - 2)
-
-__global__ __launch_bounds__(256) void gfm_h_kernel(const unsigned char* __restrict__ guide, const float* __restrict__ matte,
-                                                    float* __restrict__ out, int H, int W, int r) {
-  __shared__ float row[GF_MAXW + 2 * GF_MAXR];
-  const int y = blockIdx.x, pl = blockIdx.y, b = blockIdx.z;
-  const int64_t P = (int64_t)H * W;
-  for (int i = threadIdx.x; i < W + 2 * r; i += 256) {
-    const int64_t o = ((int64_t)b * H + y) * W + reflect_idx(i - r, W);
-    const unsigned char* g = guide + o * 3;
-    const float I0 = g[0], I1 = g[1], I2 = g[2];
-    const float p = rintf(255.f * fminf(fmaxf(matte[o], 0.f), 1.f));
-    float v;
-    switch (pl) {
-      case 0: v = I0; break; case 1: v = I1; break; case 2: v = I2; break; case 3: v = p; break;
-      case 4: v = I0 * I0; break; case 5: v = I0 * I1; break; case 6: v = I0 * I2; break;
-      case 7: v = I1 * I1; break; case 8: v = I1 * I2; break; case 9: v = I2 * I2; break;
-      case 10: v = I0 * p; break; case 11: v = I1 * p; break; default: v = I2 * p; break;
-    }
-    row[i] = v;
-  }
-  __syncthreads();
-  float* o = out + ((int64_t)b * 13 + pl) * P + (int64_t)y * W;
-  for (int x = threadIdx.x; x < W; x += 256) {
-    float s = 0.f;
-    for (int k = 0; k <= 2 * r; ++k) s += row[x + k];
-    o[x] = s;
-  }
-}
-
-// means: [B][13][P] -> ab: [B][4][P] (a_0, a_1, a_2, b)
-__global__ __launch_bounds__(256) void gfm_solve_kernel(const float* __restrict__ m, float* __restrict__ ab, int64_t P, float eps, int64_t total) {
-#pragma clang fp contract(off)
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-    int64_t b = t / P, p = t - b * P;
-    const float* mp = m + b * 13 * P + p;
-#define GF_M(i) mp[GFM_PLANE(i) * P]
-    GF_SOLVE_DET(GF_M, eps);
-    const float i00 = c00 / det, i01 = c01 / det, i02 = c02 / det, i11 = c11 / det, i12 = c12 / det, i22 = c22 / det;
-    float* o = ab + b * 4 * P + p;
-    GF_SOLVE_AB(GF_M, 0);
-    o[0] = A0; o[P] = A1; o[2 * P] = A2; o[3 * P] = bb;
-#undef GF_M
-  }
+// (the route's radius rule: r = 90, the fused radius above GF_MAXR, has no fp32-plane form)
+extern "C" int ppst_guided_filter_coeffs(const void* guide_u8, const void* src_u8, void* coeffs, int B, int h, int w, int r, float eps,
+                                         void* work, void* stream) {
+  return gf_coeffs<GF_SRC_COLOUR, 21, 3>(guide_u8, src_u8, coeffs, B, h, w, r, eps, work, stream);
 }
 
 // (26 planes: 13 + 13 fp32 planes handed through the workspace)
@@ -776,27 +748,7 @@ extern "C" int64_t ppst_guided_matte_ws(int B, int h, int w) { return (int64_t)B
 
 extern "C" int ppst_guided_matte_coeffs(const void* guide_u8, const void* matte_f32, void* mcoeffs, int B, int h, int w, int r, float eps,
                                         void* work, void* stream) {
-  if (B < 0 || h <= 0 || w <= 0 || w > GF_MAXW || r <= 0 || r > GF_MAXR || r >= h || r >= w) return PPST_EINVAL;   // ppst_guided_filter_coeffs' rule
-  if (B == 0) return PPST_OK;
-  if (!guide_u8 || !matte_f32 || !mcoeffs || !work) return PPST_ENULL;
-  hipStream_t st = as_stream(stream);
-  const int64_t P = (int64_t)h * w;
-  const unsigned char* g = (const unsigned char*)guide_u8;
-  float* bufA = (float*)work;                // [B][13][P]
-  float* bufB = bufA + (int64_t)B * 13 * P;  // [B][13][P]
-  auto blocks_for = [](int64_t total) { int64_t b = cdiv64(total, 256); return (unsigned)(b > 256 * 32 ? 256 * 32 : b); };
-  int e;
-  PPST_LAUNCH(gfm_h_kernel, dim3(h, 13, B), dim3(256), 0, st, g, (const float*)matte_f32, bufA, h, w, r);
-  if ((e = PPST_LAUNCH_CHECK())) return e;
-  const int64_t t13 = (int64_t)B * 13 * P, t4 = (int64_t)B * 4 * P;
-  PPST_LAUNCH(gfc_v_kernel, dim3(blocks_for(t13)), dim3(256), 0, st, (const float*)bufA, bufB, h, w, r, t13);
-  if ((e = PPST_LAUNCH_CHECK())) return e;
-  PPST_LAUNCH(gfm_solve_kernel, dim3(blocks_for(B * P)), dim3(256), 0, st, (const float*)bufB, bufA, P, eps, (int64_t)B * P);
-  if ((e = PPST_LAUNCH_CHECK())) return e;
-  PPST_LAUNCH(gf_h_kernel<false>, dim3(h, 4, B), dim3(256), 0, st, g, g, (const float*)bufA, bufB, h, w, r, 4);
-  if ((e = PPST_LAUNCH_CHECK())) return e;
-  PPST_LAUNCH(gfc_v_kernel, dim3(blocks_for(t4)), dim3(256), 0, st, (const float*)bufB, (float*)mcoeffs, h, w, r, t4);
-  return PPST_LAUNCH_CHECK();
+  return gf_coeffs<GF_SRC_MATTE, 13, 1>(guide_u8, matte_f32, mcoeffs, B, h, w, r, eps, work, stream);
 }
 
 extern "C" int ppst_guided_filter_apply(const void* coeffs, int h, int w, const void* guide_u8, void* out_u8, void* out_f32, int B, int H,

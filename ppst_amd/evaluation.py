@@ -20,6 +20,7 @@ the GPU (imageio.encode_png: the threads only write bytes), the reference's file
 files instead, by the same switch: Pillow on the threads, or imageio.encode_jpeg on the GPU.
 """
 import contextlib
+import os
 import threading
 
 import torch
@@ -406,6 +407,8 @@ def baseline_grid(contents, styles, content_labels=None, style_labels=None, meth
 
 # ------------------------------------------------------------------------------------------------- file front ends
 _IMG_EXT = (".jpg", ".jpeg", ".png", ".bmp", ".webp")
+_stem = lambda p: os.path.splitext(os.path.basename(p))[0]
+_as_list = lambda p: [p] if isinstance(p, (str, bytes, os.PathLike)) else list(p)       # one path or a list of paths
 
 
 def _decode(path):
@@ -559,23 +562,39 @@ def save_images(images, paths, pool=None, encoder="host", format="png", jpeg_qua
     return write_png_batch(glue.tensor2im(images), paths, pool, encoder, format, jpeg_quality, jpeg_subsampling)
 
 
+def _check_files(png, format, jpeg_quality, jpeg_subsampling):
+    """what every file front end refuses before it reads a file"""
+    _check_encoder(png)
+    _check_format(format, jpeg_quality, jpeg_subsampling)
+    _check_decoder(current_decoder())
+
+
+def _swap_name(out_dir, structure, texture, alpha, format):
+    """<structure>_<texture>_<alpha %.2f> with the format's extension (simple_swapping_evaluator.py:61-62)"""
+    return os.path.join(out_dir, "%s_%s_%.2f%s" % (_stem(structure), _stem(texture), alpha, FORMATS[format]))
+
+
+def _spread(structures, v, message):
+    """one entry serves every structure, otherwise the lists pair up; an absent list (None) stays absent"""
+    v = v * len(structures) if v is not None and len(v) == 1 else v
+    if v is not None and len(v) != len(structures):
+        raise ValueError(message % (len(structures), len(v)))
+    return v
+
+
 def evaluate_swap_files(model, structure_path, texture_path, out_dir, alphas=(1.0,), load_size=512, device="cuda", png="host",
                         format="png", jpeg_quality=90, jpeg_subsampling="4:2:0"):
     """evaluation/simple_swapping_evaluator.py:38-76: one structure image, one texture image, one output per mix alpha named
     <structure>_<texture>_<alpha %.2f>.png (ToPILImage quantisation of the clamped image, :61-62).  ``png``: where the files are
     encoded (write_png_batch).  ``format="jpeg"``: JPEG files of that quality and subsampling, named .jpg.  The two inputs are decoded where
     ``evaluation.decoder`` says (load_images).  Returns the paths."""
-    import os
-    _check_encoder(png)
-    _check_format(format, jpeg_quality, jpeg_subsampling)
-    _check_decoder(current_decoder())
+    _check_files(png, format, jpeg_quality, jpeg_subsampling)
     os.makedirs(out_dir, exist_ok=True)
     c, s_ = load_images([os.path.expanduser(structure_path), os.path.expanduser(texture_path)], load_size, device)
     outs = simple_swap(model, c, s_, alphas)
-    stem = lambda p: os.path.splitext(os.path.basename(p))[0]
     paths = []
     for alpha in alphas:
-        path = os.path.join(out_dir, "%s_%s_%.2f%s" % (stem(structure_path), stem(texture_path), alpha, FORMATS[format]))
+        path = _swap_name(out_dir, structure_path, texture_path, alpha, format)
         paths += write_png_batch(to_uint8_image(outs[alpha])[:1], [path], None, png, format, jpeg_quality, jpeg_subsampling)
     return paths
 
@@ -613,32 +632,34 @@ def evaluate_swap_files_native(model, structure_path, texture_path, out_dir, alp
     at their own size (square, side >= load_size) where ``evaluation.decoder`` says, textures as today (load_images); structures
     of one size run as one batch.  Files are written through write_png_batch, named as evaluate_swap_files names them; a size the
     device encoder has no bound for is encoded on the host.  Returns the paths, structure by structure, alpha by alpha."""
-    import os
-    _check_encoder(png)
-    _check_format(format, jpeg_quality, jpeg_subsampling)
-    _check_decoder(current_decoder())
-    as_list = lambda p: [p] if isinstance(p, (str, bytes, os.PathLike)) else list(p)
-    structures, textures = as_list(structure_path), as_list(texture_path)
-    if len(textures) == 1:
-        textures = textures * len(structures)
-    if len(textures) != len(structures):
-        raise ValueError("evaluate_swap_files_native pairs structures and textures: %d structure and %d texture paths"
-                         % (len(structures), len(textures)))
+    _check_files(png, format, jpeg_quality, jpeg_subsampling)
+    structures = _as_list(structure_path)
+    textures = _spread(structures, _as_list(texture_path),
+                       "evaluate_swap_files_native pairs structures and textures: %d structure and %d texture paths")
     os.makedirs(out_dir, exist_ok=True)
     natives = load_native([os.path.expanduser(p) for p in structures], device)
     for n in natives:                                          # (before any model pass: a wrong size fails at once)
         native_size_rule((1,) + tuple(n.shape), load_size)
     styles = load_images([os.path.expanduser(p) for p in textures], load_size, device)
-    stem = lambda p: os.path.splitext(os.path.basename(p))[0]
+    swap = lambda idx: simple_swap_native(model, torch.stack([natives[i] for i in idx]), torch.cat([styles[i] for i in idx], 0), alphas,
+                                          load_size)
+    return _swap_groups_to_files(structures, textures, natives, styles, swap, out_dir, alphas, png, format, jpeg_quality, jpeg_subsampling)
+
+
+def _swap_groups_to_files(structures, textures, natives, styles, swap, out_dir, alphas, png, format, jpeg_quality, jpeg_subsampling):
+    """The tail of the front ends that keep the structure FILE's size: structures of one size (and one texture size) share a
+    batch, ``swap(idx)`` -> {alpha: uint8 (len(idx),H,W,3)} runs it, the files are named as evaluate_swap_files names them and
+    written through write_png_batch (a size the device encoder has no bound for: on the host).  Returns the paths, structure by
+    structure, alpha by alpha."""
     groups = {}
-    for i, n in enumerate(natives):                            # structures of one size (and one texture size) share a batch
+    for i, n in enumerate(natives):
         groups.setdefault((tuple(n.shape), tuple(styles[i].shape)), []).append(i)
     paths = {}
     for (shape, _), idx in groups.items():
-        outs = simple_swap_native(model, torch.stack([natives[i] for i in idx]), torch.cat([styles[i] for i in idx], 0), alphas, load_size)
+        outs = swap(idx)
         encoder = png if png == "host" or _device_encoder_takes(shape, format, jpeg_subsampling) else "host"
         for alpha in alphas:
-            names = [os.path.join(out_dir, "%s_%s_%.2f%s" % (stem(structures[i]), stem(textures[i]), alpha, FORMATS[format])) for i in idx]
+            names = [_swap_name(out_dir, structures[i], textures[i], alpha, format) for i in idx]
             for i, p in zip(idx, write_png_batch(outs[alpha], names, None, encoder, format, jpeg_quality, jpeg_subsampling)):
                 paths.setdefault(i, []).append(p)
     return [p for i in range(len(structures)) for p in paths[i]]
@@ -782,24 +803,17 @@ def _swap_files_region(model, structure_path, texture_path, out_dir, structure_b
                        format, jpeg_quality, jpeg_subsampling, label_path, keep, matte_feather, matte_grow, gmatte):
     """the region file front ends' one body.  ``gmatte``: None, or (matte_radius, matte_eps) of the guided matte"""
     import functools
-    import os
-    swap = simple_swap_region_matte if gmatte is None else functools.partial(simple_swap_region_gmatte, matte_radius=gmatte[0],
-                                                                             matte_eps=gmatte[1])
+    region_swap = simple_swap_region_matte if gmatte is None else functools.partial(simple_swap_region_gmatte, matte_radius=gmatte[0],
+                                                                                    matte_eps=gmatte[1])
     from . import imageio
-    _check_encoder(png)
-    _check_format(format, jpeg_quality, jpeg_subsampling)
-    _check_decoder(current_decoder())
-    as_list = lambda p: [p] if isinstance(p, (str, bytes, os.PathLike)) else list(p)
+    _check_files(png, format, jpeg_quality, jpeg_subsampling)
     boxes = lambda b: [tuple(b)] if not hasattr(b[0], "__len__") else [tuple(v) for v in b]
-    structures, textures, sboxes = as_list(structure_path), as_list(texture_path), boxes(structure_box)
-    tboxes = None if texture_box is None else boxes(texture_box)
-    spread = lambda v: v * len(structures) if len(v) == 1 else v
-    textures, sboxes = spread(textures), spread(sboxes)
-    tboxes = None if tboxes is None else spread(tboxes)
-    lpaths = None if label_path is None else spread(as_list(label_path))
-    for v, what in ((textures, "texture paths"), (sboxes, "structure boxes"), (tboxes, "texture boxes"), (lpaths, "label paths")):
-        if v is not None and len(v) != len(structures):
-            raise ValueError("evaluate_swap_files_region pairs its lists: %d structure paths and %d %s" % (len(structures), len(v), what))
+    structures = _as_list(structure_path)
+    lists = ((_as_list(texture_path), "texture paths"), (boxes(structure_box), "structure boxes"),
+             (None if texture_box is None else boxes(texture_box), "texture boxes"),
+             (None if label_path is None else _as_list(label_path), "label paths"))
+    textures, sboxes, tboxes, lpaths = [_spread(structures, v, "evaluate_swap_files_region pairs its lists: %d structure paths and %d " + what)
+                                        for v, what in lists]
     os.makedirs(out_dir, exist_ok=True)
     to_xf = lambda box: imageio.crop_transform((box[0], box[1]), box[2], box[3] if len(box) > 3 else 0.0, load_size)
     sxf = [to_xf(b) for b in sboxes]
@@ -822,21 +836,10 @@ def _swap_files_region(model, structure_path, texture_path, out_dir, structure_b
             im = Image.open(os.path.expanduser(p)).convert("L")
             return np.asarray(im if im.size == (load_size, load_size) else im.resize((load_size, load_size), Image.NEAREST))
         labels = torch.from_numpy(np.stack([read(p) for p in lpaths])).to(device)
-    stem = lambda p: os.path.splitext(os.path.basename(p))[0]
-    groups = {}
-    for i, n in enumerate(photos):                             # structures of one size (and one texture size) share a batch
-        groups.setdefault((tuple(n.shape), tuple(styles[i].shape)), []).append(i)
-    paths = {}
-    for (shape, _), idx in groups.items():
-        outs = swap(model, torch.stack([photos[i] for i in idx]), [sxf[i] for i in idx], torch.cat([styles[i] for i in idx], 0), alphas,
-                    load_size, feather, labels=None if labels is None else labels[idx], keep=keep, matte_feather=matte_feather,
-                    matte_grow=matte_grow)
-        encoder = png if png == "host" or _device_encoder_takes(shape, format, jpeg_subsampling) else "host"
-        for alpha in alphas:
-            names = [os.path.join(out_dir, "%s_%s_%.2f%s" % (stem(structures[i]), stem(textures[i]), alpha, FORMATS[format])) for i in idx]
-            for i, p in zip(idx, write_png_batch(outs[alpha], names, None, encoder, format, jpeg_quality, jpeg_subsampling)):
-                paths.setdefault(i, []).append(p)
-    return [p for i in range(len(structures)) for p in paths[i]]
+    swap = lambda idx: region_swap(model, torch.stack([photos[i] for i in idx]), [sxf[i] for i in idx], torch.cat([styles[i] for i in idx], 0),
+                                   alphas, load_size, feather, labels=None if labels is None else labels[idx], keep=keep,
+                                   matte_feather=matte_feather, matte_grow=matte_grow)
+    return _swap_groups_to_files(structures, textures, photos, styles, swap, out_dir, alphas, png, format, jpeg_quality, jpeg_subsampling)
 
 
 def evaluate_grid_folder(model, dataroot, out_dir, rank=0, world=1, smooth=True, load_size=512, device="cuda", workers=8,
@@ -851,10 +854,7 @@ def evaluate_grid_folder(model, dataroot, out_dir, rank=0, world=1, smooth=True,
     ``format="jpeg"``: JPEG files of that quality and subsampling under the same names with .jpg, by the same switch.
     Inside ``with evaluation.decoder("device"):`` the threads read bytes and the HIP decoders take the JPEG and PNG files they can in one
     batched call (load_images); otherwise Pillow decodes on the worker threads."""
-    import os
-    _check_encoder(png)
-    _check_format(format, jpeg_quality, jpeg_subsampling)
-    _check_decoder(current_decoder())
+    _check_files(png, format, jpeg_quality, jpeg_subsampling)
     ext, fmt = FORMATS[format], (format, jpeg_quality, jpeg_subsampling)
     from concurrent.futures import ThreadPoolExecutor
     cdir, sdir = os.path.join(dataroot, "content"), os.path.join(dataroot, "style")
@@ -864,7 +864,6 @@ def evaluate_grid_folder(model, dataroot, out_dir, rank=0, world=1, smooth=True,
         raise RuntimeError("need images under %s and %s" % (cdir, sdir))
     img_dir = os.path.join(out_dir, "images")
     os.makedirs(img_dir, exist_ok=True)
-    stem = lambda p: os.path.splitext(os.path.basename(p))[0]
     with ThreadPoolExecutor(max_workers=workers) as pool:
         imgs = load_images(cpaths + spaths, load_size, device, pool)
         if len({tuple(t.shape) for t in imgs}) != 1:
@@ -872,12 +871,12 @@ def evaluate_grid_folder(model, dataroot, out_dir, rank=0, world=1, smooth=True,
         contents, styles = torch.cat(imgs[:len(cpaths)], 0), torch.cat(imgs[len(cpaths):], 0)
         futures = []
         if rank == 0:   # the top row / first column of the reference's page: the inputs themselves
-            futures += save_images(torch.cat((contents, styles), 0), [os.path.join(img_dir, stem(p) + ext) for p in cpaths + spaths], pool, png, *fmt)
+            futures += save_images(torch.cat((contents, styles), 0), [os.path.join(img_dir, _stem(p) + ext) for p in cpaths + spaths], pool, png, *fmt)
         out = swapping_grid(model, contents, styles, rank, world, smooth, pair_batch, image_batch)
         keys = sorted(out)
         for k in range(0, len(keys), pair_batch):
             chunk = keys[k:k + pair_batch]
-            names = [os.path.join(img_dir, "%s_%s%s" % (stem(cpaths[i]), stem(spaths[j]), ext)) for i, j in chunk]
+            names = [os.path.join(img_dir, "%s_%s%s" % (_stem(cpaths[i]), _stem(spaths[j]), ext)) for i, j in chunk]
             futures += save_images(torch.stack([out[ij] for ij in chunk], 0), names, pool, png, *fmt)
         written = [f.result() for f in futures]
     return written

@@ -1817,19 +1817,45 @@ def tensor2im_u8(x):
     return y
 
 
+def _need_cuda(who, what, dtype, *tensors):
+    """``who`` needs ``what``: every one of ``tensors`` a CUDA tensor of ``dtype``"""
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+            raise RuntimeError("%s needs %s" % (who, what))
+
+
+def _need_shapes(who, what, ok, *tensors):
+    """``who`` needs ``what``, the shape family that ``ok`` tested on ``tensors``"""
+    if not ok:
+        raise RuntimeError("%s needs %s, got %s" % (who, what, " and ".join(str(tuple(t.shape)) for t in tensors)))
+
+
+def _need_match(who, what, t, shape, like, whose):
+    """``who`` needs ``what`` = ``shape`` (the batch and extents of ``like``) on ``like``'s device -> ``t``, contiguous"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != like.device or tuple(t.shape) != shape:
+        raise RuntimeError("%s needs %s = %s on the %s's device" % (who, what, shape, whose))
+    return t.contiguous()
+
+
+_is_image = lambda t: t.dim() == 4 and t.shape[3] == 3                            # (B,H,W,3)
+_is_coeffs = lambda t: t.dim() == 4 and t.shape[1] == 12                          # (B,12,h,w)
+
+
+def _guide_and_source(who, guide_u8, src_u8, dims):
+    """the filter's two inputs, checked -> (guide, source, workspace), the two contiguous"""
+    _need_cuda(who, "CUDA uint8 tensors", torch.uint8, guide_u8, src_u8)
+    _need_shapes(who, "guide and source of one shape %s" % dims, _is_image(guide_u8) and src_u8.shape == guide_u8.shape,
+                 guide_u8, src_u8)                                                # (the kernels index both by the guide's extents)
+    ws = torch.empty(lib.ppst_guided_filter_ws(*guide_u8.shape[:3]), device=guide_u8.device, dtype=torch.uint8)
+    return guide_u8.contiguous(), src_u8.contiguous(), ws
+
+
 def guided_filter(guide_u8, src_u8, r=30, eps=(0.02 * 255) ** 2, want_u8=False):
     """guide/src (B,H,W,3) uint8 -> fp32 NCHW in [-1,1] (and the uint8 HWC result).  r = 30, 60 and 90 run as two fused
     launches (the radii of 512^2, 1024^2 and 1536^2 images, ppst_model.guided_filter_radius); every other r <= 64 runs the
     five-launch generic path; any other r, r >= H, r >= W and W > 2048 are refused."""
-    for t in (guide_u8, src_u8):
-        if not t.is_cuda or t.dtype != torch.uint8:
-            raise RuntimeError("guided_filter needs CUDA uint8 tensors")
-    if guide_u8.dim() != 4 or guide_u8.shape[3] != 3 or src_u8.shape != guide_u8.shape:      # (the kernels index both by the guide's extents)
-        raise RuntimeError("guided_filter needs guide and source of one shape (B,H,W,3), got %s and %s"
-                           % (tuple(guide_u8.shape), tuple(src_u8.shape)))
-    guide_u8, src_u8 = guide_u8.contiguous(), src_u8.contiguous()
+    guide_u8, src_u8, ws = _guide_and_source("guided_filter", guide_u8, src_u8, "(B,H,W,3)")
     B, H, W, _ = guide_u8.shape
-    ws = torch.empty(lib.ppst_guided_filter_ws(B, H, W), device=guide_u8.device, dtype=torch.uint8)
     out = torch.empty((B, 3, H, W), device=guide_u8.device, dtype=torch.float32)
     out_u8 = torch.empty((B, H, W, 3), device=guide_u8.device, dtype=torch.uint8) if want_u8 else None
     check(lib.ppst_guided_filter(_p(guide_u8), _p(src_u8), _p(out), _p(out_u8), B, H, W, r, float(eps), _p(ws), _stream()),
@@ -1841,15 +1867,8 @@ def guided_filter_coeffs(guide_u8, src_u8, r=30, eps=(0.02 * 255) ** 2):
     """guide/src (B,h,w,3) uint8 -> (B,12,h,w) fp32: the filter's mean coefficient planes (plane 4c + k: k = 0..2 mean a_ck,
     k = 3 mean b_c), what ``guided_filter_apply`` upsamples.  Five launches through fp32 planes at every radius: 0 < r <= 64
     (30 and 60 included, 90 refused), r < h, r < w, w <= 2048."""
-    for t in (guide_u8, src_u8):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
-            raise RuntimeError("guided_filter_coeffs needs CUDA uint8 tensors")
-    if guide_u8.dim() != 4 or guide_u8.shape[3] != 3 or src_u8.shape != guide_u8.shape:
-        raise RuntimeError("guided_filter_coeffs needs guide and source of one shape (B,h,w,3), got %s and %s"
-                           % (tuple(guide_u8.shape), tuple(src_u8.shape)))
-    guide_u8, src_u8 = guide_u8.contiguous(), src_u8.contiguous()
+    guide_u8, src_u8, ws = _guide_and_source("guided_filter_coeffs", guide_u8, src_u8, "(B,h,w,3)")
     B, h, w, _ = guide_u8.shape
-    ws = torch.empty(lib.ppst_guided_filter_ws(B, h, w), device=guide_u8.device, dtype=torch.uint8)
     coeffs = torch.empty((B, 12, h, w), device=guide_u8.device, dtype=torch.float32)
     check(lib.ppst_guided_filter_coeffs(_p(guide_u8), _p(src_u8), _p(coeffs), B, h, w, int(r), float(eps), _p(ws), _stream()),
           "ppst_guided_filter_coeffs")
@@ -1860,14 +1879,10 @@ def guided_filter_apply(coeffs, guide_full_u8, want_f32=False):
     """coeffs (B,12,h,w) fp32 (``guided_filter_coeffs``), guide (B,H,W,3) uint8 with H >= h, W >= w -> uint8 (B,H,W,3): the
     coefficients upsampled bilinearly (half-pixel centres, any ratio per axis) and applied to the guide at its own size, one
     launch; ``want_f32``: also the fp32 NCHW image (q/255 - 0.5)*2 of those bytes.  H < h, W < w and H W > 2^28 are refused."""
-    if not isinstance(coeffs, torch.Tensor) or not coeffs.is_cuda or coeffs.dtype != torch.float32:
-        raise RuntimeError("guided_filter_apply needs CUDA float32 coefficients")
-    if not isinstance(guide_full_u8, torch.Tensor) or not guide_full_u8.is_cuda or guide_full_u8.dtype != torch.uint8:
-        raise RuntimeError("guided_filter_apply needs a CUDA uint8 guide")
-    if (coeffs.dim() != 4 or coeffs.shape[1] != 12 or guide_full_u8.dim() != 4 or guide_full_u8.shape[3] != 3
-            or guide_full_u8.shape[0] != coeffs.shape[0]):
-        raise RuntimeError("guided_filter_apply needs coefficients (B,12,h,w) and a guide (B,H,W,3) of one batch, got %s and %s"
-                           % (tuple(coeffs.shape), tuple(guide_full_u8.shape)))
+    _need_cuda("guided_filter_apply", "CUDA float32 coefficients", torch.float32, coeffs)
+    _need_cuda("guided_filter_apply", "a CUDA uint8 guide", torch.uint8, guide_full_u8)
+    _need_shapes("guided_filter_apply", "coefficients (B,12,h,w) and a guide (B,H,W,3) of one batch",
+                 _is_coeffs(coeffs) and _is_image(guide_full_u8) and guide_full_u8.shape[0] == coeffs.shape[0], coeffs, guide_full_u8)
     coeffs, guide_full_u8 = coeffs.contiguous(), guide_full_u8.contiguous()
     B, _, h, w = coeffs.shape
     _, H, W, _ = guide_full_u8.shape
@@ -1901,10 +1916,8 @@ def extract_similarity(photo_u8, xf, n=512):
     row serves a whole batch) -> (B,n,n,3) uint8: the n x n crop of each photo under its similarity transform, Pillow's
     antialiased bicubic in the crop's frame, the photo read with edge replication (csrc/imageio.hip
     extract_similarity_kernel).  Transforms with s < 1 or s > 8 photo pixels per crop pixel are refused."""
-    if not isinstance(photo_u8, torch.Tensor) or not photo_u8.is_cuda or photo_u8.dtype != torch.uint8:
-        raise RuntimeError("extract_similarity needs a CUDA uint8 photo")
-    if photo_u8.dim() != 4 or photo_u8.shape[3] != 3:
-        raise RuntimeError("extract_similarity needs a photo (B,H,W,3), got %s" % (tuple(photo_u8.shape),))
+    _need_cuda("extract_similarity", "a CUDA uint8 photo", torch.uint8, photo_u8)
+    _need_shapes("extract_similarity", "a photo (B,H,W,3)", _is_image(photo_u8), photo_u8)
     photo_u8 = photo_u8.contiguous()
     B, H, W, _ = photo_u8.shape
     host, dev = _crop_transforms(xf, B, photo_u8.device, "extract_similarity")
@@ -1919,10 +1932,8 @@ def label_matte(labels, keep=(1, 2), feather=16, grow=8, want_distance=False):
     pixels (csrc/matte.hip; the semantics are at ppst_label_matte in include/ppst_hip.h).  grow = 0 feathers inwards only,
     grow = feather / 2 centres the ramp on the boundary; both in [0, 255].  ``want_distance``: also the exact int32 signed squared
     distance (B,h,w), clipped to +-R^2, R = max(grow, max(feather - grow, 0)) + 1."""
-    if not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dtype != torch.uint8:
-        raise RuntimeError("label_matte needs CUDA uint8 labels")
-    if labels.dim() != 3:
-        raise RuntimeError("label_matte needs labels (B,h,w), got %s" % (tuple(labels.shape),))
+    _need_cuda("label_matte", "CUDA uint8 labels", torch.uint8, labels)
+    _need_shapes("label_matte", "labels (B,h,w)", labels.dim() == 3, labels)
     mask = 0
     for k in keep:
         if int(k) != k or not 0 <= int(k) <= 31:
@@ -1953,6 +1964,35 @@ def _paste_out(photo_u8, out, who):
     return out, out
 
 
+def _paste(who, coeffs, photo_u8, xf, feather, out, extra=None, want_weight=False):
+    """The one body of the pastes (csrc/guided_filter.hip gf_paste<>).  ``extra``: None, or (tensor, what, planes) of the matte
+    form -- planes () for a matte plane (B,n,n), (4,) for guided-matte coefficients (B,4,n,n), the form with a weight output."""
+    _need_cuda(who, "CUDA float32 coefficients", torch.float32, coeffs)
+    _need_cuda(who, "a CUDA uint8 photo", torch.uint8, photo_u8)
+    _need_shapes(who, "coefficients (B,12,n,n) and a photo (B,H,W,3) of one batch",
+                 _is_coeffs(coeffs) and coeffs.shape[2] == coeffs.shape[3] and _is_image(photo_u8) and photo_u8.shape[0] == coeffs.shape[0],
+                 coeffs, photo_u8)
+    B, _, n, _ = coeffs.shape
+    _, H, W, _ = photo_u8.shape
+    if extra is not None:
+        m, what, planes = extra
+        m = _need_match(who, what, m, (B,) + planes + (n, n), photo_u8, "photo")
+    photo_u8, out = _paste_out(photo_u8, out, who)
+    host, dev = _crop_transforms(xf, B, out.device, who)
+    coeffs = coeffs.contiguous()
+    geom = (B, H, W, _p(host), _p(dev), int(feather), _stream())
+    if extra is None:
+        check(lib.ppst_guided_filter_paste(_p(coeffs), n, _p(photo_u8), _p(out), *geom), "ppst_guided_filter_paste")
+        return out
+    if not planes:
+        check(lib.ppst_guided_filter_paste_matte(_p(coeffs), _p(m), n, _p(photo_u8), _p(out), *geom), "ppst_guided_filter_paste_matte")
+        return out
+    weight = torch.zeros((B, H, W), device=out.device, dtype=torch.uint8) if want_weight else None
+    check(lib.ppst_guided_filter_paste_gmatte(_p(coeffs), _p(m), n, _p(photo_u8), _p(out), _p(weight), *geom),
+          "ppst_guided_filter_paste_gmatte")
+    return (out, weight) if want_weight else out
+
+
 def guided_filter_paste(coeffs, photo_u8, xf, feather=0, out=None, matte=None):
     """coeffs (B,12,n,n) fp32 (``guided_filter_coeffs`` of the crops ``extract_similarity`` took), photo (B,H,W,3) uint8, the same
     crop transforms -> uint8 (B,H,W,3): inside each crop square the photo's own pixels re-coloured by the bilinearly interpolated
@@ -1962,31 +2002,8 @@ def guided_filter_paste(coeffs, photo_u8, xf, feather=0, out=None, matte=None):
     filled with the photo first.  ``matte``: fp32 (B,n,n) on the photo's device, in the crop's frame (``label_matte``): the blend
     weight is the edge feather times the matte sampled like the coefficients, and pixels of weight 0 keep the photo's byte (the
     caller keeps its values in [0, 1]); None: no matte."""
-    if not isinstance(coeffs, torch.Tensor) or not coeffs.is_cuda or coeffs.dtype != torch.float32:
-        raise RuntimeError("guided_filter_paste needs CUDA float32 coefficients")
-    if not isinstance(photo_u8, torch.Tensor) or not photo_u8.is_cuda or photo_u8.dtype != torch.uint8:
-        raise RuntimeError("guided_filter_paste needs a CUDA uint8 photo")
-    if (coeffs.dim() != 4 or coeffs.shape[1] != 12 or coeffs.shape[2] != coeffs.shape[3] or photo_u8.dim() != 4 or photo_u8.shape[3] != 3
-            or photo_u8.shape[0] != coeffs.shape[0]):
-        raise RuntimeError("guided_filter_paste needs coefficients (B,12,n,n) and a photo (B,H,W,3) of one batch, got %s and %s"
-                           % (tuple(coeffs.shape), tuple(photo_u8.shape)))
-    B, _, n, _ = coeffs.shape
-    _, H, W, _ = photo_u8.shape
-    if matte is not None:
-        if not isinstance(matte, torch.Tensor) or matte.dtype != torch.float32 or matte.device != photo_u8.device \
-                or tuple(matte.shape) != (B, n, n):
-            raise RuntimeError("guided_filter_paste needs a float32 matte (B,n,n) = %s on the photo's device" % ((B, n, n),))
-        matte = matte.contiguous()
-    photo_u8, out = _paste_out(photo_u8, out, "guided_filter_paste")
-    host, dev = _crop_transforms(xf, B, out.device, "guided_filter_paste")
-    coeffs = coeffs.contiguous()
-    if matte is not None:
-        check(lib.ppst_guided_filter_paste_matte(_p(coeffs), _p(matte), n, _p(photo_u8), _p(out), B, H, W, _p(host), _p(dev), int(feather),
-                                                 _stream()), "ppst_guided_filter_paste_matte")
-        return out
-    check(lib.ppst_guided_filter_paste(_p(coeffs), n, _p(photo_u8), _p(out), B, H, W, _p(host), _p(dev), int(feather), _stream()),
-          "ppst_guided_filter_paste")
-    return out
+    return _paste("guided_filter_paste", coeffs, photo_u8, xf, feather, out,
+                  None if matte is None else (matte, "a float32 matte (B,n,n)", ()))
 
 
 def guided_matte_coeffs(guide_u8, matte, r=8, eps=(0.01 * 255) ** 2):
@@ -1995,15 +2012,11 @@ def guided_matte_coeffs(guide_u8, matte, r=8, eps=(0.01 * 255) ** 2):
     al.'s guided feathering; ppst_guided_matte_coeffs in include/ppst_hip.h).  Bit-equal to planes 0..3 of
     ``guided_filter_coeffs`` on the replicated source, through 13 of its 21 moment planes and 4 of its 12 coefficient planes; the
     radius rule is ``guided_filter_coeffs``'."""
-    if not isinstance(guide_u8, torch.Tensor) or not guide_u8.is_cuda or guide_u8.dtype != torch.uint8:
-        raise RuntimeError("guided_matte_coeffs needs a CUDA uint8 guide")
-    if guide_u8.dim() != 4 or guide_u8.shape[3] != 3:
-        raise RuntimeError("guided_matte_coeffs needs a guide (B,h,w,3), got %s" % (tuple(guide_u8.shape),))
+    _need_cuda("guided_matte_coeffs", "a CUDA uint8 guide", torch.uint8, guide_u8)
+    _need_shapes("guided_matte_coeffs", "a guide (B,h,w,3)", _is_image(guide_u8), guide_u8)
     B, h, w, _ = guide_u8.shape
-    if not isinstance(matte, torch.Tensor) or matte.dtype != torch.float32 or matte.device != guide_u8.device \
-            or tuple(matte.shape) != (B, h, w):
-        raise RuntimeError("guided_matte_coeffs needs a float32 matte (B,h,w) = %s on the guide's device" % ((B, h, w),))
-    guide_u8, matte = guide_u8.contiguous(), matte.contiguous()
+    matte = _need_match("guided_matte_coeffs", "a float32 matte (B,h,w)", matte, (B, h, w), guide_u8, "guide")
+    guide_u8 = guide_u8.contiguous()
     ws = torch.empty(lib.ppst_guided_matte_ws(B, h, w), device=guide_u8.device, dtype=torch.uint8)
     mcoeffs = torch.empty((B, 4, h, w), device=guide_u8.device, dtype=torch.float32)
     check(lib.ppst_guided_matte_coeffs(_p(guide_u8), _p(matte), _p(mcoeffs), B, h, w, int(r), float(eps), _p(ws), _stream()),
@@ -2017,27 +2030,8 @@ def guided_filter_paste_gmatte(coeffs, mcoeffs, photo_u8, xf, feather=0, out=Non
     so the matte follows the photo's edges; the blend weight is the edge feather times m^, and pixels of weight 0 keep the photo's
     byte.  ``out`` as in ``guided_filter_paste``.  ``want_weight``: also the weight rint(255 g) as uint8 (B,H,W), 0 outside the
     square."""
-    if not isinstance(coeffs, torch.Tensor) or not coeffs.is_cuda or coeffs.dtype != torch.float32:
-        raise RuntimeError("guided_filter_paste_gmatte needs CUDA float32 coefficients")
-    if not isinstance(photo_u8, torch.Tensor) or not photo_u8.is_cuda or photo_u8.dtype != torch.uint8:
-        raise RuntimeError("guided_filter_paste_gmatte needs a CUDA uint8 photo")
-    if (coeffs.dim() != 4 or coeffs.shape[1] != 12 or coeffs.shape[2] != coeffs.shape[3] or photo_u8.dim() != 4 or photo_u8.shape[3] != 3
-            or photo_u8.shape[0] != coeffs.shape[0]):
-        raise RuntimeError("guided_filter_paste_gmatte needs coefficients (B,12,n,n) and a photo (B,H,W,3) of one batch, got %s and %s"
-                           % (tuple(coeffs.shape), tuple(photo_u8.shape)))
-    B, _, n, _ = coeffs.shape
-    _, H, W, _ = photo_u8.shape
-    if not isinstance(mcoeffs, torch.Tensor) or mcoeffs.dtype != torch.float32 or mcoeffs.device != photo_u8.device \
-            or tuple(mcoeffs.shape) != (B, 4, n, n):
-        raise RuntimeError("guided_filter_paste_gmatte needs float32 matte coefficients (B,4,n,n) = %s on the photo's device" % ((B, 4, n, n),))
-    mcoeffs = mcoeffs.contiguous()
-    photo_u8, out = _paste_out(photo_u8, out, "guided_filter_paste_gmatte")
-    host, dev = _crop_transforms(xf, B, out.device, "guided_filter_paste_gmatte")
-    coeffs = coeffs.contiguous()
-    weight = torch.zeros((B, H, W), device=out.device, dtype=torch.uint8) if want_weight else None
-    check(lib.ppst_guided_filter_paste_gmatte(_p(coeffs), _p(mcoeffs), n, _p(photo_u8), _p(out), _p(weight), B, H, W, _p(host), _p(dev),
-                                              int(feather), _stream()), "ppst_guided_filter_paste_gmatte")
-    return (out, weight) if want_weight else out
+    return _paste("guided_filter_paste_gmatte", coeffs, photo_u8, xf, feather, out,
+                  (mcoeffs, "float32 matte coefficients (B,4,n,n)", (4,)), want_weight)
 
 
 def _encode(name, u8, limits, geom=(), settings=()):

@@ -358,14 +358,7 @@ class PPSTModel(nn.Module):
         ``guided_filter_radius``, upsampled bilinearly and applied to ``native_u8`` (B,H,W,3) uint8, the image ``target`` was made
         from, H >= h, W >= w.  -> uint8 (B,H,W,3).  The coefficient entry runs radii up to 64: ValueError for any other
         ("scaled" at 1536^2 gives 90)."""
-        h, w = int(target.shape[-2]), int(target.shape[-1])
-        r = guided_filter_radius(self.opt, h, w)
-        if not 0 < r <= 64 or r >= h or r >= w or w > 2048:           # (from shapes alone, before the generator runs)
-            raise ValueError("decode_native: the coefficient planes are computed at radii 0 < r <= 64 with r < h, r < w and "
-                             "w <= 2048, got r = %d at %d x %d" % (r, h, w))
-        out = self.G(spatial_code, global_code, noise=self.noise)
-        coeffs = ops.guided_filter_coeffs(glue.tensor2im(target), glue.tensor2im(out), r, (0.02 * 255) ** 2)
-        return ops.guided_filter_apply(coeffs, native_u8)
+        return ops.guided_filter_apply(self._decode_coeffs("decode_native", spatial_code, global_code, target), native_u8)
 
     def decode_region(self, spatial_code, global_code, target, photo_u8, xf, feather=0):
         """``decode_native`` for a crop INSIDE a photograph: ``target`` (B,3,n,n) is the normalised crop that
@@ -378,7 +371,7 @@ class PPSTModel(nn.Module):
     def decode_region_matte(self, spatial_code, global_code, target, photo_u8, xf, feather=0, matte=None):
         """``decode_region`` blended through a matte: ``matte`` fp32 (B,n,n) in the crop's frame (``ops.label_matte``) multiplies the
         edge feather, and photo pixels where it is 0 keep their bytes.  ``matte=None`` is ``decode_region``."""
-        coeffs = self._region_coeffs(spatial_code, global_code, target)
+        coeffs = self._decode_coeffs("decode_region", spatial_code, global_code, target, square=True)
         return ops.guided_filter_paste(coeffs, photo_u8, xf, feather, matte=matte)
 
     def decode_region_gmatte(self, spatial_code, global_code, target, photo_u8, xf, feather=0, matte=None, matte_radius=8,
@@ -392,19 +385,19 @@ class PPSTModel(nn.Module):
         if matte is None:
             raise ValueError("decode_region_gmatte needs a matte (decode_region_matte blends without one)")
         r = guided_matte_radius(matte_radius, min(int(target.shape[-2]), int(target.shape[-1])))
-        coeffs = self._region_coeffs(spatial_code, global_code, target)
+        coeffs = self._decode_coeffs("decode_region", spatial_code, global_code, target, square=True)
         mcoeffs = ops.guided_matte_coeffs(glue.tensor2im(target), matte, r, matte_eps)
         return ops.guided_filter_paste_gmatte(coeffs, mcoeffs, photo_u8, xf, feather, want_weight=want_weight)
 
-    def _region_coeffs(self, spatial_code, global_code, target):
-        """the colour coefficients (B,12,n,n) of the region commands: ``decode_native``'s, at a square target"""
+    def _decode_coeffs(self, who, spatial_code, global_code, target, square=False):
+        """the colour coefficients (B,12,h,w) of ``decode_native`` and, at a ``square`` target, of the region commands"""
         h, w = int(target.shape[-2]), int(target.shape[-1])
         r = guided_filter_radius(self.opt, h, w)
         if not 0 < r <= 64 or r >= h or r >= w or w > 2048:           # (from shapes alone, before the generator runs)
-            raise ValueError("decode_region: the coefficient planes are computed at radii 0 < r <= 64 with r < h, r < w and "
-                             "w <= 2048, got r = %d at %d x %d" % (r, h, w))
-        if h != w:
-            raise ValueError("decode_region: the crop is a square, got a target of %d x %d" % (h, w))
+            raise ValueError("%s: the coefficient planes are computed at radii 0 < r <= 64 with r < h, r < w and "
+                             "w <= 2048, got r = %d at %d x %d" % (who, r, h, w))
+        if square and h != w:
+            raise ValueError("%s: the crop is a square, got a target of %d x %d" % (who, h, w))
         out = self.G(spatial_code, global_code, noise=self.noise)
         return ops.guided_filter_coeffs(glue.tensor2im(target), glue.tensor2im(out), r, (0.02 * 255) ** 2)
 
