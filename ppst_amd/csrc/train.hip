@@ -18,7 +18,114 @@
 // partial[split][step][n][32] = sum over this split's pixels of dY[p][n] * X[p + tap(step)][chan(step) + k]
 // grid = (cout/128 n-tiles, chunks, splits); block = 4 waves, wave w owns n = n0 + 32w .. +31;
 // one block handles ONE chunk = up to 9 consecutive steps that share chan_off (registers: 9 x 16).
+// Four kernels take this sum -- conv_wgrad_kernel (fp32, operands from L1 / L2), conv_wgrad_lds_kernel (fp32, LDS-staged),
+// conv_wgrad_tr2_kernel (bf16 hi / lo split of fp32 tiles: production) and conv_wgrad_tr2b_kernel (bf16-stored operands) -- and
+// differ in how a tile reaches the matrix pipe.  What surrounds that is stated once, here:
+//   WgChunk, wg_chunk_load, wg_chan_of    a chunk of the step table: first step, length, channel offset, the taps' (dy, dx)
+//   wg_zero                               the accumulators
+//   wg_range, wg_tile                     the pixel split's range of tiles (conv_wgrad_kernel: of rows); a tile's image and origin
+//   wg_block_xcd                          the XCD-aware block map to (x = n tile, y = chunk group, z = pixel split)
+//   wg_units, wg_csum_finish              the (pixel, channel quad) units of the live 32-channel slabs of dY dealt to the threads,
+//                                         and the block's column sums of dY (the bias gradient) from the threads' sums over them
+//   WG_STORE_TILE                         one accumulator (the MFMA's 32 x 32 D tile) into partial
+// The tap loops stay apart: conv_wgrad_tr2_kernel's and conv_wgrad_tr2b_kernel's differ in the fragment reader and the pass count, the
+// two fp32 kernels' pixel loops in where an operand comes from.
 #define WG_MAXT 9
+#define WG_TR 2                     // the tile of the three staged kernels: 2 x 32 pixels of dY
+#define WG_TC 32
+template <int TM> struct WgChunk { int s0, T, chan; int tdy[TM], tdx[TM]; };
+// (taps beyond the chunk's length T repeat tap 0: their offsets are loaded, never used.  I: the caller's index type -- blockIdx.y is
+// unsigned, and widening it as an int gives other address arithmetic)
+template <int TM, typename I>
+__device__ __forceinline__ void wg_chunk_load(WgChunk<TM>& c, const int4* steps, const int* chunk_start, I chunk) {
+  c.s0 = chunk_start[chunk];
+  c.T = chunk_start[chunk + 1] - c.s0;
+  c.chan = steps[c.s0].x;
+#pragma unroll
+  for (int t = 0; t < TM; ++t) {
+    int4 d = steps[c.s0 + (t < c.T ? t : 0)];
+    c.tdy[t] = d.y; c.tdx[t] = d.z;
+  }
+}
+// channel offset of chunk ci, a wave-uniform RUNTIME index, written as selects.  ``chan`` is a copy of the chunks' offsets in an
+// array of its own: at NCH = 4 hipcc turns the selects back into an indexed read and keeps that array in memory (16 bytes per thread,
+// which it places in LDS) -- indexed inside the chunks, all of them would go to scratch
+template <int NCH>
+__device__ __forceinline__ int wg_chan_of(const int (&chan)[NCH], int ci) {
+  int c = chan[0];
+#pragma unroll
+  for (int j = 1; j < NCH; ++j) c = ci == j ? chan[j] : c;
+  return c;
+}
+template <int N>
+__device__ __forceinline__ void wg_zero(f32x16 (&acc)[N]) {
+#pragma unroll
+  for (int t = 0; t < N; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+}
+template <int M, int N>
+__device__ __forceinline__ void wg_zero(f32x16 (&acc)[M][N]) {
+#pragma unroll
+  for (int ci = 0; ci < M; ++ci) wg_zero(acc[ci]);
+}
+struct WgRange { int begin, end; };
+__device__ __forceinline__ WgRange wg_range(int split, int per_split, int total) {
+  const int begin = split * per_split;
+  return {begin, min(begin + per_split, total)};
+}
+struct WgTile { int b, ty0, tx0; };
+__device__ __forceinline__ WgTile wg_tile(int tile, int tiles_per_image, int tiles_x) {
+  const int b = tile / tiles_per_image;
+  const int r = tile - b * tiles_per_image;
+  return {b, (r / tiles_x) * WG_TR, (r - (r / tiles_x) * tiles_x) * WG_TC};
+}
+struct WgBlock { int x, y, z; };
+__device__ __forceinline__ WgBlock wg_block_xcd() {      // (conv_common.h; why: the comment in front of conv_wgrad_tr2_kernel)
+  const int nb = gridDim.x * gridDim.y * gridDim.z;
+  const int id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+  int v = xcd_block_id(id, nb);
+  WgBlock k;
+  k.x = v % (int)gridDim.x; v /= (int)gridDim.x;
+  k.y = v % (int)gridDim.y; k.z = v / (int)gridDim.y;
+  return k;
+}
+// The 64 pixels x NQ = 8 nslab channel quads of a dY tile's live slabs, dealt to the block's 256 threads: thread tid < stride takes
+// the units i = tid, tid + stride, .. < 64 NQ; unit i is (pixel i / NQ, quad i % NQ).  stride is 256 rounded down to a multiple of
+// NQ (8, 16, 32: 256; 24: 240), so a thread keeps ONE quad, tid % NQ, in every pass -- its column sums need no index.
+struct WgUnits { int NQ, stride; };
+__device__ __forceinline__ WgUnits wg_units(int nslab) {
+  const int NQ = 8 * nslab;
+  return {NQ, (256 / NQ) * NQ};
+}
+// csum[split][n0 ..] = the block's column sums of dY: cs = this thread's sums of its quad; the threads with equal tid % NQ share a
+// quad and are added in thread order.  red: 4 KB of LDS that no wave reads any more (barrier inside)
+__device__ __forceinline__ void wg_csum_finish(float4 cs, float4* red, int nslab, int tid, float* csum, int split, int n0, int cout) {
+  const WgUnits u = wg_units(nslab);
+  __syncthreads();
+  red[tid] = tid < u.stride ? cs : make_float4(0.f, 0.f, 0.f, 0.f);
+  __syncthreads();
+  if (tid < u.NQ) {
+    float4 a = red[tid];
+    for (int r = tid + u.NQ; r < u.stride; r += u.NQ) { const float4 v = red[r]; a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
+    const int n = n0 + tid * 4;
+    float* o = csum + (int64_t)split * cout + n;
+    if (n < cout) { o[0] = a.x; if (n + 1 < cout) o[1] = a.y; if (n + 2 < cout) o[2] = a.z; if (n + 3 < cout) o[3] = a.w; }
+  }
+}
+// D tile of a wave whose first output channel is nw0: col = lane & 31 (k within the 32-channel chunk),
+// row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) (n).  Reads the kernel's partial, nsteps, cout and lane.  (Expanded as text:
+// the same lines as a __forceinline__ function gave every kernel another instruction stream, and conv_wgrad_lds_kernel 40 more
+// bytes of scratch -- profiles/wgrad_shared_isa.txt.)
+#define WG_STORE_TILE(acc, split, step, nw0)                                                  \
+  do {                                                                                          \
+    float* o = partial + (((int64_t)(split) * nsteps + step) * cout) * 32;                      \
+    _Pragma("unroll") for (int rg = 0; rg < 16; ++rg) {                                         \
+      int nn = nw0 + (rg & 3) + 8 * (rg >> 2) + 4 * (lane >> 5);                                \
+      if (nn < cout) o[(int64_t)nn * 32 + (lane & 31)] = (acc)[rg];                             \
+    }                                                                                           \
+  } while (0)
+
 __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                          const int4* __restrict__ steps, const int* __restrict__ chunk_start,
                                                          float* __restrict__ partial, int B, int in_h, int in_w, int in_ld,
@@ -26,37 +133,26 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const float* __restr
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 31, lk = lane >> 5;
   const int n = blockIdx.x * 128 + wave * 32 + li;
-  const int s0 = chunk_start[blockIdx.y], s1 = chunk_start[blockIdx.y + 1];
-  const int T = s1 - s0;
-  const int chan = steps[s0].x;
-  int tdy[WG_MAXT], tdx[WG_MAXT];
-#pragma unroll
-  for (int t = 0; t < WG_MAXT; ++t) {
-    int4 d = steps[s0 + (t < T ? t : 0)];
-    tdy[t] = d.y; tdx[t] = d.z;
-  }
+  WgChunk<WG_MAXT> ck;
+  wg_chunk_load(ck, steps, chunk_start, blockIdx.y);
+  const int T = ck.T;
   if (blockIdx.x * 128 + wave * 32 >= cout) return;   // waves beyond the last output channel (no barrier in this kernel)
   f32x16 acc[WG_MAXT];
-#pragma unroll
-  for (int t = 0; t < WG_MAXT; ++t)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
-  const int rows_total = B * oh;
-  const int r_begin = blockIdx.z * rows_per_split;
-  const int r_end = min(r_begin + rows_per_split, rows_total);
+  wg_zero(acc);
+  const WgRange rows = wg_range(blockIdx.z, rows_per_split, B * oh);
   const bool nok = n < cout;
   const int nc = nok ? n : 0;
-  for (int r = r_begin; r < r_end; ++r) {
+  for (int r = rows.begin; r < rows.end; ++r) {
     const int b = r / oh, y = r - b * oh;
     const float* dyr = dy + ((int64_t)(b * oh + y) * ow) * dy_ld + nc;
-    const float* xb = x + (int64_t)b * in_h * in_w * in_ld + chan + li;
+    const float* xb = x + (int64_t)b * in_h * in_w * in_ld + ck.chan + li;
     // per-row tap state: row pointer (clamped) and validity, so the pixel loop issues unconditional loads
     // (select afterwards): the compiler can then hoist the loads of the next pixel pair above this pair's MFMAs
     const float* rowp[WG_MAXT];
     bool rowok[WG_MAXT];
 #pragma unroll
     for (int t = 0; t < WG_MAXT; ++t) {
-      const int iy = y + tdy[t];
+      const int iy = y + ck.tdy[t];
       rowok[t] = t < T && iy >= 0 && iy < in_h;
       rowp[t] = xb + (int64_t)(rowok[t] ? iy : 0) * in_w * in_ld;
     }
@@ -69,7 +165,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const float* __restr
       float bv[WG_MAXT];
 #pragma unroll
       for (int t = 0; t < WG_MAXT; ++t) {
-        const int ix = xx + tdx[t];
+        const int ix = xx + ck.tdx[t];
         const bool ok = rowok[t] && xok && ix >= 0 && ix < in_w;
         const float v = rowp[t][(int64_t)(ok ? ix : 0) * in_ld];
         bv[t] = ok ? v : 0.f;
@@ -79,18 +175,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const float* __restr
         if (t < T) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[t], acc[t], 0, 0, 0);
     }
   }
-  // D tile: col = lane&31 (k within the 32-channel chunk), row = (reg&3) + 8*(reg>>2) + 4*(lane>>5) (n)
 #pragma unroll
-  for (int t = 0; t < WG_MAXT; ++t) {
-    if (t < T) {
-      float* o = partial + (((int64_t)blockIdx.z * nsteps + s0 + t) * cout) * 32;
-#pragma unroll
-      for (int rg = 0; rg < 16; ++rg) {
-        int nn = blockIdx.x * 128 + wave * 32 + (rg & 3) + 8 * (rg >> 2) + 4 * lk;
-        if (nn < cout) o[(int64_t)nn * 32 + li] = acc[t][rg];
-      }
-    }
-  }
+  for (int t = 0; t < WG_MAXT; ++t)
+    if (t < T) WG_STORE_TILE(acc[t], blockIdx.z, ck.s0 + t, blockIdx.x * 128 + wave * 32);
 }
 
 // LDS-staged variant (round 2): the block stages a 2 x 32-pixel tile of dY (64 px x 128 n, 32 KB) and the matching
@@ -99,8 +186,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const float* __restr
 // step tables; the round-1 kernel above was latency bound (26 TFLOP/s = 17 % of the fp32 MFMA peak: two waves per SIMD
 // each waiting ~500 cycles per operand fetch).  49 KB of LDS, 3 blocks per CU: one block's staging overlaps the
 // others' MFMAs.
-#define WG_TR 2
-#define WG_TC 32
 __global__ __launch_bounds__(256, 3) void conv_wgrad_lds_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                               const int4* __restrict__ steps, const int* __restrict__ chunk_start,
                                                               float* __restrict__ partial, int B, int in_h, int in_w, int in_ld,
@@ -112,27 +197,15 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_lds_kernel(const float* __r
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lk = lane >> 5;
   const int n0 = blockIdx.x * 128;
-  const int s0 = chunk_start[blockIdx.y], s1 = chunk_start[blockIdx.y + 1];
-  const int T = s1 - s0;
-  const int chan = steps[s0].x;
-  int tdy[WG_MAXT], tdx[WG_MAXT];
-#pragma unroll
-  for (int t = 0; t < WG_MAXT; ++t) {
-    int4 d = steps[s0 + (t < T ? t : 0)];
-    tdy[t] = d.y; tdx[t] = d.z;
-  }
+  WgChunk<WG_MAXT> ck;
+  wg_chunk_load(ck, steps, chunk_start, blockIdx.y);
+  const int T = ck.T, chan = ck.chan;
   f32x16 acc[WG_MAXT];
-#pragma unroll
-  for (int t = 0; t < WG_MAXT; ++t)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
-  const int t_begin = blockIdx.z * tiles_per_split;
-  const int t_end = min(t_begin + tiles_per_split, tiles_total);
+  wg_zero(acc);
+  const WgRange tiles = wg_range(blockIdx.z, tiles_per_split, tiles_total);
   const bool wave_live = n0 + wave * 32 < cout;          // waves beyond the last output channel only help staging
-  for (int tile = t_begin; tile < t_end; ++tile) {
-    const int b = tile / tiles_per_image;
-    const int r = tile - b * tiles_per_image;
-    const int ty0 = (r / tiles_x) * WG_TR, tx0 = (r - (r / tiles_x) * tiles_x) * WG_TC;
+  for (int tile = tiles.begin; tile < tiles.end; ++tile) {
+    const auto [b, ty0, tx0] = wg_tile(tile, tiles_per_image, tiles_x);
     __syncthreads();                                       // previous tile's reads are done
     // dY tile: 64 px x 128 n (zeros outside the image / beyond cout)
     for (int i = tid; i < WG_TR * WG_TC * 32; i += 256) {
@@ -163,7 +236,7 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_lds_kernel(const float* __r
         const float av = sdy[p][wave * 32 + li];
         float bv[WG_MAXT];
 #pragma unroll
-        for (int t = 0; t < WG_MAXT; ++t) bv[t] = sx[(py + 1 + tdy[t]) * XW + px + 1 + tdx[t]][li];
+        for (int t = 0; t < WG_MAXT; ++t) bv[t] = sx[(py + 1 + ck.tdy[t]) * XW + px + 1 + ck.tdx[t]][li];
 #pragma unroll
         for (int t = 0; t < WG_MAXT; ++t)
           if (t < T) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[t], acc[t], 0, 0, 0);
@@ -172,16 +245,8 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_lds_kernel(const float* __r
   }
   if (!wave_live) return;
 #pragma unroll
-  for (int t = 0; t < WG_MAXT; ++t) {
-    if (t < T) {
-      float* o = partial + (((int64_t)blockIdx.z * nsteps + s0 + t) * cout) * 32;
-#pragma unroll
-      for (int rg = 0; rg < 16; ++rg) {
-        int nn = n0 + wave * 32 + (rg & 3) + 8 * (rg >> 2) + 4 * lk;
-        if (nn < cout) o[(int64_t)nn * 32 + li] = acc[t][rg];
-      }
-    }
-  }
+  for (int t = 0; t < WG_MAXT; ++t)
+    if (t < T) WG_STORE_TILE(acc[t], blockIdx.z, ck.s0 + t, n0 + wave * 32);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -249,47 +314,21 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2_kernel(const float* __r
   unsigned char* const imdy = smem;                           // [slab 0..3][64 px][8 quads][16 B]
   unsigned char* const imx = smem + IMG_DY;                   // NCH x [136 px][8 quads][16 B]
   const int tid = threadIdx.x, lane = tid & 63, nw = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 31, kb = lane >> 5;
-  int bx, by, bz;                                             // XCD-aware block map (conv_common.h; the comment in front of conv_wgrad_tr2_kernel)
-  {
-    const int nb = gridDim.x * gridDim.y * gridDim.z;
-    const int id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    int v = xcd_block_id(id, nb);
-    bx = v % (int)gridDim.x; v /= (int)gridDim.x;
-    by = v % (int)gridDim.y; bz = v / (int)gridDim.y;
-  }
-  const int n0 = bx * 128;
-  int s0[NCH], T[NCH], chan[NCH];
-  int tdy[NCH][TM], tdx[NCH][TM];
+  const WgBlock blk = wg_block_xcd();
+  const int n0 = blk.x * 128;
+  WgChunk<TM> ck[NCH];
+  int chan[NCH];                                              // (for wg_chan_of)
 #pragma unroll
   for (int ci = 0; ci < NCH; ++ci) {
-    s0[ci] = chunk_start[by * NCH + ci];
-    T[ci] = chunk_start[by * NCH + ci + 1] - s0[ci];
-    chan[ci] = steps[s0[ci]].x;
-#pragma unroll
-    for (int t = 0; t < TM; ++t) {
-      int4 d = steps[s0[ci] + (t < T[ci] ? t : 0)];
-      tdy[ci][t] = d.y; tdx[ci][t] = d.z;
-    }
+    wg_chunk_load(ck[ci], steps, chunk_start, blk.y * NCH + ci);
+    chan[ci] = ck[ci].chan;
   }
-  auto chan_of = [&](int ci) {                               // (wave-uniform runtime index: no dynamically indexed register array)
-    int c = chan[0];
-#pragma unroll
-    for (int j = 1; j < NCH; ++j) c = ci == j ? chan[j] : c;
-    return c;
-  };
   f32x16 acc[NCH][TM];
-#pragma unroll
-  for (int ci = 0; ci < NCH; ++ci)
-#pragma unroll
-    for (int t = 0; t < TM; ++t)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[ci][t][i] = 0.f;
-  const int t_begin = bz * tiles_per_split;
-  const int t_end = min(t_begin + tiles_per_split, tiles_total);
+  wg_zero(acc);
+  const WgRange tiles = wg_range(blk.z, tiles_per_split, tiles_total);
   const bool wave_live = n0 + nw * 32 < cout;
   const int nslab = min(4, (cout - n0 + 31) >> 5);            // 32-channel slabs of dY this block has any use for
-  const bool want_csum = csum != nullptr && by == 0;
+  const bool want_csum = csum != nullptr && blk.y == 0;
   float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);               // this thread's 4 channels (quad tid % (8 nslab)) over its pixels of every tile
   // transposed-read lane geometry (the comment above): channel quad 4 (g & 1) + pp, pixel 8 kb + qd (+ 4 for the second read)
   const int g = lane >> 4, qd = (lane & 15) >> 2, pp = lane & 3;
@@ -311,10 +350,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2_kernel(const float* __r
       l = h;
     }
   };
-  for (int tile = t_begin; tile < t_end; ++tile) {
-    const int b = tile / tiles_per_image;
-    const int r = tile - b * tiles_per_image;
-    const int ty0 = (r / tiles_x) * WG_TR, tx0 = (r - (r / tiles_x) * tiles_x) * WG_TC;
+  for (int tile = tiles.begin; tile < tiles.end; ++tile) {
+    const auto [b, ty0, tx0] = wg_tile(tile, tiles_per_image, tiles_x);
     __syncthreads();                                        // the previous tile's MFMA reads are done
     // ---- LDS-DMA: 32 pieces of dY (slab s, pixels 8 j .. 8 j + 7: 8 x 128 B) + 17 per chunk of the input halo (8 pixels x 128 B)
     for (int wi = nw; wi < 32 + NCH * XPC; wi += 4) {
@@ -333,7 +370,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2_kernel(const float* __r
         const int row = P / XW, col = P - row * XW;
         const int iy = ty0 - XO + row, ix = tx0 - XO + col;
         if (iy >= 0 && iy < in_h && ix >= 0 && ix < in_w)
-          src = x + (((int64_t)b * in_h + iy) * in_w + ix) * in_ld + chan_of(ci) + q * 4;
+          src = x + (((int64_t)b * in_h + iy) * in_w + ix) * in_ld + wg_chan_of(chan, ci) + q * 4;
         dst = imx + (wi - 32) * 1024;
       }
       __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src, (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
@@ -356,12 +393,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2_kernel(const float* __r
         else *(uint4*)u = sw ? make_uint4(lo.x, lo.y, hi.x, hi.y) : make_uint4(hi.x, hi.y, lo.x, lo.y);
       }
     } else {
-      // fewer live slabs (cout - n0 <= 96): NQ = 8 nslab channel quads; unit i -> quad i % NQ (= tid % NQ in every pass: 256 is a
-      // multiple of 8, 16 and -- with the pass stride rounded down to a multiple of 24 -- of 24), pixel i / NQ
-      const int NQ = 8 * nslab, stride = (256 / NQ) * NQ;
-      if (tid < stride)
-        for (int i = tid; i < 64 * NQ; i += stride) {
-          const int p = i / NQ, cq = i - p * NQ;
+      // fewer live slabs (cout - n0 <= 96): the unit walk of wg_units (the loop above is that walk at NQ = 32, unrolled)
+      const WgUnits un = wg_units(nslab);
+      if (tid < un.stride)
+        for (int i = tid; i < 64 * un.NQ; i += un.stride) {
+          const int p = i / un.NQ, cq = i - p * un.NQ;
           unsigned char* u = imdy + (cq >> 3) * 8192 + p * 128 + (cq & 7) * 16;
           const float4 v = *(const float4*)u;
           if (want_csum) { cs.x += v.x; cs.y += v.y; cs.z += v.z; cs.w += v.w; }
@@ -397,15 +433,15 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2_kernel(const float* __r
 #pragma unroll
         for (int ci = 0; ci < NCH; ++ci) {
           const unsigned char* const im = imx + ci * IMG_X;
-          const int pb0 = (row + XO + tdy[ci][0]) * XW + xh + XO + tdx[ci][0];
+          const int pb0 = (row + XO + ck[ci].tdy[0]) * XW + xh + XO + ck[ci].tdx[0];
           bf16x8 b_h, b_l;
           frag(im + pb0 * 128 + tr_unit, (((pb0 & 3) + qd) >> 1) & 1, b_h, b_l);
 #pragma unroll
           for (int t = 0; t < TM; ++t) {
-            if (EXACT || t < T[ci]) {
+            if (EXACT || t < ck[ci].T) {
               bf16x8 n_h = b_h, n_l = b_l;
-              if (t + 1 < TM && (EXACT || t + 1 < T[ci])) {   // the next tap's fragments are requested before this tap's MFMAs
-                const int pb = (row + XO + tdy[ci][t + 1]) * XW + xh + XO + tdx[ci][t + 1];
+              if (t + 1 < TM && (EXACT || t + 1 < ck[ci].T)) {   // the next tap's fragments are requested before this tap's MFMAs
+                const int pb = (row + XO + ck[ci].tdy[t + 1]) * XW + xh + XO + ck[ci].tdx[t + 1];
                 frag(im + pb * 128 + tr_unit, (((pb & 3) + qd) >> 1) & 1, n_h, n_l);
               }
               if (!X1) {
@@ -420,36 +456,14 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2_kernel(const float* __r
       }
     }
   }
-  if (want_csum) {                                            // column sums of dY: the threads with equal tid % NQ share a channel quad
-    __syncthreads();
-    float4* red = (float4*)smem;                              // [256] float4, thread order
-    const int NQ = 8 * nslab, stride = (256 / NQ) * NQ;
-    red[tid] = tid < stride ? cs : make_float4(0.f, 0.f, 0.f, 0.f);
-    __syncthreads();
-    if (tid < NQ) {
-      float4 a = red[tid];
-      for (int r = tid + NQ; r < stride; r += NQ) { const float4 v = red[r]; a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
-      const int n = n0 + tid * 4;
-      float* o = csum + (int64_t)bz * cout + n;
-      if (n < cout) { o[0] = a.x; if (n + 1 < cout) o[1] = a.y; if (n + 2 < cout) o[2] = a.z; if (n + 3 < cout) o[3] = a.w; }
-    }
-  }
+  if (want_csum) wg_csum_finish(cs, (float4*)smem, nslab, tid, csum, blk.z, n0, cout);
   if (!wave_live) return;
 #pragma unroll
   for (int ci = 0; ci < NCH; ++ci)
 #pragma unroll
-    for (int t = 0; t < TM; ++t) {
-      if (EXACT || t < T[ci]) {
-        float* o = partial + (((int64_t)bz * nsteps + s0[ci] + t) * cout) * 32;
-#pragma unroll
-        for (int rg = 0; rg < 16; ++rg) {
-          int nn = n0 + nw * 32 + (rg & 3) + 8 * (rg >> 2) + 4 * kb;
-          if (nn < cout) o[(int64_t)nn * 32 + li] = acc[ci][t][rg];
-        }
-      }
-    }
+    for (int t = 0; t < TM; ++t)
+      if (EXACT || t < ck[ci].T) WG_STORE_TILE(acc[ci][t], blk.z, ck[ci].s0 + t, n0 + nw * 32);
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Round 5: the same weight gradient on bf16-STORED operands (precision mode 1 with half-precision storage of the training
@@ -474,47 +488,22 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2b_kernel(const unsigned 
   static_assert(!HALO ? TM == 1 : true, "the no-halo image serves 1x1 tables");
   __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63, nw = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 31, kb = lane >> 5;
-  int bx, by, bz;                                             // XCD-aware block map (conv_common.h; the comment in front of conv_wgrad_tr2_kernel)
-  {
-    const int nb = gridDim.x * gridDim.y * gridDim.z;
-    const int id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    int v = xcd_block_id(id, nb);
-    bx = v % (int)gridDim.x; v /= (int)gridDim.x;
-    by = v % (int)gridDim.y; bz = v / (int)gridDim.y;
-  }
-  const int n0 = bx * 128;
-  int s0[NCH], T[NCH], chan[NCH];
-  int tdy[NCH][TM], tdx[NCH][TM];
+  const WgBlock blk = wg_block_xcd();
+  const int n0 = blk.x * 128;
+  WgChunk<TM> ck[NCH];
+  int chan[NCH];                                              // (for wg_chan_of)
 #pragma unroll
   for (int ci = 0; ci < NCH; ++ci) {
-    s0[ci] = chunk_start[by * NCH + ci];
-    T[ci] = chunk_start[by * NCH + ci + 1] - s0[ci];
-    chan[ci] = steps[s0[ci]].x;
-#pragma unroll
-    for (int t = 0; t < TM; ++t) {
-      int4 d = steps[s0[ci] + (t < T[ci] ? t : 0)];
-      tdy[ci][t] = d.y; tdx[ci][t] = d.z;
-    }
+    wg_chunk_load(ck[ci], steps, chunk_start, blk.y * NCH + ci);
+    chan[ci] = ck[ci].chan;
   }
-  auto chan_of = [&](int ci) {
-    int c = chan[0];
-#pragma unroll
-    for (int j = 1; j < NCH; ++j) c = ci == j ? chan[j] : c;
-    return c;
-  };
   f32x16 acc[NCH][TM];
-#pragma unroll
-  for (int ci = 0; ci < NCH; ++ci)
-#pragma unroll
-    for (int t = 0; t < TM; ++t)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[ci][t][i] = 0.f;
-  const int t_begin = bz * tiles_per_split;
-  const int t_end = min(t_begin + tiles_per_split, tiles_total);
+  wg_zero(acc);
+  const WgRange tiles = wg_range(blk.z, tiles_per_split, tiles_total);
+  const int t_begin = tiles.begin, t_end = tiles.end;
   const bool wave_live = n0 + nw * 32 < cout;
   const int nslab = min(4, (cout - n0 + 31) >> 5);
-  const bool want_csum = csum != nullptr && by == 0;
+  const bool want_csum = csum != nullptr && blk.y == 0;
   float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);
   const int g = lane >> 4, qd = (lane & 15) >> 2, pp = lane & 3;
   const int tr_unit = (8 * (g >> 1) + qd) * PXB + (4 * (g & 1) + pp) * 8;
@@ -525,9 +514,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2b_kernel(const unsigned 
   };
   // LDS-DMA of one tile: 16 pieces of dY (slab, 16 pixels: 16 x 64 B) + XPC per chunk of the input image; lane = (pixel, 16-byte quarter)
   auto issue = [&](int tile, unsigned char* buf) {
-    const int b = tile / tiles_per_image;
-    const int r = tile - b * tiles_per_image;
-    const int ty0 = (r / tiles_x) * WG_TR, tx0 = (r - (r / tiles_x) * tiles_x) * WG_TC;
+    const auto [b, ty0, tx0] = wg_tile(tile, tiles_per_image, tiles_x);
     const int q = lane & 3, pl = lane >> 2;
     for (int wi = nw; wi < 16 + NCH * XPC; wi += 4) {
       const void* src = g_wg_zero;
@@ -542,7 +529,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2b_kernel(const unsigned 
         const int row = P / XW, col = P - row * XW;
         const int iy = ty0 - XO + row, ix = tx0 - XO + col;
         if (P < XPX && iy >= 0 && iy < in_h && ix >= 0 && ix < in_w)
-          src = x + (((int64_t)b * in_h + iy) * in_w + ix) * in_ld + chan_of(ci) + q * 8;
+          src = x + (((int64_t)b * in_h + iy) * in_w + ix) * in_ld + wg_chan_of(chan, ci) + q * 8;
       }
       unsigned char* dst = buf + (wi < 16 ? wi * 1024 : IMG_DY + (wi - 16) * 1024);
       __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src, (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
@@ -554,11 +541,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2b_kernel(const unsigned 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's pieces of the current tile have landed (hipcc adds no wait for LDS-DMA)
     __syncthreads();                                        // ... everybody's have, and the previous tile's MFMA reads are done
     if (tile + 1 < t_end) issue(tile + 1, smem + (((tile - t_begin) & 1) ^ 1) * BUF);
-    if (want_csum) {                                        // bias column sums: 4 channels per thread over its pixels of the dY image
-      const int NQ = 8 * nslab, stride = (256 / NQ) * NQ;
-      if (tid < stride)
-        for (int i = tid; i < 64 * NQ; i += stride) {
-          const int p = i / NQ, cq = i - p * NQ;
+    if (want_csum) {                                        // bias column sums: 4 channels per thread over its units of the dY image
+      const WgUnits un = wg_units(nslab);
+      if (tid < un.stride)
+        for (int i = tid; i < 64 * un.NQ; i += un.stride) {
+          const int p = i / un.NQ, cq = i - p * un.NQ;
           const uint2 u = *(const uint2*)(cur + (cq >> 3) * SLAB + p * PXB + (cq & 7) * 8);
           cs.x += __uint_as_float(u.x << 16); cs.y += __uint_as_float(u.x & 0xffff0000u);
           cs.z += __uint_as_float(u.y << 16); cs.w += __uint_as_float(u.y & 0xffff0000u);
@@ -573,15 +560,15 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2b_kernel(const unsigned 
 #pragma unroll
         for (int ci = 0; ci < NCH; ++ci) {
           const unsigned char* const im = cur + IMG_DY + ci * IMG_X;
-          const int pb0 = (row + XO + tdy[ci][0]) * XW + xh + XO + tdx[ci][0];
+          const int pb0 = (row + XO + ck[ci].tdy[0]) * XW + xh + XO + ck[ci].tdx[0];
           bf16x8 b_h;
           frag(im + pb0 * PXB + tr_unit, b_h);
 #pragma unroll
           for (int t = 0; t < TM; ++t) {
-            if (EXACT || t < T[ci]) {
+            if (EXACT || t < ck[ci].T) {
               bf16x8 n_h = b_h;
-              if (t + 1 < TM && (EXACT || t + 1 < T[ci])) {
-                const int pb = (row + XO + tdy[ci][t + 1]) * XW + xh + XO + tdx[ci][t + 1];
+              if (t + 1 < TM && (EXACT || t + 1 < ck[ci].T)) {
+                const int pb = (row + XO + ck[ci].tdy[t + 1]) * XW + xh + XO + ck[ci].tdx[t + 1];
                 frag(im + pb * PXB + tr_unit, n_h);
               }
               acc[ci][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, b_h, acc[ci][t], 0, 0, 0);
@@ -592,34 +579,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tr2b_kernel(const unsigned 
       }
     }
   }
-  if (want_csum) {
-    __syncthreads();
-    float4* red = (float4*)smem;
-    const int NQ = 8 * nslab, stride = (256 / NQ) * NQ;
-    red[tid] = tid < stride ? cs : make_float4(0.f, 0.f, 0.f, 0.f);
-    __syncthreads();
-    if (tid < NQ) {
-      float4 a = red[tid];
-      for (int r = tid + NQ; r < stride; r += NQ) { const float4 v = red[r]; a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
-      const int n = n0 + tid * 4;
-      float* o = csum + (int64_t)bz * cout + n;
-      if (n < cout) { o[0] = a.x; if (n + 1 < cout) o[1] = a.y; if (n + 2 < cout) o[2] = a.z; if (n + 3 < cout) o[3] = a.w; }
-    }
-  }
+  if (want_csum) wg_csum_finish(cs, (float4*)smem, nslab, tid, csum, blk.z, n0, cout);
   if (!wave_live) return;
 #pragma unroll
   for (int ci = 0; ci < NCH; ++ci)
 #pragma unroll
-    for (int t = 0; t < TM; ++t) {
-      if (EXACT || t < T[ci]) {
-        float* o = partial + (((int64_t)bz * nsteps + s0[ci] + t) * cout) * 32;
-#pragma unroll
-        for (int rg = 0; rg < 16; ++rg) {
-          int nn = n0 + nw * 32 + (rg & 3) + 8 * (rg >> 2) + 4 * kb;
-          if (nn < cout) o[(int64_t)nn * 32 + li] = acc[ci][t][rg];
-        }
-      }
-    }
+    for (int t = 0; t < TM; ++t)
+      if (EXACT || t < ck[ci].T) WG_STORE_TILE(acc[ci][t], blk.z, ck[ci].s0 + t, n0 + nw * 32);
 }
 
 // profiling brackets of conv_mfma.hip: a weight-gradient launch is recorded with info = {B, oh, ow, nsteps, cout, nchunks, splits, 0}
@@ -1030,20 +996,29 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const float* __restri
     dw[t] = accumulate ? dw[t] + s * scale : s * scale;
   }
 }
-// K % 4 == 0, 16-byte aligned x / dw: four columns per thread
+// K % 4 == 0, 16-byte aligned x / dw: four columns per thread.  FUSED (round 5, LinearFn of ppst_amd/autograd.py: the E2 projector
+// chains ran 7 launches per linear and backward) folds in the passes around the gradient: ``relu_in`` -- x is read as max(x, 0) (the
+// linear sits behind nn.ReLU, encoder_col.py:47-93); ``db`` -- the bias gradient bscale * sum_b dY[b][n] from the thread that owns
+// column 0 of row n (dY's rows are read by it anyway).  Without FUSED those four arguments are not read.
+template <bool FUSED>
 __global__ __launch_bounds__(256) void linear_wgrad4_kernel(const float* __restrict__ dy, const float4* __restrict__ x, float4* __restrict__ dw,
-                                                            int B, int N, int K4, float scale, int accumulate, int64_t total4) {
+                                                            float* __restrict__ db, int B, int N, int K4, float scale, float bscale,
+                                                            int accumulate, int b_accumulate, int relu_in, int64_t total4) {
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total4; t += (int64_t)gridDim.x * 256) {
     const int k4 = (int)(t % K4), n = (int)(t / K4);
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    float sd = 0.f;
     for (int b = 0; b < B; ++b) {
       const float d = dy[(int64_t)b * N + n];
-      const float4 v = x[(int64_t)b * K4 + k4];
+      float4 v = x[(int64_t)b * K4 + k4];
+      if (FUSED && relu_in) { v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f; }
       s.x += d * v.x; s.y += d * v.y; s.z += d * v.z; s.w += d * v.w;
+      sd += d;
     }
     float4 o = make_float4(s.x * scale, s.y * scale, s.z * scale, s.w * scale);
     if (accumulate) { const float4 p = dw[t]; o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w; }
     dw[t] = o;
+    if (FUSED && db && k4 == 0) db[n] = b_accumulate ? db[n] + sd * bscale : sd * bscale;
   }
 }
 // dX = dY W streams the weight matrix once (4*N*K bytes): block (kx, ns) owns 256 columns k and the LDG_ROWS rows
@@ -1084,8 +1059,11 @@ __global__ __launch_bounds__(256) void linear_dgrad_partial_kernel(const float* 
       if (b0 + b < B) partial[((int64_t)blockIdx.y * B + b0 + b) * K + k] = acc[b];
   }
 }
-__global__ __launch_bounds__(256) void linear_dgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dx, int nsplit,
-                                                                  int64_t bk, float scale) {
+// GATE: dX is multiplied by [gate > 0] (gate: B x K) in the slice reduction -- the backward of the nn.ReLU in front of the linear;
+// without it ``gate`` is not read
+template <bool GATE>
+__global__ __launch_bounds__(256) void linear_dgrad_reduce_kernel(const float* __restrict__ partial, const float* __restrict__ gate,
+                                                                  float* __restrict__ dx, int nsplit, int64_t bk, float scale) {
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < bk; t += (int64_t)gridDim.x * 256) {
     float s = 0.f;
     int i = 0;
@@ -1096,7 +1074,7 @@ __global__ __launch_bounds__(256) void linear_dgrad_reduce_kernel(const float* _
       s += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
     }
     for (; i < nsplit; ++i) s += partial[(int64_t)i * bk + t];
-    dx[t] = s * scale;
+    dx[t] = (!GATE || gate[t] > 0.f) ? s * scale : 0.f;
   }
 }
 extern "C" int ppst_linear_wgrad(const void* dy, const void* x, void* dw, int B, int N, int K, float scale, int accumulate, void* stream) {
@@ -1106,37 +1084,14 @@ extern "C" int ppst_linear_wgrad(const void* dy, const void* x, void* dw, int B,
   if (K % 4 == 0 && ((uintptr_t)x | (uintptr_t)dw) % 16 == 0) {
     blocks = cdiv64(total / 4, 256);
     if (blocks > 8192) blocks = 8192;
-    PPST_LAUNCH(linear_wgrad4_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const float*)dy, (const float4*)x, (float4*)dw,
-                B, N, K / 4, scale, accumulate, total / 4);
+    PPST_LAUNCH(linear_wgrad4_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const float*)dy, (const float4*)x,
+                (float4*)dw, (float*)nullptr, B, N, K / 4, scale, 0.f, accumulate, 0, 0, total / 4);
     return PPST_LAUNCH_CHECK();
   }
   if (blocks > 4096) blocks = 4096;
   PPST_LAUNCH(linear_wgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const float*)dy, (const float*)x, (float*)dw, B, N,
               K, scale, accumulate, total);
   return PPST_LAUNCH_CHECK();
-}
-// Round 5: the same two gradients with the passes around them folded in (LinearFn of ppst_amd/autograd.py: the E2 projector chains
-// ran 7 launches per linear and backward): ``relu_in`` -- x is read as max(x, 0) (the linear sits behind nn.ReLU, encoder_col.py:47-93);
-// ``db`` -- the bias gradient bscale * sum_b dY[b][n] from the thread that owns column 0 of row n (dY's rows are read by it anyway).
-__global__ __launch_bounds__(256) void linear_wgrad4_fused_kernel(const float* __restrict__ dy, const float4* __restrict__ x, float4* __restrict__ dw,
-                                                                  float* __restrict__ db, int B, int N, int K4, float scale, float bscale,
-                                                                  int accumulate, int b_accumulate, int relu_in, int64_t total4) {
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total4; t += (int64_t)gridDim.x * 256) {
-    const int k4 = (int)(t % K4), n = (int)(t / K4);
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    float sd = 0.f;
-    for (int b = 0; b < B; ++b) {
-      const float d = dy[(int64_t)b * N + n];
-      float4 v = x[(int64_t)b * K4 + k4];
-      if (relu_in) { v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f; }
-      s.x += d * v.x; s.y += d * v.y; s.z += d * v.z; s.w += d * v.w;
-      sd += d;
-    }
-    float4 o = make_float4(s.x * scale, s.y * scale, s.z * scale, s.w * scale);
-    if (accumulate) { const float4 p = dw[t]; o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w; }
-    dw[t] = o;
-    if (db && k4 == 0) db[n] = b_accumulate ? db[n] + sd * bscale : sd * bscale;
-  }
 }
 extern "C" int ppst_linear_wgrad_fused(const void* dy, const void* x, void* dw, void* db, int B, int N, int K, float scale, float bscale,
                                        int accumulate, int b_accumulate, int relu_in, void* stream) {
@@ -1146,55 +1101,35 @@ extern "C" int ppst_linear_wgrad_fused(const void* dy, const void* x, void* dw, 
   const int64_t total4 = (int64_t)N * K / 4;
   int64_t blocks = cdiv64(total4, 256);
   if (blocks > 8192) blocks = 8192;
-  PPST_LAUNCH(linear_wgrad4_fused_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const float*)dy, (const float4*)x,
+  PPST_LAUNCH(linear_wgrad4_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const float*)dy, (const float4*)x,
               (float4*)dw, (float*)db, B, N, K / 4, scale, bscale, accumulate, b_accumulate, relu_in, total4);
   return PPST_LAUNCH_CHECK();
 }
-// ``gate`` (B x K, optional): dX is multiplied by [gate > 0] in the slice reduction (the backward of the nn.ReLU in front of the linear)
-__global__ __launch_bounds__(256) void linear_dgrad_reduce_gate_kernel(const float* __restrict__ partial, const float* __restrict__ gate,
-                                                                       float* __restrict__ dx, int nsplit, int64_t bk, float scale) {
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < bk; t += (int64_t)gridDim.x * 256) {
-    float s = 0.f;
-    int i = 0;
-    for (; i + 8 <= nsplit; i += 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = partial[(int64_t)(i + u) * bk + t];
-      s += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    }
-    for (; i < nsplit; ++i) s += partial[(int64_t)i * bk + t];
-    dx[t] = gate[t] > 0.f ? s * scale : 0.f;
-  }
+// the partial launches and the slice reduction behind both input-gradient entries (gate null: the plain one)
+static int linear_dgrad_launch(const void* dy, const void* w, void* dx, void* ws, const void* gate, int B, int N, int K, float scale,
+                               void* stream) {
+  const int nsplit = cdiv(N, LDG_ROWS);
+  for (int b0 = 0; b0 < B; b0 += LDG_BMAX)
+    PPST_LAUNCH(linear_dgrad_partial_kernel, dim3(cdiv(K, 256), nsplit), dim3(256), 0, as_stream(stream), (const float*)dy, (const float*)w,
+                (float*)ws, B, N, K, b0);
+  const int64_t bk = (int64_t)B * K;
+  int64_t blocks = cdiv64(bk, 256);
+  if (blocks > 4096) blocks = 4096;
+  PPST_LAUNCH(gate ? linear_dgrad_reduce_kernel<true> : linear_dgrad_reduce_kernel<false>, dim3((unsigned)blocks), dim3(256), 0,
+              as_stream(stream), (const float*)ws, (const float*)gate, (float*)dx, nsplit, bk, scale);
+  return PPST_LAUNCH_CHECK();
 }
 extern "C" int ppst_linear_dgrad_gate(const void* dy, const void* w, void* dx, void* ws, const void* gate, int B, int N, int K, float scale,
                                       void* stream) {
   if (B <= 0 || N <= 0 || K <= 0) return PPST_EINVAL;
   if (!dy || !w || !dx || !ws || !gate) return PPST_ENULL;
-  const int nsplit = cdiv(N, LDG_ROWS);
-  for (int b0 = 0; b0 < B; b0 += LDG_BMAX)
-    PPST_LAUNCH(linear_dgrad_partial_kernel, dim3(cdiv(K, 256), nsplit), dim3(256), 0, as_stream(stream), (const float*)dy, (const float*)w,
-                (float*)ws, B, N, K, b0);
-  const int64_t bk = (int64_t)B * K;
-  int64_t blocks = cdiv64(bk, 256);
-  if (blocks > 4096) blocks = 4096;
-  PPST_LAUNCH(linear_dgrad_reduce_gate_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const float*)ws, (const float*)gate,
-              (float*)dx, nsplit, bk, scale);
-  return PPST_LAUNCH_CHECK();
+  return linear_dgrad_launch(dy, w, dx, ws, gate, B, N, K, scale, stream);
 }
-
 extern "C" int64_t ppst_linear_dgrad_ws(int B, int N, int K) { return (int64_t)cdiv(N, LDG_ROWS) * B * K * (int64_t)sizeof(float); }
 extern "C" int ppst_linear_dgrad(const void* dy, const void* w, void* dx, void* ws, int B, int N, int K, float scale, void* stream) {
   if (B <= 0 || N <= 0 || K <= 0) return PPST_EINVAL;
   if (!dy || !w || !dx || !ws) return PPST_ENULL;
-  const int nsplit = cdiv(N, LDG_ROWS);
-  for (int b0 = 0; b0 < B; b0 += LDG_BMAX)
-    PPST_LAUNCH(linear_dgrad_partial_kernel, dim3(cdiv(K, 256), nsplit), dim3(256), 0, as_stream(stream), (const float*)dy, (const float*)w,
-                (float*)ws, B, N, K, b0);
-  const int64_t bk = (int64_t)B * K;
-  int64_t blocks = cdiv64(bk, 256);
-  if (blocks > 4096) blocks = 4096;
-  PPST_LAUNCH(linear_dgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const float*)ws, (float*)dx, nsplit, bk, scale);
-  return PPST_LAUNCH_CHECK();
+  return linear_dgrad_launch(dy, w, dx, ws, nullptr, B, N, K, scale, stream);
 }
 
 // ------------------------------------------------------------ loss / Adam ----

@@ -1407,11 +1407,25 @@ def _cw_bias_acc(c):
     return bool(c.p.get("bias_acc", c.p.get("acc")))
 
 
-def _cw_eval(c, inp, dt, drop_row=False, dy_scale=None, acc=True, off=None, flip=False, wscale=None, drop_tap=None):
+def wg_first_pass(c):
+    """(H, W, dc) mask of the (pixel, channel) pairs the FIRST pass of the weight-gradient kernels' unit walk reaches
+    (csrc/train.hip, wg_units): a 128-channel n tile with nslab live 32-channel slabs has NQ = 8 nslab channel quads, and the
+    block's threads cover the pixels 0 .. 256 // NQ - 1 of each 2 x 32-pixel tile in one pass"""
+    p = c.p
+    dc = _cw_chan(c)[1]
+    pix = (torch.arange(p["H"])[:, None] % 2) * 32 + torch.arange(p["W"])[None, :] % 32          # index within the tile
+    nslab = torch.tensor([min(4, -(-(dc - n // 128 * 128) // 32)) for n in range(dc)])
+    return pix[:, :, None] < (256 // (8 * nslab))[None, None, :]
+
+
+def _cw_eval(c, inp, dt, drop_row=False, dy_scale=None, acc=True, off=None, flip=False, wscale=None, drop_tap=None, drop_cols=0,
+             csum_first_pass=False):
     p, kind = c.p, _cw_kind(c)
     xc, dc = _cw_chan(c)
     x = _sl(c, inp, "x", C=xc, off=off).to(dt)
     dy = _sl(c, inp, "dy", C=dc).to(dt).clone()
+    if drop_cols:                        # the kernel's dy operand without its last pixel columns (all three kinds)
+        dy[:, :, -drop_cols:] = 0
     scale = p["scale"] if wscale is None else wscale
     w = torch.zeros(p["cout"], p["cin"], p["k"], p["k"], dtype=dt, requires_grad=True)
     if kind == "dgradT":
@@ -1440,7 +1454,7 @@ def _cw_eval(c, inp, dt, drop_row=False, dy_scale=None, acc=True, off=None, flip
         out["dw"] = out["dw"].clone()
         out["dw"][:, :, drop_tap[0], drop_tap[1]] = 0
     if p.get("bias"):
-        out["db"] = dy.sum((0, 1, 2))
+        out["db"] = (dy * wg_first_pass(c).to(dt) if csum_first_pass else dy).sum((0, 1, 2))
         if "db0" in inp and acc and _cw_bias_acc(c):
             out["db"] = out["db"] + inp["db0"].to(dt)
     if "dw0" in inp and acc:
@@ -1448,10 +1462,17 @@ def _cw_eval(c, inp, dt, drop_row=False, dy_scale=None, acc=True, off=None, flip
     return out
 
 
+def _cw_last_cols(c):
+    """pixel columns of the last (ragged) column of 2 x 32-pixel tiles"""
+    return c.p["W"] - (c.p["W"] - 1) // 32 * 32
+
+
 def _cw_mut(c, inp):
     p, kind = c.p, _cw_kind(c)
     f = lambda **kw: _cw_eval(c, inp, torch.float64, **kw)
-    out = [("last image row left out", f(drop_row=True))]
+    out = [("last image row left out", f(drop_row=True)), ("last tile column lost", f(drop_cols=_cw_last_cols(c)))]
+    if _cw_branch(c).endswith("csum"):
+        out.append(("column sums skip the units beyond stride", f(csum_first_pass=True)))
     if not (kind == "dgradT" and p.get("acc")):       # (the blurred kernel's own gradient carries no scale)
         out.append(("weight scale ignored", f(wscale=1.0)))
     if p["k"] == 3:
@@ -1536,6 +1557,66 @@ _case("conv_wgrad", "p0-k3-33x37-splits1", prec=0, k=3, B=2, H=33, W=37, cin=32,
 _case("conv_wgrad", "p0-k3-33x37-splits-many-dyscale-acc", prec=0, k=3, B=2, H=33, W=37, cin=32, cout=64, scale=0.5, splits=10000, dy_scale=0.37, acc=True)
 _case("conv_wgrad", "p0-k3-33x37-dyscale", prec=0, k=3, B=2, H=33, W=37, cin=32, cout=64, scale=0.5, dy_scale=0.37)
 _case("conv_wgrad", "p2-k3-33x37-dyscale-acc", prec=2, k=3, B=2, H=33, W=37, cin=32, cout=64, scale=0.5, dy_scale=0.37, acc=True)
+# three live slabs of dY: NQ = 24 channel quads, stride 240 -- the one unit walk (wg_units) that is no power of two
+_case("conv_wgrad", "p0-k3-9x11-32to96-bias", prec=0, k=3, B=1, H=9, W=11, cin=32, cout=96, scale=0.5, bias=True)
+
+
+# ====================================================================================================== conv_wgrad_p1
+# The two single-pass operand forms of ppst_conv_wgrad_tr2_st (process precision mode 1, ops.set_precision(1)): passes == 1 on
+# fp32-stored operands -> conv_wgrad_tr2_kernel<.., X1 = true, ..>, and bf16-stored operands (st == PPST_ST_BF16: cout and both ld
+# multiples of 8) -> conv_wgrad_tr2b_kernel; the table's chunk lengths pick the instantiation as for three passes (_cw_branch).
+# x and dy are rounded to bfloat16 first: every product is then exact in fp32, and both forms differ from float64 by their fp32
+# accumulation alone -- the bar of the same case at precision 0 (``bar``: _cw_cls).  The GPU test runs a case through both forms:
+# fp32 storage against float64 at that bar, bf16 storage against the fp32-storage result at STORAGE_BAR.
+# ``slabs``: live 32-channel slabs of dY in the last n tile -- 4: conv_wgrad_tr2_kernel's unrolled conversion pass, fewer: its unit
+# walk; conv_wgrad_tr2b_kernel's column sums take the walk at every count.
+STORAGE_BAR = 1e-6            # gpu_diag.t_train_half's: max|bf16-stored - fp32-stored| <= 1e-6 max|fp32-stored|
+
+
+def storage_violations(ref, got):
+    ref, got = np.asarray(ref, np.float64), np.asarray(got, np.float64)
+    err = np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-300)
+    return (["max|a - b| / max|ref| = %.3e > %.0e" % (err, STORAGE_BAR)] if not err <= STORAGE_BAR else []), float(err)
+
+
+def _cp_make(c):
+    inp = _cw_make(c)
+    for k in ("x", "dy"):
+        inp[k] = inp[k].bfloat16().float()
+    return inp
+
+
+def _cp_eval(c, inp, dt, **kw):
+    out = _cw_eval(c, inp, dt, **kw)
+    out.pop("dw3", None)                     # (the blur of dw: not this kernel's)
+    return out
+
+
+def _cp_branch(c):
+    xc, dc = _cw_chan(c)
+    assert _cw_aligned(c) and dc % 8 == 0 and xc % 8 == 0, "bf16 storage: channel counts and strides multiples of 8"
+    kind, kern, bias = _cw_branch(c).split(":")[1:]
+    return "conv_wgrad_p1:%s:%s:slabs%d:%s" % (kind, kern, min(4, -(-(dc % 128 or 128) // 32)), bias)
+
+
+def _cp_mut(c, inp):
+    f = lambda **kw: _cp_eval(c, inp, torch.float64, **kw)
+    out = [("last tile column lost", f(drop_cols=_cw_last_cols(c))), ("last image row left out", f(drop_row=True))]
+    if c.p.get("bias"):
+        out.append(("column sums skip the units beyond stride", f(csum_first_pass=True)))
+    return out
+
+
+OPS["conv_wgrad_p1"] = Spec(_cp_make, _cp_eval, _cp_branch, _cp_mut, _cw_cls)
+# one case per dispatch branch, at the smallest extents with a ragged last tile in both directions and several tiles per block
+_case("conv_wgrad_p1", "k1-17x19-128to64-bias", prec=1, k=1, B=2, H=17, W=19, cin=128, cout=64, scale=0.5, bias=True)
+_case("conv_wgrad_p1", "k1-20x36-64to256-bias", prec=1, k=1, B=2, H=20, W=36, cin=64, cout=256, scale=0.5, bias=True)
+_case("conv_wgrad_p1", "dgradT-17x19-64to32", kind="dgradT", prec=1, k=3, B=2, H=17, W=19, cin=64, cout=32, scale=0.5)
+_case("conv_wgrad_p1", "s2d-33x37-32to64-bias", kind="s2d", prec=1, k=3, B=1, H=33, W=37, cin=32, cout=64, scale=0.5, bias=True)
+# 68 tiles in ONE block: conv_wgrad_tr2b_kernel's two image buffers alternate
+_case("conv_wgrad_p1", "k3-33x37-32to32-bias-splits1", prec=1, k=3, B=2, H=33, W=37, cin=32, cout=32, scale=0.5, bias=True, splits=1)
+_case("conv_wgrad_p1", "k1-9x11-32to32", prec=1, k=1, B=3, H=9, W=11, cin=32, cout=32, scale=0.5)
+_case("conv_wgrad_p1", "k3-9x11-32to96-bias", prec=1, k=3, B=1, H=9, W=11, cin=32, cout=96, scale=0.5, bias=True)
 
 
 # ========================================================================================================= conv_dgrad
@@ -1633,8 +1714,13 @@ FAMILIES = ["bilinear_bwd:gather", "bilinear_bwd:scatter", "pad2d:fwd-float4:bwd
             "conv_wgrad:conv:tr2-one2:csum", "conv_wgrad:conv:tr2-quad:csum", "conv_wgrad:conv:f32-lds:nobias", "conv_wgrad:conv:f32-lds:colsum",
             "conv_wgrad:conv:f32-direct:colsum", "conv_wgrad:s2d:tr2-pair:csum", "conv_wgrad:s2d:tr2-pair:nobias", "conv_wgrad:s2d:f32-lds:colsum",
             "conv_wgrad:s2d:f32-lds:nobias", "conv_wgrad:dgradT:tr2-pair-exact:nobias", "conv_wgrad:dgradT:f32-lds:nobias",
+            # conv_wgrad_p1: the same six instantiations in their single-pass forms (fp32 tiles and bf16 storage), at every count of
+            # live dY slabs
+            "conv_wgrad_p1:conv:tr2-quad:slabs2:csum", "conv_wgrad_p1:conv:tr2-one2:slabs4:csum", "conv_wgrad_p1:dgradT:tr2-pair-exact:slabs2:nobias",
+            "conv_wgrad_p1:s2d:tr2-pair:slabs2:csum", "conv_wgrad_p1:conv:tr2-single-exact:slabs1:csum", "conv_wgrad_p1:conv:tr2-single:slabs1:nobias",
+            "conv_wgrad_p1:conv:tr2-single-exact:slabs3:csum",
             "conv_dgrad:k3:bf16x3", "conv_dgrad:k3:fp32", "conv_dgrad:k1:bf16x3", "conv_dgrad:k1:fp32", "conv_dgrad:four-group:bf16x3",
             "conv_dgrad:four-group:fp32", "conv_dgrad:stack:bf16x3", "conv_dgrad:stack:fp32", "conv_dgrad:entry-stack:bf16x3",
             "conv_dgrad:entry-four-group:bf16x3"]
-# In no case: the half-storage (`_st`) instances of every launcher (held bit-equal to these fp32 forms by gpu_diag.t_train_half)
-# and the lpips entries (tests/test_gpu_lpips.py).
+# In no case: the half-storage (`_st`) instances of every launcher but the weight gradient's (held bit-equal to these fp32 forms by
+# gpu_diag.t_train_half) and the lpips entries (tests/test_gpu_lpips.py).

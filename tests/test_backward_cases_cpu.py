@@ -214,6 +214,35 @@ def test_bar_passes_the_reference_and_rejects_every_seeded_defect(cid):
         assert seen, "the inputs of %s cannot show the defect '%s' at the bar" % (cid, name)
 
 
+@pytest.mark.parametrize("c", _of("conv_wgrad_p1"), ids=lambda c: c.id)
+def test_storage_bar_passes_equal_results_and_rejects_every_seeded_defect(c):
+    """the second comparison of the single-pass weight-gradient test (bf16-stored against fp32-stored operands, C.STORAGE_BAR):
+    the reference passes it against itself, every seeded defect misses it in some output; the case's operands are
+    bfloat16-representable and its table is the one of the issue"""
+    ref = {k: v.astype(np.float32) for k, v in C.reference(c.id).items()}
+    for k, v in ref.items():
+        assert not C.storage_violations(v, v)[0]
+    for name, out in C.mutations(c):
+        assert any(C.storage_violations(ref[k], v.astype(np.float32))[0] for k, v in out.items()), (c.id, name)
+    names = {n for n, _ in C.mutations(c)}
+    assert "last tile column lost" in names and (not c.p.get("bias") or "column sums skip the units beyond stride" in names)
+    inp = C.inputs(c.id)
+    for k in ("x", "dy"):
+        assert torch.equal(inp[k], inp[k].bfloat16().float())
+
+
+def test_single_pass_weight_gradient_table_is_the_issues():
+    got = {(c.p.get("kind", "conv"), c.p["k"], c.p["B"], c.p["H"], c.p["W"], c.p["cin"], c.p["cout"], bool(c.p.get("bias")), c.p.get("splits"))
+           for c in _of("conv_wgrad_p1")}
+    assert got == {("conv", 1, 2, 17, 19, 128, 64, True, None), ("conv", 1, 2, 20, 36, 64, 256, True, None), ("dgradT", 3, 2, 17, 19, 64, 32, False, None),
+                   ("s2d", 3, 1, 33, 37, 32, 64, True, None), ("conv", 3, 2, 33, 37, 32, 32, True, 1), ("conv", 1, 3, 9, 11, 32, 32, False, None),
+                   ("conv", 3, 1, 9, 11, 32, 96, True, None)}
+    # the unit walk that is no power of two (three live slabs: NQ 24, stride 240) is in the fp32-class table as well
+    assert any(C._cw_chan(c)[1] == 96 and C.branch_of(c).endswith("csum") for c in _of("conv_wgrad"))
+    first = C.wg_first_pass(C.by_id("conv_wgrad_p1-k3-9x11-32to96-bias"))         # 256 // 24 = 10 pixels of a tile's first row
+    assert first[0, :10].all() and not first[0, 10:].any() and not first[1].any() and first[2, :10].all()
+
+
 def test_every_op_has_two_kinds_of_defect_and_the_listed_kinds_occur():
     kinds = {}
     for c in C.CASES:

@@ -247,6 +247,30 @@ def _run_conv_wgrad(c, inp, ops):
     return res
 
 
+def _wgrad_p1(c, inp, ops, dtype):
+    """ops.conv_wgrad in precision mode 1 on operands stored as ``dtype`` (the case's values are bfloat16-representable)"""
+    dev, p = _dev(), c.p
+    xc, dc = C._cw_chan(c)
+    prev = ops.PRECISION["value"]
+    ops.set_precision(1)
+    try:
+        plan = ops.ConvPlan(inp["w"].to(dev), p.get("kind", "conv"), scale=p["scale"], precision=1)
+        r = ops.conv_wgrad(plan, _put(c, inp, "x", xc).to(dtype), _put(c, inp, "dy", dc).to(dtype), splits=p.get("splits"),
+                           want_bias=bool(p.get("bias")))
+        torch.cuda.synchronize()
+    finally:
+        ops.set_precision(prev)
+    dw, db = r if isinstance(r, tuple) else (r, None)
+    res = {"dw": dw.view(C._cw_wshape(c))}
+    if p.get("bias"):
+        res["db"] = db
+    return res
+
+
+def _run_conv_wgrad_p1(c, inp, ops):
+    return _wgrad_p1(c, inp, ops, torch.float32)           # single pass on fp32 tiles: the form the float64 table judges
+
+
 class _OneWeightNet:
     """what ops.dgrad_s2d asks of a network: the parameter and its plans"""
 
@@ -308,6 +332,27 @@ def test_against_float64_reference(cid):
         again = _run(c)
         for k in got:
             assert np.array_equal(again[k], got[k]), "%s: two runs differ" % k
+
+
+# ------------------------------------------------------------------------- the weight gradient's two single-pass operand forms
+@pytest.mark.parametrize("cid", [c.id for c in C.CASES if c.op == "conv_wgrad_p1"])
+def test_wgrad_single_pass_forms_against_float64_and_each_other(cid):
+    """precision mode 1 on bfloat16-representable operands: fp32 storage (conv_wgrad_tr2_kernel, one pass on fp32 tiles) against
+    float64 at the case's bar; bf16 storage (conv_wgrad_tr2b_kernel) against the fp32-storage result at C.STORAGE_BAR"""
+    from ppst_amd import ops
+    c, inp = C.by_id(cid), C.inputs(cid)
+    ref = C.reference(cid)
+    f32 = {k: _np(v) for k, v in _wgrad_p1(c, inp, ops, torch.float32).items()}
+    b16 = {k: _np(v) for k, v in _wgrad_p1(c, inp, ops, torch.bfloat16).items()}
+    assert set(f32) == set(b16) == set(ref)
+    fails = []
+    for k in sorted(ref):
+        bad, err = C.judge(c, k, f32[k])
+        bad2, err2 = C.storage_violations(f32[k], b16[k])
+        print("%-58s %-3s fp32-stored vs float64 %.2e (bar %.2e)  bf16-stored vs fp32-stored %.2e (bar %.0e) bit-equal %s  %s"
+              % (cid, k, err, C.bar(c, k), err2, C.STORAGE_BAR, np.array_equal(f32[k], b16[k]), C.branch_of(c)))
+        fails += ["%s fp32-stored: %s" % (k, m) for m in bad] + ["%s bf16-stored: %s" % (k, m) for m in bad2]
+    assert not fails, "%s [%s]: %s" % (cid, C.branch_of(c), "; ".join(fails))
 
 
 # ------------------------------------------------------------------------------------------------------ adjoint identities
