@@ -844,7 +844,8 @@ _case("head_tail", "P2-D1-C8-slices-prelu", B=3, C=8, H=6, W=4, P=2, D=1, act=_P
 
 
 # ============================================================================================================ blur_nhwc
-# launcher (ppst_blur_nhwc_st -> launch_chan<K, K, ST, CV>): CV = 8 for a half tensor with C % 8 == 0 and 3 x 3 taps, else 4;
+# launcher (ppst_blur_nhwc_st -> launch_chan<K, K, ST, CV>): CV = 8 for a half tensor with C % 8 == 0 and 3 x 3 taps, else 4
+# (``off``: x starts that many elements into its buffer -- a half tensor off the 16-byte grid takes CV = 4, its items are 8 bytes);
 # the sliding form for 4 x 4 taps, down == 1, a half tensor and eh >= 192 (eh: out_h, rounded up to even with s2d), else the
 # patch form: templates <DOWN = 1, S2D>, <DOWN = 2>, <DOWN = 1>.  Taps: true convolution (the kernel is flipped).
 def _bk(ks):
@@ -900,7 +901,7 @@ def _bn_eval(c, inp, dt, plain=None, **kw):
 def blur_form(c):
     p = c.p
     st = p.get("st", "f32")
-    cv = 8 if (st != "f32" and p["C"] % 8 == 0 and p["ks"] == 3) else 4
+    cv = 8 if (st != "f32" and p["C"] % 8 == 0 and p["ks"] == 3 and (p.get("off", 0) * 2) % 16 == 0) else 4
     oh, ow = blur_out_hw(p)
     eh = (oh + 1) & ~1 if p.get("s2d") else oh
     slide = p["ks"] == 4 and p.get("down", 1) == 1 and st != "f32" and eh >= 192
@@ -916,7 +917,7 @@ def _bn_branch(c):
 
 def _bn_facets(c):
     p = c.p
-    _, slide, eh, ew = blur_form(c)
+    cv, slide, eh, ew = blur_form(c)
     oh, ow = blur_out_hw(p)
     out = ["blur:pad-%s-%d-%d" % ("reflect" if p.get("mode") else "zero", p["pads"][0], p["pads"][1]), "blur:in_ss-%s" % (p.get("in_ss") or "none"),
            "blur:out_w%%4=%d" % (ow % 4)]
@@ -926,6 +927,8 @@ def _bn_facets(c):
         out.append("blur:s2d:%s-rows-%s-columns" % ("odd" if oh % 2 else "even", "odd" if ow % 2 else "even"))
     if p["H"] < p["ks"] and p["W"] < p["ks"]:
         out.append("blur:input-smaller-than-the-taps")
+    if cv == 4 and p.get("st", "f32") != "f32" and p["C"] % 8 == 0 and p["ks"] == 3:
+        out.append("blur:CV4-by-pointer")
     return out
 
 
@@ -998,6 +1001,9 @@ for _ks in (3, 4):
                        B=2, C=_C, H=_H, W=_W, ks=_ks, st=_st, s2d=_out == "s2d", down=2 if _out == "down2" else 1, **_v)
 _bcase("k3-f16-plain-C4-7x10-zero-p11", B=2, C=4, H=7, W=10, ks=3, st="f16", pads=(1, 1), mode=_Z)
 _bcase("k3-bf16-s2d-C4-7x10-reflect-p21-affine", B=2, C=4, H=7, W=10, ks=3, st="bf16", pads=(2, 1), mode=_R, s2d=True, in_ss="affine")
+# a half tensor 8 bytes into the 16-byte grid: the 4-channel form where the aligned tensor takes the 8-channel one
+for _st in ("bf16", "f16"):
+    _bcase("k3-%s-plain-C8-7x10-zero-p11-off4" % _st, B=2, C=8, H=7, W=10, ks=3, st=_st, pads=(1, 1), mode=_Z, off=4)
 # the sliding form: eh in {192, 198, 209}, about 10 wide, C in {4, 12}
 _bcase("k4-f16-slide-C4-192x10-zero-p21", B=2, C=4, H=192, W=10, ks=4, st="f16", pads=(2, 1), mode=_Z)                                  # 12 full bands
 _bcase("k4-bf16-slide-C12-208x9-reflect-p22-lrelu", B=2, C=12, H=208, W=9, ks=4, st="bf16", pads=(2, 2), mode=_R, in_ss="lrelu")           # 209 x 10 out

@@ -19,7 +19,8 @@ reference).  What is particular here:
               most kh kw products in double, the device may contract them into fused multiply-adds), one rounding of the final
               product for the bias-activation.
   pointers    ``off``: x, y (and ref) start ``off`` elements into their buffers -- off the 16-byte grid the fp32 four-wide forms
-              give way to the generic / scalar kernel.
+              give way to the generic / scalar kernel; a half tensor on the 8-byte grid but off the 16-byte one keeps its four-wide
+              form (its items are 8 bytes).
   inputs      taps are random with mixed sign (asymmetric under a flip and under a transposition); mode 30 keeps |x + b| >= 1e-3,
               mode 31 draws ``ref`` independently of x (about half of the signs disagree) with |ref| >= 1e-3.
 
@@ -167,6 +168,8 @@ def _uf_facets(c):
         out.append("pad:px!=py")
     if p["M"] == 1:
         out.append("major=1")
+    if p["st"] in ("f16", "bf16") and not _aligned(p, 16):
+        out.append("half:on-8-off-16-byte-grid")
     if form.startswith("generic"):
         if kh != kw:
             out.append("generic:kh!=kw")
@@ -293,6 +296,10 @@ for _st in ("f32", "f16", "bf16"):
             _n += 1
 _uf("chan-k4-plain-f32-C4-192x6-p21", H=192, W=6, C=4, k=(4, 4), pads=(2, 1, 2, 1))            # fp32 never slides
 _uf("chan-k4-plain-f16-C4-191x6-p21", st="f16", M=1, H=191, W=6, C=4, k=(4, 4), pads=(2, 1, 2, 1))   # one row below the threshold
+# half tensors on the 8-byte grid, off the 16-byte one: the same forms (an fp32 tensor there goes to the generic kernel)
+_uf("chan-k3-plain-bf16-C8-7x10-p1111-off4", st="bf16", H=7, W=10, C=8, pads=(1, 1, 1, 1), off=4)
+_uf("chan-k4-down2-f16-C4-9x6-p1111-off4", st="f16", H=9, W=6, C=4, k=(4, 4), down=(2, 2), pads=(1, 1, 1, 1), off=4)
+_uf("up2-k4-bf16-C4-4x6-p2121-off4", st="bf16", H=4, W=6, C=4, k=(4, 4), up=(2, 2), pads=(2, 1, 2, 1), off=4)
 # the sliding form reached through ppst_upfirdn2d: 4 x 4 taps, half storage, >= 192 output rows
 _uf("slide-k4-f16-C4-192x6-p21", st="f16", H=192, W=6, C=4, k=(4, 4), pads=(2, 1, 2, 1))       # 12 full bands
 _uf("slide-k4-bf16-C8-205x5-p12", st="bf16", H=205, W=5, C=8, k=(4, 4), pads=(1, 2, 1, 2))      # 205 rows: the last band has 13

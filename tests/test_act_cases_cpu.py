@@ -25,8 +25,7 @@ import act_cases as C  # noqa: E402
 IDS = [c.id for c in C.CASES]
 BIG = 1 << 18            # pixels from which a case counts as one of the four chunk-size cases
 
-# every form a launcher of these ops can pick (its ``if``s, both sides; the 8-channel 4 x 4 blur exists only under an environment
-# switch the library reads once and is not in the table) ...
+# every form a launcher of these ops can pick (its ``if``s, both sides; there is no 8-channel 4 x 4 blur) ...
 FORMS = {
     "affine_act:V1:f32>f32", "affine_act:V4:bf16>bf16", "affine_act:V4:bf16>f32", "affine_act:V4:f16>f16",
     "affine_act:V4:f16>f32", "affine_act:V4:f32>bf16", "affine_act:V4:f32>f16", "affine_act:V4:f32>f32",
@@ -54,7 +53,7 @@ FORMS = {
 FACETS = {
     "affine_act_stats:rep_pad", "affine_act_stats:vec4:masked-lanes", "bilinear:down-fractional", "bilinear:down-integer",
     "bilinear:identity", "bilinear:up-by-2", "bilinear:up-by-4", "bilinear:up-by-8", "bilinear:up-fractional",
-    "blur:in_ss-affine", "blur:in_ss-lrelu", "blur:in_ss-none", "blur:input-smaller-than-the-taps", "blur:out_w%4=0",
+    "blur:CV4-by-pointer", "blur:in_ss-affine", "blur:in_ss-lrelu", "blur:in_ss-none", "blur:input-smaller-than-the-taps", "blur:out_w%4=0",
     "blur:out_w%4=1", "blur:out_w%4=2", "blur:out_w%4=3", "blur:pad-reflect-1-1", "blur:pad-reflect-2-1",
     "blur:pad-reflect-2-2", "blur:pad-zero-1-0", "blur:pad-zero-1-1", "blur:pad-zero-2-1", "blur:pad-zero-2-2",
     "blur:s2d:even-rows-odd-columns", "blur:s2d:odd-rows-even-columns", "blur:s2d:odd-rows-odd-columns",
@@ -341,6 +340,10 @@ def test_the_table_of_the_issue_is_present():
     assert {C.blur_form(c)[2] for c in sl} == {192, 198, 209} and {c.p["C"] for c in sl} == {4, 12}
     assert {(bool(c.p.get("s2d")), c.p.get("mode", 0), bool(c.p.get("in_ss"))) for c in sl} >= {(True, 0, True), (True, 1, False), (False, 0, False), (False, 1, True)}
     assert {c.p["pads"] for c in _of("blur_nhwc")} == {(1, 1), (2, 1), (2, 2), (1, 0)}
+    off4 = [c for c in _of("blur_nhwc") if c.p.get("off")]
+    assert {(c.p["st"], c.p["off"], c.p["B"], c.p["H"], c.p["W"], c.p["C"], c.p["ks"], c.p["pads"]) for c in off4} == {(s, 4, 2, 7, 10, 8, 3, (1, 1)) for s in ("bf16", "f16")}
+    assert {C.branch_of(c) for c in off4} == {"blur:k3:%s:CV4:patch:plain" % s for s in ("bf16", "f16")}
+    assert all(C.blur_form(c._replace(p=dict(c.p, off=0)))[0] == 8 for c in off4), "on the 16-byte grid the same tensor takes 8 channels"
     assert {c.p["cin"] for c in _of("conv1x1_small_cin")} == {1, 2, 3, 4} and {c.p["cout"] for c in _of("conv1x1_small_cin")} == {4, 32, 36}
     assert {c.p["cout"] for c in _of("conv1x1_small_cout")} == {1, 2, 3, 4}
     assert any(c.p["cout"] == 3 and c.p["npix"] % 8 for c in _of("conv1x1_small_cout"))

@@ -1,5 +1,5 @@
 """No GPU: the references, the inputs and the bars of tests/test_gpu_fir.py are proven here before the device is trusted by them
-(tests/fir_cases.py): 105 cases (71 of ppst_upfirdn2d, 34 of ppst_fused_bias_act), 34 launch forms (27 + 7), 53 facets, 22 kinds
+(tests/fir_cases.py): 108 cases (74 of ppst_upfirdn2d, 34 of ppst_fused_bias_act), 34 launch forms (27 + 7), 54 facets, 22 kinds
 of seeded defect (13 + 9).
   * ``upfirdn_ref`` equals the oracle's upfirdn2d_full on every case, its output-side twin ``upfirdn_gather`` equals it on every
     small case, and both references reproduce the stored outputs of tests/golden/ops.npz and ops_f64.npz at the bars of
@@ -39,7 +39,7 @@ FACETS = {
     "generic:second-trip", "pad:pad0<0", "pad:pad1<0", "pad:both<0", "pad:px!=py", "planes:one-tile", "planes:32x64-exact",
     "planes:33x65-seams", "planes:seams", "planes:1x1-out", "planes:input-smaller-than-the-taps", "up2:odd-in", "up2:even-in",
     "up2:adjoint-k3-p10", "up2:adjoint-k4-p11", "up2:adjoint-k4-p21", "up2:adjoint-k4-p22", "up2:second-trip", "major=1",
-    "slide:last-band-partial", "slide:last-band-full",
+    "slide:last-band-partial", "slide:last-band-full", "half:on-8-off-16-byte-grid",
     "fba:mode-30", "fba:mode-31", "fba:mode-32", "fba:mode-10", "fba:mode-11", "fba:mode-12", "fba:no-bias", "fba:step_b%4==0", "fba:step_b-35",
     "fba:2-D", "fba:scalar-by-n", "fba:scalar-by-step_b", "fba:scalar-by-pointer", "fba:alpha-0", "fba:alpha-0.2", "fba:alpha-1.5", "fba:scale!=1",
     "fba:vec:second-trip", "fba:scalar:second-trip",
@@ -213,9 +213,9 @@ def test_every_form_and_every_facet_has_a_case():
 
 
 def test_the_counts_of_the_module_docstring():
-    assert (len(C.CASES), len(_of("upfirdn2d")), len(_of("fba"))) == (105, 71, 34)
+    assert (len(C.CASES), len(_of("upfirdn2d")), len(_of("fba"))) == (108, 74, 34)
     assert len({f for f in FORMS if not f.startswith("fba")}) == 27 and len({f for f in FORMS if f.startswith("fba")}) == 7
-    assert len(FACETS) == 53
+    assert len(FACETS) == 54
     assert (len(DEFECTS["upfirdn2d"]), len(DEFECTS["fba"])) == (13, 9)
 
 
@@ -228,6 +228,9 @@ def test_the_table_of_the_issue_is_present():
     # each reason for the scalar form of fused_bias_act is the only reason of some case; alpha 0, 0.2, 1.5; a scale that is not 1
     assert {tuple(C.fba_reasons(c.p)) for c in fb if c.p["st"] != "f64"} >= {(), ("n",), ("step_b",), ("pointer",)}
     assert {c.p["alpha"] for c in fb} == {0.0, 0.2, 1.5} and any(c.p["scale"] < 0 for c in fb)
+    # half tensors 8 bytes into the 16-byte grid (M = 2) keep the four-wide form of their geometry
+    off4 = {C.branch_of(c) for c in uf if "half:on-8-off-16-byte-grid" in C.facets_of(c) and c.p["off"] == 4 and c.p["M"] == 2}
+    assert off4 == {"chan:k3:plain:bf16", "chan:k4:down2:f16", "up2_chan:bf16"}
     # the generic kernel on half storage: minor > 1, kh != kw, up_x != up_y, down = 3
     for st in ("f16", "bf16"):
         gen = [c for c in uf if C.branch_of(c) == "generic:" + st]

@@ -164,7 +164,10 @@ def _run_head_tail(c, inp, ops, widen):
 
 def _run_blur_nhwc(c, inp, ops, widen):
     p = c.p
-    y, hw = ops.blur_nhwc(_put(c, inp, "x", st=_st(c, "st", widen)), inp["k"].to(_dev()), p["pads"][0], p["pads"][1], p.get("mode", 0), p.get("down", 1),
+    x = _put(c, inp, "x", st=_st(c, "st", widen))
+    if p.get("off"):                                   # the tensor starts ``off`` elements into its buffer
+        x = torch.empty(x.numel() + p["off"], device=_dev(), dtype=x.dtype)[p["off"]:].view(x.shape).copy_(x)
+    y, hw = ops.blur_nhwc(x, inp["k"].to(_dev()), p["pads"][0], p["pads"][1], p.get("mode", 0), p.get("down", 1),
                           bool(p.get("s2d")), _opt(inp, "ss"), C.ACT_LRELU if p.get("in_ss") == "lrelu" else C.ACT_NONE)
     assert tuple(hw) == C.blur_out_hw(p)
     return {"y": y}
