@@ -161,7 +161,7 @@ def build(kind, cout, cin, k):
     """the record of one (kind, weight shape): ``cout, cin, k`` are the FORWARD weight's (Cout, Cin, k)"""
     if kind not in KINDS:
         raise ValueError(kind)
-    assert cin % 32 == 0, "fused conv needs Cin % 32 == 0 (got %d)" % cin
+    assert cin % 32 == 0, "fused conv needs Cin %% 32 == 0 (got %d)" % cin
     t = KINDS[kind](cout, cin, k)
     r = types.SimpleNamespace(kind=kind, cout=t.cout, cin=t.cin, k=k, bn=128 if t.cout >= 128 else 64, n_groups=t.n_groups,
                               halo=t.halo, wstrides=t.wstrides, wsource=t.wsource, src=t.src)

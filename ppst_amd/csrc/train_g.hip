@@ -609,10 +609,10 @@ extern "C" int ppst_gap_gmp_bwd_st(const void* x, const void* mask, const void* 
   if (!x || !v || !g || !dx || !arg_ws) return PPST_ENULL;
   const int64_t total = (int64_t)B * hw * C;
   if (total > PPST_IDX32_MAX) return PPST_EINVAL;
+  if (st && (C % 4 || ld % 4 || hw % GMP_NP || ((uintptr_t)x | (uintptr_t)dx) % 8 || ((uintptr_t)v | (uintptr_t)g | (uintptr_t)arg_ws) % 16))
+    return PPST_EINVAL;          // half storage: the strip form only (refused before anything is written: arg_ws too)
   hipError_t e = hipMemsetAsync(arg_ws, 0x7f, (size_t)B * C * sizeof(int), as_stream(stream));   // 0x7f7f7f7f: above any pixel index
   if (e != hipSuccess) return (int)e;
-  if (st && (C % 4 || ld % 4 || hw % GMP_NP || ((uintptr_t)x | (uintptr_t)dx) % 8 || ((uintptr_t)v | (uintptr_t)g | (uintptr_t)arg_ws) % 16))
-    return PPST_EINVAL;          // half storage: the strip form only
   if (four_wide_ok(st, {C, ld}, {x, dx}, {v, g, arg_ws})) {
     const int64_t t4 = total / 4;
     if (hw % GMP_NP == 0) {

@@ -29,16 +29,13 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from bwd_cases import (BAR_EW, BAR_MOVE, Case, Spec, _gen, _mask_vals, _nchw, _nhwc, _pad_fwd, _randn, _s2d_stack, _sl,  # noqa: F401
-                       _sum_bar, _vec_ok, _wide, _zero_tail, compare)
+from bwd_cases import (BAR_EW, BAR_MOVE, DTYPE, HALF, PBITS, Case, Spec, _gen, _mask_vals, _nchw, _nhwc, _pad_fwd, _randn,  # noqa: F401
+                       _s2d_stack, _sl, _store, _sum_bar, _vec_ok, _wide, _zero_tail, compare, compare_half, half_allowed)
 
 ACT_NONE, ACT_LRELU, ACT_PRELU = 0, 1, 2           # ops.ACT_*
 SQRT2 = 1.41421356237309515
 GROUP_MAX = 32                                      # PPST_GROUP_MAX
 UF_SLIDE = 16                                       # csrc/upfirdn2d.hip
-HALF = {"f16": torch.float16, "bf16": torch.bfloat16}
-PBITS = {"f16": 11, "bf16": 8}
-DTYPE = dict(HALF, f32=torch.float32)
 
 OPS = {}
 CASES = []
@@ -52,11 +49,6 @@ def _case(op, cid, seed=0, **p):
 
 def cdiv(a, b):
     return (a + b - 1) // b
-
-
-def _store(t, st):
-    """the float32 tensor holding what a tensor of storage type st holds (one round to nearest)"""
-    return t if st == "f32" else t.to(HALF[st]).float()
 
 
 def _act(t, act, slope=0.0):
@@ -1302,23 +1294,6 @@ def bar(c, name):
     if cls == 0:
         return 0.0
     return max(cls, 4.0 * err32(c.id)[name])
-
-
-def half_allowed(ref, b, s, st):
-    """the error a half-stored output may carry: one round to nearest of a value within b s of ref"""
-    return b * s + 2.0 ** -PBITS[st] * (np.abs(ref) + b * s)
-
-
-def compare_half(ref, got, b, st, scale=None):
-    """-> (violations, err): ``compare`` for an output stored in st; err in units of the allowed error (<= 1 passes)"""
-    ref, got = np.asarray(ref, np.float64), np.asarray(got, np.float64)
-    assert ref.shape == got.shape, (ref.shape, got.shape)
-    if not np.isfinite(got).all():
-        return ["%d non-finite values" % (~np.isfinite(got)).sum()], float("inf")
-    s = np.abs(ref).max() if scale is None else scale
-    ratio = np.abs(got - ref) / half_allowed(ref, b, s, st)
-    bad = ratio > 1.0
-    return (["%d values outside b s + 2^-%d (|ref| + b s), worst %.2f x" % (bad.sum(), PBITS[st], ratio.max())] if bad.any() else []), float(ratio.max())
 
 
 def as_stored(c, name, arr):

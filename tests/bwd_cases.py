@@ -24,6 +24,17 @@ on the border rows and columns alone with THEIR max|ref| as the scale, so that a
 Decisions (arg-max, gates, ReLU) are taken from the float32 operands handed to the kernel, never from a rounded intermediate;
 tie inputs are quantised so that the products m * x are exact and tie exactly; gate inputs keep |value| >= 1e-3.  No element is
 left out of any comparison.
+
+Storage (the convention tests/act_cases.py shares): ``st`` in a case's p names the storage type of the operands its launcher types
+(``TYPED``: f32 -- the default --, f16, bf16); every other operand, every statistic and every parameter gradient is float32.
+``make`` returns float32 tensors that hold exactly the stored values (rounded once), and whatever derives from a stored operand
+(the forward maximum, mean / rstd, the ties) is computed after the rounding: the float64 reference reads what the kernel reads.
+``OUT_ST`` names the half-stored outputs; one is judged element by element with the allowed error b s + 2^-p (|ref| + b s): one
+round to nearest (p = 11 fp16, 8 bf16) of a value within the case's bar b of the reference, s = max|ref|.  An fp32 output of a half
+case keeps the bar of the text above, data movement stays bit equal to the stored values.  The half launchers take the four-channel
+forms only; ``same_form_as_f32`` says whether the fp32 launch of the same (widened) operands takes the same kernel form -- where it
+does the GPU test also asks for bit equality with that launch, rounded once.  ``mutations`` adds to a half case the defects only a
+half kernel can have: a half output stored by truncation, the operands read as the other half type.
 """
 import collections
 import functools
@@ -38,6 +49,17 @@ BAR_MOVE, BAR_EW, BAR_SUM = 0.0, 2e-6, 1e-5     # data movement / fp32 elementwi
 
 def _sum_bar(terms):
     return BAR_SUM if terms >= 4096 else BAR_EW
+
+HALF = {"f16": torch.float16, "bf16": torch.bfloat16}
+PBITS = {"f16": 11, "bf16": 8}
+DTYPE = dict(HALF, f32=torch.float32)
+# op -> the operands its launcher types (stored as the case's ``st``; on the device they travel as HALF[st])
+TYPED = {"bilinear_bwd": ("dy", "x"), "pad2d": ("x", "dy"), "gap_gmp_bwd": ("x", "out0"), "gap_gmp_multi_bwd": ("x", "out0"), "colsum": ("x",),
+         "noise_wgrad": ("dpre",), "wgrad_small_cin": ("dy",), "in_bwd": ("g", "y", "gate"), "space_to_depth": ("x",), "conv_dgrad": ("g",)}
+# op -> the outputs that take the storage type of the case (every sum and parameter gradient stays float32)
+OUT_ST = {"bilinear_bwd": ("dx",), "pad2d": ("y", "dx"), "gap_gmp_bwd": ("dx",), "gap_gmp_multi_bwd": ("dx",), "in_bwd": ("dx",),
+          "space_to_depth": ("s", "back")}
+# (conv_dgrad's dx is bf16-stored as well, but the bar the conv tests hold precision mode 1 to already covers that rounding: plain ``compare``)
 
 Case = collections.namedtuple("Case", "op id p seed")
 Spec = collections.namedtuple("Spec", "make ref branch mutations cls")
@@ -58,8 +80,21 @@ def _randn(g, *shape):
     return torch.randn(*shape, generator=g, dtype=torch.float32)
 
 
+def st_of(c):
+    return c.p.get("st", "f32")
+
+
+def _store(t, st):
+    """the float32 tensor holding what a tensor of storage type st holds (one round to nearest)"""
+    return t if st == "f32" else t.to(HALF[st]).float()
+
+
+def out_st(c, name):
+    return st_of(c) if name in OUT_ST.get(c.op, ()) else "f32"
+
+
 def _away(t, lo=1e-3):
-    """push values off a decision boundary at 0: |t| >= lo (sign kept)"""
+    """push values off a decision boundary at 0: |t| >= lo (sign kept; half-stored operands: lo = 2^-9, which every type holds)"""
     return torch.where(t.abs() < lo, torch.where(t < 0, -lo, lo).to(t.dtype), t)
 
 
@@ -126,18 +161,47 @@ def compare(ref, got, bar, scale=None):
     return out, err
 
 
+def half_allowed(ref, b, s, st):
+    """the error a half-stored output may carry: one round to nearest of a value within b s of ref"""
+    return b * s + 2.0 ** -PBITS[st] * (np.abs(ref) + b * s)
+
+
+def compare_half(ref, got, b, st, scale=None):
+    """-> (violations, err): ``compare`` for an output stored in st; err in units of the allowed error (<= 1 passes)"""
+    ref, got = np.asarray(ref, np.float64), np.asarray(got, np.float64)
+    assert ref.shape == got.shape, (ref.shape, got.shape)
+    if not np.isfinite(got).all():
+        return ["%d non-finite values" % (~np.isfinite(got)).sum()], float("inf")
+    s = np.abs(ref).max() if scale is None else scale
+    d, lim = np.abs(got - ref), half_allowed(ref, b, s, st)
+    ratio = np.where(d > 0, d / np.where(lim > 0, lim, 1e-300), 0.0)       # (an all-zero reference allows nothing but zeros)
+    bad = ratio > 1.0
+    return (["%d values outside b s + 2^-%d (|ref| + b s), worst %.2f x" % (bad.sum(), PBITS[st], ratio.max())] if bad.any() else []), float(ratio.max())
+
+
+def as_stored(c, name, arr):
+    """a float64 result as the output tensor would hold it: rounded once to the output's storage type"""
+    return torch.from_numpy(np.asarray(arr, np.float64)).to(DTYPE[out_st(c, name)]).double().numpy()
+
+
 BORDER_OPS = ("bilinear_bwd", "pad2d", "avgpool_bwd")
 
 
 def judge(c, out_name, got):
-    """-> (violations, err) of one output of a case against its float64 reference, at the case's bar"""
-    ref, b = reference(c.id)[out_name], bar(c, out_name)
-    bad, err = compare(ref, got, b, scale_of(c, out_name))
+    """-> (violations, err) of one output of a case against its float64 reference, at the case's bar.  A half-stored output: the
+    half rule (err in units of the allowed error); data movement: bit equality; the rest: ``compare``."""
+    ref, b, st = reference(c.id)[out_name], bar(c, out_name), out_st(c, out_name)
+    got = np.asarray(got, np.float64)
+    if b == 0 or st == "f32":
+        cmp_ = lambda r, g, s=None: compare(r, g, b, s)
+    else:
+        cmp_ = lambda r, g, s=None: compare_half(r, g, b, st, s)
+    bad, err = cmp_(ref, got, scale_of(c, out_name))
     if c.op in BORDER_OPS and ref.ndim == 4:
         edge = np.zeros(ref.shape[1:3], bool)
         edge[[0, -1], :] = True
         edge[:, [0, -1]] = True
-        bad2, err2 = compare(ref[:, edge], np.asarray(got)[:, edge], b)
+        bad2, err2 = cmp_(ref[:, edge], got[:, edge])
         bad += ["border: " + m for m in bad2]
         err = max(err, err2)
     return bad, err
@@ -186,9 +250,78 @@ def branch_of(c):
     return OPS[c.op].branch(c)
 
 
+def truncated(arr, st):
+    """float64 values stored in st by truncation (round toward zero) instead of round to nearest"""
+    t = np.asarray(arr, np.float64).astype(np.float32)
+    if st == "bf16":
+        return (t.view(np.uint32) & np.uint32(0xffff0000)).view(np.float32).astype(np.float64)
+    h = t.astype(np.float16)
+    over = np.abs(h.astype(np.float32)) > np.abs(t)           # rounded away from zero: one step back
+    bits = h.view(np.uint16).copy()
+    bits[over] -= 1
+    return bits.view(np.float16).astype(np.float64)
+
+
+def as_other_half(t, st):
+    """the stored values of t, their 16 bits read as the other half type"""
+    other = torch.bfloat16 if st == "f16" else torch.float16
+    return t.to(HALF[st]).view(torch.int16).view(other).float()
+
+
+def _half_mutations(c, inp):
+    """the defects only a half kernel can have, on top of the op's own: a half output stored by truncation (every half-stored
+    output that is computed, not copied) and the typed operands read as the other half type (where the kernel computes with them:
+    a copy moves the same bits whatever it calls them)"""
+    st, out = st_of(c), []
+    ref = reference(c.id)
+    cut = {k: torch.from_numpy(truncated(v, st)) for k, v in ref.items() if out_st(c, k) != "f32" and bar(c, k) != 0}
+    # (an output whose every value the type holds exactly -- the x8 reduction's 0.25 dy -- is stored alike by either rounding: no defect)
+    cut = {k: v for k, v in cut.items() if not np.array_equal(v.numpy(), as_stored(c, k, ref[k]))}
+    if cut:
+        out.append(("half output stored by truncation", cut))
+    computes = any(bar(c, k) != 0 for k in ref)
+    if computes and c.op not in ("gap_gmp_bwd", "gap_gmp_multi_bwd"):        # (those seed it themselves: the match with the forward's maximum)
+        i2 = dict(inp)
+        for k in TYPED[c.op]:
+            if k in inp and k != "out0" and not (c.op == "bilinear_bwd" and k == "x"):
+                i2[k] = as_other_half(inp[k], st)
+        r = OPS[c.op].ref(c, i2, torch.float64)
+        out.append(("operands read as the other half type", {k: v for k, v in r.items() if bar(c, k) != 0}))
+    return out
+
+
 def mutations(c):
     with torch.enable_grad():
-        return [(n, {k: v.detach().numpy() for k, v in o.items()}) for n, o in OPS[c.op].mutations(c, inputs(c.id))]
+        inp = inputs(c.id)
+        muts = list(OPS[c.op].mutations(c, inp))
+        if st_of(c) != "f32":
+            muts += _half_mutations(c, inp)
+        return [(n, {k: v.detach().numpy() for k, v in o.items()}) for n, o in muts]
+
+
+def as_f32(c):
+    """the fp32 twin of a half case: the same operands (the stored values, widened), fp32 storage"""
+    return c._replace(p=dict(c.p, st="f32"))
+
+
+def same_form_as_f32(c):
+    """does the fp32 launch on the widened operands take the kernel form of the half launch?  The half launchers take the
+    four-channel forms only, and every half case's shapes send fp32 there too -- but for noise_wgrad, whose fp32 launcher keeps the
+    scalar kernel where C / 4 < 256 does not divide 256, and ops.dgrad_s2d, whose stack form needs cin % 8 of a half gradient (and
+    the convs round their operands inside the kernel: their storage forms are compared by the conv tests, not here)."""
+    assert st_of(c) != "f32"
+    if c.op == "conv_dgrad":
+        return False
+    twin = branch_of(as_f32(c))
+    if c.op == "noise_wgrad":
+        return twin == "noise_wgrad:four"
+    assert not any(w in twin for w in ("scalar", "scatter", "float:", ":4e")), (c.id, twin)
+    return True
+
+
+def _fam(name, c):
+    """the family name of a launcher's branch: the half instances are families of their own"""
+    return name if st_of(c) == "f32" else "%s:%s" % (name, st_of(c))
 
 
 # ======================================================================================================== bilinear_bwd
@@ -196,7 +329,7 @@ def mutations(c):
 def _bil_make(c):
     g = _gen(c)
     p = c.p
-    return {"dy": _wide(c, g, "dy", p["B"], p["OH"], p["OW"]), "x": _randn(g, p["B"], p["H"], p["W"], p["C"])}
+    return {"dy": _store(_wide(c, g, "dy", p["B"], p["OH"], p["OW"]), st_of(c)), "x": _store(_randn(g, p["B"], p["H"], p["W"], p["C"]), st_of(c))}
 
 
 def _bil_bwd(dy, H, W, dt):
@@ -212,7 +345,7 @@ def _bil_ref(c, inp, dt):
 
 
 def _bil_branch(c):
-    return "bilinear_bwd:gather" if _vec_ok(c, c.p["C"], "dy") else "bilinear_bwd:scatter"
+    return _fam("bilinear_bwd:gather" if _vec_ok(c, c.p["C"], "dy") else "bilinear_bwd:scatter", c)
 
 
 def _bil_mut(c, inp):
@@ -242,6 +375,13 @@ for _C in (3, 6):
 _case("bilinear_bwd", "C8-slice-ld16-off4", B=3, C=8, H=5, W=7, OH=12, OW=9, dy_ld=16, dy_off=4)
 _case("bilinear_bwd", "C8-slice-ld14-off4", B=3, C=8, H=12, W=9, OH=5, OW=7, dy_ld=14, dy_off=4)      # ld % 4 != 0 -> scatter
 _case("bilinear_bwd", "C8-slice-ld16-off2", B=1, C=8, H=5, W=7, OH=12, OW=9, dy_ld=16, dy_off=2)      # pointer off the 16-byte grid
+# half storage (bilinear_bwd_gather_kernel<ST>; the scatter form is fp32 only): up, down, the x8 reduction, and a slice whose start
+# (4 halves) is 8-byte but not 16-byte aligned
+for _st in ("f16", "bf16"):
+    _case("bilinear_bwd", "%s-C8-5x7-to-12x9" % _st, st=_st, B=3, C=8, H=5, W=7, OH=12, OW=9)
+    _case("bilinear_bwd", "%s-C8-12x9-to-5x7" % _st, st=_st, B=1, C=8, H=12, W=9, OH=5, OW=7)
+    _case("bilinear_bwd", "%s-C4-64x64-to-8x8" % _st, st=_st, B=1, C=4, H=64, W=64, OH=8, OW=8)
+    _case("bilinear_bwd", "%s-C8-slice-ld16-off4" % _st, st=_st, B=3, C=8, H=5, W=7, OH=12, OW=9, dy_ld=16, dy_off=4)
 
 
 # ================================================================================================== pad2d, pad2d_bwd
@@ -286,7 +426,8 @@ def _pad_make(c):
     g = _gen(c)
     p = c.p
     py0, py1, px0, px1 = p["pads"]
-    return {"x": _wide(c, g, "x", p["B"], p["H"], p["W"]), "dy": _randn(g, p["B"], p["H"] + py0 + py1, p["W"] + px0 + px1, p["C"])}
+    return {"x": _store(_wide(c, g, "x", p["B"], p["H"], p["W"]), st_of(c)),
+            "dy": _store(_randn(g, p["B"], p["H"] + py0 + py1, p["W"] + px0 + px1, p["C"]), st_of(c))}
 
 
 def _pad_ref(c, inp, dt):
@@ -296,6 +437,9 @@ def _pad_ref(c, inp, dt):
 
 def _pad_branch(c):
     # two launchers: the forward looks at C, x_ld and the pointers; the backward (dy and dx dense) at C alone
+    if st_of(c) != "f32":        # half: four channels as one 8-byte item (pad2d_kernel<uint2>) and pad2d_bwd_kernel<4, ST>, or refused
+        assert _vec_ok(c, c.p["C"], "x")
+        return _fam("pad2d:fwd-uint2:bwd-float4", c)
     return "pad2d:fwd-%s:bwd-%s" % ("float4" if _vec_ok(c, c.p["C"], "x") else "float", "float4" if c.p["C"] % 4 == 0 else "float")
 
 
@@ -337,6 +481,14 @@ _case("pad2d", "reflect-C8-largest", B=1, C=8, H=5, W=4, pads=(4, 3, 3, 2), mode
 _case("pad2d", "reflect-C3-largest", B=2, C=3, H=5, W=4, pads=(4, 3, 3, 2), mode=1)
 _case("pad2d", "replicate-C8-slice-ld16-off4", B=2, C=8, H=6, W=9, pads=(2, 1, 0, 3), mode=2, x_ld=16, x_off=4)
 _case("pad2d", "reflect-C8-slice-ld14-off4", B=2, C=8, H=6, W=9, pads=(2, 1, 0, 3), mode=1, x_ld=14, x_off=4)
+# half storage: the forward's third instantiation (uint2 items) and pad2d_bwd_kernel<4, ST>
+for _st in ("f16", "bf16"):
+    for _m, _mn in ((0, "zero"), (1, "reflect"), (2, "replicate")):
+        _case("pad2d", "%s-%s-C8-asym" % (_st, _mn), st=_st, B=2, C=8, H=6, W=9, pads=(2, 1, 0, 3), mode=_m)
+        _case("pad2d", "%s-%s-C8-crop" % (_st, _mn), st=_st, B=1, C=8, H=7, W=8, pads=(-2, 1, 2, -3), mode=_m)
+        _case("pad2d", "%s-%s-C8-H2" % (_st, _mn), st=_st, B=2, C=8, H=2, W=5, pads=(1, 1, 2, 1), mode=_m)
+    _case("pad2d", "%s-reflect-C8-largest" % _st, st=_st, B=1, C=8, H=5, W=4, pads=(4, 3, 3, 2), mode=1)
+    _case("pad2d", "%s-replicate-C8-slice-ld16-off4" % _st, st=_st, B=2, C=8, H=6, W=9, pads=(2, 1, 0, 3), mode=2, x_ld=16, x_off=4)
 
 
 # ======================================================================================================== avgpool_bwd
@@ -378,13 +530,14 @@ _case("avgpool_bwd", "f2-C8-slice-ld13-off5", B=2, C=8, oh=5, ow=7, f=2, dy_ld=1
 # ================================================================================== gap_gmp_bwd, gap_gmp_multi_bwd
 # launcher (ppst_gap_gmp_bwd_st, fp32): C % 4 == 0 and ld % 4 == 0 and 16-byte pointers -> (hw % 16 == 0 ? the strip kernel :
 # gmp_argmax_kernel<4>) + gap_gmp_bwd_kernel<4>, else the <1> pair.  ppst_gap_gmp_multi_bwd: the strip form only (refuses everything else).
-def _quant(g, kind, *shape):
-    """float32 values on a 0.5 grid in [-2, 2] ('quant'), or that with constant 4 x 4 plateaus ('plateau'): ties in most channels"""
+def _quant(g, kind, *shape, top=4):
+    """float32 values on a 0.5 grid in [-top / 2, top / 2] ('quant'), or that with constant 4 x 4 plateaus ('plateau'): ties in most
+    channels.  (The half cases take top = 3: 2.0 is 0x4000 in fp16 AND in bfloat16, so a maximum of 2.0 could not tell the types apart.)"""
     B, H, W, C = shape
     if kind == "plateau":
-        small = torch.round(_randn(g, B, (H + 3) // 4, (W + 3) // 4, C) * 2).clamp(-4, 4) / 2
+        small = torch.round(_randn(g, B, (H + 3) // 4, (W + 3) // 4, C) * 2).clamp(-top, top) / 2
         return small.repeat_interleave(4, 1).repeat_interleave(4, 2)[:, :H, :W].contiguous()
-    return torch.round(_randn(g, *shape) * 2).clamp(-4, 4) / 2
+    return torch.round(_randn(g, *shape) * 2).clamp(-top, top) / 2
 
 
 def _mask_vals(g, *shape):
@@ -405,7 +558,8 @@ def _gmp_make(c):
     p = c.p
     B, H, W, C = p["B"], p["H"], p["W"], p["C"]
     ld = p.get("x_ld", C)
-    x = _quant(g, p["ties"], B, H, W, ld) if p.get("ties") else _randn(g, B, H, W, ld)
+    top = 4 if st_of(c) == "f32" else 3
+    x = _store(_quant(g, p["ties"], B, H, W, ld, top=top) if p.get("ties") else _randn(g, B, H, W, ld), st_of(c))    # (the 0.5 grid: exact in every type)
     inp = {"x": x, "g": _randn(g, B, 2 * C)}
     if p.get("mask"):
         m = _mask_vals(g, B, H, W)
@@ -413,18 +567,23 @@ def _gmp_make(c):
             m[0] = 0
         inp["mask"] = m
     if p.get("acc"):
-        inp["out0"] = _randn(g, B, H, W, C)
+        inp["out0"] = _store(_randn(g, B, H, W, C), st_of(c))      # the gradient buffer added into: of x's storage type
     inp["v"] = gmp_forward32(_sl(c, inp, "x"), inp.get("mask"))
     return inp
 
 
-def gmp_bwd_explicit(x, mask, g, dt, last=False):
+def gmp_bwd_explicit(x, mask, g, dt, last=False, vmax=None):
     """dx = m (g_mean / P + g_max [p == arg]); arg = numpy.argmax over the row-major pixels of the float32 products m * x
-    (first occurrence by contract; ``last``: the seeded defect, the last occurrence)"""
+    (first occurrence by contract; ``last``: the seeded defect, the last occurrence).  ``vmax`` (B, C): the kernel's own rule, seeded
+    defects only -- arg = the first pixel whose product EQUALS the forward's maximum, no pixel: no routed term (what a kernel
+    finds that reads x as another type than the forward did)"""
     B, H, W, C = x.shape
     P = H * W
     mx = (x if mask is None else x * mask[..., None]).reshape(B, P, C).numpy()
     arg = P - 1 - np.argmax(mx[:, ::-1], axis=1) if last else np.argmax(mx, axis=1)          # (B, C)
+    if vmax is not None:
+        eq = mx == vmax.numpy()[:, None, :]
+        arg = np.where(eq.any(1), np.argmax(eq, axis=1), -1)
     hit = torch.from_numpy(np.arange(P)[None, :, None] == arg[:, None, :]).to(dt)
     g = g.to(dt)
     dx = g[:, None, :C] / P + g[:, None, C:] * hit
@@ -449,8 +608,12 @@ def _gmp_ref(c, inp, dt):
 
 def _gmp_branch(c):
     if not _vec_ok(c, c.p["C"], "x"):
+        assert st_of(c) == "f32", "half storage: the strip form only"
         return "gap_gmp_bwd:scalar"
-    return "gap_gmp_bwd:strip" if (c.p["H"] * c.p["W"]) % 16 == 0 else "gap_gmp_bwd:4e"
+    if (c.p["H"] * c.p["W"]) % 16:
+        assert st_of(c) == "f32", "half storage: the strip form only"
+        return "gap_gmp_bwd:4e"
+    return _fam("gap_gmp_bwd:strip", c)
 
 
 def _gmp_mut(c, inp):
@@ -477,6 +640,9 @@ def _gmp_mut(c, inp):
         out.append(("slice offset ignored", {"dx": gmp_bwd_explicit(_sl(c, inp, "x", off=0), m, g, torch.float64) + acc}))
     if p["C"] % 4:
         out.append(("scalar tail channels zero", {"dx": _zero_tail(gmp_bwd_explicit(x, m, g, torch.float64) + acc, p["C"] % 4)}))
+    if st_of(c) != "f32":        # (the 16 bits of either type order alike: the arg-max of the misread x is that of x, but no value equals v's)
+        out.append(("operands read as the other half type",
+                    {"dx": gmp_bwd_explicit(as_other_half(x, st_of(c)), m, g, torch.float64, vmax=inp["v"][:, p["C"]:]) + acc}))
     return out
 
 
@@ -491,6 +657,15 @@ for _name, _kw in (("strip-C8-16x12", dict(C=8, H=16, W=12)), ("4e-C8-15x7", dic
 _case("gap_gmp_bwd", "strip-C8-slice-ld16-off4-ties", B=2, C=8, H=16, W=12, ties="plateau", x_ld=16, x_off=4)
 _case("gap_gmp_bwd", "4e-C8-slice-ld12-off4-mask", B=2, C=8, H=15, W=7, ties="plateau", mask="rand", x_ld=12, x_off=4)
 _case("gap_gmp_bwd", "scalar-C8-slice-ld14-off3", B=2, C=8, H=16, W=12, ties="quant", x_ld=14, x_off=3)      # ld % 4 != 0 -> scalar
+# half storage: gmp_argmax4_kernel<ST> + gap_gmp_bwd_kernel<4, ST> (the strip form only); zero-image-acc adds into a half buffer
+for _st in ("f16", "bf16"):
+    _kw = dict(st=_st, C=8, H=16, W=12)
+    _case("gap_gmp_bwd", "%s-strip-C8-16x12-plain" % _st, B=2, **_kw)
+    _case("gap_gmp_bwd", "%s-strip-C8-16x12-mask" % _st, B=2, mask="rand", **_kw)
+    _case("gap_gmp_bwd", "%s-strip-C8-16x12-quant-ties" % _st, B=3, ties="quant", **_kw)
+    _case("gap_gmp_bwd", "%s-strip-C8-16x12-plateau-ties-mask" % _st, B=2, ties="plateau", mask="rand", **_kw)
+    _case("gap_gmp_bwd", "%s-strip-C8-16x12-zero-image-acc" % _st, B=2, ties="quant", mask="zero_image", acc=True, **_kw)
+    _case("gap_gmp_bwd", "%s-strip-C8-slice-ld16-off4-ties" % _st, B=2, ties="plateau", x_ld=16, x_off=4, **_kw)
 
 
 def _gmm_make(c):
@@ -498,9 +673,9 @@ def _gmm_make(c):
     p = c.p
     B, H, W, C, nm = p["B"], p["H"], p["W"], p["C"], p["nm"]
     heads = nm + (1 if p["plain"] else 0)
-    inp = {"x": _quant(g, p["ties"], B, H, W, p.get("x_ld", C)), "masks": _mask_vals(g, B, H, W, nm), "g": _randn(g, heads * B, 2 * C)}
+    inp = {"x": _store(_quant(g, p["ties"], B, H, W, p.get("x_ld", C), top=4 if st_of(c) == "f32" else 3), st_of(c)), "masks": _mask_vals(g, B, H, W, nm), "g": _randn(g, heads * B, 2 * C)}
     if p.get("acc"):
-        inp["out0"] = _randn(g, B, H, W, C)
+        inp["out0"] = _store(_randn(g, B, H, W, C), st_of(c))
     x = _sl(c, inp, "x")
     inp["v"] = torch.cat([gmp_forward32(x, m) for m in _gmm_heads(c, inp)], 0)
     return inp
@@ -510,10 +685,13 @@ def _gmm_heads(c, inp):
     return ([None] if c.p["plain"] else []) + [inp["masks"][..., i] for i in range(c.p["nm"])]
 
 
-def _gmm_sum(c, inp, g, dt, last=False, off=None):
-    B = c.p["B"]
+def _gmm_sum(c, inp, g, dt, last=False, off=None, misread=False):
+    B, C = c.p["B"], c.p["C"]
     x = _sl(c, inp, "x", off=off)
-    dx = sum(gmp_bwd_explicit(x, m, g[h * B:(h + 1) * B], dt, last=last) for h, m in enumerate(_gmm_heads(c, inp)))
+    if misread:
+        x = as_other_half(x, st_of(c))
+    dx = sum(gmp_bwd_explicit(x, m, g[h * B:(h + 1) * B], dt, last=last, vmax=inp["v"][h * B:(h + 1) * B, C:] if misread else None)
+             for h, m in enumerate(_gmm_heads(c, inp)))
     return dx + inp["out0"].to(dt) if "out0" in inp else dx
 
 
@@ -531,23 +709,31 @@ def _gmm_mut(c, inp):
         out.append(("accumulate overwrites", {"dx": _gmm_sum(c, inp, g, torch.float64) - inp["out0"].double()}))
     if c.p.get("x_off", 0):
         out.append(("slice offset ignored", {"dx": _gmm_sum(c, inp, g, torch.float64, off=0)}))
+    if st_of(c) != "f32":
+        out.append(("operands read as the other half type", {"dx": _gmm_sum(c, inp, g, torch.float64, misread=True)}))
     return out
 
 
-OPS["gap_gmp_multi_bwd"] = Spec(_gmm_make, lambda c, inp, dt: {"dx": _gmm_sum(c, inp, inp["g"], dt)}, lambda c: "gap_gmp_multi_bwd:strip",
+OPS["gap_gmp_multi_bwd"] = Spec(_gmm_make, lambda c, inp, dt: {"dx": _gmm_sum(c, inp, inp["g"], dt)}, lambda c: _fam("gap_gmp_multi_bwd:strip", c),
                                 _gmm_mut, BAR_EW)
 for _nm in (1, 3):
     for _pl in (True, False):
         _case("gap_gmp_multi_bwd", "nm%d-%s-quant" % (_nm, "plain" if _pl else "noplain"), B=2, C=8, H=16, W=12, nm=_nm, plain=_pl, ties="quant")
 _case("gap_gmp_multi_bwd", "nm3-plain-plateau-acc", B=3, C=8, H=8, W=20, nm=3, plain=True, ties="plateau", acc=True)
 _case("gap_gmp_multi_bwd", "nm1-noplain-plateau-slice-ld16-off8", B=1, C=4, H=8, W=20, nm=1, plain=False, ties="plateau", x_ld=16, x_off=8)
+for _st in ("f16", "bf16"):
+    _case("gap_gmp_multi_bwd", "%s-nm3-plain-quant" % _st, st=_st, B=2, C=8, H=16, W=12, nm=3, plain=True, ties="quant")
+    _case("gap_gmp_multi_bwd", "%s-nm3-plain-plateau-acc" % _st, st=_st, B=3, C=8, H=8, W=20, nm=3, plain=True, ties="plateau", acc=True)
+    # (B = 6: with one head and four channels only the routed elements stand above b s, where a rounding shows -- one image has four)
+    _case("gap_gmp_multi_bwd", "%s-nm1-noplain-plateau-slice-ld16-off8" % _st, st=_st, B=6, C=4, H=8, W=20, nm=1, plain=False, ties="plateau",
+          x_ld=16, x_off=8)
 
 
 # ============================================================================================================= colsum
 # launcher (ppst_colsum_st, fp32): C % 4 == 0 and ld % 4 == 0 and 16-byte x -> colsum4 else scalar; cdiv(rows, 2048) blocks
 def _cs_make(c):
     g = _gen(c)
-    inp = {"x": _wide(c, g, "x", c.p["rows"])}
+    inp = {"x": _store(_wide(c, g, "x", c.p["rows"]), st_of(c))}
     if c.p.get("acc"):
         inp["out0"] = _randn(g, c.p["C"])
     return inp
@@ -573,11 +759,14 @@ def _cs_mut(c, inp):
         out.append(("slice offset ignored", _cs_eval(c, inp, torch.float64, x=_sl(c, inp, "x", off=0))))
     if c.p["C"] % 4:
         out.append(("scalar tail channels zero", {"out": _zero_tail(_cs_eval(c, inp, torch.float64)["out"], c.p["C"] % 4)}))
+    if c.p["C"] > 1024 and _vec_ok(c, c.p["C"], "x"):        # colsum4_partial_kernel: 256 lanes of 4 channels per pass
+        out.append(("channels beyond the first channel pass zero", {"out": _zero_tail(_cs_eval(c, inp, torch.float64)["out"], c.p["C"] - 1024)}))
     return out
 
 
 def _cs_branch(c):
-    return ("colsum:four" if _vec_ok(c, c.p["C"], "x") else "colsum:scalar") + (":blocks>1" if c.p["rows"] > 2048 else ":one-block")
+    assert st_of(c) == "f32" or _vec_ok(c, c.p["C"], "x"), "half storage: the four-channel form only"
+    return _fam(("colsum:four" if _vec_ok(c, c.p["C"], "x") else "colsum:scalar") + (":blocks>1" if c.p["rows"] > 2048 else ":one-block"), c)
 
 
 OPS["colsum"] = Spec(_cs_make, _cs_eval, _cs_branch, _cs_mut, lambda c, n: _sum_bar(c.p["rows"]))
@@ -587,6 +776,13 @@ for _rows in (1, 2047, 2048, 2049):
 _case("colsum", "rows2049-C64-slice-ld80-off8-scale-acc", rows=2049, C=64, x_ld=80, x_off=8, scale=0.37, acc=True)
 _case("colsum", "rows300-C8-slice-ld11-off3-scale", rows=300, C=8, x_ld=11, x_off=3, scale=-1.5)
 _case("colsum", "rows4100-C3-acc", rows=4100, C=3, acc=True)
+# half storage (colsum4_partial_kernel<ST>; the sums fp32): the four-in-flight loop and its tail at C = 8 (2 lanes, 128 row slots: rows 1,
+# 7 tail only, 2048 the unrolled loop alone, 2049 a second block), a slice, and C = 1028: 257 lanes of 4, a second channel pass
+for _st in ("f16", "bf16"):
+    for _rows in (1, 7, 2048, 2049):
+        _case("colsum", "%s-rows%d-C8" % (_st, _rows), st=_st, rows=_rows, C=8)
+    _case("colsum", "%s-rows2049-C64-slice-ld80-off8-scale-acc" % _st, st=_st, rows=2049, C=64, x_ld=80, x_off=8, scale=0.37, acc=True)
+    _case("colsum", "%s-rows37-C1028" % _st, st=_st, rows=37, C=1028)
 
 
 # ============================================================================================================= linear
@@ -669,15 +865,22 @@ _case("linear", "B3-N1100-K64-relu", B=3, N=1100, K=64, relu_in=True)
 def _nw_make(c):
     g = _gen(c)
     p = c.p
-    inp = {"dpre": _wide(c, g, "dpre", p["B"], p["H"], p["W"]), "noise": _randn(g, p["B"], p["H"], p["W"])}
+    inp = {"dpre": _store(_wide(c, g, "dpre", p["B"], p["H"], p["W"]), st_of(c)), "noise": _randn(g, p["B"], p["H"], p["W"])}
     if p.get("acc"):
         inp["out0"] = _randn(g, 1)
     return inp
 
 
-def _nw_eval(c, inp, dt, drop=0, off=None, acc=True, ctail=0):
+def _nw_eval(c, inp, dt, drop=0, off=None, acc=True, ctail=0, idle_slots=False):
     d = _sl(c, inp, "dpre", off=off).to(dt).reshape(-1, c.p["C"])
     n = inp["noise"].to(dt).reshape(-1)
+    if idle_slots:
+        # the seeded defect of the widths where C / 4 does not divide 256 (noise_wgrad4_kernel): the 256 % (C / 4) threads behind the
+        # last whole pixel slot take a pixel of their own, one more slot per pass, which only their channel quads reach
+        lanes = c.p["C"] // 4
+        slots, tail = 256 // lanes + 1, 256 % lanes
+        d = d.clone()
+        d[slots - 1::slots, 4 * tail:] = 0
     if ctail:
         d = d[:, :-ctail]
     if drop:
@@ -692,11 +895,20 @@ def _nw_mut(c, inp):
         out.append(("accumulate overwrites", _nw_eval(c, inp, torch.float64, acc=False)))
     if c.p.get("dpre_off", 0):
         out.append(("slice offset ignored", _nw_eval(c, inp, torch.float64, off=0)))
+    C = c.p["C"]
+    if _nw_branch(c).startswith("noise_wgrad:four"):
+        if C // 4 < 256 and 256 % (C // 4):
+            out.append(("idle tail lanes take a pixel slot that their channel quads alone reach", _nw_eval(c, inp, torch.float64, idle_slots=True)))
+        if C // 4 > 256:
+            out.append(("channels past the first 1024 left out", _nw_eval(c, inp, torch.float64, ctail=C - 1024)))
     return out
 
 
 def _nw_branch(c):
     C = c.p["C"]
+    if st_of(c) != "f32":          # a half tensor takes the four-channel form at every width (or is refused)
+        assert _vec_ok(c, C, "dpre")
+        return _fam("noise_wgrad:four", c)
     return "noise_wgrad:four" if (_vec_ok(c, C, "dpre") and (C // 4 >= 256 or 256 % (C // 4) == 0)) else "noise_wgrad:scalar"
 
 
@@ -707,13 +919,22 @@ _case("noise_wgrad", "C12-9x11-acc", B=1, C=12, H=9, W=11, acc=True)            
 _case("noise_wgrad", "C32-33x37-slice-ld40-off8", B=2, C=32, H=33, W=37, dpre_ld=40, dpre_off=8)
 _case("noise_wgrad", "C6-9x11-slice-ld9-off2", B=2, C=6, H=9, W=11, dpre_ld=9, dpre_off=2)
 _case("noise_wgrad", "C1024-3x3", B=1, C=1024, H=3, W=3)                             # C / 4 >= 256
+# half storage: noise_wgrad4_kernel<ST> at every width.  C96: 24 lanes, 10 pixel slots, threads 240..255 idle -- fp32 takes the scalar
+# kernel there (same_form_as_f32: float64 alone judges it); C1028: 257 channel quads on 256 lanes, the `c += lanes` loop
+for _st in ("f16", "bf16"):
+    _case("noise_wgrad", "%s-C4-5x7" % _st, st=_st, B=2, C=4, H=5, W=7)
+    _case("noise_wgrad", "%s-C4-5x7-acc" % _st, st=_st, B=2, C=4, H=5, W=7, acc=True)
+    _case("noise_wgrad", "%s-C96-9x11" % _st, st=_st, B=1, C=96, H=9, W=11)
+    _case("noise_wgrad", "%s-C1024-3x3" % _st, st=_st, B=1, C=1024, H=3, W=3)
+    _case("noise_wgrad", "%s-C1028-3x3" % _st, st=_st, B=1, C=1028, H=3, W=3)
+    _case("noise_wgrad", "%s-C32-33x37-slice-ld40-off4" % _st, st=_st, B=2, C=32, H=33, W=37, dpre_ld=40, dpre_off=4)
 
 
 # ppst_wgrad_small_cin_st (fp32 dy): cout % 4 == 0 and 256 % (cout / 4) == 0 and 16-byte dy -> four-channel, else scalar; 1024 pixels per block
 def _wsc_make(c):
     g = _gen(c)
     p = c.p
-    inp = {"x": _wide(c, g, "x", 1, 1, p["npix"], C=p["cin"]), "dy": _randn(g, 1, 1, p["npix"], p["cout"])}
+    inp = {"x": _wide(c, g, "x", 1, 1, p["npix"], C=p["cin"]), "dy": _store(_randn(g, 1, 1, p["npix"], p["cout"]), st_of(c))}
     if p.get("acc"):
         inp["out0"] = _randn(g, p["cout"], p["cin"], 1, 1)
     return inp
@@ -744,8 +965,9 @@ def _wsc_mut(c, inp):
 
 def _wsc_branch(c):
     co = c.p["cout"]
-    return ("wgrad_small_cin:four" if (co % 4 == 0 and co // 4 <= 256 and 256 % (co // 4) == 0) else "wgrad_small_cin:scalar") + \
-        (":blocks>1" if c.p["npix"] > 1024 else ":one-block")
+    four = co % 4 == 0 and co // 4 <= 256 and 256 % (co // 4) == 0
+    assert four or st_of(c) == "f32", "a half dy: the four-channel form only"
+    return _fam(("wgrad_small_cin:four" if four else "wgrad_small_cin:scalar") + (":blocks>1" if c.p["npix"] > 1024 else ":one-block"), c)
 
 
 OPS["wgrad_small_cin"] = Spec(_wsc_make, _wsc_eval, _wsc_branch, _wsc_mut, lambda c, n: _sum_bar(c.p["npix"]))
@@ -755,6 +977,14 @@ for _cin in (1, 3, 4):
 _case("wgrad_small_cin", "cin3-npix1025-cout12-acc", cin=3, npix=1025, cout=12, acc=True)         # 256 % 3 != 0 -> scalar
 _case("wgrad_small_cin", "cin3-npix77-cout70-acc", cin=3, npix=77, cout=70, acc=True, scale=2.0)  # two passes of 64 lanes
 _case("wgrad_small_cin", "cin3-npix1025-cout32-slice-ld8-off5", cin=3, npix=1025, cout=32, x_ld=8, x_off=5)
+# a half dy (wgrad_small_cin4_kernel<ST>; x and dw fp32): Q = 8 channel quads, 32 pixel slots -- 1025 pixels: the four-in-flight loop, its
+# tail and a second block of one pixel; 77: two passes and a ragged tail; cout 1024: Q = 256, ONE pixel slot
+for _st in ("f16", "bf16"):
+    for _cin in (1, 3, 4):
+        _case("wgrad_small_cin", "%s-cin%d-npix1025-cout32" % (_st, _cin), st=_st, cin=_cin, npix=1025, cout=32, scale=0.5)
+    _case("wgrad_small_cin", "%s-cin3-npix77-cout32-acc" % _st, st=_st, cin=3, npix=77, cout=32, acc=True, scale=2.0)
+    _case("wgrad_small_cin", "%s-cin3-npix1025-cout32-slice-ld8-off5" % _st, st=_st, cin=3, npix=1025, cout=32, x_ld=8, x_off=5)
+    _case("wgrad_small_cin", "%s-cin3-npix5-cout1024" % _st, st=_st, cin=3, npix=5, cout=1024)
 
 
 # ============================================================================================================ row ops
@@ -1006,12 +1236,14 @@ def _in_make(c):
     g = _gen(c)
     p = c.p
     B, hw, C = p["B"], p["hw"], p["C"]
+    st = st_of(c)
+    lo = 1e-3 if st == "f32" else 2.0 ** -9             # (a bound every storage type holds exactly)
     y = _wide(c, g, "y", B, hw, 1)
     if p.get("big_mean"):
         y = y + 100.0                                    # channel mean 100 x its standard deviation
-    inp = {"g": _wide(c, g, "g", B, hw, 1), "y": _away(y)}
+    inp = {"g": _store(_wide(c, g, "g", B, hw, 1), st), "y": _away(_store(y, st), lo)}
     if p.get("gate"):
-        inp["gate"] = _away(_wide(c, g, "gate", B, hw, 1))
+        inp["gate"] = _away(_store(_wide(c, g, "gate", B, hw, 1), st), lo)
     if p.get("style"):
         inp["style"] = _randn(g, B, 2 * C) * 0.3
     y64 = _sl(c, inp, "y").double()
@@ -1096,8 +1328,10 @@ def _in_mut(c, inp):
 
 
 def _in_branch(c):
-    return "in_bwd:%s:%s:%s" % ("four" if _vec_ok(c, c.p["C"], "g", "y", "gate") else "scalar", "chunks>1" if c.p["hw"] > 64 else "one-chunk",
-                                "norm" if c.p.get("norm", True) else "no-norm")
+    four = _vec_ok(c, c.p["C"], "g", "y", "gate")
+    assert four or st_of(c) == "f32", "half storage: the four-channel forms only"
+    return _fam("in_bwd:%s:%s:%s" % ("four" if four else "scalar", "chunks>1" if c.p["hw"] > 64 else "one-chunk",
+                                     "norm" if c.p.get("norm", True) else "no-norm"), c)
 
 
 OPS["in_bwd"] = Spec(_in_make, in_bwd_explicit, _in_branch, _in_mut, BAR_EW)
@@ -1115,6 +1349,17 @@ _case("in_bwd", "hw480-C32-big-mean-style-dstyle", B=2, hw=480, C=32, style=True
 # dual_stats_kernel<V> walks the channels 256 lanes of V at a time: more than one pass only for C > 256 (V = 1) and C > 1024 (V = 4)
 _case("in_bwd", "hw15-C258-gate-style-dstyle", B=2, hw=15, C=258, gate=True, style=True, want_dstyle=True)      # scalar, two channel passes
 _case("in_bwd", "hw15-C1032-gate-style-dstyle", B=2, hw=15, C=1032, gate=True, style=True, want_dstyle=True)    # 258 lanes of 4: two passes
+# half storage of g, y, gate and dx (dual_stats_kernel<4, ST>, in_bwd_apply_kernel<4, ST>; partial sums, coef and dstyle fp32): one
+# ragged chunk, several partial rows, both gates, no norm, two channel passes, and slices that start 4 and 8 halves in -- 8-byte
+# aligned pointers, g and gate not 16-byte aligned
+for _st in ("f16", "bf16"):
+    _case("in_bwd", "%s-hw35-C8-plain" % _st, st=_st, B=2, hw=35, C=8)
+    _case("in_bwd", "%s-hw480-C8-gate-style-dstyle" % _st, st=_st, B=2, hw=480, C=8, gate=True, style=True, want_dstyle=True)
+    _case("in_bwd", "%s-hw480-C8-post-gate-style" % _st, st=_st, B=3, hw=480, C=8, post_gate=True, style=True)
+    _case("in_bwd", "%s-hw480-C32-no-norm" % _st, st=_st, B=2, hw=480, C=32, norm=False)
+    _case("in_bwd", "%s-hw15-C1032-gate-style-dstyle" % _st, st=_st, B=2, hw=15, C=1032, gate=True, style=True, want_dstyle=True)
+    _case("in_bwd", "%s-hw480-C8-slices-gate-style-dstyle" % _st, st=_st, B=2, hw=480, C=8, gate=True, style=True, want_dstyle=True,
+          g_ld=12, g_off=4, y_ld=16, y_off=8, gate_ld=12, gate_off=4)
 
 
 # ppst_in_finalize_train: one kernel; partial rows of (sum, sum of squares) -> scale_shift, mean_rstd.  The judge takes the float32
@@ -1629,7 +1874,7 @@ _case("conv_wgrad_p1", "k3-9x11-32to96-bias", prec=1, k=3, B=1, H=9, W=11, cin=3
 def _cd_make(c):
     g = _gen(c)
     p = c.p
-    return {"g": _wide(c, g, "g", p["B"], p["H"], p["W"], C=p["cout"]), "w": _randn(g, p["cout"], p["cin"], p["k"], p["k"])}
+    return {"g": _store(_wide(c, g, "g", p["B"], p["H"], p["W"], C=p["cout"]), st_of(c)), "w": _randn(g, p["cout"], p["cin"], p["k"], p["k"])}
 
 
 def _cd_eval(c, inp, dt, drop_row=False, off=None, flip=False, wscale=None, odd_rows=True):
@@ -1667,16 +1912,22 @@ def _cd_mut(c, inp):
 def _cd_form(c):
     p = c.p
     if p.get("via") == "entry":
-        return "entry-stack" if (p["cin"] <= 64 and p["cin"] % 4 == 0) else "entry-four-group"
+        per = 4 if st_of(c) == "f32" else 8       # ops.depth_to_space moves 16-byte items: 8 channels of a half gradient
+        return "entry-stack" if (p["cin"] <= 64 and p["cin"] % per == 0) else "entry-four-group"
     return {"dgrad": "k%d" % p["k"], "dgrad_s2d": "four-group", "dgrad_s2ds": "stack"}[p["kind"]]
 
 
 def _cd_branch(c):
-    return "conv_dgrad:%s:%s" % (_cd_form(c), "fp32" if c.p["prec"] == 2 else "bf16x3")
+    return _fam("conv_dgrad:%s:%s" % (_cd_form(c), {0: "bf16x3", 1: "bf16x1", 2: "fp32"}[c.p["prec"]]), c)
 
 
-# the project's bar of the bf16x3 convs; the exact-fp32 conv: the fp32 class, sums of cout k k terms
-OPS["conv_dgrad"] = Spec(_cd_make, _cd_eval, _cd_branch, _cd_mut, lambda c, n: 3e-5 if c.p["prec"] != 2 else _sum_bar(c.p["cout"] * c.p["k"] ** 2))
+def _cd_cls(c, name):
+    # the project's bar of the bf16x3 convs; the exact-fp32 conv: the fp32 class, sums of cout k k terms; the single-pass bf16 conv on
+    # bf16-stored tensors (precision mode 1): the bar the conv tests hold that mode to (tests/conv_epi_cases.py BAR[1], gpu_diag.t_conv)
+    return {0: 3e-5, 1: 2e-2, 2: _sum_bar(c.p["cout"] * c.p["k"] ** 2)}[c.p["prec"]]
+
+
+OPS["conv_dgrad"] = Spec(_cd_make, _cd_eval, _cd_branch, _cd_mut, _cd_cls)
 for _prec in (0, 2):
     _case("conv_dgrad", "p%d-k3-33x70-32to32" % _prec, kind="dgrad", prec=_prec, k=3, B=1, H=33, W=70, cin=32, cout=32, scale=0.5)
     _case("conv_dgrad", "p%d-k3-30x34-96to160" % _prec, kind="dgrad", prec=_prec, k=3, B=1, H=30, W=34, cin=96, cout=160, scale=0.5)
@@ -1690,6 +1941,55 @@ for _prec in (0, 2):
     _case("conv_dgrad", "p%d-s2d-stack-33x37-of-68x75" % _prec, kind="dgrad_s2ds", prec=_prec, k=3, B=2, H=33, W=37, bhw=(68, 75), cin=64, cout=32, scale=0.5)
 _case("conv_dgrad", "p0-s2d-entry-33x37-cin32", kind="dgrad_s2ds", via="entry", prec=0, k=3, B=1, H=33, W=37, bhw=(67, 75), cin=32, cout=32, scale=0.5)
 _case("conv_dgrad", "p0-s2d-entry-15x9-cin96", kind="dgrad_s2d", via="entry", prec=0, k=3, B=1, H=15, W=9, bhw=(31, 19), cin=96, cout=32, scale=0.5)
+# a bf16-stored gradient through ops.dgrad_s2d (precision mode 1): cin 32 takes the stack form, cin 96 the four-group form.  The
+# entry's switch asks cin % 8 of a half gradient where it asks cin % 4 of an fp32 one (_cd_form restates both) -- but no ConvPlan exists
+# for a forward Cin that is no multiple of 32 (conv_tables.build), so a cin such as 12, where the two rules part, never reaches either
+# form: CIN12 states the rule for the CPU test, the GPU test shows that ops refuses it by name.
+_case("conv_dgrad", "p1-bf16-s2d-entry-33x37-cin32", kind="dgrad_s2ds", via="entry", prec=1, st="bf16", k=3, B=1, H=33, W=37, bhw=(67, 75), cin=32, cout=32,
+      scale=0.5)
+_case("conv_dgrad", "p1-bf16-s2d-entry-15x9-cin96", kind="dgrad_s2d", via="entry", prec=1, st="bf16", k=3, B=1, H=15, W=9, bhw=(31, 19), cin=96, cout=32,
+      scale=0.5)
+CIN12 = Case("conv_dgrad", "conv_dgrad-p1-bf16-s2d-entry-15x9-cin12", dict(kind="dgrad_s2d", via="entry", prec=1, st="bf16", k=3, B=1, H=15, W=9,
+                                                                           bhw=(31, 19), cin=12, cout=32, scale=0.5), 0)
+
+
+# ============================================================================================= space_to_depth, depth_to_space
+# ppst_space_to_depth_st, half storage: four channels travel as one 8-byte item (s2d_kernel<uint2>; C % 4, x_ld % 4, 8-byte pointers);
+# ppst_depth_to_space_st moves 16-byte items, 8 channels of a half tensor (C % 8).  's': the phase-major copy; 'back' (C % 8 == 0):
+# depth_to_space of it at the input's extent, the input again.  (The fp32 forms: tests/test_gpu_backward_kernels.py, on their own.)
+def _sd_stack(x, edge="zero"):
+    if edge == "replicate":
+        x = _nhwc(F.pad(_nchw(x), [0, x.shape[2] % 2, 0, x.shape[1] % 2], mode="replicate"))
+    return _s2d_stack(x.contiguous())
+
+
+def _sd_eval(c, inp, dt, off=None, edge="zero", swap=False):
+    p = c.p
+    x = _sl(c, inp, "x", off=off).to(dt)
+    s = _sd_stack(x, edge)
+    if swap:
+        s = torch.cat([s[..., :p["C"]], s[..., 2 * p["C"]:3 * p["C"]], s[..., p["C"]:2 * p["C"]], s[..., 3 * p["C"]:]], -1)
+    out = {"s": s}
+    if p["C"] % 8 == 0:
+        out["back"] = _s2d_unstack(s, p["H"], p["W"]).contiguous()
+    return out
+
+
+def _sd_mut(c, inp):
+    out = [("phases (0, 1) and (1, 0) exchanged", _sd_eval(c, inp, torch.float64, swap=True)),
+           ("the row / column beyond an odd extent copied from the edge, not zero", {"s": _sd_eval(c, inp, torch.float64, edge="replicate")["s"]})]
+    if c.p.get("x_off", 0):
+        out.append(("slice offset ignored", _sd_eval(c, inp, torch.float64, off=0)))
+    return out
+
+
+OPS["space_to_depth"] = Spec(lambda c: {"x": _store(_wide(c, _gen(c), "x", c.p["B"], c.p["H"], c.p["W"]), st_of(c))}, _sd_eval,
+                             lambda c: _fam("space_to_depth:uint2" + ("+depth_to_space" if c.p["C"] % 8 == 0 else ""), c), _sd_mut, BAR_MOVE)
+for _st in ("f16", "bf16"):
+    _case("space_to_depth", "%s-33x37-C8" % _st, st=_st, B=2, H=33, W=37, C=8)
+    _case("space_to_depth", "%s-6x5-C8" % _st, st=_st, B=2, H=6, W=5, C=8)
+    _case("space_to_depth", "%s-1x7-C12" % _st, st=_st, B=2, H=1, W=7, C=12)
+    _case("space_to_depth", "%s-5x7-C8-slice-ld16-off4" % _st, st=_st, B=2, H=5, W=7, C=8, x_ld=16, x_off=4)
 
 _BY_ID = {c.id: c for c in CASES}
 assert len(_BY_ID) == len(CASES), "case ids must be unique"
@@ -1721,6 +2021,14 @@ FAMILIES = ["bilinear_bwd:gather", "bilinear_bwd:scatter", "pad2d:fwd-float4:bwd
             "conv_wgrad_p1:conv:tr2-single-exact:slabs3:csum",
             "conv_dgrad:k3:bf16x3", "conv_dgrad:k3:fp32", "conv_dgrad:k1:bf16x3", "conv_dgrad:k1:fp32", "conv_dgrad:four-group:bf16x3",
             "conv_dgrad:four-group:fp32", "conv_dgrad:stack:bf16x3", "conv_dgrad:stack:fp32", "conv_dgrad:entry-stack:bf16x3",
-            "conv_dgrad:entry-four-group:bf16x3"]
-# In no case: the half-storage (`_st`) instances of every launcher but the weight gradient's (held bit-equal to these fp32 forms by
-# gpu_diag.t_train_half) and the lpips entries (tests/test_gpu_lpips.py).
+            "conv_dgrad:entry-four-group:bf16x3",
+            # a bf16 gradient through ops.dgrad_s2d (precision mode 1): its switch to the stack form is cin % 8
+            "conv_dgrad:entry-stack:bf16x1:bf16", "conv_dgrad:entry-four-group:bf16x1:bf16"]
+# the half-storage (`_st`) instances: every form a half tensor can take (the launchers refuse it the one-channel forms), in both types
+HALF_FAMILIES = ["bilinear_bwd:gather", "pad2d:fwd-uint2:bwd-float4", "gap_gmp_bwd:strip", "gap_gmp_multi_bwd:strip", "colsum:four:one-block",
+                 "colsum:four:blocks>1", "noise_wgrad:four", "wgrad_small_cin:four:one-block", "wgrad_small_cin:four:blocks>1",
+                 "in_bwd:four:one-chunk:norm", "in_bwd:four:chunks>1:norm", "in_bwd:four:chunks>1:no-norm", "space_to_depth:uint2",
+                 "space_to_depth:uint2+depth_to_space"]
+FAMILIES += ["%s:%s" % (f, st) for f in HALF_FAMILIES for st in ("f16", "bf16")]
+# In no case: the lpips entries (tests/test_gpu_lpips.py), and the convs' input gradient on an fp16-stored tensor (precision mode 3 does
+# not train: ops.train_dtype is bfloat16 or float32).

@@ -204,13 +204,14 @@ def test_bar_passes_the_reference_and_rejects_every_seeded_defect(cid):
     c = C.by_id(cid)
     ref = C.reference(cid)
     for k, v in ref.items():
-        bad, _ = C.judge(c, k, v.astype(np.float32))
-        assert not bad, "%s: the float32 rounding of the reference misses its own bar: %s" % (k, bad)
+        # (as the output tensor would hold it: float32, or rounded once to the case's half type)
+        bad, _ = C.judge(c, k, C.as_stored(c, k, v.astype(np.float32)))
+        assert not bad, "%s: the stored rounding of the reference misses its own bar: %s" % (k, bad)
     muts = C.mutations(c)
     assert len(muts) >= 2, "a case carries at least two seeded defects"
     for name, out in muts:
-        assert set(out) <= set(ref)
-        seen = [k for k, v in out.items() if C.judge(c, k, v.astype(np.float32))[0]]
+        assert set(out) <= set(ref) and out, (name, set(out))
+        seen = [k for k, v in out.items() if C.judge(c, k, C.as_stored(c, k, v.astype(np.float32)) if "truncation" not in name else v)[0]]
         assert seen, "the inputs of %s cannot show the defect '%s' at the bar" % (cid, name)
 
 
@@ -261,7 +262,9 @@ def test_bars_print():
         for k, e in C.err32(c.id).items():
             b = C.bar(c, k)
             print("%-58s %-9s bar %.2e  (float32 reference error %.2e)  %s" % (c.id, k, b, e, C.branch_of(c)))
-            assert b == 0 or b < 1e-4, "a bar this wide says the case is ill-conditioned: fix the inputs"
+            # (precision mode 1 on bf16-stored tensors carries the conv tests' bar of that mode, 2e-2: a class bar, not a measured one)
+            assert b == 0 or b < 1e-4 or (c.p.get("prec") == 1 and C.st_of(c) == "bf16" and 4 * e < 1e-4 and b == 2e-2), \
+                "a bar this wide says the case is ill-conditioned: fix the inputs"
 
 
 # -------------------------------------------------------------------------------------------------------------- coverage
@@ -288,13 +291,96 @@ def test_the_minimum_table_of_the_issue_is_present():
     wg = {(c.p.get("kind", "conv"), c.p["prec"]) for c in _of("conv_wgrad")}
     assert wg == {(k, q) for k in ("conv", "s2d", "dgradT") for q in (0, 2)}
     assert any(c.p.get("kind") == "s2d" and (c.p["H"], c.p["W"]) == (33, 37) for c in _of("conv_wgrad"))
-    assert {(c.p["kind"], c.p["prec"]) for c in _of("conv_dgrad")} == {(k, q) for k in ("dgrad", "dgrad_s2d", "dgrad_s2ds") for q in (0, 2)}
+    assert {(c.p["kind"], c.p["prec"]) for c in _of("conv_dgrad") if C.st_of(c) == "f32"} == {(k, q) for k in ("dgrad", "dgrad_s2d", "dgrad_s2ds") for q in (0, 2)}
     ragged = {(33, 70), (30, 34), (20, 36), (33, 37)}
     assert {(c.p["H"], c.p["W"]) for c in _of("conv_dgrad")} >= ragged and {(c.p["H"], c.p["W"]) for c in _of("conv_wgrad")} >= ragged
     # bias buffers: written and added into, with dw written and added into, on either bias path
     for path in ("csum", "colsum"):
         seen = {(bool(c.p.get("acc")), C._cw_bias_acc(c), "db0" in C.inputs(c.id)) for c in _of("conv_wgrad") if C.branch_of(c).endswith(path)}
         assert seen >= {(False, False, False), (False, False, True), (False, True, True), (True, False, True), (True, True, True)}, (path, seen)
+
+
+HALF_CASES = [c for c in C.CASES if C.st_of(c) != "f32"]
+
+
+@pytest.mark.parametrize("c", HALF_CASES, ids=lambda c: c.id)
+def test_half_case_inputs_hold_stored_values_and_side_operands_stay_float32(c):
+    """the typed operands are exactly representable in the case's type (rounded once), what derives from them was computed after
+    the rounding, gates keep their distance, masks their four values; the half rule passes a correctly rounded reference and the
+    seeded half defects are there"""
+    inp, st = C.inputs(c.id), C.st_of(c)
+    typed = [k for k in C.TYPED[c.op] if k in inp]
+    assert typed and typed[0] == C.TYPED[c.op][0]
+    for k in typed:
+        assert torch.equal(inp[k], inp[k].to(C.HALF[st]).float()), k
+    for k in ("g", "v", "noise", "style", "mr", "w"):           # the side operands stay float32: not rounded
+        if k in inp and k not in typed and inp[k].numel() > 8:
+            assert not torch.equal(inp[k], inp[k].to(C.HALF[st]).float()), k
+    for k in ("mask", "masks"):
+        if k in inp:
+            assert set(inp[k].unique().tolist()) <= {0.0, 0.25, 0.5, 1.0}
+    if c.op in ("gap_gmp_bwd", "gap_gmp_multi_bwd"):          # the forward maximum is the maximum of the STORED values
+        x = C._sl(c, inp, "x")
+        heads = [inp.get("mask")] if c.op == "gap_gmp_bwd" else C._gmm_heads(c, inp)
+        assert torch.equal(inp["v"], torch.cat([C.gmp_forward32(x, m) for m in heads], 0))
+    if c.op == "in_bwd":
+        for k in ("y", "gate"):
+            if k in inp:
+                assert C._sl(c, inp, k).abs().min() >= 2.0 ** -9
+    names = [n for n, _ in C.mutations(c)]
+    ref = C.reference(c.id)
+    half_out = [k for k in ref if C.out_st(c, k) != "f32" and C.bar(c, k) != 0 and not np.array_equal(C.as_stored(c, k, ref[k]), ref[k])]
+    assert ("half output stored by truncation" in names) == bool(half_out), (names, half_out)
+    if c.op in ("in_bwd", "gap_gmp_bwd", "gap_gmp_multi_bwd") or (c.op == "pad2d" and c.p["mode"]) or (c.op == "bilinear_bwd" and c.p["H"] < 64):
+        assert half_out or not c.p.get("norm", True), "a computed half output whose values the type holds exactly shows no rounding"
+    if any(C.bar(c, k) != 0 for k in C.reference(c.id)):
+        assert "operands read as the other half type" in names
+    if any(c.p.get(k + "_off") for k in typed):
+        assert any("offset" in n for n in names), names
+
+
+def test_half_table_of_the_issue_is_present_and_forms_are_stated():
+    ids = {c.id for c in HALF_CASES}
+    for st in ("f16", "bf16"):
+        want = ["in_bwd-%s-hw35-C8-plain", "in_bwd-%s-hw480-C8-gate-style-dstyle", "in_bwd-%s-hw480-C8-post-gate-style", "in_bwd-%s-hw480-C32-no-norm",
+                "in_bwd-%s-hw15-C1032-gate-style-dstyle", "in_bwd-%s-hw480-C8-slices-gate-style-dstyle", "pad2d-%s-reflect-C8-largest",
+                "pad2d-%s-replicate-C8-slice-ld16-off4", "bilinear_bwd-%s-C8-5x7-to-12x9", "bilinear_bwd-%s-C8-12x9-to-5x7", "bilinear_bwd-%s-C4-64x64-to-8x8",
+                "bilinear_bwd-%s-C8-slice-ld16-off4", "gap_gmp_bwd-%s-strip-C8-16x12-plain", "gap_gmp_bwd-%s-strip-C8-16x12-mask",
+                "gap_gmp_bwd-%s-strip-C8-16x12-quant-ties", "gap_gmp_bwd-%s-strip-C8-16x12-plateau-ties-mask", "gap_gmp_bwd-%s-strip-C8-16x12-zero-image-acc",
+                "gap_gmp_bwd-%s-strip-C8-slice-ld16-off4-ties", "gap_gmp_multi_bwd-%s-nm3-plain-quant", "gap_gmp_multi_bwd-%s-nm3-plain-plateau-acc",
+                "gap_gmp_multi_bwd-%s-nm1-noplain-plateau-slice-ld16-off8", "colsum-%s-rows1-C8", "colsum-%s-rows7-C8", "colsum-%s-rows2048-C8",
+                "colsum-%s-rows2049-C8", "colsum-%s-rows2049-C64-slice-ld80-off8-scale-acc", "colsum-%s-rows37-C1028", "noise_wgrad-%s-C4-5x7",
+                "noise_wgrad-%s-C4-5x7-acc", "noise_wgrad-%s-C96-9x11", "noise_wgrad-%s-C1024-3x3", "noise_wgrad-%s-C1028-3x3",
+                "noise_wgrad-%s-C32-33x37-slice-ld40-off4", "wgrad_small_cin-%s-cin1-npix1025-cout32", "wgrad_small_cin-%s-cin3-npix1025-cout32",
+                "wgrad_small_cin-%s-cin4-npix1025-cout32", "wgrad_small_cin-%s-cin3-npix77-cout32-acc", "wgrad_small_cin-%s-cin3-npix1025-cout32-slice-ld8-off5",
+                "wgrad_small_cin-%s-cin3-npix5-cout1024", "space_to_depth-%s-33x37-C8", "space_to_depth-%s-6x5-C8", "space_to_depth-%s-1x7-C12",
+                "space_to_depth-%s-5x7-C8-slice-ld16-off4"]
+        want += ["pad2d-%%s-%s-C8-%s" % (m, k) for m in ("zero", "reflect", "replicate") for k in ("asym", "crop", "H2")]
+        assert not [w % st for w in want if w % st not in ids]
+    assert {"conv_dgrad-p1-bf16-s2d-entry-33x37-cin32", "conv_dgrad-p1-bf16-s2d-entry-15x9-cin96"} <= ids
+    assert C.branch_of(C.by_id("conv_dgrad-p1-bf16-s2d-entry-33x37-cin32")) == "conv_dgrad:entry-stack:bf16x1:bf16"
+    assert C.branch_of(C.by_id("conv_dgrad-p1-bf16-s2d-entry-15x9-cin96")) == "conv_dgrad:entry-four-group:bf16x1:bf16"
+    # the half rule of the entry's switch: cin 12 goes to the four-group form, where the fp32 rule sends it to the stack (no conv plan
+    # takes a cin that is no multiple of 32: the rule is stated, the case cannot run)
+    assert C.branch_of(C.CIN12) == "conv_dgrad:entry-four-group:bf16x1:bf16" and C._cd_form(C.as_f32(C.CIN12)) == "entry-stack"
+    assert C.CIN12.id not in ids
+    # the slices of the half cases start 4 or 8 elements in: 8-byte aligned, and at 4 not 16-byte aligned
+    offs = {c.p[k] for c in HALF_CASES for k in c.p if k.endswith("_off") and k[:-4] in C.TYPED[c.op]}
+    assert offs == {4, 8}
+    # the fp32 launch takes another kernel form for: noise_wgrad C96 (24 lanes do not divide 256), and the convs (not compared here)
+    other = sorted(c.id for c in HALF_CASES if not C.same_form_as_f32(c))
+    assert other == sorted(["noise_wgrad-%s-C96-9x11" % st for st in ("f16", "bf16")] + ["conv_dgrad-p1-bf16-s2d-entry-33x37-cin32",
+                                                                                          "conv_dgrad-p1-bf16-s2d-entry-15x9-cin96"]), other
+    names = {n for c in HALF_CASES if c.op == "noise_wgrad" for n, _ in C.mutations(c)}
+    assert {"idle tail lanes take a pixel slot that their channel quads alone reach", "channels past the first 1024 left out"} <= names
+
+
+def test_truncation_and_other_type_are_what_they_say():
+    v = np.array([1.0 + 2.0 ** -7 - 2.0 ** -20, -(1.0 + 2.0 ** -7 - 2.0 ** -20), 3.0, 1.0 + 2.0 ** -10 - 2.0 ** -20])
+    assert np.array_equal(C.truncated(v, "bf16"), [1.0, -1.0, 3.0, 1.0])
+    assert np.array_equal(C.truncated(v, "f16"), [1.0 + 2.0 ** -8 + 2.0 ** -9 + 2.0 ** -10, -(1.0 + 2.0 ** -8 + 2.0 ** -9 + 2.0 ** -10), 3.0, 1.0])
+    one = torch.tensor([1.0])
+    assert C.as_other_half(one, "bf16").item() == 1.875 and C.as_other_half(one, "f16").item() == 2.0 ** -7
 
 
 def test_space_to_depth_of_the_references_is_pixel_unshuffle():

@@ -11,6 +11,10 @@ Next to the references: the adjoint identity <op(x), dy> = <x, op_bwd(dy)> of th
 device's outputs), bit-identical repeats of every kernel without float atomics, a batch equal to its single-image calls, and
 guard values around the outputs the caller places (out= destinations, the in-place softmax gradient, and dx reached through the
 C entry with dx_ld > C).  Outputs that ops allocates itself sit in the allocator's blocks and carry no guard.
+
+The half-storage (`_st`) instances run through the same path: the operands a launcher types travel as float16 / bfloat16 (the case's
+``st``), a half-stored output is judged by the half rule of bwd_cases, and where the fp32 launch takes the same kernel form the half
+launch must equal it, rounded once, bit for bit.  What a half tensor may not be is refused through the C entries, nothing written.
 """
 import ctypes
 import os
@@ -31,9 +35,19 @@ def _dev():
     return torch.device("cuda", 0)
 
 
+def _dt(c, name):
+    """the type an operand travels in: the case's storage type for the operands its launcher types (C.TYPED), else float32.  (The
+    case's float32 values are exactly the stored ones: the conversion rounds nothing.)"""
+    return C.DTYPE[C.st_of(c)] if name in C.TYPED.get(c.op, ()) else torch.float32
+
+
+def _whole(c, inp, name):
+    return inp[name].to(_dev()).to(_dt(c, name))
+
+
 def _put(c, inp, name, C_=None):
     """the operand on the device, as the case stores it: the channel slice of the wider tensor (a view: ld and offset kept)"""
-    t = inp[name].to(_dev())
+    t = _whole(c, inp, name)
     C_ = c.p["C"] if C_ is None else C_
     off = c.p.get(name + "_off", 0)
     return t[..., off:off + C_] if t.shape[-1] != C_ else t
@@ -43,16 +57,19 @@ def _np(t):
     return t.detach().double().cpu().numpy()
 
 
-def _guarded(shape, fill=None):
-    """a contiguous tensor of ``shape`` inside a larger buffer the test owns, POISON before and after; -> (view, check)"""
+def _guarded(shape, fill=None, dtype=torch.float32):
+    """a contiguous tensor of ``shape`` and ``dtype`` inside a larger buffer the test owns, POISON before and after; -> (view, check)
+    (256 elements in front: the view starts 512 or 1024 bytes in, aligned for every launcher)"""
     n = int(np.prod(shape))
-    buf = torch.full((n + 512,), POISON, device=_dev(), dtype=torch.float32)
+    buf = torch.full((n + 512,), POISON, device=_dev(), dtype=dtype)
     view = buf[256:256 + n].view(*shape)
     if fill is not None:
         view.copy_(fill)
 
+    poison = torch.full((1,), POISON, device=_dev(), dtype=dtype)        # (POISON as the buffer's type holds it)
+
     def check():
-        assert bool((buf[:256] == POISON).all()) and bool((buf[256 + n:] == POISON).all()), "wrote outside its output"
+        assert bool((buf[:256] == poison).all()) and bool((buf[256 + n:] == poison).all()), "wrote outside its output"
     return view, check
 
 
@@ -63,7 +80,7 @@ def _run_bilinear_bwd(c, inp, ops):
 
 def _run_pad2d(c, inp, ops):
     p = c.p
-    return {"y": ops.pad2d(_put(c, inp, "x"), *p["pads"], p["mode"]), "dx": ops.pad2d_bwd(inp["dy"].to(_dev()), *p["pads"], p["mode"])}
+    return {"y": ops.pad2d(_put(c, inp, "x"), *p["pads"], p["mode"]), "dx": ops.pad2d_bwd(_whole(c, inp, "dy"), *p["pads"], p["mode"])}
 
 
 def _run_avgpool_bwd(c, inp, ops):
@@ -74,8 +91,8 @@ def _run_gap_gmp_bwd(c, inp, ops):
     dev = _dev()
     mask = inp["mask"].to(dev) if "mask" in inp else None
     out, check = (None, lambda: None)
-    if "out0" in inp:
-        out, check = _guarded(inp["out0"].shape, inp["out0"].to(dev))
+    if "out0" in inp:        # (the buffer added into has x's storage type: a half out= sits between POISON values of that type)
+        out, check = _guarded(inp["out0"].shape, _whole(c, inp, "out0"), _dt(c, "out0"))
     dx = ops.gap_gmp_bwd(_put(c, inp, "x"), mask, inp["v"].to(dev), inp["g"].to(dev), out=out)
     torch.cuda.synchronize()
     check()
@@ -86,7 +103,7 @@ def _run_gap_gmp_multi_bwd(c, inp, ops):
     dev = _dev()
     out, check = (None, lambda: None)
     if "out0" in inp:
-        out, check = _guarded(inp["out0"].shape, inp["out0"].to(dev))
+        out, check = _guarded(inp["out0"].shape, _whole(c, inp, "out0"), _dt(c, "out0"))
     dx = ops.gap_gmp_multi_bwd(_put(c, inp, "x"), inp["masks"].to(dev), inp["v"].to(dev), inp["g"].to(dev), with_plain=c.p["plain"], out=out)
     torch.cuda.synchronize()
     check()
@@ -129,7 +146,7 @@ def _run_noise_wgrad(c, inp, ops):
 def _run_wgrad_small_cin(c, inp, ops):
     p = c.p
     out, check = _guarded((p["cout"], p["cin"], 1, 1), inp["out0"].to(_dev()) if "out0" in inp else None)
-    r = ops.wgrad_small_cin(_put(c, inp, "x", p["cin"]), inp["dy"].to(_dev()), p.get("scale", 1.0), out=out, accumulate="out0" in inp)
+    r = ops.wgrad_small_cin(_put(c, inp, "x", p["cin"]), _whole(c, inp, "dy"), p.get("scale", 1.0), out=out, accumulate="out0" in inp)
     torch.cuda.synchronize()
     check()
     return {"dw": r.view(p["cout"], p["cin"], 1, 1)}
@@ -223,6 +240,11 @@ def _run_transpose_last2(c, inp, ops):
     return {"y": ops.transpose_last2(inp["x"].to(_dev()))}
 
 
+def _run_space_to_depth(c, inp, ops):
+    s = ops.space_to_depth(_put(c, inp, "x"))
+    return {"s": s, "back": ops.depth_to_space(s, (c.p["H"], c.p["W"]))} if c.p["C"] % 8 == 0 else {"s": s}
+
+
 def _run_conv_wgrad(c, inp, ops):
     dev, p = _dev(), c.p
     kind = p.get("kind", "conv")
@@ -302,24 +324,28 @@ RUN = {k[5:]: v for k, v in list(globals().items()) if k.startswith("_run_")}
 ATOMIC = {"bilinear_bwd:scatter"}          # float atomics: equal to the reference within the bar, not bit for bit between runs
 
 
-def _run(c):
+def _run(c, inp=None, raw=False):
     from ppst_amd import ops
-    out = RUN[c.op](c, C.inputs(c.id), ops)
+    out = RUN[c.op](c, C.inputs(c.id) if inp is None else inp, ops)
     torch.cuda.synchronize()
-    return {k: _np(v) for k, v in out.items()}
+    return out if raw else {k: _np(v) for k, v in out.items()}
 
 
 # --------------------------------------------------------------------------------------------- against the float64 reference
 @pytest.mark.parametrize("cid", [c.id for c in C.CASES])
 def test_against_float64_reference(cid):
     c = C.by_id(cid)
-    ref, got = C.reference(cid), _run(c)
+    ref, raw = C.reference(cid), _run(c, raw=True)
+    got = {k: _np(v) for k, v in raw.items()}
     assert set(got) == set(ref)
     fails = []
     for k in sorted(ref):
-        b = C.bar(c, k)
+        b, st = C.bar(c, k), C.out_st(c, k)
+        if C.st_of(c) != "f32":          # the activation-shaped outputs take the case's type, every sum stays fp32
+            assert raw[k].dtype == (C.DTYPE[st] if c.op != "conv_dgrad" else torch.bfloat16) or (st == "f32" and k == "sums"), (k, raw[k].dtype)
         bad, err = C.judge(c, k, got[k])
-        print("%-58s %-9s err %.2e  bar %.2e  %s" % (cid, k, err, b, C.branch_of(c)))
+        # (a half-stored output: err in units of the allowed error b s + 2^-p (|ref| + b s), <= 1 passes)
+        print("%-58s %-9s err %.2e%s  bar %.2e  %s" % (cid, k, err, " x allowed (%s)" % st if (st != "f32" and b) else "", b, C.branch_of(c)))
         fails += ["%s: %s" % (k, m) for m in bad]
     if c.op in ("gap_gmp_bwd", "gap_gmp_multi_bwd") and not c.p.get("acc"):
         # the routed term is exact: where no gradient arrives the kernel writes 0, bit for bit
@@ -332,6 +358,29 @@ def test_against_float64_reference(cid):
         again = _run(c)
         for k in got:
             assert np.array_equal(again[k], got[k]), "%s: two runs differ" % k
+
+
+# --------------------------------------------------------------------- a half launch is the fp32 launch, rounded once
+HALF_SAME_FORM = [c.id for c in C.CASES if C.st_of(c) != "f32" and C.same_form_as_f32(c)]
+
+
+@pytest.mark.parametrize("cid", HALF_SAME_FORM)
+def test_half_launch_is_the_fp32_launch_rounded_once(cid):
+    """the 2^-p of the half rule cannot see a double rounding or a half-precision accumulator: where the fp32 launch takes the same
+    kernel form (bwd_cases.same_form_as_f32), the half launch equals it on the widened operands bit for bit -- statistics and
+    parameter gradients as they are, activation-shaped outputs after ONE rounding of the fp32 result (common.h; what
+    gpu_diag.t_train_half asks at its one shape)"""
+    c = C.by_id(cid)
+    half, wide = _run(c, raw=True), _run(C.as_f32(c), C.inputs(cid), raw=True)
+    assert set(half) == set(wide)
+    for k in sorted(half):
+        st = C.out_st(c, k)
+        want = wide[k].to(C.DTYPE[st]) if st != "f32" else wide[k]
+        assert half[k].dtype == want.dtype and wide[k].dtype != C.DTYPE[C.st_of(c)], (k, half[k].dtype, wide[k].dtype)
+        same = torch.equal(half[k], want)
+        print("%-58s %-9s %s == fp32 launch%s: %s" % (cid, k, C.st_of(c), " rounded once" if st != "f32" else "", same))
+        assert same, "%s: %d values differ from the fp32 launch%s, max %.3e" % (
+            k, int((half[k] != want).sum()), " rounded once" if st != "f32" else "", float((half[k].double() - want.double()).abs().max()))
 
 
 # ------------------------------------------------------------------------- the weight gradient's two single-pass operand forms
@@ -365,20 +414,29 @@ def _adjoint(y, dy, x, dx, bar):
 
 
 # (the forwards ppst_bilinear and ppst_avgpool take C % 4 == 0 only: the adjoint of the scalar backward forms has no forward to meet)
-@pytest.mark.parametrize("c", [c for c in C.CASES if c.op == "bilinear_bwd" and not c.p.get("dy_off") and c.p["C"] % 4 == 0], ids=lambda c: c.id)
+def _adjoint_bar(c):
+    """fp32: the elementwise class bar; a half case: the half rule's relative term 2^-p (each output is rounded once to its type)"""
+    return C.BAR_EW if C.st_of(c) == "f32" else 2.0 ** -C.PBITS[C.st_of(c)]
+
+
+# (one half case each: the outputs are widened to float64 on the host)
+@pytest.mark.parametrize("c", [c for c in C.CASES if c.op == "bilinear_bwd" and not c.p.get("dy_off") and c.p["C"] % 4 == 0
+                               and (C.st_of(c) == "f32" or c.id == "bilinear_bwd-bf16-C8-5x7-to-12x9")], ids=lambda c: c.id)
 def test_bilinear_pair_is_adjoint(c):
     from ppst_amd import ops
     inp = C.inputs(c.id)
-    x, dy = inp["x"].to(_dev()), inp["dy"].to(_dev())
-    _adjoint(ops.bilinear(x, c.p["OH"], c.p["OW"]).cpu(), dy.cpu(), x.cpu(), ops.bilinear_bwd(dy, c.p["H"], c.p["W"]).cpu(), C.BAR_EW)
+    x, dy = _whole(c, inp, "x"), _whole(c, inp, "dy")
+    # (the forward is an fp32 kernel: it reads the stored values of x widened)
+    _adjoint(ops.bilinear(x.float(), c.p["OH"], c.p["OW"]).cpu(), dy.cpu(), x.cpu(), ops.bilinear_bwd(dy, c.p["H"], c.p["W"]).cpu(), _adjoint_bar(c))
 
 
-@pytest.mark.parametrize("c", [c for c in C.CASES if c.op == "pad2d" and not c.p.get("x_off")], ids=lambda c: c.id)
+@pytest.mark.parametrize("c", [c for c in C.CASES if c.op == "pad2d" and not c.p.get("x_off")
+                               and (C.st_of(c) == "f32" or c.id == "pad2d-f16-reflect-C8-asym")], ids=lambda c: c.id)
 def test_pad_pair_is_adjoint(c):
     from ppst_amd import ops
     inp = C.inputs(c.id)
-    x, dy = inp["x"].to(_dev()), inp["dy"].to(_dev())
-    _adjoint(ops.pad2d(x, *c.p["pads"], c.p["mode"]).cpu(), dy.cpu(), x.cpu(), ops.pad2d_bwd(dy, *c.p["pads"], c.p["mode"]).cpu(), C.BAR_EW)
+    x, dy = _whole(c, inp, "x"), _whole(c, inp, "dy")
+    _adjoint(ops.pad2d(x, *c.p["pads"], c.p["mode"]).cpu(), dy.cpu(), x.cpu(), ops.pad2d_bwd(dy, *c.p["pads"], c.p["mode"]).cpu(), _adjoint_bar(c))
 
 
 @pytest.mark.parametrize("c", [c for c in C.CASES if c.op == "avgpool_bwd" and not c.p.get("dy_off") and c.p["C"] % 4 == 0], ids=lambda c: c.id)
@@ -408,6 +466,21 @@ def test_space_to_depth_and_depth_to_space_are_adjoint_and_inverse(H, W, Cc):
     assert abs(lhs - rhs) <= 1e-12 * (s.double() * d.double()).abs().sum().item()
 
 
+@pytest.mark.parametrize("st", ["f16", "bf16"])
+@pytest.mark.parametrize("H,W", [(33, 37), (6, 5)])
+def test_half_space_to_depth_and_depth_to_space_are_adjoint(st, H, W):
+    """the 8-byte and 16-byte items of the half forms (the copies themselves: the space_to_depth cases of bwd_cases): every product
+    of <s2d(x), d> appears once in <x, d2s(d)>, exactly, in float64 on the host"""
+    from ppst_amd import ops
+    g = torch.Generator().manual_seed(H * 100 + W)
+    x = torch.randn(2, H, W, 8, generator=g).to(_dev()).to(C.HALF[st])
+    d = torch.randn(2, (H + 1) // 2, (W + 1) // 2, 32, generator=g).to(_dev()).to(C.HALF[st])
+    s, back = ops.space_to_depth(x), ops.depth_to_space(d, (H, W))
+    assert s.dtype == back.dtype == C.HALF[st]
+    lhs, rhs = (s.double() * d.double()).sum().item(), (x.double() * back.double()).sum().item()
+    assert abs(lhs - rhs) <= 1e-12 * (s.double() * d.double()).abs().sum().item()
+
+
 @pytest.mark.parametrize("Cc,ld,off", [(3, 3, 0), (8, 14, 4), (8, 16, 2)])
 def test_space_to_depth_scalar_form_is_the_phase_major_copy(Cc, ld, off):
     """C % 4 != 0, x_ld % 4 != 0 or a pointer off the 16-byte grid: the one-channel-per-thread form of ppst_space_to_depth"""
@@ -420,7 +493,8 @@ def test_space_to_depth_scalar_form_is_the_phase_major_copy(Cc, ld, off):
 # -------------------------------------------------------------------------------------------- a batch is its single calls
 @pytest.mark.parametrize("cid", ["bilinear_bwd-C4-5x7-to-12x9", "bilinear_bwd-C4-64x64-to-8x8", "avgpool_bwd-f4-C3-16x24", "pad2d-reflect-C8-asym",
                                  "pad2d-replicate-C3-asym", "gap_gmp_bwd-strip-C8-16x12-quant-ties", "gap_gmp_bwd-4e-C8-15x7-quant-ties",
-                                 "gap_gmp_bwd-scalar-C6-15x7-quant-ties", "prelu_bwd-C32-ss"])
+                                 "gap_gmp_bwd-scalar-C6-15x7-quant-ties", "prelu_bwd-C32-ss",
+                                 "bilinear_bwd-bf16-C8-5x7-to-12x9", "pad2d-f16-reflect-C8-asym", "gap_gmp_bwd-bf16-strip-C8-16x12-quant-ties"])
 def test_batch_equals_single_calls(cid):
     from ppst_amd import ops
     c = C.by_id(cid)
@@ -512,3 +586,65 @@ def test_refusals_return_einval_and_write_nothing():
     with pytest.raises(RuntimeError, match="ppst_gap_gmp_multi_bwd"):       # the strip form only: hw % 16 != 0 is refused
         ops.gap_gmp_multi_bwd(torch.zeros(1, 5, 3, 8, device=dev), torch.ones(1, 5, 3, 1, device=dev), torch.zeros(1, 16, device=dev),
                               torch.zeros(1, 16, device=dev), with_plain=False)
+
+
+def test_dgrad_s2d_names_the_cin_no_conv_plan_takes():
+    """bwd_cases.CIN12: the cin at which the half and fp32 rules of ops.dgrad_s2d part has no conv plan in either form -- refused by
+    name (the message once failed to format and surfaced as a ValueError about a format character)"""
+    from ppst_amd import ops
+    c = C.CIN12
+    inp = C.OPS[c.op].make(c)
+    with pytest.raises(AssertionError, match="Cin % 32 == 0 .got 12."):
+        _run_conv_dgrad(c, inp, ops)
+
+
+def test_half_storage_refusals_return_einval_and_write_nothing():
+    """the `_st` entries on what a half tensor may not be: a channel count or pixel stride that is no multiple of 4 (8 for
+    depth_to_space), a pointer off the 8-byte grid, hw % 16 != 0 for the pooling adjoint, a cout whose quads do not divide 256, and a
+    storage type that is none.  Each returns PPST_EINVAL before any launch or memset: every buffer passed -- workspaces included --
+    keeps its fill."""
+    from ppst_amd._lib import lib
+    dev = _dev()
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    n = 1 << 14
+    fills = {"a": (torch.bfloat16, 3.0), "b": (torch.bfloat16, 7.0), "f": (torch.float32, 5.0), "f2": (torch.float32, 6.0), "w": (torch.float32, 9.0),
+             "wi": (torch.int32, 77)}
+    buf = {k: torch.full((n,), v, device=dev, dtype=dt) for k, (dt, v) in fills.items()}
+    a, b, f, f2, w, wi = (_vp(buf[k]) for k in ("a", "b", "f", "f2", "w", "wi"))
+    a_off = ctypes.c_void_p(buf["a"].data_ptr() + 2)                    # 2 bytes past the 8-byte grid
+    assert buf["a"].data_ptr() % 16 == 0
+
+    def entries(st, C_=8, ld=8, hw=16, cout=32, d2s_c=8, x=a):
+        """every `_st` entry on one small valid problem, but for the named deviation"""
+        return {
+            "dual_stats": lambda: lib.ppst_dual_stats_st(x, a, None, f, 1, hw, C_, ld, ld, 0, None, st, stream),
+            "in_bwd_apply": lambda: lib.ppst_in_bwd_apply_st(x, a, None, f, b, 1, hw, C_, ld, ld, 0, C_, 0, st, stream),
+            "pad2d": lambda: lib.ppst_pad2d_st(x, b, 1, 5, 4, C_, ld, 1, 1, 1, 1, 0, st, stream),
+            "pad2d_bwd": lambda: lib.ppst_pad2d_bwd_st(x, b, 1, 5, 4, C_, 1, 1, 1, 1, 0, st, stream),
+            "bilinear_bwd": lambda: lib.ppst_bilinear_bwd_st(x, b, 1, 5, 4, C_, C_, 8, 8, ld, st, stream),
+            "colsum": lambda: lib.ppst_colsum_st(x, f, w, 20, C_, ld, 1.0, 0, st, stream),
+            "noise_wgrad": lambda: lib.ppst_noise_wgrad_st(x, f, f2, w, 20, C_, ld, 0, st, stream),
+            "space_to_depth": lambda: lib.ppst_space_to_depth_st(x, b, 1, 5, 4, C_, ld, st, stream),
+            "gap_gmp_bwd": lambda: lib.ppst_gap_gmp_bwd_st(x, None, f, f2, b, wi, 1, hw, C_, ld, 0, st, stream),
+            "gap_gmp_multi_bwd": lambda: lib.ppst_gap_gmp_multi_bwd(x, f, f, f2, b, wi, 1, hw, C_, ld, 1, 0, 0, st, stream),
+            "wgrad_small_cin": lambda: lib.ppst_wgrad_small_cin_st(f, x, f2, w, 20, 3, 3, cout, 1.0, 0, st, stream),
+            "depth_to_space": lambda: lib.ppst_depth_to_space_st(x, b, 1, 4, 4, 8, 8, d2s_c, st, stream),
+        }
+
+    calls = []
+    for st in (1, 2):
+        e6, e10 = entries(st, C_=6, ld=6), entries(st, ld=10)
+        calls += [("%s C = 6, st %d" % (k, st), e6[k]) for k in ("dual_stats", "in_bwd_apply", "pad2d", "pad2d_bwd", "bilinear_bwd", "colsum", "noise_wgrad",
+                                                                 "space_to_depth")]
+        calls += [("%s x_ld = 10, st %d" % (k, st), e10[k]) for k in ("pad2d", "space_to_depth")]
+        calls += [("gap_gmp_bwd hw = 15, st %d" % st, entries(st, hw=15)["gap_gmp_bwd"]),
+                  ("wgrad_small_cin cout = 12, st %d" % st, entries(st, cout=12)["wgrad_small_cin"]),
+                  ("depth_to_space C = 12, st %d" % st, entries(st, d2s_c=12)["depth_to_space"])]
+    calls.append(("pad2d pointer 2 bytes past the 8-byte grid, st 2", entries(2, x=a_off)["pad2d"]))
+    calls += [("%s st = 3" % k, call) for k, call in entries(3).items()]
+    for why, call in calls:
+        rc = call()
+        torch.cuda.synchronize()
+        assert rc == -1, "%s: returned %d, not PPST_EINVAL" % (why, rc)
+        for k, (dt, v) in fills.items():
+            assert bool((buf[k] == torch.full((1,), v, device=dev, dtype=dt)).all()), "%s: a refused call wrote %s" % (why, k)
